@@ -15,11 +15,14 @@ with more than one rank -- one RCCL gather of the reduced product to rank 0.
 A "point" is one complex TFR coefficient of the CWT or Stockwell panel; points per step = 2 * channels * bands * n
 per GPU (the STFT's coefficients are reported separately, they are < 1 % of the step's bytes).
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR]
+    python bench.py --gpus 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
+Without --full a run is the headline leg alone (set-up, warmup, the timed steps, the line); --full adds the other legs,
+the CPU baselines, the stage timing and rooflines and the side measurements.  Prints ONE JSON line on rank 0 (see
+DESIGN.md "Measurement" for every field).
 """
 import argparse
 import json
@@ -81,7 +84,19 @@ def parse():
                     help="1: a ONE-rank run initialises the process group too (nccl = RCCL, world size 1) and every step ends in "
                          "the real pipelined gather-to-self: the multi-rank code path on a one-GPU box")
     ap.add_argument("--stub-dump", default="", help="with --stub: rank 0 saves the last gathered buffers here (torch.save)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline leg: the CPU baselines, the configs[2] / float64 / configs[4] legs of a "
+                         "run without --config (configs1_per_gpu with N ranks), the per-stage timing and rooflines, the STFT's "
+                         "own timing, the NumPy wrappers, the two-stream steps and the host-to-device copy rate.  Without it a "
+                         "run sets up, warms up, times --steps steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / "
+                         "float64; complex arrays as [..., 2] real / imaginary pairs; an array of more than 2^20 real values is "
+                         "replaced by a fixed, seeded sample of them, <name>_sample.npy; rank<r>_<name> with N ranks)")
+    args = ap.parse_args()
+    if args.legs and not args.full:
+        ap.error("--legs selects legs of the --full run (a run without --full has one leg)")
+    return args
 
 
 def required_bytes(n_ch, n_b, n, real_bytes):
@@ -99,6 +114,53 @@ def survey_bytes(n_ch, n_b, n, length, real_bytes):
 
 FP64_VALU_PEAK_GINST = 1024 * 2.4 / 4  # wave instructions / ns: 1024 SIMDs x 2.4 GHz, a double-precision wave64 instruction
 # issues over 4 cycles (78.6 TFLOP/s of float64 vector FMA = 614.4 G wave-FMAs / s x 64 lanes x 2)
+
+
+DUMP_VALUES = 1 << 20  # real values per dumped array at most (8 MB in float64; < 64 MB over every array of a step)
+DUMP_SEED = 20250213
+
+
+def dump_outputs(outdir, named, prefix=""):
+    """--dump-outputs: each (name, tensor) of `named` to outdir/<prefix><name>.npy.  A complex tensor becomes [..., 2] real /
+    imaginary pairs; a tensor of more than DUMP_VALUES real values is replaced by a stratified sample of its flat elements
+    (one per stride, its offset in the stride from a fixed seed): the same elements for the same shape in every run."""
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for name, t in named:
+        if t is None:
+            continue
+        flat = t.detach().reshape(-1)
+        cap = DUMP_VALUES // (2 if flat.is_complex() else 1)
+        n = flat.numel()
+        if n > cap:
+            stride = n // cap
+            idx = np.arange(cap, dtype=np.int64) * n // cap + np.random.default_rng(DUMP_SEED).integers(0, stride, cap)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            name += "_sample"
+        if flat.is_complex():
+            flat = torch.view_as_real(flat)
+        arr = flat.cpu().numpy()
+        if arr.dtype not in (np.float32, np.float64):
+            raise TypeError(f"{name}: {arr.dtype} output (float32 / float64 expected)")
+        np.save(os.path.join(outdir, f"{prefix}{name}.npy"), arr)
+        total += arr.nbytes
+    if total > 64 << 20:
+        raise RuntimeError(f"--dump-outputs wrote {total} bytes (64 MB at most)")
+
+
+def result_arrays(results):
+    """(name, tensor) pairs of what a qi_cwt_stx call hands its caller: per transform the band table, the panel and the
+    reduced products (None where the call produced none)."""
+    import torch
+
+    named = []
+    for key, r in zip(("cwt", "stx"), results):
+        named += [(f"{key}_frequency_hz", torch.from_numpy(np.ascontiguousarray(r.frequency_hz, dtype=np.float64))),
+                  (f"{key}_coef", r.coef), (f"{key}_power_band", r.power_band), (f"{key}_power_time", r.power_time),
+                  (f"{key}_stats", r.stats)]
+    return named
 
 
 def load_traffic():
@@ -209,7 +271,8 @@ def stream_bench(args, ctx, cpu):
     n_ch = args.channels
     n_b = len(qi.scales_dyadic.log_frequency_hz_from_fft_points(fs, n, order))
     warm_req = 3 if args.warmup is None else args.warmup
-    chunks = max(args.stream_chunks, warm_req + 2)
+    # --steps given: exactly that many timed items (this rank's share of the record set is `chunks` items)
+    chunks = warm_req + args.steps if args.steps_given else max(args.stream_chunks, warm_req + 2)
     total = n + (chunks - 1) * hop
     # this rank's block of the record set (weak scaling: the 24 h job has 128 channels x 131 chunks per GPU)
     rows = np.empty((n_ch, total), dtype=npd)
@@ -237,15 +300,18 @@ def stream_bench(args, ctx, cpu):
     if ctx.coll:
         dist.barrier()
     t0 = time.perf_counter()
-    done, entropy, seen = 0, 0.0, []
+    done, entropy, seen, last = 0, 0.0, [], None
     for item in it:
         entropy += float(item.cwt.stats[0, 1])  # (touch the result: the item is complete)
         seen.append((item.first_channel, item.chunk))
         done += 1
+        last = item
     ctx.sync()
     if ctx.coll:
         dist.barrier()
     dt_local = time.perf_counter() - t0
+    if args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, result_arrays((last.cwt, last.stx)), f"rank{rank}_" if world > 1 else "")
     rank_dt = [dt_local]
     rank_items_done = [done]
     dt = dt_local
@@ -263,7 +329,7 @@ def stream_bench(args, ctx, cpu):
         points_item = 2 * n_ch * n_b * n
         value = points_item * sum(rank_items_done) / dt / 1e6
         h2d_ms = None
-        if not stub:  # plain host -> device copy rate of one item (pinned), for the PCIe share of a step
+        if args.full and not stub:  # plain host -> device copy rate of one item (pinned), for the PCIe share of a step
             x = torch.empty((n_ch, n), dtype=tdtype).pin_memory()
             d = torch.empty((n_ch, n), dtype=tdtype, device=dev)
             torch.cuda.synchronize()
@@ -404,6 +470,7 @@ def leg_args(args, config, **over):
     a.dtype = a.dtype or "f32"
     a.stream = a.stream or 0
     small = a.channels * a.order <= 12
+    a.steps_given = a.steps is not None
     if a.steps is None:
         a.steps = 200 if small else 20
     if a.warmup is None:
@@ -494,6 +561,7 @@ def run_leg(a, ctx, cpu, extras=True):
     pipe = qdist.GatherPipeline(depth=depth, dst=0, timing=ctx.coll and not small, force_collective=ctx.coll)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if not stub else None
     stft_ms = []
+    last = [outs[0]]  # the outputs the latest step wrote
 
     def step(time_stft=False):
         if stft is not None:
@@ -505,10 +573,12 @@ def run_leg(a, ctx, cpu, extras=True):
         if not ctx.coll:
             plan.cwt_stx(sig, out=outs[0])  # qi_cwt_stx: both transforms of the same records in one call
             msg = qdist.pack_reduced(list(outs[0]))
+            last[0] = outs[0]
         else:
             i = pipe.acquire()
             plan.cwt_stx(sig, out=outs[i])
             msg = pipe.submit(i, qdist.pack_reduced(list(outs[i])))
+            last[0] = outs[i]
         if time_stft and stft is not None:
             device_sync()
             stft_ms.append(ev[0].elapsed_time(ev[1]))
@@ -540,29 +610,31 @@ def run_leg(a, ctx, cpu, extras=True):
         for _ in range(10):
             step()
         settle_steps += 10
-    # untimed: every stage timed with HIP events, to find the dominant stage and report the breakdown
-    plan.profile(True)
-    for _ in range(3):
-        step(time_stft=True)
-    device_sync()
-    stage_all = plan.profile_read()
+    stage_all, timed_stages, producing, dominant = {}, [], {}, None
+    if a.full:
+        # untimed: every stage timed with HIP events, to find the dominant stage and report the breakdown
+        plan.profile(True)
+        for _ in range(3):
+            step(time_stft=True)
+        device_sync()
+        stage_all = plan.profile_read()
 
-    # (of the stages that PRODUCE panel rows: block, zoom, pass2, inverse -- pass 1 of the two-pass engine, the forward
-    # transform and the coarse stage write no coefficient)
-    def produces(name):
-        try:
-            sb = plan.stage_bands(name)
-        except ValueError:
-            return False
-        return sb[0] + sb[2] > 0
+        # (of the stages that PRODUCE panel rows: block, zoom, pass2, inverse -- pass 1 of the two-pass engine, the forward
+        # transform and the coarse stage write no coefficient)
+        def produces(name):
+            try:
+                sb = plan.stage_bands(name)
+            except ValueError:
+                return False
+            return sb[0] + sb[2] > 0
 
-    producing = {k: v for k, v in stage_all.items() if v[1] and produces(k)}
-    dominant = max((producing or stage_all).items(), key=lambda kv: kv[1][0])[0]
-    # timed region: HIP events around the dominant stage's launches only, on every 7th transform call (odd, so that the
-    # CWT and the Stockwell calls of a step are sampled alike) -- every event is a bubble in the stream.  A step of many
-    # records is tens of milliseconds: there every producing stage is timed on every call.
-    timed_stages = [dominant] if small else (list(producing) or [dominant])
-    plan.profile(True, stages=timed_stages, period=7 if small else 1)
+        producing = {k: v for k, v in stage_all.items() if v[1] and produces(k)}
+        dominant = max((producing or stage_all).items(), key=lambda kv: kv[1][0])[0]
+        # timed region: HIP events around the dominant stage's launches only, on every 7th transform call (odd, so that the
+        # CWT and the Stockwell calls of a step are sampled alike) -- every event is a bubble in the stream.  A step of many
+        # records is tens of milliseconds: there every producing stage is timed on every call.
+        timed_stages = [dominant] if small else (list(producing) or [dominant])
+        plan.profile(True, stages=timed_stages, period=7 if small else 1)
     pipe.reset_timing()
     fence()
     t0 = time.perf_counter()
@@ -571,8 +643,15 @@ def run_leg(a, ctx, cpu, extras=True):
     fence()
     dt_local = time.perf_counter() - t0
     dt = dt_local
-    stage = plan.profile_read()
-    plan.profile(False)
+    if a.dump_outputs:  # (before anything else runs on these buffers)
+        named = result_arrays(last[0])
+        if stft is not None:
+            named += [("stft_coef", stft.z), ("stft_bits", stft.bits)]
+        dump_outputs(a.dump_outputs, named, f"rank{rank}_" if world > 1 else "")
+    stage = {}
+    if a.full:
+        stage = plan.profile_read()
+        plan.profile(False)
     rank_dt = [dt_local]
     wait_ms = [pipe.wait_ms() / max(a.steps, 1)]
     n_ranks = 1
@@ -680,10 +759,12 @@ def run_leg(a, ctx, cpu, extras=True):
                 "rank_seconds": [round(v, 6) for v in rank_dt],
                 "gather_wait_ms_per_step": [round(v, 4) for v in wait_ms] if pipe.timing else None,
                 "gather_message_bytes_per_rank": int(2 * slots * 8) if ctx.coll else 0,
-                "rank_stage_ms_per_step": rank_stage_ms if ctx.coll else None,
+                "rank_stage_ms_per_step": rank_stage_ms if ctx.coll and a.full else None,
             },
-            "roofline": stage_roofline(dominant),
-            "step_roofline": {
+        }
+        if a.full:
+            line["roofline"] = stage_roofline(dominant)
+            line["step_roofline"] = {
                 "required_bytes_per_step": int(req),
                 "wall_ms_per_step": round(wall_ms, 4),
                 "achieved_gbs": round(req / (wall_ms * 1e-3) / 1e9, 1),
@@ -694,14 +775,13 @@ def run_leg(a, ctx, cpu, extras=True):
                 "note": "required bytes = records in + complex panels out + marginals out (+ the STFT's in / out) over the "
                         "timed wall step; stage breakdown from 3 untimed steps with every stage under HIP events; "
                         "survey_bytes adds SURVEY s8(d)'s atom-bank read, which this engine never performs",
-            },
-        }
+            }
         others = [k for k in producing if k != dominant]
         if others:
             line["stage_rooflines"] = {k: stage_roofline(k) for k in others}
         if budget:
             line["config"]["hbm_budget"] = budget
-        if stft_info:
+        if stft_info and a.full:
             line["stft"] = stft_info
         if extras and world == 1 and not stub and a.wrappers and n_ch == 1:
             # the drop-in call as the tutorials make it (s04_tone_tfr.py:84-99): NumPy in, NumPy out, one transform per
@@ -796,6 +876,7 @@ def main():
     #                 under their own keys, configs[2] (64 records x order 12, the full stack) and a float64 leg;
     #   N ranks    -> `value` = configs[3]: configs[2]'s 64 records per GPU, sharded, one gather of the reduced product per
     #                 step; the one-record-per-GPU latency case rides along as `configs1_per_gpu`.
+    # Without --full only the first of these legs runs, and without its CPU baseline.
     if not composite:
         legs = [("", leg_args(args, args.config or 1), args.cpu_seconds)]
     elif world == 1:
@@ -808,6 +889,10 @@ def main():
     if args.legs:
         keep = set(args.legs.split(","))
         legs = [l for l in legs if (l[0] or "main") in keep]
+    if not args.full:
+        legs = [(key, a, 0.0) for key, a, _ in legs[:1]]
+    for _, a, _ in legs[1:]:  # (--steps and --dump-outputs are the first leg's: the one `value` is quoted on)
+        a.steps_given, a.dump_outputs = False, ""
     # CPU baselines first: the forked workers must exist before anything initialises the GPU
     cpus = []
     for key, a, budget in legs:
@@ -850,7 +935,7 @@ def main():
         if a.stream:
             rec = stream_bench(a, ctx, cpu)
         else:
-            rec = run_leg(a, ctx, cpu, extras=(key == ""))
+            rec = run_leg(a, ctx, cpu, extras=(key == "" and args.full))
         if rank == 0:
             if line is None:
                 line = rec

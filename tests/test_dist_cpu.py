@@ -137,7 +137,7 @@ def test_bench_rank_plumbing_world2(tmp_path):
     dump = os.path.join(str(tmp_path), "stub.pt")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--stub", "1", "--log2n", "12", "--channels", "3", "--settle-ms", "0", "--stub-dump", dump]
+           "--stub", "1", "--log2n", "12", "--channels", "3", "--settle-ms", "0", "--stub-dump", dump, "--full"]
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -180,7 +180,7 @@ def test_bench_default_multirank_run_is_configs3_world2():
     """`bench.py --gpus N` with no --config (what the driver's scaling run launches): `value` is BASELINE configs[3] -- 64
     records per GPU, order 12, the STFT in the step, one gather of the reduced product -- and the one-record-per-GPU case
     rides along under its own key.  Stub transforms, short records (2^12), two gloo ranks."""
-    line = _torchrun(["--steps", "2", "--warmup", "1", "--stub", "1", "--log2n", "12", "--settle-ms", "0"])
+    line = _torchrun(["--steps", "2", "--warmup", "1", "--stub", "1", "--log2n", "12", "--settle-ms", "0", "--full"])
     cfg = line["config"]
     assert line["n_gpus"] == 2 and cfg["world_size"] == 2 and cfg["backend"].startswith("gloo")
     assert cfg["channels_per_gpu"] == 64 and "configs[3]" in cfg["workload"] and "128 channels" in cfg["workload"]
@@ -201,7 +201,7 @@ def test_bench_default_multirank_run_world8():
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-           "--stub", "1", "--log2n", "10", "--settle-ms", "0"]
+           "--stub", "1", "--log2n", "10", "--settle-ms", "0", "--full"]
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -252,7 +252,7 @@ def test_bench_scaling_base_consistent_with_multirank_value_world2():
     import json
     import subprocess
 
-    common = ["--steps", "2", "--warmup", "1", "--stub", "1", "--stub-ms", "400", "--log2n", "12", "--settle-ms", "0"]
+    common = ["--steps", "2", "--warmup", "1", "--stub", "1", "--stub-ms", "400", "--log2n", "12", "--settle-ms", "0", "--full"]
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "main,configs2", *common],
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -311,3 +311,82 @@ def test_forced_collective_on_one_rank_gloo():
     line = json.loads(run.stdout.strip().splitlines()[-1])
     assert line["config"]["backend"] == "gloo" and line["config"]["world_size"] == 1
     assert line["config"]["gather_message_bytes_per_rank"] > 0 and line["config"]["gather_wait_ms_per_step"] is not None
+
+
+def _bench_one_rank(args, tmp_path=None):
+    import json
+    import subprocess
+
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    for k in ("MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=300,
+                         env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def test_bench_plain_run_is_the_headline_leg_only(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: one leg (configs[1]), no CPU baseline, no profiled steps, no
+    side measurements; exactly N timed steps (stub transforms count the calls); --dump-outputs writes the last step's
+    outputs as float32 / float64 .npy files, the same from run to run."""
+    import torch
+
+    dumps = []
+    for k in range(2):
+        dump, stub = os.path.join(str(tmp_path), f"out{k}"), os.path.join(str(tmp_path), f"stub{k}.pt")
+        line = _bench_one_rank(["--gpus", "1", "--steps", "5", "--warmup", "2", "--stub", "1", "--log2n", "12", "--settle-ms", "0",
+                                "--dump-outputs", dump, "--stub-dump", stub])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 5 and line["warmup"] == 2 and line["dtype"] == "f32" and "configs[1]" in line["config"]["workload"]
+        for key in ("cpu_baseline", "configs2", "f64", "configs4", "roofline", "step_roofline", "numpy_wrappers", "two_streams"):
+            assert key not in line, key
+        assert torch.load(stub)["calls"] == 1 + 2 + 5  # the set-up call (one message buffer), the warmup, the timed steps
+        files = sorted(os.listdir(dump))
+        assert "cwt_power_band.npy" in files and "stx_stats.npy" in files and "stx_power_time.npy" in files
+        arrays = {f: np.load(os.path.join(dump, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    # a streaming headline leg: --steps sets the timed items too
+    line = _bench_one_rank(["--config", "4", "--steps", "3", "--warmup", "2", "--stub", "1", "--log2n", "12", "--channels", "2",
+                            "--dump-outputs", os.path.join(str(tmp_path), "stream")])
+    assert line["steps"] == 3 and "cpu_baseline" not in line
+    assert os.path.exists(os.path.join(str(tmp_path), "stream", "cwt_power_band.npy"))
+
+
+def test_bench_dump_outputs_sampling(tmp_path):
+    """bench.dump_outputs on arrays shaped like the real step's: a reversed (negative-stride) band table, a complex panel of
+    more than 2^20 values (a [k, 2] sample of fixed elements), a float32 per-time row; float32 / float64 only, <= 64 MB."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    from quantum_inferno_amd.engine import TfrResult
+
+    n, n_b = 1 << 16, 40
+    f = np.arange(n_b, dtype=np.float64)[::-1]
+    results = []
+    for k in range(2):
+        r = TfrResult(frequency_hz=f)
+        r.coef = torch.randn(2, n_b, n, dtype=torch.complex64, generator=torch.Generator().manual_seed(k))
+        r.power_band, r.power_time, r.stats = torch.rand(2, n_b, dtype=torch.float64), torch.rand(2, n), torch.rand(2, 4, dtype=torch.float64)
+        results.append(r)
+    for d in ("a", "b"):
+        bench.dump_outputs(os.path.join(str(tmp_path), d), bench.result_arrays(results))
+    got = {fn: np.load(os.path.join(str(tmp_path), "a", fn)) for fn in os.listdir(os.path.join(str(tmp_path), "a"))}
+    assert np.array_equal(got["cwt_frequency_hz.npy"], f)
+    coef = got["stx_coef_sample.npy"]
+    assert coef.dtype == np.float32 and coef.shape == (bench.DUMP_VALUES // 2, 2)
+    flat = results[1].coef.reshape(-1)
+    hits = np.isin(coef[:, 0], flat.real.numpy())
+    assert hits.all()  # every sampled value is an element of the panel
+    assert got["cwt_power_time.npy"].dtype == np.float32 and got["cwt_power_time.npy"].shape == (2 * n,)
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    for fn, a in got.items():
+        assert np.array_equal(a, np.load(os.path.join(str(tmp_path), "b", fn))), fn

@@ -5,7 +5,7 @@ args=$1; shift
 for rep in 1 2; do
   for cfg in "$@"; do
     echo -n "[$cfg] "
-    env QI_TUNE=1 $cfg python bench.py $args --cpu-seconds 0 --two-streams 0 --wrappers 0 2> /dev/null | python -c "
+    env QI_TUNE=1 $cfg python bench.py --full $args --cpu-seconds 0 --two-streams 0 --wrappers 0 2> /dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['step_roofline'].get('stage_ms_per_step'))" || exit 1

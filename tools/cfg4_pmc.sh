@@ -1,10 +1,11 @@
 #!/bin/bash
 # configs[4] streaming sample: vector instructions and HBM bytes per streamed item (16 records x 2^20, order 12, float64),
 # summed over every kernel of the run and divided by the items (separate --pmc passes; FETCH_SIZE x 2, KiB units)
+repo=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/${1:-cfg4_pmc}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-A="python3 $GRAFT_REPO_ROOT/bench.py --config 4 --cpu-seconds 0 --stream-chunks 9 --warmup 2"
+A="python3 $repo/bench.py --full --config 4 --cpu-seconds 0 --stream-chunks 9 --warmup 2"
 for ctr in SQ_INSTS_VALU FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 400 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out/$ctr -- $A > $out/$ctr.log 2>&1
   echo "$ctr rc=$?"

@@ -8,12 +8,12 @@ tag=${1:-r05}; what=${2:-all}
 out=$GRAFT_REPO_ROOT/gpurun_out/prof_$tag
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-declare -A LEG=( [cfg1]="--legs main --two-streams 0 --wrappers 0" [cfg2]="--legs configs2" [f64]="--legs f64" )
+declare -A LEG=( [cfg1]="--full --legs main --two-streams 0 --wrappers 0" [cfg2]="--full --legs configs2" [f64]="--full --legs f64" )
 if [ "$what" != "pmc" ]; then
-  bash tools/prof_leg.sh prof_$tag/cfg1 --legs main --steps 200 --warmup 20 --two-streams 0 --wrappers 0 > $out/cfg1.txt 2>&1; tail -9 $out/cfg1.txt
-  bash tools/prof_leg.sh prof_$tag/cfg2 --legs configs2 --steps 10 --warmup 3 > $out/cfg2.txt 2>&1; tail -9 $out/cfg2.txt
-  bash tools/prof_leg.sh prof_$tag/f64 --legs f64 --steps 20 --warmup 5 > $out/f64.txt 2>&1; tail -9 $out/f64.txt
-  bash tools/prof_leg.sh prof_$tag/cfg4 --config 4 > $out/cfg4.txt 2>&1; tail -9 $out/cfg4.txt
+  bash tools/prof_leg.sh prof_$tag/cfg1 --full --legs main --steps 200 --warmup 20 --two-streams 0 --wrappers 0 > $out/cfg1.txt 2>&1; tail -9 $out/cfg1.txt
+  bash tools/prof_leg.sh prof_$tag/cfg2 --full --legs configs2 --steps 10 --warmup 3 > $out/cfg2.txt 2>&1; tail -9 $out/cfg2.txt
+  bash tools/prof_leg.sh prof_$tag/f64 --full --legs f64 --steps 20 --warmup 5 > $out/f64.txt 2>&1; tail -9 $out/f64.txt
+  bash tools/prof_leg.sh prof_$tag/cfg4 --full --config 4 > $out/cfg4.txt 2>&1; tail -9 $out/cfg4.txt
 fi
 if [ "$what" != "stats" ]; then
   for leg in cfg1 cfg2 f64; do
