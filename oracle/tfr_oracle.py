@@ -425,6 +425,26 @@ def cwt_chirp_fft(sig, fs, order=3, index_shift=0.0, ref_hz=1.0, base=G2, dict_t
     return out, to_log2_with_epsilon(out), np.arange(n) / fs, f
 
 
+def cwt_chirp_conv(sig, fs, order=3, index_shift=0.0, dict_type="norm", bands=None, ref_hz=1.0, base=G2):
+    """Returns (cwt, bits, t, f), linear-correlation back-end.  ref: cwt_atoms.py:423-435 (cwt_type='conv'):
+    signal.convolve(sig, conj(atom)[::-1], mode='same') restated as cwt_fft restates fftconvolve -- both operands
+    zero-padded to L = next_fast_len(2n-1) (= 2n for n a power of two), spectra multiplied, inverse, the centred
+    [(n-1)//2 : (n-1)//2 + n] kept."""
+    sig = np.asarray(sig)
+    n = len(sig)
+    order_n, f_flipped = chirp_band_table(order, n, fs, index_shift, ref_hz, base)
+    f = np.flip(f_flipped)
+    big = 2 * n if n & (n - 1) == 0 else _sfft.next_fast_len(2 * n - 1, False)
+    spec = _fft(sig, big)
+    rows = range(len(f)) if bands is None else bands
+    out = np.empty((len(f) if bands is None else len(bands), n), dtype=np.complex128)
+    start = (n - 1) // 2
+    for i, j in enumerate(rows):
+        h = np.conj(chirp_atom(order_n, n, f[j], fs, index_shift, base, dict_type))[::-1]
+        out[i] = _ifft(spec * _fft(h, big))[start : start + n]
+    return out, to_log2_with_epsilon(out), np.arange(n) / fs, f
+
+
 # --------------------------------------------------------------------------- tfr_info
 def scale_power_bits(power):
     """log2(P + eps64) - max.  ref: tfr_info.py:65-79."""

@@ -69,7 +69,9 @@ __global__ void __launch_bounds__(256) k_fft_marginal(const cplx<T>* __restrict_
   const T inv = (T)(1.0 / total_of(partial + c * nspan, nspan));
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nf; i += (int64_t)gridDim.x * 256) {
     const cplx<T> z = X[c * nf + i];
-    if (angle) angle[c * nf + i] = (T)atan2((double)z.y, (double)z.x);
+    // (the DC bin of a real record is real: its imaginary part is taken as +0, as scipy.fft.rfft returns it -- the
+    // transform's -0 would put arg at -pi instead of pi for a record of negative mean, and the whole unwrapped phase 2 pi off)
+    if (angle) angle[c * nf + i] = (T)atan2(i == 0 ? 0.0 : (double)z.y, (double)z.x);
     marginal[c * nf + i] = (z.x * z.x + z.y * z.y) * inv;
   }
 }

@@ -251,6 +251,7 @@ class TfrPlan:
             res = out
             if (res.coef is not None and res.coef.shape[0] != n_ch) or (res.stats is not None and res.stats.shape[0] != n_ch):
                 raise ValueError("out= buffers were made for another channel count")
+            res.power_scale = power_scale  # the reductions about to be written are those of this call's scale
         else:
             res = TfrResult(frequency_hz=f_hz, power_scale=power_scale)
             if coef:

@@ -136,6 +136,11 @@ class StreamPipeline:
         assert self._pinned_np[0].dtype == np_dtype
         self._dev = [torch.empty((self.block, plan.n), dtype=plan.rdtype, device=plan.device) for _ in range(2)]
         self._copy_stream = torch.cuda.Stream(device=plan.device) if self._gpu else None
+        # the device buffers come from the caching allocator of the current stream, which hands out a freed block at once:
+        # work queued there before may still read or write that memory, so the copy stream's first writes wait for it
+        self._allocated = torch.cuda.Event() if self._gpu else None
+        if self._gpu:
+            self._allocated.record(torch.cuda.current_stream(plan.device))
         self._copied = [torch.cuda.Event() for _ in range(2)] if self._gpu else None    # H2D of buffer j done
         self._consumed = [torch.cuda.Event() for _ in range(2)] if self._gpu else None  # transforms that read buffer j done
         self._used = [False, False]
@@ -154,6 +159,8 @@ class StreamPipeline:
         with torch.cuda.stream(self._copy_stream):
             if self._used[j]:
                 self._copy_stream.wait_event(self._consumed[j])  # the transforms that read device buffer j are done
+            else:
+                self._copy_stream.wait_event(self._allocated)  # what was queued where device buffer j was allocated is done
             self._dev[j][:cb].copy_(self._pinned[j][:cb], non_blocking=True)
             self._copied[j].record(self._copy_stream)
         self._used[j] = True

@@ -1225,9 +1225,17 @@ def test_shannon_1d_family_vs_reference(golden, tag, dtype):
         np.testing.assert_allclose(obj.isnr, g[f"{name}_isnr_{tag}"], rtol=0, atol=1e-9 if dtype == np.float64 else 2e-4)
         np.testing.assert_allclose(obj.esnr, g[f"{name}_esnr_{tag}"], rtol=1e-9 if dtype == np.float64 else 1e-4,
                                    atol=10 * rel * g[f"{name}_esnr_{tag}"].max())
-    # batched records through the same kernels
-    both = tfr_info.ShannonTDR(np.stack([sig, sig[::-1]]))
-    np.testing.assert_array_equal(both.marginal[0], tdr.marginal)
+    # batched records through the same kernels: every record equals its single-record run (records of different energy,
+    # so a partial sum or an unwrap carry taken from the wrong record shows)
+    other = 0.5 * sig[::-1] + 0.25 * sig
+    assert other.dtype == dtype
+    both_t, both_f = tfr_info.ShannonTDR(np.stack([sig, other])), tfr_info.ShannonFFT(np.stack([sig, other]))
+    one_t, one_f = tfr_info.ShannonTDR(other), tfr_info.ShannonFFT(other)
+    for k, (t_ref, f_ref) in enumerate(((tdr, fft), (one_t, one_f))):
+        np.testing.assert_array_equal(both_t.marginal[k], t_ref.marginal)
+        np.testing.assert_array_equal(both_t.sig[k], t_ref.sig)
+        np.testing.assert_array_equal(both_f.marginal[k], f_ref.marginal)
+        np.testing.assert_array_equal(both_f.angle_rads[k], f_ref.angle_rads)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -1252,9 +1260,11 @@ def test_short_time_fft_wrappers_vs_reference(golden, dtype):
         cdt = np.complex128 if dtype == np.float64 else np.complex64
         ts, x = stf.istft_tukey(g[f"S_{tag}"].astype(cdt), fs, alpha, seg, ov, scaling)
         assert np.array_equal(ts, g[f"ts_{tag}"]) and relmax(x, g[f"x_{tag}"]) <= 10 * tol, (tag, relmax(x, g[f"x_{tag}"]))
-    # a batch of records through the same kernels
-    two = stf.stft_tukey(np.stack([sig, sig[::-1]]), 800.0, 0.25, 256, 128)[2]
+    # a batch of records (of different energy) through the same kernels: every record equals its single-record run
+    other = 0.5 * sig[::-1] + 0.25 * sig
+    two = stf.stft_tukey(np.stack([sig, other]), 800.0, 0.25, 256, 128)[2]
     assert np.array_equal(two[0], stf.stft_tukey(sig, 800.0, 0.25, 256, 128)[2])
+    assert np.array_equal(two[1], stf.stft_tukey(other, 800.0, 0.25, 256, 128)[2])
 
 @pytest.mark.parametrize("dtype,seg,ov,log2n", [(np.float32, 2048, 1024, 17), (np.float32, 1024, 768, 16), (np.float32, 4096, 2048, 17),
                                                 (np.float64, 2048, 1024, 16), (np.float64, 512, 384, 15), (np.float32, 300, 150, 15)])

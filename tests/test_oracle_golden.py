@@ -77,6 +77,16 @@ def test_cwt_atoms_conv_backend_matches_away_from_edges(golden):
     assert relmax(a[-12:, 256:768], b[-12:, 256:768]) < 1e-6
 
 
+def test_cwt_chirp_conv(golden):
+    """The conv back end (cwt_atoms.py:423-435) against the reference's own panel, every band."""
+    g = golden("small_n1024.npz")
+    sig = g["sig_o3_fs1000"]
+    c, bits, t, f = orc.cwt_chirp_conv(sig, 1000.0, 3)
+    assert np.array_equal(f, g["chirp_f_o3_fs1000"]) and np.array_equal(t, g["t_o3_fs1000"])
+    assert relmax(c, g["chirp_cwt_conv_o3_fs1000"]) < 1e-12
+    assert relmax(orc.cwt_chirp_conv(sig, 1000.0, 3, bands=[0, 7, len(f) - 1])[0], c[[0, 7, len(f) - 1]]) == 0.0
+
+
 def test_tfr_info(golden):
     g = golden("small_n1024.npz")
     p = g["info_power"]
