@@ -18,7 +18,7 @@ int stft_impl(int device, const void* sig, int64_t C, int64_t n, const void* win
   if (!fused_off && stft_fused_supported(sizeof(T) == 8 ? QI_F64 : QI_F32, seg, hop, nfft)) {  // one kernel: segments, transform and store from LDS
     const int rc = launch_stft_fused<T>(static_cast<const T*>(sig), static_cast<const T*>(window), static_cast<cplx<T>*>(Z),
                                         static_cast<T*>(bits), C, n, seg, hop, nfft, nseg, seg / 2, scale,
-                                        eps == 0.0 ? 2.220446049250313e-16 : eps, st);
+                                        qi::host::eps_or_default(eps), st);
     if (rc != QI_ERR_UNSUPPORTED) return rc;  // (a device with less LDS per workgroup than the tile needs: the three-kernel path below)
   }
   T* frames = reinterpret_cast<T*>(scratch);
@@ -30,7 +30,7 @@ int stft_impl(int device, const void* sig, int64_t C, int64_t n, const void* win
     QI_TRY(fft_r2c<T>(g_stft_fft[device], frames, F, nfft, C * nseg, st));
   }
   return launch_stft_transpose<T>(F, static_cast<cplx<T>*>(Z), static_cast<T*>(bits), C, nseg, nf, (T)scale,
-                                  (T)(eps == 0.0 ? 2.220446049250313e-16 : eps), st);
+                                  (T)qi::host::eps_or_default(eps), st);
 }
 
 template <typename T>

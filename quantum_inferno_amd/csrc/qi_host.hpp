@@ -195,25 +195,13 @@ using namespace qi;  // (internal header of the host translation units only)
 
 // qi_cwt_stx: the CWT run leaves its block launch and its tail to the Stockwell run, which issues them together with
 // its own (one launch each: the two block launches share the forward transform of every block)
-struct TailCall {  // the arguments of one native::launch_tail
-  const float* time_part = nullptr;
-  float* out_time = nullptr;
-  int64_t ct = 0, n = 0;
-  int chunk_total = 0;
-  const double* part_band = nullptr;
-  const double* part_stat = nullptr;
-  double* power_band = nullptr;
-  double* stats = nullptr;
-  int64_t B = 0, nbk = 0, stat_slots = 0;
-  const int32_t* band_slots = nullptr;
-};
 struct FusedCarry {
   bool active = false;
   size_t ws_used = 0;  // bytes of the workspace the CWT run's scratch occupies (kept until its deferred launches ran)
   native::BlockArgs<float> blk{};
   int demod = 0;
   int64_t ct = 0;
-  TailCall tail;
+  native::TailCall<float> tail;
   bool has_zoom = false;  // the gather / coarse / interpolation launches of the CWT run are deferred as well
   native::ZoomArgs<float> zoom{};
 };
@@ -398,6 +386,9 @@ namespace qi {
 namespace host {
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+// a request (qi_tfr_out, the plan-less entry points) that leaves power_scale / eps at zero asks for the defaults
+inline double power_scale_or_default(double power_scale) { return power_scale == 0.0 ? 1.0 : power_scale; }
+inline double eps_or_default(double eps) { return eps == 0.0 ? 2.220446049250313e-16 : eps; }
 enum class Kind { Linear, Circular, Stockwell };
 // Host sanitizer build (tests/sanitize: the library's host code on a stand-in HIP runtime under AddressSanitizer /
 // UBSan): every region a run carves out of the plan's scratch is reported here and checked -- inside the workspace, and

@@ -1024,10 +1024,6 @@ int launch_time_reduce(const T* part, T* out, int64_t C, int64_t n, int nchunk, 
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
-template <typename T>
-int launch_tail(const T* part, T* out, int64_t C, int64_t n, int nchunk, const T* edge_time, int64_t wmax,
-                const double* part_band, const double* part_stat, double* power_band, double* stats, int64_t B,
-                int64_t nblk, int64_t nstat, const int32_t* band_slots, hipStream_t st);
 // two tails (the two transforms of qi_cwt_stx) in one launch: blockIdx.z selects the transform
 template <typename T>
 struct TailPack {
@@ -1051,55 +1047,46 @@ __global__ void __launch_bounds__(256) k_tail2(TailPack<T> p0, TailPack<T> p1) {
 }
 
 template <typename T>
-int launch_tail2(const T* part0, T* out0, int nchunk0, const double* part_band0, const double* part_stat0,
-                 double* power_band0, double* stats0, int64_t B0, int64_t nblk0, int64_t nstat0,
-                 const int32_t* band_slots0, const T* part1, T* out1, int nchunk1, const double* part_band1,
-                 const double* part_stat1, double* power_band1, double* stats1, int64_t B1, int64_t nblk1, int64_t nstat1,
-                 const int32_t* band_slots1, int64_t C, int64_t n, hipStream_t st) {
-  const bool aligned = n % 4 == 0 && reinterpret_cast<uintptr_t>(out0) % 16 == 0 && reinterpret_cast<uintptr_t>(part0) % 16 == 0 &&
-                       reinterpret_cast<uintptr_t>(out1) % 16 == 0 && reinterpret_cast<uintptr_t>(part1) % 16 == 0;
-  if (!aligned) {
-    if (int rc = launch_tail<T>(part0, out0, C, n, nchunk0, nullptr, 0, part_band0, part_stat0, power_band0, stats0, B0, nblk0,
-                                nstat0, band_slots0, st))
-      return rc;
-    return launch_tail<T>(part1, out1, C, n, nchunk1, nullptr, 0, part_band1, part_stat1, power_band1, stats1, B1, nblk1,
-                          nstat1, band_slots1, st);
+int launch_tail(const TailCall<T>& t, hipStream_t st) {
+  const bool aligned = t.n % 4 == 0 && reinterpret_cast<uintptr_t>(t.out_time) % (4 * sizeof(T)) == 0 &&
+                       reinterpret_cast<uintptr_t>(t.time_part) % (4 * sizeof(T)) == 0;
+  if (!aligned) {  // (cannot happen for the engine's power-of-two records: two launches)
+    if (int rc = launch_time_reduce<T>(t.time_part, t.out_time, t.ct, t.n, t.chunk_total, t.edge_time, t.wmax, st)) return rc;
+    return launch_finalize(t.part_band, t.part_stat, t.power_band, t.stats, t.ct, t.B, t.nbk, t.stat_slots, st, t.band_slots);
   }
-  TailPack<T> p0{part0, out0, n, nchunk0, (int)B0 + 1, TailFin{part_band0, part_stat0, power_band0, stats0, B0, nblk0, nstat0, band_slots0}};
-  TailPack<T> p1{part1, out1, n, nchunk1, (int)B1 + 1, TailFin{part_band1, part_stat1, power_band1, stats1, B1, nblk1, nstat1, band_slots1}};
-  const int64_t gt = ceil_div(n, 1024) > 4096 ? 4096 : ceil_div(n, 1024);
-  const int nfin = p0.nfin > p1.nfin ? p0.nfin : p1.nfin;
-  dim3 g((unsigned)(gt + nfin), (unsigned)C, 2);
-  k_tail2<T, 4><<<g, 256, 0, st>>>(p0, p1);
+  const TailFin f{t.part_band, t.part_stat, t.power_band, t.stats, t.B, t.nbk, t.stat_slots, t.band_slots};
+  const int nfin = (int)t.B + 1;
+  const int64_t gt = ceil_div(t.n, 1024) > 4096 ? 4096 : ceil_div(t.n, 1024);
+  dim3 g((unsigned)(gt + nfin), (unsigned)t.ct);
+  k_tail<T, 4><<<g, 256, 0, st>>>(t.time_part, t.out_time, t.n, t.chunk_total, t.edge_time, t.wmax, f, nfin);
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
 
 template <typename T>
-int launch_tail(const T* part, T* out, int64_t C, int64_t n, int nchunk, const T* edge_time, int64_t wmax,
-                const double* part_band, const double* part_stat, double* power_band, double* stats, int64_t B,
-                int64_t nblk, int64_t nstat, const int32_t* band_slots, hipStream_t st) {
-  const bool aligned = n % 4 == 0 && reinterpret_cast<uintptr_t>(out) % (4 * sizeof(T)) == 0 &&
-                       reinterpret_cast<uintptr_t>(part) % (4 * sizeof(T)) == 0;
-  if (!aligned) {  // (cannot happen for the engine's power-of-two records: two launches)
-    if (int rc = launch_time_reduce<T>(part, out, C, n, nchunk, edge_time, wmax, st)) return rc;
-    return launch_finalize(part_band, part_stat, power_band, stats, C, B, nblk, nstat, st, band_slots);
+int launch_tail2(const TailCall<T>& t0, const TailCall<T>& t1, hipStream_t st) {
+  const int64_t n = t1.n;
+  const bool aligned = n % 4 == 0 && reinterpret_cast<uintptr_t>(t0.out_time) % 16 == 0 &&
+                       reinterpret_cast<uintptr_t>(t0.time_part) % 16 == 0 && reinterpret_cast<uintptr_t>(t1.out_time) % 16 == 0 &&
+                       reinterpret_cast<uintptr_t>(t1.time_part) % 16 == 0;
+  if (!aligned) {
+    if (int rc = launch_tail<T>(t0, st)) return rc;
+    return launch_tail<T>(t1, st);
   }
-  const TailFin f{part_band, part_stat, power_band, stats, B, nblk, nstat, band_slots};
-  const int nfin = (int)B + 1;
+  TailPack<T> p0{t0.time_part, t0.out_time, n, t0.chunk_total, (int)t0.B + 1,
+                 TailFin{t0.part_band, t0.part_stat, t0.power_band, t0.stats, t0.B, t0.nbk, t0.stat_slots, t0.band_slots}};
+  TailPack<T> p1{t1.time_part, t1.out_time, n, t1.chunk_total, (int)t1.B + 1,
+                 TailFin{t1.part_band, t1.part_stat, t1.power_band, t1.stats, t1.B, t1.nbk, t1.stat_slots, t1.band_slots}};
   const int64_t gt = ceil_div(n, 1024) > 4096 ? 4096 : ceil_div(n, 1024);
-  dim3 g((unsigned)(gt + nfin), (unsigned)C);
-  k_tail<T, 4><<<g, 256, 0, st>>>(part, out, n, nchunk, edge_time, wmax, f, nfin);
+  const int nfin = p0.nfin > p1.nfin ? p0.nfin : p1.nfin;
+  dim3 g((unsigned)(gt + nfin), (unsigned)t1.ct, 2);
+  k_tail2<T, 4><<<g, 256, 0, st>>>(p0, p1);
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
-template int launch_tail2<float>(const float*, float*, int, const double*, const double*, double*, double*, int64_t, int64_t,
-                                 int64_t, const int32_t*, const float*, float*, int, const double*, const double*, double*,
-                                 double*, int64_t, int64_t, int64_t, const int32_t*, int64_t, int64_t, hipStream_t);
-template int launch_tail<float>(const float*, float*, int64_t, int64_t, int, const float*, int64_t, const double*,
-                                const double*, double*, double*, int64_t, int64_t, int64_t, const int32_t*, hipStream_t);
-template int launch_tail<double>(const double*, double*, int64_t, int64_t, int, const double*, int64_t, const double*,
-                                 const double*, double*, double*, int64_t, int64_t, int64_t, const int32_t*, hipStream_t);
+template int launch_tail2<float>(const TailCall<float>&, const TailCall<float>&, hipStream_t);
+template int launch_tail<float>(const TailCall<float>&, hipStream_t);
+template int launch_tail<double>(const TailCall<double>&, hipStream_t);
 template int launch_time_reduce<float>(const float*, float*, int64_t, int64_t, int, const float*, int64_t, hipStream_t);
 template int launch_time_reduce<double>(const double*, double*, int64_t, int64_t, int, const double*, int64_t,
                                         hipStream_t);

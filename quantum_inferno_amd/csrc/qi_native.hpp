@@ -349,17 +349,27 @@ void zoom_weights(int level, int lane_off, float* w /*[zoom_taps(level)][64]*/);
 template <typename T>
 int launch_time_reduce(const T* part, T* out, int64_t C, int64_t n, int nchunk, const T* edge_time, int64_t wmax,
                        hipStream_t st);
-// time reduction + finalisation of the reductions in one launch (both requested)
+// time reduction + finalisation of the reductions in one launch (both requested): its arguments
 template <typename T>
-int launch_tail(const T* part, T* out, int64_t C, int64_t n, int nchunk, const T* edge_time, int64_t wmax,
-                const double* part_band, const double* part_stat, double* power_band, double* stats, int64_t B,
-                int64_t nblk, int64_t nstat, const int32_t* band_slots, hipStream_t st);
+struct TailCall {
+  const T* time_part = nullptr;  // [ct][chunk_total][n] per-time planes
+  T* out_time = nullptr;
+  int64_t ct = 0, n = 0;
+  int chunk_total = 0;
+  const T* edge_time = nullptr;  // corrected first / last samples of the short-atom bands, or null
+  int64_t wmax = 0;
+  const double* part_band = nullptr;
+  const double* part_stat = nullptr;
+  double* power_band = nullptr;
+  double* stats = nullptr;
+  int64_t B = 0, nbk = 0, stat_slots = 0;
+  const int32_t* band_slots = nullptr;
+};
 template <typename T>
-int launch_tail2(const T* part0, T* out0, int nchunk0, const double* part_band0, const double* part_stat0,
-                 double* power_band0, double* stats0, int64_t B0, int64_t nblk0, int64_t nstat0,
-                 const int32_t* band_slots0, const T* part1, T* out1, int nchunk1, const double* part_band1,
-                 const double* part_stat1, double* power_band1, double* stats1, int64_t B1, int64_t nblk1, int64_t nstat1,
-                 const int32_t* band_slots1, int64_t C, int64_t n, hipStream_t st);
+int launch_tail(const TailCall<T>& t, hipStream_t st);
+// two tails (the two transforms of qi_cwt_stx, same records) in one launch
+template <typename T>
+int launch_tail2(const TailCall<T>& t0, const TailCall<T>& t1, hipStream_t st);
 template <typename T>
 int launch_even_bins(const cplx<T>* x2, cplx<T>* x1, int64_t C, int64_t n, hipStream_t st);
 template <typename T>
