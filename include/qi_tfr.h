@@ -123,6 +123,30 @@ int64_t qi_plan_bands(const qi_plan* plan, int which /* qi_bank, or 2 for the ST
  * PASS2 or BLOCK on the native engine, INVERSE on the hipFFT engine); used to price a stage's algorithmic bytes. */
 int64_t qi_plan_stage_bands(const qi_plan* plan, int which, int stage);
 
+/* Which kernels produce row `band` of table `which` in a call of `records` records (a read-only query: tests and
+ * diagnostics use it to tell which path a band takes; it changes nothing).  `records` means the records that go through
+ * together: a call whose records do not fit the plan's scratch runs in tiles, and each tile takes the route of its own
+ * record count.
+ *   stage    qi_stage below: ZOOM, BLOCK, PASS2, or INVERSE (the hipFFT engine: the whole table, or the pass behind
+ *            the native run)
+ *   cls      ZOOM, float32: the band's class 0..6 in the table, after small classes have joined their neighbours
+ *            (0..4 coarse-grid level with the 10-tap interpolator, 5 / 6 the 6- / 4-tap classes of level 0);
+ *            ZOOM, float64: the coarse-grid level 0..4;  BLOCK: reach group 1, 2, 4, or 8 (8192-sample long blocks)
+ *   run_cls  ZOOM, float32: the class the band runs as in this call (classes 5 and 6 run as 0 in calls of few
+ *            records); ZOOM, float64: the class of the fine kernel, or -1 (k_z64_interp);  otherwise = cls
+ *   flags    QI_ROUTE_* bits */
+typedef struct {
+  int32_t stage, cls, run_cls, flags;
+} qi_band_route;
+#define QI_ROUTE_ANALYTIC(f) ((f) & 3)        /* BLOCK: 0 filter spectrum from the bank row, 1 Gaussian, 2 aliased Gaussian */
+#define QI_ROUTE_NARROW(f) (((f) >> 2) & 3)   /* BLOCK: 0 full spectrum, 1 a 256-bin window, 2 the lower half               */
+#define QI_ROUTE_NOWRAP 16                    /* BLOCK: weights without wrap-around logic                                    */
+#define QI_ROUTE_SPLIT 32                     /* ZOOM: split band (tapered atom on the zoom engine + edge pieces)            */
+#define QI_ROUTE_PASS2_KIND(f) (((f) >> 6) & 3) /* PASS2: 0 one-pass loader, 1 general (two passes), 2 short-atom table      */
+#define QI_ROUTE_BEHIND 256                   /* INVERSE: Stockwell row of the hipFFT pass behind the native run             */
+#define QI_ROUTE_F64_ZOOM 512                 /* ZOOM: the float64 zoom engine                                               */
+int qi_plan_band_route(const qi_plan* plan, int which, int32_t band, int64_t records, qi_band_route* route);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Stages of one transform call, timed with HIP events on the caller's stream when profiling is on
  * (bench.py's roofline leg; off by default, two event records per stage launch when on). */

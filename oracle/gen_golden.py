@@ -157,6 +157,38 @@ def gen_stx_general():
     save("stx_general_n1024.npz", **d)
 
 
+STX_GENERAL_LARGE = {
+    "lin": dict(frequency_min=20.0, frequency_max=400.0, frequency_step=20.0),
+    "geo": dict(scale_order_input=3.0, frequency_min=10.0, frequency_max=450.0, is_geometric=True),
+    "inferno": dict(scale_order_input=3.0, frequency_min=8.0, frequency_max=400.0, is_geometric=True, is_inferno=True),
+    "qpr": dict(frequency_min=25.0, frequency_max=300.0, frequency_step=25.0, factor_q=0.5, power_p=1.0, power_r=0.75),
+    "const_width": dict(frequency_min=5.0, frequency_max=495.0, frequency_step=10.0, power_r=0.0),
+    "q2p1": dict(frequency_min=2.0, frequency_max=480.0, frequency_step=6.0, factor_q=2.0, power_p=1.0),
+    "short_windows": dict(scale_order_input=2.0, frequency_min=100.0, frequency_max=480.0, frequency_step=20.0),
+}
+
+
+def gen_stx_general_large():
+    """styx_stx.tfr_stx_fft at n_fft = 2^16 (a length the native engines of the GPU library classify): the four parameter
+    sets of gen_stx_general, a constant-width set (power_r = 0), a q = 2, p = 1 set and a set whose windows are shorter
+    than 2.75 samples; per set `f`, `f_fft` and six sampled rows at the dense time samples."""
+    n, fs = 1 << 16, 1000.0
+    # (chirp + noise: a pure chirp leaves the bands above its last frequency at 1e-3 of the panel, where single precision
+    # cannot hold 2e-5 of the ROW's maximum whatever the algorithm)
+    sig = synth_chirp(n, fs, dtype=np.float64) + 0.25 * np.random.default_rng(65536).standard_normal(n)
+    d = {"sig_samples": sig[:: n // 4096]}
+    tsel = time_samples(n, dense=True)
+    tsel = tsel[tsel < n]
+    d["tsel"] = tsel
+    for name, kw in STX_GENERAL_LARGE.items():
+        tfr, psd, f, f_fft, win = quiet(styx_stx.tfr_stx_fft, sig, 1 / fs, n_fft_in=n, **kw)
+        rows = np.unique(np.round(np.linspace(0, len(f) - 1, 6)).astype(np.int64))
+        d[f"{name}_f"], d[f"{name}_ffft"], d[f"{name}_rowsel"] = f, f_fft, rows
+        d[f"{name}_rows"] = tfr[rows][:, tsel]
+        d[f"{name}_psum_band"] = (np.abs(tfr) ** 2).sum(axis=1)
+    save("stx_general_n65536.npz", **d)
+
+
 def gen_stft():
     d = {}
     for log2n, fs in ((13, 1000.0), (13, 800.0), (16, 1000.0)):
@@ -372,6 +404,8 @@ if __name__ == "__main__":
         gen_stft_large()
     if "stxgen" in todo:
         gen_stx_general()
+    if "stxgen16" in todo:
+        gen_stx_general_large()
     if "shannon1d" in todo:
         gen_shannon1d()
     if "stfft" in todo:

@@ -374,6 +374,53 @@ def stx_general(sig, dt, order=8.0, f_min=None, f_max=None, f_step=None, q=0.0, 
     return tfr, psd, f_stx, f_snap, win
 
 
+# --------------------------------------------------------------------------- table-driven (the C ABI's own definition)
+def gabor_table_fft(sig, p_re, p_im, omega, amp, bands=None, circular=False, x=None):
+    """The Gabor transform of include/qi_tfr.h for ANY band table (qi_plan_set_gabor_bank + qi_cwt), float64:
+    atom_j[k] = amp_j exp(-(p_re_j + i p_im_j) x_k^2) exp(i omega_j x_k) on the exact axis x_k = k - (n - 1) / 2.
+    Linear kind (QI_BANK_STYX): fftconvolve(sig, conj(atom)[::-1], mode="same") as cwt_fft restates it; circular kind
+    (QI_BANK_ATOMS): ifft(fft(sig) conj(fft(atom))) of length n rolled by n / 2, as cwt_chirp_fft does it.
+    `x`: other sample positions [n] (qi_gabor_atoms_at's argument; the reference's own axis fs (t - t[-1] / 2) differs
+    from the exact one by its rounding).  Returns [len(bands) or B, n] complex128."""
+    sig = np.asarray(sig, dtype=np.float64)
+    n = len(sig)
+    p_re, p_im, omega, amp = (np.asarray(a, dtype=np.float64) for a in (p_re, p_im, omega, amp))
+    x = np.arange(n, dtype=np.float64) - (n - 1) / 2.0 if x is None else np.asarray(x, dtype=np.float64)
+    rows = range(len(p_re)) if bands is None else bands
+    out = np.empty((len(rows), n), dtype=np.complex128)
+    if circular:
+        spec = _np_fft(sig)
+    else:
+        big = 2 * n if n & (n - 1) == 0 else _sfft.next_fast_len(2 * n - 1, False)
+        spec = _fft(sig, big)
+        start = (n - 1) // 2
+    for i, j in enumerate(rows):
+        atom = amp[j] * (np.exp(-(p_re[j] + 1j * p_im[j]) * x * x) * np.exp(1j * omega[j] * x))
+        if circular:
+            raw = _np_ifft(spec * np.conj(_np_fft(atom)))
+            out[i] = np.append(raw[n // 2 :], raw[0 : n // 2])
+        else:
+            out[i] = _ifft(spec * _fft(np.conj(atom[::-1]), big))[start : start + n]
+    return out
+
+
+def stx_table_fft(sig, shift_index, sigma, bands=None, fs=1.0):
+    """The Stockwell transform of include/qi_tfr.h for ANY band table (qi_plan_set_stx_bands + qi_stx): the body of
+    stx_fft with the table handed in.  `fs` only reproduces the rounding of the reference's bin frequencies
+    omega_k = 2 pi fftfreq(n, 1 / fs)_k / fs (fs = 1: the exact 2 pi k / n)."""
+    sig = np.asarray(sig)
+    n = len(sig)
+    spec = _fft(sig)
+    cat = np.concatenate([spec, spec])
+    omega_fft = 2 * np.pi * np.fft.fftfreq(n, 1 / fs) / fs
+    rows = range(len(sigma)) if bands is None else bands
+    out = np.empty((len(rows), n), dtype=np.complex128)
+    for i, j in enumerate(rows):
+        win = np.exp(-0.5 * (sigma[j] ** 2.0) * (omega_fft ** 2.0))
+        out[i] = _ifft(cat[shift_index[j] : shift_index[j] + n] * win)
+    return out
+
+
 # --------------------------------------------------------------------------- cwt_atoms
 def chirp_mqg_from_n(order, index_shift=0.0, base=G2):
     """(M_q, Q, gamma).  ref: cwt_atoms.py:122-144."""

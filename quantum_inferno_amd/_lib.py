@@ -12,6 +12,20 @@ QI_F32, QI_F64 = 0, 1
 QI_BANK_STYX, QI_BANK_ATOMS, QI_TABLE_STX = 0, 1, 2
 QI_ENGINE_AUTO, QI_ENGINE_HIPFFT, QI_ENGINE_NATIVE = 0, 1, 2
 STAGES = ("forward", "multiply", "inverse", "epilogue", "pass1", "pass2", "block", "zoom", "zoom_coarse")
+# qi_band_route.flags (QI_ROUTE_* of include/qi_tfr.h)
+ROUTE_NOWRAP, ROUTE_SPLIT, ROUTE_BEHIND, ROUTE_F64_ZOOM = 16, 32, 256, 512
+
+
+def route_analytic(flags):
+    return flags & 3
+
+
+def route_narrow(flags):
+    return (flags >> 2) & 3
+
+
+def route_pass2_kind(flags):
+    return (flags >> 6) & 3
 
 
 class QiError(RuntimeError):
@@ -27,6 +41,10 @@ class PlanDesc(C.Structure):
         ("flags", C.c_int32),
         ("workspace_bytes", C.c_int64),
     ]
+
+
+class BandRoute(C.Structure):
+    _fields_ = [("stage", C.c_int32), ("cls", C.c_int32), ("run_cls", C.c_int32), ("flags", C.c_int32)]
 
 
 class TfrOut(C.Structure):
@@ -59,6 +77,7 @@ PROTOTYPES = {
     "qi_plan_set_stx_bands": (_int, [_P, _i32, _I64, _D]),
     "qi_plan_bands": (_i64, [_P, _int]),
     "qi_plan_stage_bands": (_i64, [_P, _int, _int]),
+    "qi_plan_band_route": (_int, [_P, _int, _i32, _i64, C.POINTER(BandRoute)]),
     "qi_plan_profile": (_int, [_P, _int]),
     "qi_plan_profile_read": (_int, [_P, _D, _I64, _i32]),
     "qi_cwt": (_int, [_P, _int, _P, _i64, C.POINTER(TfrOut), _P]),

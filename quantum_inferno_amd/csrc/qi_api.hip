@@ -188,6 +188,12 @@ int qi_plan_set_gabor_bank(qi_plan* p, int bank, int32_t B, const double* p_re, 
   QI_REQUIRE(p && p_re && p_im && omega && amp, "null argument");
   QI_REQUIRE(bank == QI_BANK_STYX || bank == QI_BANK_ATOMS, "bad bank %d", bank);
   QI_REQUIRE(B > 0 && B <= 65535, "band count %d out of range", B);
+  // every atom a decaying Gaussian with finite parameters (p_re <= 0 is no atom: the support analysis divides by it)
+  for (int32_t j = 0; j < B; ++j) {
+    QI_REQUIRE(std::isfinite(p_re[j]) && p_re[j] > 0.0, "p_re[%d] = %g: must be positive and finite", j, p_re[j]);
+    QI_REQUIRE(std::isfinite(p_im[j]) && std::isfinite(omega[j]) && std::isfinite(amp[j]),
+               "band %d: p_im, omega and amp must be finite (got %g, %g, %g)", j, p_im[j], omega[j], amp[j]);
+  }
   DeviceGuard g(p->d.device);
   p->table_gen++;
   hipStream_t st = (hipStream_t)stream;
@@ -335,6 +341,9 @@ int qi_plan_set_stx_bands(qi_plan* p, int32_t B, const int64_t* shift_index, con
   for (int32_t j = 0; j < B; ++j)
     QI_REQUIRE(shift_index[j] >= 0 && shift_index[j] < p->n, "shift_index[%d] = %lld outside [0, n)", j,
                (long long)shift_index[j]);
+  // (sigma = 0 would be the identity window: the reference never makes one, and every engine's support rule divides by it)
+  for (int32_t j = 0; j < B; ++j)
+    QI_REQUIRE(std::isfinite(sigma[j]) && sigma[j] > 0.0, "sigma[%d] = %g: must be positive and finite", j, sigma[j]);
   DeviceGuard g(p->d.device);
   p->table_gen++;
   if (p->d_stx_idx) {
@@ -382,6 +391,63 @@ int64_t qi_plan_stage_bands(const qi_plan* p, int which, int stage) {
   if (stage == QI_STAGE_ZOOM) return zoom;
   if (stage == QI_STAGE_INVERSE) return left;
   return stage == QI_STAGE_PASS2 ? total - blk - zoom - left : 0;
+}
+
+int qi_plan_band_route(const qi_plan* p, int which, int32_t band, int64_t records, qi_band_route* route) {
+  QI_REQUIRE(p && route, "null argument");
+  QI_REQUIRE(which >= 0 && which <= 2, "bad table %d", which);
+  QI_REQUIRE(band >= 0 && band < qi_plan_bands(p, which), "band %d outside the table's %lld rows", band,
+             (long long)qi_plan_bands(p, which));
+  QI_REQUIRE(records > 0, "records must be positive");
+  *route = qi_band_route{QI_STAGE_INVERSE, 0, 0, 0};
+  const auto& t = p->nat[which];
+  if (!t.ready) return QI_OK;  // the hipFFT engine runs the whole table
+  if (which == 2 && p->stx_left_n > 0 && band >= p->stx_left_lo && band < p->stx_left_lo + p->stx_left_n) {
+    route->flags = QI_ROUTE_BEHIND;
+    return QI_OK;
+  }
+  int found = 0;
+  const bool split = which == 0 && std::find(p->h_split_bands.begin(), p->h_split_bands.end(), band) != p->h_split_bands.end();
+  for (const auto& z : t.h_zoom)
+    if (z.first == band) {
+      const int run = records < p->native_zoom_short_from && z.second >= native::kZoomLevels ? 0 : z.second;
+      *route = qi_band_route{QI_STAGE_ZOOM, z.second, run, split ? QI_ROUTE_SPLIT : 0};
+      ++found;
+    }
+  for (size_t q = 0; q < t.h_z64.size(); ++q)
+    if (t.h_z64[q] == band) {
+      int level = -1, fine = -1;
+      for (int g = 0; g < native::kZ64Levels; ++g)
+        if ((int32_t)q >= t.z64_first[g] && (int32_t)q < t.z64_first[g] + t.z64_count[g]) level = g;
+      for (int c = 0; c < native::kZ64FineClasses; ++c)
+        if ((int32_t)q >= t.zf_first[c] && (int32_t)q < t.zf_first[c] + t.zf_count[c]) fine = c;
+      *route = qi_band_route{QI_STAGE_ZOOM, level, fine, QI_ROUTE_F64_ZOOM | (split ? QI_ROUTE_SPLIT : 0)};
+      ++found;
+    }
+  if (which != 1 && p->blk[which].ready) {
+    const int cut = records >= batch_from(p) ? 1 : 0;
+    for (const auto& b : p->blk[which].var[cut].h_route)
+      if (b.out_band == band) {
+        *route = qi_band_route{QI_STAGE_BLOCK, b.wq, b.wq, (b.analytic & 3) | ((b.narrow & 3) << 2) | (b.nowrap ? QI_ROUTE_NOWRAP : 0)};
+        ++found;
+      }
+  }
+  for (size_t q = 0; q < t.h_rows.size(); ++q)
+    if (t.h_rows[q] == band) {
+      *route = qi_band_route{QI_STAGE_PASS2, 0, 0, (t.h_row_mode[q] & 3) << 6};
+      ++found;
+    }
+  if (which == 0 && p->nat[3].ready)
+    for (int32_t r : p->nat[3].h_rows)
+      if (r == band) {
+        *route = qi_band_route{QI_STAGE_PASS2, 0, 0, 2 << 6};
+        ++found;
+      }
+  if (found != 1) {  // a row without a producer, or with two: the plan's tables contradict each other
+    set_error("band %d of table %d has %d producers", band, which, found);
+    return QI_ERR_STATE;
+  }
+  return QI_OK;
 }
 
 int qi_plan_profile(qi_plan* p, int enable) {

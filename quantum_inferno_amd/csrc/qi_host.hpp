@@ -237,6 +237,8 @@ struct qi_plan {
     int32_t* d_zoom_plane_band = nullptr;  // owner band of every coarse plane
     std::vector<std::pair<int32_t, int32_t>> h_zoom;  // (panel row, level) of the zoom bands
     std::vector<int32_t> h_rows;                      // panel rows of the pass-2 bands
+    std::vector<int32_t> h_row_mode;                  // ... 0 one-pass loader, 1 general (same order)
+    std::vector<int32_t> h_z64;                       // panel rows of the float64 zoom bands, in the order of d_z64
     int32_t nzoom = 0, zoom_count[native::kZoomClasses] = {0, 0, 0, 0, 0, 0, 0};
     int64_t zoom_planes = 0;  // 4096-sample planes of coarse storage per record
     int zoom_max_level = 0;
@@ -276,6 +278,10 @@ struct qi_plan {
       void* d_demod_pow = nullptr;  // float64 Stockwell tables: [bands][16] demodulation factors (BlockArgs::demod_pow)
       void* d_gauss_w = nullptr;    // float64 tables: [bands][kBlk] real Gaussian filter weights (BlockArgs::gauss_w)
       std::vector<std::pair<int32_t, int32_t>> h_bands;  // (panel row, blocks) of the block bands
+      struct Route {  // what qi_plan_band_route reports of a block band (host copy of its descriptor's path fields)
+        int32_t out_band, wq, analytic, narrow, nowrap;
+      };
+      std::vector<Route> h_route;
       native::BlockItem* d_items = nullptr;
       int32_t nitems = 0, nplanes = 0;
       int32_t nlong = 0;        // long-block items, at the front of the list

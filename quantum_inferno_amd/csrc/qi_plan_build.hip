@@ -131,10 +131,10 @@ int upload_native_table(qi_plan* p, int kind, int64_t Lf, std::vector<native::Ba
       if (g >= 0) lvl[g].push_back(d);
       else rest.push_back(d);
     }
-    // The three coarsest grids go through the fine kernel with wave-uniform windows (k_z64_fine), by CLASS = (grid,
-    // interpolator length): on the coarsest grid, where every narrower band lands, a band oversampled >= 8 / 16 / 32 / 64
-    // times takes 12 / 10 / 8 / 6 taps instead of 16 (classes 3..6; the same error bound, see z64f_ntap).  A class of fewer
-    // than four bands joins the next longer interpolator.
+    // The kZ64FineLevels (two) coarsest grids go through the fine kernel with wave-uniform windows (k_z64_fine), by CLASS =
+    // (grid, interpolator length): on the coarsest grid, where every narrower band lands, a band oversampled >= 8 / 16 / 32 /
+    // 64 times takes 12 / 10 / 8 / 6 taps instead of 16 (classes 2..5; the same error bound, see z64f_ntap).  A class of
+    // fewer than four bands joins the next longer interpolator (class 2 the 16-tap class 0).
     for (int c = 0; c < native::kZ64FineClasses; ++c) t.zf_first[c] = t.zf_count[c] = 0;
     if (p->native_z64_fine) {
       const int64_t M0 = Lf / 64;
@@ -188,6 +188,8 @@ int upload_native_table(qi_plan* p, int kind, int64_t Lf, std::vector<native::Ba
       }
     }
     t.nz64 = (int32_t)z.size();
+    t.h_z64.clear();
+    for (const auto& d : z) t.h_z64.push_back(d.out_band);
     if (!z.empty()) {
       QI_HIP(hipMalloc((void**)&t.d_z64, z.size() * sizeof(native::BandDesc)));
       QI_HIP(hipMemcpy(t.d_z64, z.data(), z.size() * sizeof(native::BandDesc), hipMemcpyHostToDevice));
@@ -227,7 +229,11 @@ int upload_native_table(qi_plan* p, int kind, int64_t Lf, std::vector<native::Ba
     bands.swap(rest);
   }
   t.h_rows.clear();
-  for (const auto& d : bands) t.h_rows.push_back(d.out_band);
+  t.h_row_mode.clear();
+  for (const auto& d : bands) {
+    t.h_rows.push_back(d.out_band);
+    t.h_row_mode.push_back(d.mode == 1 ? 1 : 0);
+  }
   if (bands.empty()) {  // every band is produced by the block / zoom engines: an empty but valid table
     t.Lf = Lf;
     t.ready = true;
@@ -500,7 +506,10 @@ int finish_block_table(qi_plan* p, int kind, int demod, const std::vector<BlockP
       if (group_count[g] == 0) continue;
       const int64_t nblocks = ceil_div(p->n, native::block_valid(wqs[g]));
       if (nblocks > bt.max_blocks) bt.max_blocks = nblocks;
-      for (int32_t q = first; q < (int32_t)list.size(); ++q) il.h_bands.push_back({list[q].out_band, (int32_t)nblocks});
+      for (int32_t q = first; q < (int32_t)list.size(); ++q) {
+        il.h_bands.push_back({list[q].out_band, (int32_t)nblocks});
+        il.h_route.push_back({list[q].out_band, wqs[g], list[q].analytic, list[q].narrow, list[q].nowrap});
+      }
     }
     std::vector<native::BlockItem> items;
     for (int g = 0; g < NG; ++g) {

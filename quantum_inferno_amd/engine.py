@@ -169,7 +169,9 @@ class TfrPlan:
         esz = 16 if _real_dtype(dtype) == torch.float64 else 8
         length = 2 * n if (n & (n - 1)) == 0 else 1 << (2 * n - 2).bit_length()
         nblk = -(-n // _EPI_SPAN)
-        per_chan = (n_bands + 1) * length * esz + n_bands * nblk * 32 + 4096
+        # (a record's spectrum and one row per band; the native engines need the spectrum, one more row -- the staging slot
+        # of their forward transform -- and the coarse planes of the zoom bands, which a table of ONE band would not leave)
+        per_chan = (max(n_bands, 2) + 1) * length * esz + n_bands * nblk * 32 + 4096
         build = min(n_bands, 16) * length * 16
         need = max(per_chan * channels, build, 1 << 24)
         return int(min(max(need, per_chan), max(cap_bytes, per_chan)))
@@ -198,12 +200,18 @@ class TfrPlan:
         f_hz = scales.log_frequency_hz_from_fft_points(fs, self.n, order)
         idx = scales.stx_shift_indices(f_hz, self.n, fs)
         sigma = scales.cycles_from_order(order) / (2 * np.pi * f_hz / fs)
-        ia, ip = _lib.iarr(idx)
-        sa, sp = _lib.darr(sigma)
-        _lib.check(self._lib.qi_plan_set_stx_bands(self._handle, len(ia), ip, sp))
-        self.freq[_lib.QI_TABLE_STX] = f_hz
-        self.stx_index = idx
+        self.set_stx_table(f_hz, idx, sigma)
         return f_hz
+
+    def set_stx_table(self, f_hz, shift_index, sigma):
+        """Any Stockwell band table (qi_plan_set_stx_bands): shift index and Gaussian width in samples per band."""
+        ia, ip = _lib.iarr(shift_index)
+        sa, sp = _lib.darr(sigma)
+        if len(ia) != len(sa):
+            raise ValueError("shift_index and sigma must have one entry per band")
+        _lib.check(self._lib.qi_plan_set_stx_bands(self._handle, len(ia), ip, sp))
+        self.freq[_lib.QI_TABLE_STX] = np.asarray(f_hz)
+        self.stx_index = ia
 
     # -- transforms ---------------------------------------------------------------------------
     # -- measurement --------------------------------------------------------------------------
@@ -224,6 +232,13 @@ class TfrPlan:
         """Bands (over the styx, atoms and Stockwell tables) whose coefficients the kernels of `stage` produce."""
         k = _lib.STAGES.index(stage)
         return [int(self._lib.qi_plan_stage_bands(self._handle, which, k)) for which in (0, 1, 2)]
+
+    def band_route(self, which, band, records=1):
+        """(stage name, cls, run_cls, flags) of the kernels that produce row `band` of table `which` in a call of
+        `records` records (qi_plan_band_route; the flag bits are _lib.ROUTE_*)."""
+        r = _lib.BandRoute()
+        _lib.check(self._lib.qi_plan_band_route(self._handle, which, int(band), int(records), C.byref(r)))
+        return _lib.STAGES[r.stage], r.cls, r.run_cls, r.flags
 
     def profile_read(self):
         """{stage name: (total ms, launches)} since the last read (qi_plan_profile_read)."""

@@ -6,7 +6,7 @@ regenerated in registers, one inverse FFT per band.
 import numpy as np
 import torch
 
-from . import _lib, engine
+from . import engine
 from . import scales_dyadic as scales
 from .utilities.rescaling import is_power_of_two
 
@@ -49,11 +49,10 @@ def sig_pad_up_to_pow2(sig_wf: np.ndarray, n_fft: int, verbosity: bool = False):
     return sig_wf, int(n_fft), zero_pad
 
 
-def tfr_stx_fft(
-    sig_wf: np.ndarray,
+def stx_general_table(
+    n_fft: int,
     time_sample_interval: float,
     scale_order_input: float = 8.0,
-    n_fft_in: int = None,
     frequency_min: float = None,
     frequency_max: float = None,
     frequency_step: float = None,
@@ -65,18 +64,15 @@ def tfr_stx_fft(
     scale_base_input: float = scales.Slice.G3,
     scale_ref_input: float = scales.Slice.T1S,
 ):
-    """General Stockwell transform: linear, geometric or inferno-standard bands, sigma tuned by q, p, r
-    (ref styx_stx.py:52-192).  Band selection and the shift indices are computed on the host exactly as upstream;
-    the transform is the same GPU path as stx_complex_any_scale_pow2 with this band table.
+    """The band table of tfr_stx_fft for records of n_fft points, on the host in float64 exactly as upstream selects it
+    (ref styx_stx.py:97-181): linear, geometric or inferno-standard bands, sigma tuned by q, p, r.
 
-    :return: tfr_stx [B x n], psd_stx = |tfr|^2 + eps [B x n], frequency_stx [B], frequency_stx_fft [B] (the bins the
-             bands were snapped to), windows_fft [B x n_fft] complex128 (the Gaussian windows)
+    :return: frequency_stx [B], shift_index [B] (int64, the FFT bins the bands were snapped to), sigma [B] (samples),
+             frequency_stx_fft [B], omega_fft [n_fft]
     """
     fs: float = 1 / time_sample_interval
     cycles_m: float = 12.0 / 5.0 * scale_order_input
     lin_fft_decimate: float = 2.0
-    sig_pow2, n_fft, zero_pad = sig_pad_up_to_pow2(sig_wf, n_fft_in)
-    n_out = n_fft - zero_pad
     frequency_fft = np.fft.fftfreq(n_fft, time_sample_interval)
     omega_fft = 2 * np.pi * frequency_fft / fs
     frequency_min_nth = cycles_m / (n_fft / fs)
@@ -108,16 +104,45 @@ def tfr_stx_fft(
         # upstream takes len() of an int here (styx_stx.py:173) and raises TypeError
         raise ValueError("tfr_stx_fft: a band snapped to the zero-frequency bin; raise frequency_min")
     sigma = cycles_m / omega_sx * ((1 + factor_q * (omega_sx ** power_p)) * (omega_sx ** (1 - power_r)))
+    return frequency_stx, idx % n_fft, sigma, frequency_stx_fft, omega_fft
+
+
+def tfr_stx_fft(
+    sig_wf: np.ndarray,
+    time_sample_interval: float,
+    scale_order_input: float = 8.0,
+    n_fft_in: int = None,
+    frequency_min: float = None,
+    frequency_max: float = None,
+    frequency_step: float = None,
+    factor_q: float = 0.0,
+    power_p: float = 0.0,
+    power_r: float = 1.0,
+    is_geometric: bool = False,
+    is_inferno: bool = False,
+    scale_base_input: float = scales.Slice.G3,
+    scale_ref_input: float = scales.Slice.T1S,
+):
+    """General Stockwell transform: linear, geometric or inferno-standard bands, sigma tuned by q, p, r
+    (ref styx_stx.py:52-192).  Band selection and the shift indices are computed on the host exactly as upstream
+    (stx_general_table); the transform is the same GPU path as stx_complex_any_scale_pow2 with this band table.
+
+    :return: tfr_stx [B x n], psd_stx = |tfr|^2 + eps [B x n], frequency_stx [B], frequency_stx_fft [B] (the bins the
+             bands were snapped to), windows_fft [B x n_fft] complex128 (the Gaussian windows)
+    """
+    sig_pow2, n_fft, zero_pad = sig_pad_up_to_pow2(sig_wf, n_fft_in)
+    n_out = n_fft - zero_pad
+    frequency_stx, idx, sigma, frequency_stx_fft, omega_fft = stx_general_table(
+        n_fft, time_sample_interval, scale_order_input, frequency_min, frequency_max, frequency_step, factor_q, power_p,
+        power_r, is_geometric, is_inferno, scale_base_input, scale_ref_input)
+    n_b = len(frequency_stx)
 
     sig, was_numpy, was_1d = engine.as_signal(sig_pow2)
     if not was_1d:
         raise ValueError("tfr_stx_fft takes one record")
     plan = engine.TfrPlan(n_fft, sig.dtype, sig.device, engine.TfrPlan.workspace_for(n_fft, n_b, sig.dtype))
     try:
-        ia, ip = _lib.iarr(idx % n_fft)
-        sa, sp = _lib.darr(sigma)
-        _lib.check(plan._lib.qi_plan_set_stx_bands(plan._handle, n_b, ip, sp))
-        plan.freq[_lib.QI_TABLE_STX] = frequency_stx
+        plan.set_stx_table(frequency_stx, idx, sigma)
         tfr = plan.stx(sig, coef=True).coef[0, :, :n_out].contiguous()
     finally:
         plan.close()

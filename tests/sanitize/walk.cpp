@@ -2,7 +2,8 @@
 // compiled for the HOST ONLY under AddressSanitizer + UndefinedBehaviorSanitizer and linked with a stand-in HIP runtime
 // (fake_hip.cpp: kernels do not run, device memory is host memory), are driven through the C ABI over every
 //   order 1 .. 12  x  record length 2^14 .. 2^22  x  float32 / float64  x  1 / 4 / 16 / 64 records
-// with the band tables the Python host code makes (gen_tables.py) and the scratch TfrPlan.workspace_for sizes for that batch:
+// with the band tables the Python host code makes (gen_tables.py) and the scratch TfrPlan.workspace_for sizes for that batch,
+// and behind them over the synthetic tables of tests/band_tables.py (not constant-Q; 1 / 4 / 16 records):
 // plan build (band assignment, zoom classes, block item lists, split bands), qi_cwt_stx / qi_cwt / qi_stx with several output
 // sets -- panels, bits, full and band-only reductions -- (scratch carving, tiles, joint launches, launch geometry).  Checked on the way:
 //   * every scratch region a run carves lies inside the workspace and no two live regions overlap (QI_LAYOUT_* hooks in
@@ -10,8 +11,14 @@
 //   * every table upload stays inside its allocation (AddressSanitizer on the malloc'ed "device" tables);
 //   * the block engine's work-item lists: each band's blocks cover the record exactly once, planes and statistics slots are
 //     in range and unique, the joint list of qi_cwt_stx holds every item of both tables exactly once;
+//   * qi_plan_band_route names exactly one producer for every row of every table, and the producers sum to the band count;
+//   * a synthetic table comes out as gen_tables.py says it must (every row on the native engines / the whole table on hipFFT);
+//   * degenerate band parameters (sigma or p_re of 0, negative, NaN, inf; NaN omega; a shift index outside [0, n)) are refused
+//     with QI_ERR_ARG and a message, and leave the plan's previous table in use;
 //   * launch geometry (fake hipLaunchKernel), signed overflow / shifts / misaligned access in the host arithmetic (UBSan).
 // Test infrastructure: built and run by tests/test_host_sanitize.py on the CPU container; never part of libqi_tfr.so.
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,7 +33,7 @@ extern "C" size_t qi_layout_regions_checked();
 namespace {
 
 struct Config {
-  int32_t order, log2n, dtype, B;
+  int32_t order, log2n, dtype, B, B2, flags;  // B: Gabor table, B2: Stockwell table
   std::vector<int64_t> records, ws;
   std::vector<double> p_re, p_im, omega, amp, sigma;
   std::vector<int64_t> idx;
@@ -45,22 +52,24 @@ std::vector<Config> read_tables(const char* path) {
     exit(2);
   }
   int32_t head[4];
-  if (fread(head, 4, 4, f) != 4 || head[0] != 0x51495354) exit(2);
+  if (fread(head, 4, 4, f) != 4 || head[0] != 0x51495354 || head[3] != 2) exit(2);
   std::vector<Config> out((size_t)head[1]);
   for (auto& c : out) {
-    int32_t h[4];
-    if (fread(h, 4, 4, f) != 4) exit(2);
-    c.order = h[0], c.log2n = h[1], c.dtype = h[2], c.B = h[3];
+    int32_t h[6];
+    if (fread(h, 4, 6, f) != 6) exit(2);
+    c.order = h[0], c.log2n = h[1], c.dtype = h[2], c.B = h[3], c.B2 = h[4], c.flags = h[5];
     c.records.resize((size_t)head[2]);
     c.ws.resize((size_t)head[2]);
     if (fread(c.records.data(), 8, c.records.size(), f) != c.records.size()) exit(2);
     if (fread(c.ws.data(), 8, c.ws.size(), f) != c.ws.size()) exit(2);
-    for (auto* v : {&c.p_re, &c.p_im, &c.omega, &c.amp, &c.sigma}) {
+    for (auto* v : {&c.p_re, &c.p_im, &c.omega, &c.amp}) {
       v->resize((size_t)c.B);
       if (fread(v->data(), 8, (size_t)c.B, f) != (size_t)c.B) exit(2);
     }
-    c.idx.resize((size_t)c.B);
-    if (fread(c.idx.data(), 8, (size_t)c.B, f) != (size_t)c.B) exit(2);
+    c.sigma.resize((size_t)c.B2);
+    c.idx.resize((size_t)c.B2);
+    if (fread(c.sigma.data(), 8, (size_t)c.B2, f) != (size_t)c.B2) exit(2);
+    if (fread(c.idx.data(), 8, (size_t)c.B2, f) != (size_t)c.B2) exit(2);
   }
   fclose(f);
   return out;
@@ -139,6 +148,95 @@ void check_dual_items(const qi_plan* p, int cut, const Config& c) {
   if (!want0.empty() || !want2.empty()) die("joint items: items of a table missing from the joint list", c, 0);
 }
 
+// qi_plan_band_route: one producer per row (it returns QI_ERR_STATE otherwise), and per stage as many rows as
+// qi_plan_stage_bands counts; written to `dump` when the caller wants the routes
+void check_routes(const qi_plan* p, int which, int64_t C, const Config& c, FILE* dump, size_t ci) {
+  const int64_t B = qi_plan_bands(p, which);
+  int64_t per_stage[QI_STAGE_COUNT] = {};
+  for (int64_t j = 0; j < B; ++j) {
+    qi_band_route r{};
+    if (qi_plan_band_route(p, which, (int32_t)j, C, &r) != QI_OK) die("qi_plan_band_route", c, C);
+    if (r.stage != QI_STAGE_ZOOM && r.stage != QI_STAGE_BLOCK && r.stage != QI_STAGE_PASS2 && r.stage != QI_STAGE_INVERSE)
+      die("band route: not a producing stage", c, C);
+    per_stage[r.stage] += 1;
+    if (dump)
+      fprintf(dump, "%zu %d %d %lld %d %lld %d %d %d %d\n", ci, c.log2n, c.dtype, (long long)C, which, (long long)j, r.stage, r.cls,
+              r.run_cls, r.flags);
+  }
+  int64_t sum = 0;
+  for (int s : {(int)QI_STAGE_ZOOM, (int)QI_STAGE_BLOCK, (int)QI_STAGE_PASS2, (int)QI_STAGE_INVERSE}) {
+    if (per_stage[s] != qi_plan_stage_bands(p, which, s)) die("band route: rows per stage differ from qi_plan_stage_bands", c, C);
+    sum += per_stage[s];
+  }
+  if (sum != B) die("band route: the producers do not sum to the band count", c, C);
+}
+
+// what gen_tables.py says a synthetic table must come out as: 1 every row on the native engines, 2 the whole table on hipFFT
+void check_expectation(const qi_plan* p, int which, int expect, const Config& c, int64_t C) {
+  const int64_t B = qi_plan_bands(p, which), inv = qi_plan_stage_bands(p, which, QI_STAGE_INVERSE);
+  if (expect == 1 && inv != 0) die("synthetic table: rows on the hipFFT engine where none were expected", c, C);
+  if (expect == 2 && inv != B) die("synthetic table: expected the whole table on the hipFFT engine", c, C);
+}
+
+// Degenerate band parameters: refused with QI_ERR_ARG and a message; the plan's previous tables stay in use.
+size_t check_degenerate(const Config& c) {
+  const int64_t n = (int64_t)1 << c.log2n;
+  size_t refused = 0;
+  qi_plan_desc desc{};
+  desc.n = n;
+  desc.dtype = c.dtype;
+  desc.engine = QI_ENGINE_AUTO;
+  desc.workspace_bytes = c.ws[0];
+  qi_plan* p = nullptr;
+  if (qi_plan_create(&p, &desc) != QI_OK) die("qi_plan_create", c, 1);
+  if (qi_plan_set_gabor_bank(p, QI_BANK_STYX, c.B, c.p_re.data(), c.p_im.data(), c.omega.data(), c.amp.data(), nullptr) != QI_OK ||
+      qi_plan_set_stx_bands(p, c.B2, c.idx.data(), c.sigma.data()) != QI_OK)
+    die("degenerate parameters: the good tables", c, 1);
+  const size_t rsz = c.dtype ? 8 : 4;
+  void *sig = nullptr, *red = nullptr;
+  const size_t Bm = (size_t)std::max(c.B, c.B2);
+  if (hipMalloc(&sig, (size_t)n * rsz) != hipSuccess || hipMalloc(&red, (Bm + 4) * 8 + (size_t)n * rsz) != hipSuccess) die("caller buffers", c, 1);
+  qi_tfr_out o{};
+  o.power_time = red;
+  o.power_band = static_cast<char*>(red) + (size_t)n * rsz;
+  o.stats = static_cast<char*>(red) + (size_t)n * rsz + Bm * 8;
+  auto still_usable = [&]() {
+    if (qi_plan_bands(p, 0) != c.B || qi_plan_bands(p, 2) != c.B2) die("degenerate parameters: the previous table is gone", c, 1);
+    if (qi_cwt(p, QI_BANK_STYX, sig, 1, &o, nullptr) != QI_OK || qi_stx(p, sig, 1, &o, nullptr) != QI_OK)
+      die("degenerate parameters: the previous table no longer runs", c, 1);
+  };
+  auto refuse = [&](int rc, const char* what) {
+    if (rc != QI_ERR_ARG || !qi_last_error() || !qi_last_error()[0]) die(what, c, 1);
+    ++refused;
+    still_usable();
+  };
+  const double nan = std::nan(""), inf = HUGE_VAL;
+  for (double bad : {0.0, -1.0, nan, inf, -inf}) {
+    std::vector<double> sg = c.sigma;
+    sg[sg.size() / 2] = bad;
+    refuse(qi_plan_set_stx_bands(p, c.B2, c.idx.data(), sg.data()), "a degenerate sigma was not refused");
+    std::vector<double> pr = c.p_re;
+    pr[pr.size() / 2] = bad;
+    refuse(qi_plan_set_gabor_bank(p, QI_BANK_STYX, c.B, pr.data(), c.p_im.data(), c.omega.data(), c.amp.data(), nullptr),
+           "a degenerate p_re was not refused");
+  }
+  for (int which = 0; which < 3; ++which) {  // NaN p_im / omega / amp
+    std::vector<double> v[3] = {c.p_im, c.omega, c.amp};
+    v[which][0] = nan;
+    refuse(qi_plan_set_gabor_bank(p, QI_BANK_STYX, c.B, c.p_re.data(), v[0].data(), v[1].data(), v[2].data(), nullptr),
+           "a NaN atom parameter was not refused");
+  }
+  for (int64_t bad : {(int64_t)-1, n, n + 5, (int64_t)1 << 40}) {
+    std::vector<int64_t> ix = c.idx;
+    ix.back() = bad;
+    refuse(qi_plan_set_stx_bands(p, c.B2, ix.data(), c.sigma.data()), "a shift index outside [0, n) was not refused");
+  }
+  (void)hipFree(sig);
+  (void)hipFree(red);
+  if (qi_plan_destroy(p) != QI_OK) die("qi_plan_destroy", c, 1);
+  return refused;
+}
+
 void check_tables(const qi_plan* p, const Config& c) {
   for (int kind : {0, 2}) {
     const auto& t = p->nat[kind];
@@ -160,18 +258,20 @@ void check_tables(const qi_plan* p, const Config& c) {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: walk tables.bin [max configs]\n");
+    fprintf(stderr, "usage: walk tables.bin [max configs (0: all)] [file to write every band's route to: config, log2n, dtype, records, table, band, stage, cls, run_cls, flags]\n");
     return 2;
   }
   const auto configs = read_tables(argv[1]);
-  const size_t limit = argc > 2 ? (size_t)atoll(argv[2]) : configs.size();
-  size_t plans = 0, calls = 0, native = 0;
+  const size_t limit = argc > 2 && atoll(argv[2]) > 0 ? (size_t)atoll(argv[2]) : configs.size();
+  FILE* dump = argc > 3 ? fopen(argv[3], "w") : nullptr;
+  size_t plans = 0, calls = 0, native = 0, syn_plans = 0, syn_native = 0, refused = 0;
   for (size_t ci = 0; ci < configs.size() && ci < limit; ++ci) {
     const Config& c = configs[ci];
     const int64_t n = (int64_t)1 << c.log2n;
     const size_t rsz = c.dtype ? 8 : 4;
     for (size_t r = 0; r < c.records.size(); ++r) {
       const int64_t C = c.records[r];
+      if (C <= 0) continue;  // (a slot this config does not use)
       qi_plan_desc desc{};
       desc.n = n;
       desc.dtype = c.dtype;
@@ -182,16 +282,25 @@ int main(int argc, char** argv) {
       if (qi_plan_create(&p, &desc) != QI_OK) die("qi_plan_create", c, C);
       if (qi_plan_set_gabor_bank(p, QI_BANK_STYX, c.B, c.p_re.data(), c.p_im.data(), c.omega.data(), c.amp.data(), nullptr) != QI_OK)
         die("qi_plan_set_gabor_bank", c, C);
-      if (qi_plan_set_stx_bands(p, c.B, c.idx.data(), c.sigma.data()) != QI_OK) die("qi_plan_set_stx_bands", c, C);
+      if (qi_plan_set_stx_bands(p, c.B2, c.idx.data(), c.sigma.data()) != QI_OK) die("qi_plan_set_stx_bands", c, C);
       ++plans;
       native += p->nat[0].ready && p->nat[2].ready;
+      if (c.order == 0) {
+        ++syn_plans;
+        syn_native += p->nat[0].ready && p->nat[2].ready;
+        check_expectation(p, 0, c.flags & 3, c, C);
+        check_expectation(p, 2, (c.flags >> 2) & 3, c, C);
+      }
       check_tables(p, c);
+      check_routes(p, 0, C, c, dump, ci);
+      check_routes(p, 2, C, c, dump, ci);
       // caller buffers: records, panels (address-space reservations), reduced products
       void *sig = nullptr, *coef0 = nullptr, *coef2 = nullptr, *bits = nullptr, *red = nullptr;
-      const size_t panel = (size_t)C * c.B * n;
+      const size_t Bm = (size_t)std::max(c.B, c.B2);  // (caller buffers sized for the larger of the two tables)
+      const size_t panel = (size_t)C * Bm * n;
       if (hipMalloc(&sig, (size_t)C * n * rsz) != hipSuccess || hipMalloc(&coef0, panel * 2 * rsz) != hipSuccess ||
           hipMalloc(&coef2, panel * 2 * rsz) != hipSuccess || hipMalloc(&bits, panel * rsz) != hipSuccess ||
-          hipMalloc(&red, 2 * ((size_t)C * (c.B + 4) * 8 + (size_t)C * n * rsz)) != hipSuccess)
+          hipMalloc(&red, 2 * ((size_t)C * (Bm + 4) * 8 + (size_t)C * n * rsz)) != hipSuccess)
         die("caller buffers", c, C);
       char* rp = static_cast<char*>(red);
       auto outs = [&](void* coef, void* b, bool reductions, int which) {
@@ -199,10 +308,10 @@ int main(int argc, char** argv) {
         o.coef = coef;
         o.bits = b;
         if (reductions) {
-          char* base = rp + (size_t)which * ((size_t)C * (c.B + 4) * 8 + (size_t)C * n * rsz);
+          char* base = rp + (size_t)which * ((size_t)C * (Bm + 4) * 8 + (size_t)C * n * rsz);
           o.power_time = base;
           o.power_band = base + (size_t)C * n * rsz;
-          o.stats = base + (size_t)C * n * rsz + (size_t)C * c.B * 8;
+          o.stats = base + (size_t)C * n * rsz + (size_t)C * Bm * 8;
         }
         return o;
       };
@@ -224,9 +333,11 @@ int main(int argc, char** argv) {
         if (qi_stx(p, sig, C, &b2, nullptr) != QI_OK) die("qi_stx (band-only reductions)", c, C);
         calls += 3;
       }
-      if (C == 4 && c.order == 3) {  // the atoms bank (cwt_atoms: circular kind) on a few shapes, then the plan's tables again
+      if ((C == 4 && c.order == 3) || (c.flags & 16)) {  // the atoms bank (cwt_atoms: circular kind) on a few shapes, then the plan's tables again
         if (qi_plan_set_gabor_bank(p, QI_BANK_ATOMS, c.B, c.p_re.data(), c.p_im.data(), c.omega.data(), c.amp.data(), nullptr) != QI_OK)
           die("qi_plan_set_gabor_bank (atoms)", c, C);
+        if (c.order == 0) check_expectation(p, 1, c.flags & 3, c, C);
+        check_routes(p, 1, C, c, dump, ci);
         if (qi_cwt(p, QI_BANK_ATOMS, sig, C, &full, nullptr) != QI_OK) die("qi_cwt (atoms bank)", c, C);
         ++calls;
       }
@@ -234,8 +345,11 @@ int main(int argc, char** argv) {
       if (qi_plan_destroy(p) != QI_OK) die("qi_plan_destroy", c, C);
     }
     if ((ci & 15) == 15) fprintf(stderr, "walk: %zu of %zu tables done\n", ci + 1, configs.size());
+    if (c.order == 0 && (c.flags & 15) == 5) refused += check_degenerate(c);  // (on the synthetic tables that are native on both sides)
   }
-  printf("{\"ok\": true, \"plans\": %zu, \"plans_on_native_engines\": %zu, \"calls\": %zu, \"kernel_launches\": %zu, \"scratch_regions_checked\": %zu}\n",
-         plans, native, calls, qi_fake_hip_launches(), qi_layout_regions_checked());
+  if (dump) fclose(dump);
+  printf("{\"ok\": true, \"plans\": %zu, \"plans_on_native_engines\": %zu, \"calls\": %zu, \"kernel_launches\": %zu, \"scratch_regions_checked\": %zu, \"synthetic_plans\": %zu, "
+         "\"synthetic_on_native\": %zu, \"degenerate_tables_refused\": %zu}\n",
+         plans, native, calls, qi_fake_hip_launches(), qi_layout_regions_checked(), syn_plans, syn_native, refused);
   return 0;
 }

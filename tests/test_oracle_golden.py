@@ -323,3 +323,154 @@ def test_round3_fixtures_rows(golden, name, log2n, order, dtype, channel, transf
         ref = g[f"{name_t}_rows_o{order}"][pick]
         assert np.max(np.abs(panel[:, tsel] - ref)) <= 1e-12 * np.abs(ref).max()
         assert np.allclose((np.abs(panel) ** 2).sum(axis=1), g[f"{name_t}_psum_band_o{order}"][pick], rtol=1e-11)
+
+
+# ---- the table-driven oracle (gabor_table_fft / stx_table_fft: include/qi_tfr.h's own definition) -----------------------
+def _styx_tables(order, n, fs):
+    f = orc.band_table(fs, n, order)
+    s, w = orc.scale_omega(order, f, fs)
+    return f, (0.5 / s ** 2, np.zeros_like(s), w, orc.wavelet_amplitude(s)[0])
+
+
+def _chirp_tables(order, n, fs, shift, dict_type="norm"):
+    order_n, f_flipped = orc.chirp_band_table(order, n, fs, shift)
+    f = np.flip(f_flipped)
+    m_q, _, gamma = orc.chirp_mqg_from_n(order_n, shift)
+    s = m_q * fs / f / (2.0 * np.pi)
+    p = (1 - 1j * shift * gamma / np.pi) / (2 * s ** 2)
+    amp = 1 / np.pi ** 0.25 / np.sqrt(s) if dict_type == "norm" else np.sqrt(np.abs(p) / np.pi)
+    return f, (p.real.copy(), p.imag.copy(), m_q / s, amp)
+
+
+def _reference_axis(n, fs):
+    t = np.arange(n) / fs
+    return fs * (t - t[-1] / 2.0)
+
+
+@pytest.mark.parametrize("log2n,order,fs", [(10, 3, 1000.0), (13, 12, 800.0), (16, 12, 1000.0), (20, 3, 800.0)])
+def test_stx_table_oracle_equals_order_n_oracle_bit_for_bit(log2n, order, fs):
+    """stx_table_fft given the dyadic table (and the reference's bin-frequency rounding, fs) IS stx_fft; with the exact
+    bin frequencies (fs = 1) it differs by that rounding only (measured 2.4e-16 of the panel maximum at n = 1024)."""
+    n = 1 << log2n
+    sig = orc.synth_chirp(n, fs, dtype=np.float64) + 0.25 * np.random.default_rng(log2n).standard_normal(n)
+    f = orc.band_table(fs, n, order)
+    idx = orc.stx_indices(f, n, fs)
+    sigma = orc.cycles_from_order(order) / (2 * np.pi * f / fs)
+    pick = sorted({0, 1, len(f) // 2, len(f) - 2, len(f) - 1}) if log2n > 13 else list(range(len(f)))
+    want = orc.stx_fft(order, sig, fs, bands=pick)[2]
+    assert np.array_equal(orc.stx_table_fft(sig, idx, sigma, bands=pick, fs=fs), want)
+    assert relmax(orc.stx_table_fft(sig, idx, sigma, bands=pick), want) <= 1e-14
+
+
+# twice the re-measured differences below (the docstring of the test has the measurements)
+AXIS_PANEL = {(16, 12, 1000.0): 2 * 8.63e-13, (20, 3, 800.0): 2 * 6.50e-12, (20, 12, 1000.0): 2 * 7.96e-12}
+AXIS_ROW = 2 * 3.05e-10
+
+
+@pytest.mark.parametrize("log2n,order,fs", sorted(AXIS_PANEL))
+def test_gabor_table_oracle_against_order_n_oracles(log2n, order, fs):
+    """gabor_table_fft (exact axis x_k = k - (n - 1) / 2) against cwt_fft, cwt_chirp_fft and cwt_chirp_conv, whose atoms
+    sit on the reference's axis fs (t - t[-1] / 2): they differ by the rounding of that axis (a phase error that grows
+    with omega and n), and by nothing else -- handed the reference's axis (x=) the table oracle is the order-N oracle
+    bit for bit, which is asserted first.  Record: chirp + 0.25 noise; bands {0, 1, B/2, B-2, B-1}.
+
+    Re-measured here (panel = max |diff| / panel max, row = worst max |diff| / row max):
+      cwt_fft        2^16 o12 fs1000: panel 8.63e-13, row 1.60e-11;  2^20 o3 fs800: panel 6.50e-12, row 1.03e-10;
+                     2^20 o12 fs1000: panel 7.96e-12, row 3.05e-10
+      cwt_chirp_fft and cwt_chirp_conv (index_shift 1), 2^16 o12 fs1000: panel 1.24e-12, row 2.42e-11
+    (the test prints them again before it asserts).  The bounds are twice the styx panel figure of each shape
+    (AXIS_PANEL) and twice the worst row of all (AXIS_ROW)."""
+    n = 1 << log2n
+    sig = orc.synth_chirp(n, fs, dtype=np.float64) + 0.25 * np.random.default_rng(1).standard_normal(n)
+    xr = _reference_axis(n, fs)
+    f, tabs = _styx_tables(order, n, fs)
+    pick = sorted({0, 1, len(f) // 2, len(f) - 2, len(f) - 1})
+    cases = [("cwt_fft", orc.cwt_fft(order, sig, fs, bands=pick)[2], tabs, False)]
+    fc, ctabs = _chirp_tables(order, n, fs, 1.0)
+    pc = sorted({0, 1, len(fc) // 2, len(fc) - 2, len(fc) - 1})
+    if log2n == 16:  # (the chirped atoms once: the axis rounding is the same mechanism)
+        cases.append(("cwt_chirp_fft", orc.cwt_chirp_fft(sig, fs, order, index_shift=1.0, bands=pc)[0], ctabs, True))
+        cases.append(("cwt_chirp_conv", orc.cwt_chirp_conv(sig, fs, order, index_shift=1.0, bands=pc)[0], ctabs, False))
+    for name, want, tb, circular in cases:
+        rows = pick if tb is tabs else pc
+        same = orc.gabor_table_fft(sig, *tb, bands=rows, circular=circular, x=xr)
+        # (the same expression up to the association of the products: rounding of one atom sample)
+        assert relmax(same, want) <= 1e-14, name
+        got = orc.gabor_table_fft(sig, *tb, bands=rows, circular=circular)
+        panel = relmax(got, want)
+        row = float((np.abs(got - want).max(axis=1) / np.abs(want).max(axis=1)).max())
+        print(f"MEASURED {name} 2^{log2n} o{order} fs{fs:g}: panel {panel:.2e} row {row:.2e}")
+        assert panel <= AXIS_PANEL[(log2n, order, fs)], (name, panel)
+        assert row <= AXIS_ROW, (name, row)
+
+
+@pytest.mark.parametrize("key,order,fs", [("o3_fs1000", 3, 1000.0), ("o12_fs800", 12, 800.0)])
+def test_table_oracles_reproduce_the_small_fixtures(golden, key, order, fs):
+    """At n = 1024 both table-driven functions reproduce the reference's own panels at the tolerances the order-N oracle
+    is held to (cwt 1e-14, stx 1e-14, cwt_atoms 1e-11) -- the Gabor kinds on the reference's time axis (x=); on the exact
+    axis the styx panel moves by the axis rounding (measured 5.0e-14 / 7.7e-14 of the panel maximum: asserted at 2e-13)."""
+    g = golden("small_n1024.npz")
+    sig = g[f"sig_{key}"]
+    n = len(sig)
+    xr = _reference_axis(n, fs)
+    f, tabs = _styx_tables(order, n, fs)
+    assert np.array_equal(f, g[f"f_{key}"])
+    assert relmax(orc.gabor_table_fft(sig, *tabs, x=xr), g[f"cwt_norm_{key}"]) < 1e-14
+    assert relmax(orc.gabor_table_fft(sig, *tabs), g[f"cwt_norm_{key}"]) < 2e-13
+    idx = orc.stx_indices(f, n, fs)
+    sigma = orc.cycles_from_order(order) / (2 * np.pi * f / fs)
+    assert relmax(orc.stx_table_fft(sig, idx, sigma, fs=fs), g[f"stx_{key}"]) < 1e-14
+    assert relmax(orc.stx_table_fft(sig, idx, sigma), g[f"stx_{key}"]) < 1e-14
+    fc, ctabs = _chirp_tables(order, n, fs, 0.0)
+    assert np.array_equal(fc, g[f"chirp_f_{key}"])
+    assert relmax(orc.gabor_table_fft(sig, *ctabs, circular=True, x=xr), g[f"chirp_cwt_{key}"]) < 1e-11
+    assert relmax(orc.gabor_table_fft(sig, *ctabs, circular=True), g[f"chirp_cwt_{key}"]) < 1e-11
+    if order == 3:
+        assert relmax(orc.gabor_table_fft(sig, *ctabs, x=xr), g[f"chirp_cwt_conv_{key}"]) < 1e-12
+
+
+@pytest.mark.parametrize("name", sorted(CASES_STX_GENERAL))
+def test_stx_table_oracle_reproduces_the_general_fixture(golden, name):
+    """stx_table_fft with tfr_stx_fft's table (styx_stx.stx_general_table: linear, geometric, inferno, q/p/r-tuned widths)
+    against the reference's own general Stockwell panels, at the tolerance stx_general is held to."""
+    from quantum_inferno_amd import styx_stx
+
+    g = golden("stx_general_n1024.npz")
+    c = CASES_STX_GENERAL[name]
+    f, idx, sigma, f_fft, _ = styx_stx.stx_general_table(
+        1024, 1 / 1000.0, c.get("order", 8.0), c.get("f_min"), c.get("f_max"), c.get("f_step"), c.get("q", 0.0),
+        c.get("p", 0.0), c.get("r", 1.0), c.get("geometric", False), c.get("inferno", False))
+    assert np.array_equal(f, g[f"{name}_f"]) and np.array_equal(f_fft, g[f"{name}_ffft"])
+    assert relmax(orc.stx_table_fft(g["sig"], idx, sigma, fs=1000.0), g[f"{name}_tfr"]) < 1e-14
+
+
+CASES_STX_GENERAL_LARGE = dict(
+    CASES_STX_GENERAL,
+    const_width=dict(f_min=5.0, f_max=495.0, f_step=10.0, r=0.0),
+    q2p1=dict(f_min=2.0, f_max=480.0, f_step=6.0, q=2.0, p=1.0),
+    short_windows=dict(order=2.0, f_min=100.0, f_max=480.0, f_step=20.0),
+)
+
+
+@pytest.mark.parametrize("name", sorted(CASES_STX_GENERAL_LARGE))
+def test_stx_general_at_65536_samples(golden, name):
+    """orc.stx_general and stx_table_fft (with styx_stx.stx_general_table's table) against the reference's tfr_stx_fft at
+    n_fft = 2^16: sampled rows at the fixture's sampled times, band powers of every row."""
+    from quantum_inferno_amd import styx_stx
+
+    g = golden("stx_general_n65536.npz")
+    n, fs = 1 << 16, 1000.0
+    sig = orc.synth_chirp(n, fs, dtype=np.float64) + 0.25 * np.random.default_rng(65536).standard_normal(n)
+    assert np.array_equal(sig[:: n // 4096], g["sig_samples"])
+    c = CASES_STX_GENERAL_LARGE[name]
+    tfr, _, f, f_fft, _ = orc.stx_general(sig, 1 / fs, **c)
+    assert np.array_equal(f, g[f"{name}_f"]) and np.array_equal(f_fft, g[f"{name}_ffft"])
+    rows, tsel, ref = g[f"{name}_rowsel"], g["tsel"], g[f"{name}_rows"]
+    assert np.max(np.abs(tfr[rows][:, tsel] - ref)) <= 1e-13 * np.abs(ref).max()
+    assert np.allclose((np.abs(tfr) ** 2).sum(axis=1), g[f"{name}_psum_band"], rtol=1e-11)
+    f2, idx, sigma, f_fft2, _ = styx_stx.stx_general_table(
+        n, 1 / fs, c.get("order", 8.0), c.get("f_min"), c.get("f_max"), c.get("f_step"), c.get("q", 0.0), c.get("p", 0.0),
+        c.get("r", 1.0), c.get("geometric", False), c.get("inferno", False))
+    assert np.array_equal(f2, f) and np.array_equal(f_fft2, f_fft)
+    got = orc.stx_table_fft(sig, idx, sigma, bands=list(rows), fs=fs)
+    assert np.max(np.abs(got[:, tsel] - ref)) <= 1e-13 * np.abs(ref).max()
