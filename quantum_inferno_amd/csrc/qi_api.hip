@@ -157,29 +157,58 @@ int qi_plan_destroy(qi_plan* p) {
   if (p->side) (void)hipStreamDestroy(p->side);
   if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
   if (p->ev_join) (void)hipEventDestroy(p->ev_join);
-  for (auto& per_cut : p->d_band_slots)
-    for (auto* b : per_cut)
-      if (b) (void)hipFree(b);
-  for (auto* w : p->d_z64_w)
-    if (w) (void)hipFree(w);
-  for (auto* w : p->d_z64f_w)
-    if (w) (void)hipFree(w);
-  if (p->d_demod_t1) (void)hipFree(p->d_demod_t1);
-  if (p->d_demod_t2) (void)hipFree(p->d_demod_t2);
-  for (auto& wc : p->d_zoom_w)
-    for (auto* w : wc)
-      if (w) (void)hipFree(w);
-  if (p->d_edge) (void)hipFree(p->d_edge);
-  if (p->split_bank) (void)hipFree(p->split_bank);
-  if (p->d_split_bands) (void)hipFree(p->d_split_bands);
-  for (auto* d : p->d_dual)
-    if (d) (void)hipFree(d);
-  for (int b = 0; b < 2; ++b)
-    if (p->bank[b]) (void)hipFree(p->bank[b]);
-  if (p->d_stx_idx) (void)hipFree(p->d_stx_idx);
-  if (p->d_stx_coef) (void)hipFree(p->d_stx_coef);
-  if (p->ws) (void)hipFree(p->ws);
+  release_styx_extras(p);
+  for (int kind = 0; kind < 3; ++kind) drop_band_slots(p, kind);
+  for (auto*& w : p->d_z64_w) free_device(w);
+  for (auto*& w : p->d_z64f_w) free_device(w);
+  for (auto*& w : p->d_zoom_w) free_device(w);
+  free_device(p->d_demod_t1);
+  free_device(p->d_demod_t2);
+  for (auto*& d : p->d_dual) free_device(d);
+  for (auto*& b : p->bank) free_device(b);
+  free_device(p->d_stx_idx);
+  free_device(p->d_stx_coef);
+  free_device(p->ws);
   delete p;
+  return QI_OK;
+}
+
+// The tables of one Gabor bank: on the native engines when `use_native` and the table allows it, else the atom spectra of the
+// hipFFT engine.
+static int build_gabor_bank(qi_plan* p, int bank, int32_t B, const double* p_re, const double* p_im, const double* omega,
+                            const double* amp, bool use_native, hipStream_t st) {
+  const bool f64 = p->d.dtype == QI_F64;
+  const int64_t L = bank == QI_BANK_ATOMS ? p->n : p->L;
+  std::vector<double> host;
+  DeviceTemp<double> d_par;
+  QI_TRY(upload_atom_params(B, p_re, p_im, omega, amp, &host, &d_par));
+  if (use_native) {
+    QI_TRY(f64 ? build_native_bank<double>(p, bank, B, d_par.ptr, host.data(), st)
+               : build_native_bank<float>(p, bank, B, d_par.ptr, host.data(), st));
+    // The zoom and block engines take any power-of-two record from 2^18 samples; the two-pass kernels run
+    // 2^20 / 2^21-point transforms only.  A table that still has bands for them at another length goes to the hipFFT engine.
+    if (!native_len_ok(L) && !p->nat[bank].h_rows.empty()) {
+      (void)hipStreamSynchronize(st);
+      drop_gabor_tables(p, bank);
+      use_native = false;
+      if (p->d.engine == QI_ENGINE_NATIVE) {
+        set_error("native engine: this band table needs the two-pass kernels, which run 2^20 / 2^21-point transforms only");
+        return QI_ERR_UNSUPPORTED;
+      }
+    }
+  }
+  if (!use_native) {
+    const size_t bytes = (size_t)B * L * (f64 ? sizeof(double2) : sizeof(float2));
+    if (hipMalloc(&p->bank[bank], bytes) != hipSuccess) {
+      set_error("hipMalloc of the %zu-byte atom-spectrum bank failed", bytes);
+      return QI_ERR_NOMEM;
+    }
+    QI_TRY(f64 ? build_bank<double>(p, bank, B, d_par.ptr, st) : build_bank<float>(p, bank, B, d_par.ptr, st));
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    set_error("bank build failed on the device: %s", hipGetErrorString(hipGetLastError()));
+    return QI_ERR_HIP;
+  }
   return QI_OK;
 }
 
@@ -197,85 +226,42 @@ int qi_plan_set_gabor_bank(qi_plan* p, int bank, int32_t B, const double* p_re, 
   DeviceGuard g(p->d.device);
   p->table_gen++;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t L = bank == QI_BANK_ATOMS ? p->n : p->L;
-  const size_t esz = p->d.dtype == QI_F64 ? sizeof(double2) : sizeof(float2);
   if (p->bank[bank]) {
     QI_HIP(hipDeviceSynchronize());
     QI_HIP(hipFree(p->bank[bank]));
     p->bank[bank] = nullptr;
     p->nb[bank] = 0;
   }
-  bool use_native = native_wanted(p, bank);
+  const bool use_native = native_wanted(p, bank);
   if (!use_native && p->d.engine == QI_ENGINE_NATIVE) {
     set_error("native engine does not support this bank at n = %lld", (long long)p->n);
     return QI_ERR_UNSUPPORTED;
   }
-  p->nat[bank].release();
-  if (bank == QI_BANK_STYX) p->blk[0].release();
-  for (auto*& b : p->d_band_slots[bank]) {
-      if (b) (void)hipFree(b);
-    b = nullptr;
-  }
-  double* d_par = nullptr;
-  QI_HIP(hipMalloc((void**)&d_par, (size_t)4 * B * sizeof(double)));
-  std::vector<double> host((size_t)4 * B);
-  memcpy(&host[0], p_re, B * sizeof(double));
-  memcpy(&host[B], p_im, B * sizeof(double));
-  memcpy(&host[2 * B], omega, B * sizeof(double));
-  memcpy(&host[3 * B], amp, B * sizeof(double));
-  int rc = QI_OK;
-  if (hipMemcpy(d_par, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("hipMemcpy of band parameters failed");
-    rc = QI_ERR_HIP;
-  }
-  if (rc == QI_OK && use_native) {
-    rc = p->d.dtype == QI_F64 ? build_native_bank<double>(p, bank, B, d_par, host.data(), st)
-                              : build_native_bank<float>(p, bank, B, d_par, host.data(), st);
-    // The zoom and block engines take any power-of-two record from 2^18 samples; the two-pass kernels run
-    // 2^20 / 2^21-point transforms only.  A table that still has bands for them at another length goes to the hipFFT engine.
-    if (rc == QI_OK && !native_len_ok(L) && !p->nat[bank].h_rows.empty()) {
-      (void)hipStreamSynchronize(st);
-      p->nat[bank].release();
-      if (bank == QI_BANK_STYX) {
-        p->blk[0].release();
-        p->nat[3].release();
-        p->nsplit = 0;
-      }
-      use_native = false;
-      if (p->d.engine == QI_ENGINE_NATIVE) {
-        set_error("native engine: this band table needs the two-pass kernels, which run 2^20 / 2^21-point transforms only");
-        rc = QI_ERR_UNSUPPORTED;
-      }
-    }
-  }
-  if (rc == QI_OK && !use_native) {
-    if (hipMalloc(&p->bank[bank], (size_t)B * L * esz) != hipSuccess) {
-      set_error("hipMalloc of the %zu-byte atom-spectrum bank failed", (size_t)B * L * esz);
-      rc = QI_ERR_NOMEM;
-    } else {
-      rc = p->d.dtype == QI_F64 ? build_bank<double>(p, bank, B, d_par, st) : build_bank<float>(p, bank, B, d_par, st);
-    }
-  }
-  if (rc == QI_OK && hipStreamSynchronize(st) != hipSuccess) {
-    set_error("bank build failed on the device: %s", hipGetErrorString(hipGetLastError()));
-    rc = QI_ERR_HIP;
-  }
-  (void)hipFree(d_par);
+  drop_gabor_tables(p, bank);
+  drop_band_slots(p, bank);
+  const int rc = build_gabor_bank(p, bank, B, p_re, p_im, omega, amp, use_native, st);
   if (rc == QI_OK) {
     p->nb[bank] = B;
-  } else {  // nothing half-built stays behind (a ready table without its block / split producers would leave rows unwritten)
-    p->nat[bank].release();
-    if (bank == QI_BANK_STYX) {
-      p->blk[0].release();
-      p->nat[3].release();
-      p->nsplit = 0;
-    }
-    if (p->bank[bank]) {
-      (void)hipFree(p->bank[bank]);
-      p->bank[bank] = nullptr;
-    }
+  } else {  // nothing half-built stays behind
+    drop_gabor_tables(p, bank);
+    free_device(p->bank[bank]);
   }
   return rc;
+}
+
+// the atoms of a bank as rows of `out`, sampled on the integer grid or at the instants `x` [n]
+static int atoms_rows(int64_t n, int32_t B, const double* p_re, const double* p_im, const double* omega, const double* amp,
+                      const double* x, void* out, hipStream_t st) {
+  std::vector<double> host;
+  DeviceTemp<double> d_par;
+  QI_TRY(upload_atom_params(B, p_re, p_im, omega, amp, &host, &d_par));
+  const double* q = d_par.ptr;
+  QI_TRY(launch_bank_rows((double2*)out, n, n, 1, q, q + B, q + 2 * B, q + 3 * B, 0, B, st, 0.0, x));
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    set_error("atom kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    return QI_ERR_HIP;
+  }
+  return QI_OK;
 }
 
 int qi_gabor_atoms(int device, int64_t n, int32_t B, const double* p_re, const double* p_im, const double* omega,
@@ -283,27 +269,7 @@ int qi_gabor_atoms(int device, int64_t n, int32_t B, const double* p_re, const d
   QI_REQUIRE(p_re && p_im && omega && amp && out, "null argument");
   QI_REQUIRE(n >= 2 && B > 0 && B <= 65535, "bad atom bank shape");
   DeviceGuard g(device);
-  double* d_par = nullptr;
-  QI_HIP(hipMalloc((void**)&d_par, (size_t)4 * B * sizeof(double)));
-  std::vector<double> host((size_t)4 * B);
-  memcpy(&host[0], p_re, B * sizeof(double));
-  memcpy(&host[B], p_im, B * sizeof(double));
-  memcpy(&host[2 * B], omega, B * sizeof(double));
-  memcpy(&host[3 * B], amp, B * sizeof(double));
-  int rc = QI_OK;
-  if (hipMemcpy(d_par, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("hipMemcpy of band parameters failed");
-    rc = QI_ERR_HIP;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (rc == QI_OK)
-    rc = launch_bank_rows((double2*)out, n, n, 1, d_par, d_par + B, d_par + 2 * B, d_par + 3 * B, 0, B, st);
-  if (rc == QI_OK && hipStreamSynchronize(st) != hipSuccess) {
-    set_error("atom kernel failed: %s", hipGetErrorString(hipGetLastError()));
-    rc = QI_ERR_HIP;
-  }
-  (void)hipFree(d_par);
-  return rc;
+  return atoms_rows(n, B, p_re, p_im, omega, amp, nullptr, out, (hipStream_t)stream);
 }
 
 int qi_gabor_atoms_at(int device, int64_t n, int32_t B, const double* p_re, const double* p_im, const double* omega,
@@ -311,28 +277,7 @@ int qi_gabor_atoms_at(int device, int64_t n, int32_t B, const double* p_re, cons
   QI_REQUIRE(p_re && p_im && omega && amp && x && out, "null argument");
   QI_REQUIRE(n >= 1 && B > 0 && B <= 65535, "bad atom bank shape");
   DeviceGuard g(device);
-  double* d_par = nullptr;
-  QI_HIP(hipMalloc((void**)&d_par, (size_t)4 * B * sizeof(double)));
-  std::vector<double> host((size_t)4 * B);
-  memcpy(&host[0], p_re, B * sizeof(double));
-  memcpy(&host[B], p_im, B * sizeof(double));
-  memcpy(&host[2 * B], omega, B * sizeof(double));
-  memcpy(&host[3 * B], amp, B * sizeof(double));
-  int rc = QI_OK;
-  if (hipMemcpy(d_par, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("hipMemcpy of band parameters failed");
-    rc = QI_ERR_HIP;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (rc == QI_OK)
-    rc = launch_bank_rows((double2*)out, n, n, 1, d_par, d_par + B, d_par + 2 * B, d_par + 3 * B, 0, B, st, 0.0,
-                          static_cast<const double*>(x));
-  if (rc == QI_OK && hipStreamSynchronize(st) != hipSuccess) {
-    set_error("atom kernel failed: %s", hipGetErrorString(hipGetLastError()));
-    rc = QI_ERR_HIP;
-  }
-  (void)hipFree(d_par);
-  return rc;
+  return atoms_rows(n, B, p_re, p_im, omega, amp, static_cast<const double*>(x), out, (hipStream_t)stream);
 }
 
 int qi_plan_set_stx_bands(qi_plan* p, int32_t B, const int64_t* shift_index, const double* sigma) {
@@ -357,17 +302,11 @@ int qi_plan_set_stx_bands(qi_plan* p, int32_t B, const int64_t* shift_index, con
   std::vector<double> coef(B);
   const double k = 2.0 * M_PI / (double)p->n * std::sqrt(0.5 * M_LOG2E);
   for (int32_t j = 0; j < B; ++j) coef[j] = sigma[j] * k;
-  QI_HIP(hipMalloc((void**)&p->d_stx_idx, B * sizeof(int64_t)));
-  QI_HIP(hipMalloc((void**)&p->d_stx_coef, B * sizeof(double)));
-  QI_HIP(hipMemcpy(p->d_stx_idx, shift_index, B * sizeof(int64_t), hipMemcpyHostToDevice));
-  QI_HIP(hipMemcpy(p->d_stx_coef, coef.data(), B * sizeof(double), hipMemcpyHostToDevice));
+  QI_TRY(upload_table(&p->d_stx_idx, std::vector<int64_t>(shift_index, shift_index + B)));
+  QI_TRY(upload_table(&p->d_stx_coef, coef));
   p->nb_stx = 0;  // committed below, once every table of the native engine has been built
-  p->nat[2].release();
-  p->blk[2].release();
-  for (auto*& b : p->d_band_slots[2]) {
-      if (b) (void)hipFree(b);
-    b = nullptr;
-  }
+  drop_stx_tables(p);
+  drop_band_slots(p, 2);
   QI_TRY(build_stx_tables(p, B, shift_index, sigma, coef));
   p->nb_stx = B;
   return QI_OK;

@@ -184,6 +184,30 @@ struct Profiler {
   }
 };
 
+// ---- device tables of the host code --------------------------------------------------------------------------------------
+// free a device table and forget it
+template <typename P>
+inline void free_device(P*& ptr) {
+  if (ptr) (void)hipFree(ptr);
+  ptr = nullptr;
+}
+// upload a host table to a freshly allocated device table: the size comes from the vector
+template <typename P, typename X>
+inline int upload_table(P** dst, const std::vector<X>& v) {
+  QI_HIP(hipMalloc((void**)dst, v.size() * sizeof(X)));
+  QI_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(X), hipMemcpyHostToDevice));
+  return QI_OK;
+}
+// a device buffer that lives as long as one table build: freed on every way out
+template <typename X>
+struct DeviceTemp {
+  X* ptr = nullptr;
+  DeviceTemp() = default;
+  DeviceTemp(const DeviceTemp&) = delete;
+  DeviceTemp& operator=(const DeviceTemp&) = delete;
+  ~DeviceTemp() { free_device(ptr); }
+};
+
 // hipFFT plans of the plan-less entry points (STFT, Welch, sliding STFT, ShannonFFT): per device, under one mutex
 extern std::mutex g_stft_mu;
 extern std::map<int, FftCache> g_stft_fft;
@@ -251,15 +275,15 @@ struct qi_plan {
     double2* d_z64_lane_ph = nullptr;  // [nz64][65] carrier factors of the lanes and the step, per band of d_z64 (Gabor kinds)
     double2* d_z64_wave_ph = nullptr;  // [Lf / kZ64FineWave] carrier factors of the waves
     void release() {
-      if (d_z64) (void)hipFree(d_z64);
-      if (d_z64_lane_ph) (void)hipFree(d_z64_lane_ph);
-      if (d_z64_wave_ph) (void)hipFree(d_z64_wave_ph);
-      if (d_zoom) (void)hipFree(d_zoom);
-      if (d_zoom_plane_band) (void)hipFree(d_zoom_plane_band);
-      if (d_bands) (void)hipFree(d_bands);
-      if (d_gen_list) (void)hipFree(d_gen_list);
-      if (Hc) (void)hipFree(Hc);
-      if (Hfull) (void)hipFree(Hfull);
+      free_device(d_z64);
+      free_device(d_z64_lane_ph);
+      free_device(d_z64_wave_ph);
+      free_device(d_zoom);
+      free_device(d_zoom_plane_band);
+      free_device(d_bands);
+      free_device(d_gen_list);
+      free_device(Hc);
+      free_device(Hfull);
       *this = NativeTable();
     }
   } nat[4];  // 0 styx bank (linear, Lf = 2n), 1 atoms bank (circular), 2 Stockwell, 3 styx short-atom bands (circular n)
@@ -291,12 +315,12 @@ struct qi_plan {
     } var[2];
     int64_t max_blocks = 0;  // partial slots a band row needs
     void release() {
-      if (bank) (void)hipFree(bank);
+      free_device(bank);
       for (auto& v : var) {
-        if (v.d_bands) (void)hipFree(v.d_bands);
-        if (v.d_demod_pow) (void)hipFree(v.d_demod_pow);
-        if (v.d_gauss_w) (void)hipFree(v.d_gauss_w);
-        if (v.d_items) (void)hipFree(v.d_items);
+        free_device(v.d_bands);
+        free_device(v.d_demod_pow);
+        free_device(v.d_gauss_w);
+        free_device(v.d_items);
       }
       *this = BlockTable();
     }
@@ -321,7 +345,7 @@ struct qi_plan {
   int native_zoom_waves = 2048; // native_zoom_wgs = 0: waves each level of a zoom launch should have at least
   int native_zoom_wgs_joint = 768;   // the same budget per table in the joint launch of qi_cwt_stx (512 .. 1024 measured within 1.5 %)
   int native_zoom_wgs = 0;      // > 0: workgroups of a zoom launch, dealt to the levels by work (measured: 1.5 % slower than the per-level rule)
-  float* d_zoom_w[native::kZoomClasses][2] = {};  // interpolation weights [class][lane offset]
+  float* d_zoom_w[native::kZoomClasses] = {};  // interpolation weights per class
   int native_z64 = 1;      // float64: narrow-spectrum bands at the decimated rate (coarse inverse FFT + 16-tap interpolation)
   int native_z64_levels = native::kZ64Levels;  // ... on coarse grids of Lf / 64 ... Lf / (64 >> (levels - 1)) samples
   double* d_z64_w[native::kZ64Levels] = {};  // interpolation weights per coarse-grid level
@@ -415,11 +439,15 @@ constexpr int kZoomListOrder[native::kZoomClasses] = {6, 5, 0, 1, 2, 3, 4};
 // ---- qi_plan_build.hip: the tables of a plan ---------------------------------------------------------------------------
 bool native_len_ok(int64_t Lf);
 bool native_wanted(const qi_plan* p, int kind);
-bool z64_table(const qi_plan* p, int table);
-int64_t narrow_limit(const qi_plan* p, int table, int64_t Lf);
 int batch_from(const qi_plan* p);
-int zoom_class(const qi_plan* p, int table, int64_t Lf, int64_t len);
-int upload_native_table(qi_plan* p, int kind, int64_t Lf, std::vector<native::BandDesc> bands);
+// nothing half-built stays behind: a ready table without its block / split producers would leave panel rows unwritten
+void release_styx_extras(qi_plan* p);  // the split and short-atom (edge) members of the styx bank
+void drop_gabor_tables(qi_plan* p, int bank);
+void drop_stx_tables(qi_plan* p);
+void drop_band_slots(qi_plan* p, int kind);
+// the four parameter arrays of a Gabor bank as one host table [4][B] (p_re | p_im | omega | amp) and its device copy
+int upload_atom_params(int32_t B, const double* p_re, const double* p_im, const double* omega, const double* amp,
+                       std::vector<double>* host, DeviceTemp<double>* d_par);
 template <typename T>
 int build_native_bank(qi_plan* p, int bank, int32_t B, const double* d_par, const double* h_par, hipStream_t st);
 template <typename T>

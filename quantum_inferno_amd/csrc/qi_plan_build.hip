@@ -41,201 +41,275 @@ int batch_from(const qi_plan* p) {
   return rows <= 24 ? 8 : 4;
 }
 
-// Order the bands into launch groups: the wide bands are dealt out `native_group` per group (all in one group when
-// 0) so that a group's intermediate is small enough to stay in the last-level cache between pass 1 and pass 2; the
-// narrow bands are spread evenly over the groups.  `bands[j].out_band` must be set by the caller.
-int upload_native_table(qi_plan* p, int kind, int64_t Lf, std::vector<native::BandDesc> bands) {
-  auto& t = p->nat[kind];
-  if (tune_env("QI_NATIVE_VERBOSE"))
-    for (const auto& d : bands)
-      fprintf(stderr, "[qi plan] table %d (Lf = %lld) band %d: %s, support [%d, +%d)\n", kind, (long long)Lf, d.out_band,
-              d.mode == 0 ? "one-pass loader" : (d.mode == 1 ? "two-pass" : "zoom"), d.k_lo, d.k_len);
-  // bands marked for the zoom engine (mode 2 + level) leave the pass-2 list, ordered by level
-  {
-    std::vector<native::BandDesc> rest;
-    std::vector<std::vector<native::BandDesc>> by_level(native::kZoomClasses);
-    for (const auto& d : bands) {
-      if (d.mode >= 2) by_level[d.mode - 2].push_back(d);
-      else rest.push_back(d);
-    }
-    // a class with only a few bands is not worth rows of its own in the launch: they join the next class that can carry
-    // them -- the 4-tap class the 6-tap one, the 6-tap class the 10-tap class of the same grid, a grid level the next
-    // occupied level up (at most two up: each level doubles their coarse grid and adds window samples)
-    auto join = [&](int from, int to) {
-      by_level[to].insert(by_level[to].begin(), by_level[from].begin(), by_level[from].end());
-      by_level[from].clear();
-    };
-    if (!by_level[6].empty() && by_level[6].size() < 6) join(6, 5);
-    if (!by_level[5].empty() && by_level[5].size() < 6) join(5, 0);
-    for (int g = 0; g + 1 < native::kZoomLevels; ++g) {
-      if (by_level[g].empty() || by_level[g].size() >= 6) continue;
-      for (int h = g + 1; h <= g + 2 && h < native::kZoomLevels; ++h)
-        if (!by_level[h].empty()) {
-          join(g, h);
-          break;
-        }
-    }
-    std::vector<native::BandDesc> zoom;
-    t.h_zoom.clear();
-    t.zoom_planes = 0;
-    t.zoom_max_level = 0;
-    for (int g = 0; g < native::kZoomClasses; ++g) t.zoom_count[g] = (int32_t)by_level[g].size();
-    for (int gi = 0; gi < native::kZoomClasses; ++gi) {
-      // list order: the short-interpolator classes first, next to the 10-tap class of their grid, so that a call with
-      // few records can run all three as one class (kZoomListOrder)
-      const int g = kZoomListOrder[gi];
-      const int grid = native::zoom_grid(g);
-      for (auto d : by_level[g]) {
-        d.edge_slot = grid;                 // level of the band's coarse grid
-        d.edge = (int32_t)t.zoom_planes;    // first plane of its coarse array
-        t.zoom_planes += ((Lf / native::kZoomD) << grid) / native::kBlk;
-        if (grid > t.zoom_max_level) t.zoom_max_level = grid;
-        zoom.push_back(d);
-        t.h_zoom.push_back({d.out_band, g});
+// ---- band-to-engine rules: every site that routes a band asks these ---------------------------------------------------
+// occupied bins of a support triple {flag, first bin, last bin} (analyse_support)
+int64_t support_len(const double* sup) {
+  const int64_t lo = (int64_t)sup[1], hi = (int64_t)sup[2];
+  return hi >= lo ? hi - lo + 1 : 0;
+}
+// A band's spectrum support ends where |H| falls below 2^-30 of the row maximum (float32 engines); float64 keeps everything
+// above 2^-50.
+double support_bits(const qi_plan* p) { return p->d.dtype == QI_F64 ? 50.0 : 30.0; }
+// Taps of an atom and Gaussian filter weights below 2^-30 of the peak are dropped (float64: 2^-52).
+double drop_bits(bool f64) { return f64 ? 52.0 : 30.0; }
+
+// Zoom engine level of a band with `len` occupied bins out of Lf (-1: not eligible): the coarsest grid
+// M_g = (Lf / 64) << g on which the band is oversampled at least 4 times.
+int zoom_class(const qi_plan* p, int table, int64_t Lf, int64_t len) {
+  if (!p->native_zoom || table == 3 || len <= 0 || Lf % native::kZoomD != 0) return -1;
+  const int64_t M0 = Lf / native::kZoomD;
+  if (!is_pow2(M0)) return -1;
+  // the coarse stage works in 4096-point planes: a short record starts at the first grid level that fills one
+  int g_min = 0;
+  while ((M0 << g_min) < native::kBlk) ++g_min;
+  for (int g = g_min; g < native::kZoomLevels; ++g) {
+    if (p->n % ((int64_t)native::kZoomD * native::zoom_steps(g) * 4) != 0) return -1;
+    if (native::kZoomOversample * len <= (M0 << g)) {
+      // (the finest grid costs more in the coarse stage than the two-pass kernels save -- where those exist; at other
+      // lengths it keeps the table off the hipFFT engine)
+      if (g > p->native_zoom_max_level && native_len_ok(Lf)) return -1;
+      // on the coarsest grid the band may be oversampled far more than 4 times: shorter interpolators (classes 5, 6)
+      if (g == 0 && p->native_zoom_short) {
+        if ((int64_t)native::zoom_design_oversampling(6) * len <= M0) return 6;
+        if ((int64_t)native::zoom_design_oversampling(5) * len <= M0) return 5;
       }
+      return g;
     }
-    if (!zoom.empty()) {
-      QI_HIP(hipMalloc((void**)&t.d_zoom, zoom.size() * sizeof(native::BandDesc)));
-      QI_HIP(hipMemcpy(t.d_zoom, zoom.data(), zoom.size() * sizeof(native::BandDesc), hipMemcpyHostToDevice));
-      t.nzoom = (int32_t)zoom.size();
-      std::vector<int32_t> owner((size_t)t.zoom_planes);
-      for (size_t j = 0; j < zoom.size(); ++j) {
-        const int64_t planes = ((Lf / native::kZoomD) << zoom[j].edge_slot) / native::kBlk;
-        for (int64_t q = 0; q < planes; ++q) owner[(size_t)(zoom[j].edge + q)] = (int32_t)j;
-      }
-      QI_HIP(hipMalloc((void**)&t.d_zoom_plane_band, owner.size() * sizeof(int32_t)));
-      QI_HIP(hipMemcpy(t.d_zoom_plane_band, owner.data(), owner.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      for (int g = 0; g < native::kZoomClasses; ++g)
-        for (int e = 0; e < 1; ++e) {
-          // (class 0 also serves the bands of classes 5 and 6 in calls with few records)
-          const bool needed = t.zoom_count[g] > 0 || (g == 0 && t.zoom_count[5] + t.zoom_count[6] > 0);
-          if (p->d_zoom_w[g][e] || !needed) continue;
-          std::vector<float> w((size_t)64 * native::zoom_taps(g));
-          native::zoom_weights(g, e, w.data());
-          QI_HIP(hipMalloc((void**)&p->d_zoom_w[g][e], w.size() * sizeof(float)));
-          QI_HIP(hipMemcpy(p->d_zoom_w[g][e], w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-    }
-    bands.swap(rest);
   }
-  if (z64_table(p, kind)) {
-    // float64: every band with a compact row goes to the float64 zoom engine, on the coarsest grid that oversamples it
-    // four times
-    std::vector<native::BandDesc> rest;
-    std::vector<std::vector<native::BandDesc>> lvl(native::kZ64Levels);
-    for (const auto& d : bands) {
-      int g = -1;
-      if (d.mode == 0)
-        for (int q = 0; q < p->native_z64_levels && g < 0; ++q)
-          if (4 * (int64_t)d.k_len <= ((Lf / 64) << q)) g = q;
-      if (g >= 0) lvl[g].push_back(d);
-      else rest.push_back(d);
-    }
-    // The kZ64FineLevels (two) coarsest grids go through the fine kernel with wave-uniform windows (k_z64_fine), by CLASS =
-    // (grid, interpolator length): on the coarsest grid, where every narrower band lands, a band oversampled >= 8 / 16 / 32 /
-    // 64 times takes 12 / 10 / 8 / 6 taps instead of 16 (classes 2..5; the same error bound, see z64f_ntap).  A class of
-    // fewer than four bands joins the next longer interpolator (class 2 the 16-tap class 0).
-    for (int c = 0; c < native::kZ64FineClasses; ++c) t.zf_first[c] = t.zf_count[c] = 0;
-    if (p->native_z64_fine) {
-      const int64_t M0 = Lf / 64;
-      std::vector<std::vector<native::BandDesc>> cls(native::kZ64FineClasses);
-      for (const auto& d : lvl[0]) {
-        int c = 0;
-        for (int q = native::kZ64FineClasses - 1; q >= native::kZ64FineLevels && c == 0; --q)
-          if ((int64_t)native::z64f_oversampling(q) * d.k_len <= M0) c = q;
-        cls[c].push_back(d);
-      }
-      for (int q = native::kZ64FineClasses - 1; q >= native::kZ64FineLevels; --q) {
-        if (cls[q].empty() || cls[q].size() >= 4) continue;
-        const int to = q == native::kZ64FineLevels ? 0 : q - 1;
-        cls[to].insert(cls[to].end(), cls[q].begin(), cls[q].end());
-        cls[q].clear();
-      }
-      lvl[0].clear();
-      int32_t pos = 0;
-      std::vector<int> order0{0};  // list order of the coarsest grid: the 16-tap class, then the shorter interpolators
-      for (int c = native::kZ64FineLevels; c < native::kZ64FineClasses; ++c) order0.push_back(c);
-      for (int c : order0) {
-        t.zf_first[c] = pos;
-        t.zf_count[c] = (int32_t)cls[c].size();
-        pos += t.zf_count[c];
-        lvl[0].insert(lvl[0].end(), cls[c].begin(), cls[c].end());
-      }
-      for (int g = 1; g < native::kZ64FineLevels && g < native::kZ64Levels; ++g) {
-        t.zf_first[g] = pos;
-        t.zf_count[g] = (int32_t)lvl[g].size();
-        pos += t.zf_count[g];
-      }
-      for (int c = 0; c < native::kZ64FineClasses; ++c) {
-        if (t.zf_count[c] == 0 || p->d_z64f_w[c]) continue;
-        std::vector<double> w((size_t)native::z64f_win(c) * 64);
-        native::z64_fine_weights(c, w.data());
-        QI_HIP(hipMalloc((void**)&p->d_z64f_w[c], w.size() * sizeof(double)));
-        QI_HIP(hipMemcpy(p->d_z64f_w[c], w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-      }
-    }
-    std::vector<native::BandDesc> z;
-    for (int g = 0; g < native::kZ64Levels; ++g) {
-      t.z64_first[g] = (int32_t)z.size();
-      t.z64_count[g] = (int32_t)lvl[g].size();
-      z.insert(z.end(), lvl[g].begin(), lvl[g].end());
-      if (!lvl[g].empty() && !p->d_z64_w[g]) {
-        const int log2d = 6 - g;
-        std::vector<double> w((size_t)(1 << log2d) * native::kZ64Taps);
-        native::z64_weights(log2d, w.data());
-        QI_HIP(hipMalloc((void**)&p->d_z64_w[g], w.size() * sizeof(double)));
-        QI_HIP(hipMemcpy(p->d_z64_w[g], w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-      }
-    }
-    t.nz64 = (int32_t)z.size();
-    t.h_z64.clear();
-    for (const auto& d : z) t.h_z64.push_back(d.out_band);
-    if (!z.empty()) {
-      QI_HIP(hipMalloc((void**)&t.d_z64, z.size() * sizeof(native::BandDesc)));
-      QI_HIP(hipMemcpy(t.d_z64, z.data(), z.size() * sizeof(native::BandDesc), hipMemcpyHostToDevice));
-    }
-    if (!z.empty() && p->native_z64_fine && kind != 2) {
-      // carrier factors of the fine kernel (Gabor kinds), exact integer phases evaluated in long double: per band
-      // exp(2 pi i k_c (lane - e) / Lf) for the 64 lanes and the step exp(2 pi i k_c 64 / Lf); per table the waves' factors
-      // exp(2 pi i j kZ64FineWave / Lf).  e = 1 for the zero-padded kind (the carrier of full-length sample tau - 1).
-      const long double two_pi = 6.283185307179586476925286766559005768L;
-      const int e = kind == 0 ? 1 : 0;
-      auto root = [&](int64_t m) {
-        m = ((m % Lf) + Lf) % Lf;
-        const long double ang = two_pi * (long double)m / (long double)Lf;
-        return make_double2((double)cosl(ang), (double)sinl(ang));
-      };
-      std::vector<double2> lane(z.size() * 65);
-      for (size_t j = 0; j < z.size(); ++j) {
-        const int64_t kc = (int64_t)z[j].k_lo + z[j].k_len / 2;
-        for (int l = 0; l < 64; ++l) lane[j * 65 + l] = root(kc * (l - e));
-        lane[j * 65 + 64] = root(kc * 64);
-      }
-      const int64_t nw = Lf / native::kZ64FineWave;
-      std::vector<double2> wave((size_t)nw);
-      for (int64_t j = 0; j < nw; ++j) wave[(size_t)j] = root(j * native::kZ64FineWave);
-      QI_HIP(hipMalloc((void**)&t.d_z64_lane_ph, lane.size() * sizeof(double2)));
-      QI_HIP(hipMemcpy(t.d_z64_lane_ph, lane.data(), lane.size() * sizeof(double2), hipMemcpyHostToDevice));
-      QI_HIP(hipMalloc((void**)&t.d_z64_wave_ph, wave.size() * sizeof(double2)));
-      QI_HIP(hipMemcpy(t.d_z64_wave_ph, wave.data(), wave.size() * sizeof(double2), hipMemcpyHostToDevice));
-    }
-    if (tune_env("QI_NATIVE_VERBOSE")) {
-      fprintf(stderr, "[qi plan] table %d: float64 zoom bands per level %d %d %d %d %d, two-pass bands %zu; fine classes (taps: bands)", kind,
-              t.z64_count[0], t.z64_count[1], t.z64_count[2], t.z64_count[3], t.z64_count[4], rest.size());
-      for (int c = 0; c < native::kZ64FineClasses; ++c)
-        fprintf(stderr, " %d@L%d: %d", native::z64f_ntap(c), native::z64f_level(c), t.zf_count[c]);
-      fprintf(stderr, "\n");
-    }
-    bands.swap(rest);
+  return -1;
+}
+
+// Float64 zoom level of a band with `len` occupied bins out of Lf (-1: the band is not for that engine): the coarsest grid
+// (Lf / 64) << g of the plan's native_z64_levels that oversamples it four times.  (The finest grid, Lf / 4 samples, is what
+// narrow_limit allows at most: at transform lengths below 2^19 the one-pass loader's limit is wider than that.)
+int z64_level(const qi_plan* p, int table, int64_t Lf, int64_t len) {
+  if (!z64_table(p, table) || len <= 0 || len > narrow_limit(p, table, Lf)) return -1;
+  for (int g = 0; g < p->native_z64_levels; ++g)
+    if (4 * len <= ((Lf / 64) << g)) return g;
+  return -1;
+}
+// ... and not on one of its finest grids when the block engine can take the band: a band of 65 536 - 131 072 bins costs
+// the float64 zoom 13.5 us per record -- a 2^19-point coarse transform and the LDS-window interpolation kernel --
+// against 7.4 us on the block engine, measured at order 12 x 4 records: native_z64_block_from
+bool z64_level_for_block(const qi_plan* p, int level) { return level >= p->native_z64_block_from; }
+
+// BandDesc::mode of a band that keeps a bank row: 2 + c zoom engine, class c; 0 a compact row (one-pass loader of pass 2;
+// float64: the float64 zoom takes it from there, z64_level); 1 a full row for the two-pass kernels
+int band_mode(const qi_plan* p, int table, int64_t Lf, int64_t len) {
+  const int zc = zoom_class(p, table, Lf, len);
+  if (zc >= 0) return 2 + zc;
+  return len > 0 && len <= narrow_limit(p, table, Lf) ? 0 : 1;
+}
+
+// a band of the block engine
+struct BlockPick {
+  int32_t band;   // panel row
+  int wq;         // reach group: taps within 256 * wq samples (1, 2 or 4)
+  int64_t shift;  // Stockwell shift index (0 for Gabor banks)
+  // analytic Gaussian filter spectrum (0: read the table row): weight(k) = amp exp2(-(cw (k - kappa))^2)
+  int analytic = 0;
+  double kappa = 0.0, cw = 0.0, amp = 0.0;
+};
+int block_group_of(double reach) { return reach <= 256.0 ? 1 : (reach <= 512.0 ? 2 : (reach <= 1024.0 ? 4 : 0)); }
+// analytic Gaussian filter spectrum of a pure Gabor atom on the 4096-bin grid: amp sqrt(pi / p) exp(-d^2 / 4p) exp(-i theta / 2)
+void gabor_gaussian(BlockPick& pk, double p_re, double om, double am) {
+  pk.kappa = om * (double)native::kBlk / (2.0 * M_PI);
+  pk.cw = (2.0 * M_PI / (double)native::kBlk) * std::sqrt(M_LOG2E / (4.0 * p_re));
+  pk.amp = am * std::sqrt(M_PI / p_re) / (double)native::kBlk;
+}
+// ... of a Stockwell band: the Gaussian window itself, centred on the band's shift index
+void stx_gaussian(BlockPick& pk, int64_t n, double sigma) {
+  pk.kappa = (double)pk.shift * (double)native::kBlk / (double)n;
+  pk.cw = (2.0 * M_PI / (double)native::kBlk) * sigma * std::sqrt(M_LOG2E / 2.0);
+  pk.amp = 1.0 / (double)native::kBlk;
+}
+
+// exp(+-2 pi i m / N) from the exact integer phase, evaluated in long double
+double2 unit_root(int64_t m, int64_t N, bool negative) {
+  const long double two_pi = 6.283185307179586476925286766559005768L;
+  const long double ang = (negative ? -two_pi : two_pi) * (long double)(((m % N) + N) % N) / (long double)N;
+  return make_double2((double)cosl(ang), (double)sinl(ang));
+}
+
+// ---- the band lists of a table -----------------------------------------------------------------------------------------
+// Bands marked for the zoom engine (mode 2 + class) leave `bands`, ordered by class.
+int upload_zoom_list(qi_plan* p, qi_plan::NativeTable& t, int64_t Lf, std::vector<native::BandDesc>& bands) {
+  std::vector<native::BandDesc> rest;
+  std::vector<std::vector<native::BandDesc>> by_level(native::kZoomClasses);
+  for (const auto& d : bands) {
+    if (d.mode >= 2) by_level[d.mode - 2].push_back(d);
+    else rest.push_back(d);
   }
+  // a class with only a few bands is not worth rows of its own in the launch: they join the next class that can carry
+  // them -- the 4-tap class the 6-tap one, the 6-tap class the 10-tap class of the same grid, a grid level the next
+  // occupied level up (at most two up: each level doubles their coarse grid and adds window samples)
+  auto join = [&](int from, int to) {
+    by_level[to].insert(by_level[to].begin(), by_level[from].begin(), by_level[from].end());
+    by_level[from].clear();
+  };
+  if (!by_level[6].empty() && by_level[6].size() < 6) join(6, 5);
+  if (!by_level[5].empty() && by_level[5].size() < 6) join(5, 0);
+  for (int g = 0; g + 1 < native::kZoomLevels; ++g) {
+    if (by_level[g].empty() || by_level[g].size() >= 6) continue;
+    for (int h = g + 1; h <= g + 2 && h < native::kZoomLevels; ++h)
+      if (!by_level[h].empty()) {
+        join(g, h);
+        break;
+      }
+  }
+  std::vector<native::BandDesc> zoom;
+  t.h_zoom.clear();
+  t.zoom_planes = 0;
+  t.zoom_max_level = 0;
+  for (int g = 0; g < native::kZoomClasses; ++g) t.zoom_count[g] = (int32_t)by_level[g].size();
+  for (int gi = 0; gi < native::kZoomClasses; ++gi) {
+    // list order: the short-interpolator classes first, next to the 10-tap class of their grid, so that a call with
+    // few records can run all three as one class (kZoomListOrder)
+    const int g = kZoomListOrder[gi];
+    const int grid = native::zoom_grid(g);
+    for (auto d : by_level[g]) {
+      d.edge_slot = grid;                 // level of the band's coarse grid
+      d.edge = (int32_t)t.zoom_planes;    // first plane of its coarse array
+      t.zoom_planes += ((Lf / native::kZoomD) << grid) / native::kBlk;
+      if (grid > t.zoom_max_level) t.zoom_max_level = grid;
+      zoom.push_back(d);
+      t.h_zoom.push_back({d.out_band, g});
+    }
+  }
+  bands.swap(rest);
+  if (zoom.empty()) return QI_OK;
+  QI_TRY(upload_table(&t.d_zoom, zoom));
+  t.nzoom = (int32_t)zoom.size();
+  std::vector<int32_t> owner((size_t)t.zoom_planes);
+  for (size_t j = 0; j < zoom.size(); ++j) {
+    const int64_t planes = ((Lf / native::kZoomD) << zoom[j].edge_slot) / native::kBlk;
+    for (int64_t q = 0; q < planes; ++q) owner[(size_t)(zoom[j].edge + q)] = (int32_t)j;
+  }
+  QI_TRY(upload_table(&t.d_zoom_plane_band, owner));
+  for (int g = 0; g < native::kZoomClasses; ++g) {
+    // (class 0 also serves the bands of classes 5 and 6 in calls with few records)
+    const bool needed = t.zoom_count[g] > 0 || (g == 0 && t.zoom_count[5] + t.zoom_count[6] > 0);
+    if (p->d_zoom_w[g] || !needed) continue;
+    std::vector<float> w((size_t)64 * native::zoom_taps(g));
+    native::zoom_weights(g, 0, w.data());
+    QI_TRY(upload_table(&p->d_zoom_w[g], w));
+  }
+  return QI_OK;
+}
+
+// The kZ64FineLevels (two) coarsest grids go through the fine kernel with wave-uniform windows (k_z64_fine), by CLASS =
+// (grid, interpolator length): on the coarsest grid, where every narrower band lands, a band oversampled >= 8 / 16 / 32 /
+// 64 times takes 12 / 10 / 8 / 6 taps instead of 16 (classes 2..5; the same error bound, see z64f_ntap).  A class of
+// fewer than four bands joins the next longer interpolator (class 2 the 16-tap class 0).  Orders the bands of the
+// coarsest grid (lvl[0]) by class and uploads the classes' lane weights.
+int order_z64_fine_classes(qi_plan* p, qi_plan::NativeTable& t, int64_t Lf, std::vector<std::vector<native::BandDesc>>& lvl) {
+  const int64_t M0 = Lf / 64;
+  std::vector<std::vector<native::BandDesc>> cls(native::kZ64FineClasses);
+  for (const auto& d : lvl[0]) {
+    int c = 0;
+    for (int q = native::kZ64FineClasses - 1; q >= native::kZ64FineLevels && c == 0; --q)
+      if ((int64_t)native::z64f_oversampling(q) * d.k_len <= M0) c = q;
+    cls[c].push_back(d);
+  }
+  for (int q = native::kZ64FineClasses - 1; q >= native::kZ64FineLevels; --q) {
+    if (cls[q].empty() || cls[q].size() >= 4) continue;
+    const int to = q == native::kZ64FineLevels ? 0 : q - 1;
+    cls[to].insert(cls[to].end(), cls[q].begin(), cls[q].end());
+    cls[q].clear();
+  }
+  lvl[0].clear();
+  int32_t pos = 0;
+  std::vector<int> order0{0};  // list order of the coarsest grid: the 16-tap class, then the shorter interpolators
+  for (int c = native::kZ64FineLevels; c < native::kZ64FineClasses; ++c) order0.push_back(c);
+  for (int c : order0) {
+    t.zf_first[c] = pos;
+    t.zf_count[c] = (int32_t)cls[c].size();
+    pos += t.zf_count[c];
+    lvl[0].insert(lvl[0].end(), cls[c].begin(), cls[c].end());
+  }
+  for (int g = 1; g < native::kZ64FineLevels && g < native::kZ64Levels; ++g) {
+    t.zf_first[g] = pos;
+    t.zf_count[g] = (int32_t)lvl[g].size();
+    pos += t.zf_count[g];
+  }
+  for (int c = 0; c < native::kZ64FineClasses; ++c) {
+    if (t.zf_count[c] == 0 || p->d_z64f_w[c]) continue;
+    std::vector<double> w((size_t)native::z64f_win(c) * 64);
+    native::z64_fine_weights(c, w.data());
+    QI_TRY(upload_table(&p->d_z64f_w[c], w));
+  }
+  return QI_OK;
+}
+
+// Carrier factors of the fine kernel (Gabor kinds), exact integer phases: per band of `z` exp(2 pi i k_c (lane - e) / Lf) for
+// the 64 lanes and the step exp(2 pi i k_c 64 / Lf); per table the waves' factors exp(2 pi i j kZ64FineWave / Lf).  e = 1 for
+// the zero-padded kind (the carrier of full-length sample tau - 1).
+int upload_z64_carriers(qi_plan::NativeTable& t, int kind, int64_t Lf, const std::vector<native::BandDesc>& z) {
+  const int e = kind == 0 ? 1 : 0;
+  std::vector<double2> lane(z.size() * 65);
+  for (size_t j = 0; j < z.size(); ++j) {
+    const int64_t kc = (int64_t)z[j].k_lo + z[j].k_len / 2;
+    for (int l = 0; l < 64; ++l) lane[j * 65 + l] = unit_root(kc * (l - e), Lf, false);
+    lane[j * 65 + 64] = unit_root(kc * 64, Lf, false);
+  }
+  const int64_t nw = Lf / native::kZ64FineWave;
+  std::vector<double2> wave((size_t)nw);
+  for (int64_t j = 0; j < nw; ++j) wave[(size_t)j] = unit_root(j * native::kZ64FineWave, Lf, false);
+  QI_TRY(upload_table(&t.d_z64_lane_ph, lane));
+  return upload_table(&t.d_z64_wave_ph, wave);
+}
+
+// float64: every band with a compact row that the float64 zoom takes (z64_level) leaves `bands`, ordered by grid level.
+int upload_z64_list(qi_plan* p, qi_plan::NativeTable& t, int kind, int64_t Lf, std::vector<native::BandDesc>& bands) {
+  std::vector<native::BandDesc> rest;
+  std::vector<std::vector<native::BandDesc>> lvl(native::kZ64Levels);
+  for (const auto& d : bands) {
+    const int g = d.mode == 0 ? z64_level(p, kind, Lf, d.k_len) : -1;
+    if (g >= 0) lvl[g].push_back(d);
+    else rest.push_back(d);
+  }
+  for (int c = 0; c < native::kZ64FineClasses; ++c) t.zf_first[c] = t.zf_count[c] = 0;
+  if (p->native_z64_fine) QI_TRY(order_z64_fine_classes(p, t, Lf, lvl));
+  std::vector<native::BandDesc> z;
+  for (int g = 0; g < native::kZ64Levels; ++g) {
+    t.z64_first[g] = (int32_t)z.size();
+    t.z64_count[g] = (int32_t)lvl[g].size();
+    z.insert(z.end(), lvl[g].begin(), lvl[g].end());
+    if (!lvl[g].empty() && !p->d_z64_w[g]) {
+      const int log2d = 6 - g;
+      std::vector<double> w((size_t)(1 << log2d) * native::kZ64Taps);
+      native::z64_weights(log2d, w.data());
+      QI_TRY(upload_table(&p->d_z64_w[g], w));
+    }
+  }
+  t.nz64 = (int32_t)z.size();
+  t.h_z64.clear();
+  for (const auto& d : z) t.h_z64.push_back(d.out_band);
+  if (!z.empty()) QI_TRY(upload_table(&t.d_z64, z));
+  if (!z.empty() && p->native_z64_fine && kind != 2) QI_TRY(upload_z64_carriers(t, kind, Lf, z));
+  if (tune_env("QI_NATIVE_VERBOSE")) {
+    fprintf(stderr, "[qi plan] table %d: float64 zoom bands per level %d %d %d %d %d, two-pass bands %zu; fine classes (taps: bands)", kind,
+            t.z64_count[0], t.z64_count[1], t.z64_count[2], t.z64_count[3], t.z64_count[4], rest.size());
+    for (int c = 0; c < native::kZ64FineClasses; ++c)
+      fprintf(stderr, " %d@L%d: %d", native::z64f_ntap(c), native::z64f_level(c), t.zf_count[c]);
+    fprintf(stderr, "\n");
+  }
+  bands.swap(rest);
+  return QI_OK;
+}
+
+// Order the bands left for the two-pass kernels into launch groups: the wide bands are dealt out `native_group` per group
+// (all in one group when 0) so that a group's intermediate is small enough to stay in the last-level cache between pass 1
+// and pass 2; the narrow bands are spread evenly over the groups.
+int upload_two_pass_groups(qi_plan* p, qi_plan::NativeTable& t, int64_t Lf, const std::vector<native::BandDesc>& bands) {
   t.h_rows.clear();
   t.h_row_mode.clear();
   for (const auto& d : bands) {
     t.h_rows.push_back(d.out_band);
     t.h_row_mode.push_back(d.mode == 1 ? 1 : 0);
   }
+  t.Lf = Lf;
   if (bands.empty()) {  // every band is produced by the block / zoom engines: an empty but valid table
-    t.Lf = Lf;
     t.ready = true;
     return QI_OK;
   }
@@ -264,18 +338,26 @@ int upload_native_table(qi_plan* p, int kind, int64_t Lf, std::vector<native::Ba
     grp.ngen = (int32_t)gen.size() - grp.gen_first;
     if (grp.count > 0) t.groups.push_back(grp);
   }
-  QI_HIP(hipMalloc((void**)&t.d_bands, ordered.size() * sizeof(native::BandDesc)));
-  QI_HIP(hipMemcpy(t.d_bands, ordered.data(), ordered.size() * sizeof(native::BandDesc), hipMemcpyHostToDevice));
-  if (!gen.empty()) {
-    QI_HIP(hipMalloc((void**)&t.d_gen_list, gen.size() * sizeof(int32_t)));
-    QI_HIP(hipMemcpy(t.d_gen_list, gen.data(), gen.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  t.Lf = Lf;
+  QI_TRY(upload_table(&t.d_bands, ordered));
+  if (!gen.empty()) QI_TRY(upload_table(&t.d_gen_list, gen));
   t.nbands = (int32_t)bands.size();
   t.ngen = (int32_t)wide.size();
   t.imd_slots = wide.empty() ? 0 : (per < (int32_t)wide.size() ? per : (int32_t)wide.size());
   t.ready = true;
   return QI_OK;
+}
+
+// The band lists of table `kind` from its descriptors, engine by engine: the float32 zoom list, the float64 zoom list, the
+// launch groups of the two-pass kernels.  `bands[j].out_band` must be set by the caller.
+int upload_native_table(qi_plan* p, int kind, int64_t Lf, std::vector<native::BandDesc> bands) {
+  auto& t = p->nat[kind];
+  if (tune_env("QI_NATIVE_VERBOSE"))
+    for (const auto& d : bands)
+      fprintf(stderr, "[qi plan] table %d (Lf = %lld) band %d: %s, support [%d, +%d)\n", kind, (long long)Lf, d.out_band,
+              d.mode == 0 ? "one-pass loader" : (d.mode == 1 ? "two-pass" : "zoom"), d.k_lo, d.k_len);
+  QI_TRY(upload_zoom_list(p, t, Lf, bands));
+  if (z64_table(p, kind)) QI_TRY(upload_z64_list(p, t, kind, Lf, bands));
+  return upload_two_pass_groups(p, t, Lf, bands);
 }
 
 // Support analysis of `count` atom spectra starting at band j0 (rows built in `circular` or linear form).
@@ -288,7 +370,7 @@ int analyse_support(qi_plan* p, int circular, int64_t L, int32_t B, int32_t j0, 
   // "Device" memory is host memory in that build: d_par is read directly.
   (void)st;
   (void)circular;
-  const double bits = p->d.dtype == QI_F64 ? 50.0 : 30.0;
+  const double bits = support_bits(p);
   sup->assign((size_t)count * 3, 0.0);
   for (int32_t q = 0; q < count; ++q) {
     const double p_re = d_par[j0 + q], om = d_par[2 * (int64_t)B + j0 + q];
@@ -317,34 +399,30 @@ int analyse_support(qi_plan* p, int circular, int64_t L, int32_t B, int32_t j0, 
     return QI_ERR_NOMEM;
   }
   double2* rows = reinterpret_cast<double2*>(p->ws);
-  double* d_sup = nullptr;
-  QI_HIP(hipMalloc((void**)&d_sup, (size_t)count * 3 * sizeof(double)));
-  // |H| below 2^-30 of the row maximum is dropped (float32 engines); float64 keeps everything above 2^-50
-  const double thr2 = p->d.dtype == QI_F64 ? std::ldexp(1.0, -100) : std::ldexp(1.0, -60);
-  int rc = QI_OK;
-  for (int32_t q = 0; q < count && rc == QI_OK; q += (int32_t)chunk) {
+  DeviceTemp<double> d_sup;
+  QI_HIP(hipMalloc((void**)&d_sup.ptr, (size_t)count * 3 * sizeof(double)));
+  const double thr2 = std::ldexp(1.0, -2 * (int)support_bits(p));  // the threshold on |H|^2
+  for (int32_t q = 0; q < count; q += (int32_t)chunk) {
     const int nbk = (count - q < chunk) ? count - q : (int)chunk;
-    rc = launch_bank_rows(rows, p->n, L, circular, d_par, d_par + B, d_par + 2 * B, d_par + 3 * B, j0 + q, nbk, st,
-                          taper_e);
-    if (rc == QI_OK) rc = fft_c2c<double>(p->fft, rows, L, nbk, HIPFFT_FORWARD, st);
-    if (rc == QI_OK) rc = native::launch_band_support(rows, L, nbk, thr2, d_sup + (size_t)q * 3, st);
+    QI_TRY(launch_bank_rows(rows, p->n, L, circular, d_par, d_par + B, d_par + 2 * B, d_par + 3 * B, j0 + q, nbk, st, taper_e));
+    QI_TRY(fft_c2c<double>(p->fft, rows, L, nbk, HIPFFT_FORWARD, st));
+    QI_TRY(native::launch_band_support(rows, L, nbk, thr2, d_sup.ptr + (size_t)q * 3, st));
   }
   sup->assign((size_t)count * 3, 0.0);
-  if (rc == QI_OK && (hipStreamSynchronize(st) != hipSuccess ||
-                      hipMemcpy(sup->data(), d_sup, sup->size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
+  if (hipStreamSynchronize(st) != hipSuccess ||
+      hipMemcpy(sup->data(), d_sup.ptr, sup->size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
     set_error("support analysis failed: %s", hipGetErrorString(hipGetLastError()));
-    rc = QI_ERR_HIP;
+    return QI_ERR_HIP;
   }
-  (void)hipFree(d_sup);
-  return rc;
+  return QI_OK;
 }
 
-// Fill the compact / full-row banks of table `t` for the bands listed in `ids` (global band ids; descriptors in
+// Fill the compact / full-row banks of table `table` for the bands listed in `ids` (global band ids; descriptors in
 // `bands`, same order) from freshly built float64 spectra.
 template <typename T>
-int fill_native_bank(qi_plan* p, qi_plan::NativeTable& t, int circular, int64_t L, int32_t B,
-                     const std::vector<int32_t>& ids, const std::vector<native::BandDesc>& bands, const double* d_par,
-                     hipStream_t st) {
+int fill_native_bank(qi_plan* p, int table, int circular, int64_t L, int32_t B, const std::vector<int32_t>& ids,
+                     const std::vector<native::BandDesc>& bands, const double* d_par, hipStream_t st) {
+  auto& t = p->nat[table];
   const size_t row64 = (size_t)L * sizeof(double2);
   int64_t chunk = (int64_t)((p->ws_bytes - 4096) / row64);
   double2* rows = reinterpret_cast<double2*>(p->ws);
@@ -361,12 +439,10 @@ int fill_native_bank(qi_plan* p, qi_plan::NativeTable& t, int circular, int64_t 
     for (int jj = 0; jj < nbk; ++jj) {
       const native::BandDesc& d = bands[q + jj];
       if (d.mode != 1) {
-        // zoom bands of the linear (styx) table: panel sample t is full-length sample t + n/2 - 1; the odd sample is a
-        // phase ramp on the band's baseband bins, exp(-2 pi i (k - k_c) / L), folded into the compact bank here
-        // (float64: the same for the bands the float64 zoom takes -- upload_native_table's rule)
-        const bool z64_band = p->d.dtype == QI_F64 && z64_table(p, 0) && d.mode == 0 &&
-                              4 * (int64_t)d.k_len <= ((L / 64) << (p->native_z64_levels - 1));
-        const double ramp = ((d.mode >= 2 || z64_band) && !circular) ? -1.0 / (double)L : 0.0;
+        // bands of the zoom engines in the linear (styx) table: panel sample t is full-length sample t + n/2 - 1; the odd
+        // sample is a phase ramp on the band's baseband bins, exp(-2 pi i (k - k_c) / L), folded into the compact bank here
+        const bool zoomed = d.mode >= 2 || z64_level(p, table, L, d.k_len) >= 0;
+        const double ramp = zoomed && !circular ? -1.0 / (double)L : 0.0;
         QI_TRY(native::launch_copy_window<T>(rows + (int64_t)jj * L, static_cast<cplx<T>*>(t.Hc) + d.src_off, d.k_lo,
                                               d.k_len, circular, 1.0 / (double)L, L, st, ramp, d.k_len / 2));
       }
@@ -381,21 +457,192 @@ int fill_native_bank(qi_plan* p, qi_plan::NativeTable& t, int circular, int64_t 
 }
 
 // ---- block engine tables ------------------------------------------------------------------------------------------
-struct BlockPick {
-  int32_t band;   // panel row
-  int wq;         // reach group: taps within 256 * wq samples (1, 2 or 4)
-  int64_t shift;  // Stockwell shift index (0 for Gabor banks)
-  // analytic Gaussian filter spectrum (0: read the table row): weight(k) = amp exp2(-(cw (k - kappa))^2)
-  int analytic = 0;
-  double kappa = 0.0, cw = 0.0, amp = 0.0;
-};
-int block_group_of(double reach) { return reach <= 256.0 ? 1 : (reach <= 512.0 ? 2 : (reach <= 1024.0 ? 4 : 0)); }
+// reach groups: taps within 256, 512, 1024 samples (4096-sample blocks), and the long blocks (8192 samples) for the
+// narrow Gaussian bands of the 1024-sample group whose spectrum lies in the lower half of the 8192-bin grid
+constexpr int kBlockGroups = 4;
+constexpr int kBlockGroupWq[kBlockGroups] = {1, 2, 4, native::kBlkLongWq};
+
+// first bin of the 256-bin window of a long band: centred on the band, kept inside the lower half of the 8192-bin grid
+// (the half a long block holds)
+int64_t long_window(const BlockPick& pk) {
+  return std::min<int64_t>(std::max<int64_t>((int64_t)std::llround(2.0 * pk.kappa) - 128, 0), native::kBlk - 256);
+}
+// does item cut `cut` run this band in long blocks?  (float32 tables only)
+bool long_ok(const qi_plan* p, const BlockPick& pk, int cut) {
+  if (cut == 0) return false;  // few records: the long blocks' own launch would cost more than the blocks save
+  if (!p->native_blk_long || !p->native_blk_analytic || !p->native_blk_narrow || pk.wq != 4 || !pk.analytic) return false;
+  if (p->n < 4 * native::kBlkLong) return false;
+  const double half8 = std::ceil(std::sqrt(drop_bits(false)) / (0.5 * pk.cw));  // weights >= 2^-30 of the peak on the 8192-bin grid
+  const int64_t klo8 = long_window(pk);
+  return 2.0 * pk.kappa - half8 - 1.0 >= (double)klo8 && 2.0 * pk.kappa + half8 + 1.0 <= (double)(klo8 + 255);
+}
+
+// The descriptor of block band `row` (its pick), on long blocks or not.
+template <typename T>
+int block_band_desc(const qi_plan* p, const BlockPick& pk, int32_t row, bool is_long, native::BlockBandT<T>* out) {
+  // (float64 tables: Gaussian weights in double from every bin -- the shortcuts below drop weights under 2^-30 of the peak)
+  constexpr bool F64 = sizeof(T) == 8;
+  native::BlockBandT<T>& b = *out;
+  memset(&b, 0, sizeof(b));
+  b.out_band = pk.band;
+  b.bank_row = row;
+  b.shift = (int32_t)pk.shift;
+  b.analytic = p->native_blk_analytic ? pk.analytic : 0;
+  const double grid = is_long ? 2.0 : 1.0;  // the band on the 8192-bin grid of a long block: twice the bins
+  const double kappa = grid * pk.kappa, cw = pk.cw / grid;
+  b.kappa_int = (int32_t)std::floor(kappa);
+  b.kappa_frac = (T)(kappa - std::floor(kappa));
+  b.cw = (T)cw;
+  b.amp = (T)(pk.amp / grid);
+  // weights >= 2^-30 of the peak: |cw dk| <= sqrt(30) (float64: 2^-52)
+  const double half = std::ceil(std::sqrt(drop_bits(F64)) / cw);
+  if (F64 && !b.analytic) {
+    set_error("block engine: float64 tables take analytic (Gaussian) bands only");
+    return QI_ERR_STATE;
+  }
+  // (float64 since round 5: `half` is then the 2^-52 half-width, the weight comes from the table -- bands of the 512- and
+  // 1024-sample reach groups; analytic = 2, an aliased spectrum, is not narrow)
+  if ((!F64 || (b.analytic == 1 && p->native_blk64_wtab && p->native_blk64_narrow)) && b.analytic && p->native_blk_narrow &&
+      2.0 * half + 2.0 <= 256.0) {
+    b.narrow = 1;
+    b.klo = is_long ? (int32_t)long_window(pk)
+                    : (int32_t)((((int64_t)std::llround(kappa) - 128) % native::kBlk + native::kBlk) % native::kBlk);
+    const int ba = b.klo >> 8;
+    b.rot_a[0] = (T)std::cos(2.0 * M_PI * ba / 16.0);
+    b.rot_a[1] = (T)std::sin(2.0 * M_PI * ba / 16.0);
+    b.rot_b[0] = (T)std::cos(2.0 * M_PI * ((ba + 1) & 15) / 16.0);
+    b.rot_b[1] = (T)std::sin(2.0 * M_PI * ((ba + 1) & 15) / 16.0);
+    b.rot8_a[0] = (T)std::cos(M_PI * ba / 16.0);  // exp(2 pi i 256 b / 8192)
+    b.rot8_a[1] = (T)std::sin(M_PI * ba / 16.0);
+    b.rot8_b[0] = (T)std::cos(M_PI * (ba + 1) / 16.0);
+    b.rot8_b[1] = (T)std::sin(M_PI * (ba + 1) / 16.0);
+  } else if (!F64 && b.analytic && p->native_blk_half && kappa - half - 1.0 >= 0.0 && kappa + half + 1.0 < (double)(native::kBlk / 2)) {
+    b.narrow = 2;  // every weight above 2^-30 of the peak lies in the lower half of the block spectrum
+  }
+  if (b.analytic && p->native_blk_fastw && b.amp > (T)0 && kappa - half - 1.0 >= 0.0 && kappa + half + 1.0 < (double)native::kBlk) {
+    b.nowrap = 1;
+    b.la = (T)std::log2(pk.amp / grid);
+  }
+  for (int k = 0; k < 4; ++k) {
+    // r^(2^k), r = exp(-2 pi i idx 256 / n), from the exact integer phase
+    const int64_t m = (int64_t)(((__int128)pk.shift * 256 * (1 << k)) % p->n);
+    const double ang = -2.0 * M_PI * (double)m / (double)p->n;
+    b.rot[2 * k] = (T)std::cos(ang);
+    b.rot[2 * k + 1] = (T)std::sin(ang);
+  }
+  const int64_t m1 = pk.shift % p->n;  // one sample: the odd sample of a long block's pair
+  b.rot1[0] = (T)std::cos(-2.0 * M_PI * (double)m1 / (double)p->n);
+  b.rot1[1] = (T)std::sin(-2.0 * M_PI * (double)m1 / (double)p->n);
+  return QI_OK;
+}
+
+// The work items of item cut `cut` of table `kind`: its bands (`list`, group g in [first[g], first[g] + count[g])) dealt to
+// workgroups, most expensive first, then the edge items of the split bands.
+template <typename T>
+std::vector<native::BlockItem> block_cut_items(const qi_plan* p, int kind, int cut, qi_plan::BlockTable::ItemList& il,
+                                               const std::vector<native::BlockBandT<T>>& list, const int32_t* first,
+                                               const int32_t* count, int64_t split_blocks) {
+  std::vector<native::BlockItem> items;
+  for (int g = 0; g < kBlockGroups; ++g) {
+    if (count[g] == 0) continue;
+    // the group's bands are dealt to `nchunk` workgroups per block (each pays one forward transform of the block)
+    const int per_wg = cut == 0 ? p->native_blk_bands : p->native_blk_bands_batch;
+    const int32_t nchunk = (int32_t)ceil_div(count[g], per_wg);
+    const int64_t nblocks = ceil_div(p->n, native::block_valid(kBlockGroupWq[g]));
+    if (tune_env("QI_NATIVE_VERBOSE")) {
+      auto count_if = [&](auto pred) { return (int)std::count_if(list.begin() + first[g], list.begin() + first[g] + count[g], pred); };
+      fprintf(stderr, "[qi plan] block table %d cut %d, reach <= %d%s: %d bands (%d analytic, %d narrow, %d half) in %d workgroups x %lld blocks\n", kind, cut,
+              g == 3 ? 1024 : 256 * (kBlockGroupWq[g] & 15), g == 3 ? " (8192-sample blocks)" : "", count[g],
+              count_if([](const native::BlockBandT<T>& b) { return b.analytic != 0; }),
+              count_if([](const native::BlockBandT<T>& b) { return b.narrow == 1; }),
+              count_if([](const native::BlockBandT<T>& b) { return b.narrow == 2; }), nchunk, (long long)nblocks);
+    }
+    for (int32_t c = 0; c < nchunk; ++c) {
+      const int32_t lo = first[g] + (int32_t)((int64_t)count[g] * c / nchunk);
+      const int32_t hi = first[g] + (int32_t)((int64_t)count[g] * (c + 1) / nchunk);
+      for (int64_t b = 0; b < nblocks; ++b) items.push_back({kBlockGroupWq[g], (int32_t)b, lo, hi - lo, il.nplanes, 0});
+      il.nplanes += 1;
+    }
+  }
+  std::stable_sort(items.begin(), items.end(), [](const native::BlockItem& x, const native::BlockItem& y) {
+    const bool lx = x.wq == native::kBlkLongWq, ly = y.wq == native::kBlkLongWq;
+    return lx != ly ? lx : x.band_count > y.band_count;
+  });
+  for (size_t i = 0; i < items.size(); ++i) items[i].stat_slot = (int32_t)i;
+  il.nitems = (int32_t)items.size();
+  il.nlong = (int32_t)std::count_if(items.begin(), items.end(), [](const native::BlockItem& x) { return x.wq == native::kBlkLongWq; });
+  if (kind == 0 && p->nsplit > 0) {
+    // the edge items of the split bands ride at the end of the launch (light items: they fill its tail); each split
+    // band has a per-time plane and one partial slot per block like the other bands of the launch
+    // -- in the table for many records one item per block covers all of them (one plane, one launch of its own)
+    const int wq = (int)(p->native_split_e / 512);
+    il.edge_merged = (cut == 1 && p->native_edge_merge != 0) || sizeof(T) == 8;  // (float64: always, k_block64_edge)
+    if (il.edge_merged) {
+      for (int64_t b = 0; b < split_blocks; ++b)
+        items.push_back({-wq, (int32_t)b, 0, p->nsplit, il.nplanes, (int32_t)items.size()});
+      il.nplanes += 1;
+    } else {
+      for (int32_t sb = 0; sb < p->nsplit; ++sb) {
+        for (int64_t b = 0; b < split_blocks; ++b)
+          items.push_back({-wq, (int32_t)b, sb, 0, il.nplanes, (int32_t)items.size()});
+        il.nplanes += 1;
+      }
+    }
+    il.nedge_items = (int32_t)items.size() - il.nitems;
+  }
+  return items;
+}
+
+// float64: the bands' real Gaussian filter weights, weight(k) = amp exp2(-(cw dk)^2) with dk = k - kappa wrapped to
+// +-kBlk / 2 (Gabor banks: the aliases of the half-sample grid alternate in sign) -- block_bands' formula, in double
+std::vector<double> block_gauss_weights(const std::vector<native::BlockBandT<double>>& list, int demod) {
+  std::vector<double> gw(list.size() * (size_t)native::kBlk);
+  for (size_t q = 0; q < list.size(); ++q) {
+    const auto& b = list[q];
+    for (int k = 0; k < native::kBlk; ++k) {
+      if (b.analytic == 2) {  // an atom shorter than 2.75 samples: every alias that matters, alternating in sign
+        double acc = 0.0;
+        for (int m = -6; m <= 6; ++m) {
+          const double e = (double)b.cw * ((double)(k - b.kappa_int) - (double)b.kappa_frac + (double)native::kBlk * m);
+          acc += ((m & 1) && !demod ? -1.0 : 1.0) * std::exp2(-e * e);
+        }
+        gw[q * native::kBlk + k] = (double)b.amp * acc;
+        continue;
+      }
+      double dk = (double)(k - b.kappa_int) - (double)b.kappa_frac, amp = (double)b.amp;
+      if (dk > (double)(native::kBlk / 2)) {
+        dk -= (double)native::kBlk;
+        if (!demod) amp = -amp;
+      }
+      if (demod && dk < -(double)(native::kBlk / 2)) dk += (double)native::kBlk;
+      const double e = (double)b.cw * dk;
+      gw[q * native::kBlk + k] = amp * std::exp2(-e * e);
+    }
+  }
+  return gw;
+}
+
+// demodulation tables of the float64 Stockwell bands (exact integer phases): per band exp(-2 pi i idx 256 i / n), i < 16; per
+// plan exp(-2 pi i 1024 j / n) and exp(-2 pi i j / n)
+int upload_demod_tables(qi_plan* p, qi_plan::BlockTable::ItemList& il, const std::vector<native::BlockBandT<double>>& list) {
+  std::vector<double2> pw(list.size() * 16);
+  for (size_t q = 0; q < list.size(); ++q)
+    for (int i = 0; i < 16; ++i) pw[q * 16 + i] = unit_root((int64_t)(((__int128)list[q].shift * 256 * i) % p->n), p->n, true);
+  QI_TRY(upload_table(&il.d_demod_pow, pw));
+  if (p->d_demod_t1 || p->n < 1024) return QI_OK;
+  std::vector<double2> t1((size_t)(p->n / 1024)), t2(1024);
+  for (int64_t j = 0; j < p->n / 1024; ++j) t1[(size_t)j] = unit_root(1024 * j, p->n, true);
+  for (int64_t j = 0; j < 1024; ++j) t2[(size_t)j] = unit_root(j, p->n, true);
+  QI_TRY(upload_table(&p->d_demod_t1, t1));
+  return upload_table(&p->d_demod_t2, t2);
+}
 
 // `taps` holds one 4096-sample circular-convolution kernel per pick (float64, on the device, same order):
 // transform them, convert to the engine's precision and upload the per-group band lists.
 template <typename T>
 int finish_block_table(qi_plan* p, int kind, int demod, const std::vector<BlockPick>& picks, double2* taps,
                        hipStream_t st) {
+  constexpr bool F64 = sizeof(T) == 8;
   auto& bt = p->blk[kind];
   bt.release();
   p->dual_valid[0] = p->dual_valid[1] = false;
@@ -408,222 +655,38 @@ int finish_block_table(qi_plan* p, int kind, int demod, const std::vector<BlockP
                                 1.0 / (double)native::kBlk, st));
   bt.rows = rows;
   bt.demod = demod;
-  // reach groups: taps within 256, 512, 1024 samples (4096-sample blocks), and the long blocks (8192 samples) for the
-  // narrow Gaussian bands of the 1024-sample group whose spectrum lies in the lower half of the 8192-bin grid
-  constexpr int NG = 4;
-  const int wqs[NG] = {1, 2, 4, native::kBlkLongWq};
-  // (float64 tables: Gaussian weights in double from every bin -- the shortcuts below drop weights under 2^-30 of the peak)
-  constexpr bool F64 = sizeof(T) == 8;
-  const double drop_bits = F64 ? 52.0 : 30.0;
-  // first bin of the 256-bin window of a long band: centred on the band, kept inside the lower half of the 8192-bin grid
-  // (the half a long block holds)
-  auto long_window = [&](const BlockPick& pk) {
-    return std::min<int64_t>(std::max<int64_t>((int64_t)std::llround(2.0 * pk.kappa) - 128, 0), native::kBlk - 256);
-  };
-  auto long_ok = [&](const BlockPick& pk, int cut) {
-    if (F64) return false;
-    if (cut == 0) return false;  // few records: the long blocks' own launch would cost more than the blocks save
-    if (!p->native_blk_long || !p->native_blk_analytic || !p->native_blk_narrow || pk.wq != 4 || !pk.analytic) return false;
-    if (p->n < 4 * native::kBlkLong) return false;
-    const double half8 = std::ceil(std::sqrt(30.0) / (0.5 * pk.cw));  // weights >= 2^-30 of the peak on the 8192-bin grid
-    const int64_t klo8 = long_window(pk);
-    return 2.0 * pk.kappa - half8 - 1.0 >= (double)klo8 && 2.0 * pk.kappa + half8 + 1.0 <= (double)(klo8 + 255);
-  };
-  int64_t split_blocks = 0;
-  if (kind == 0 && p->nsplit > 0) {
-    split_blocks = ceil_div(p->n, native::block_valid((int)(p->native_split_e / 512)));
-    if (split_blocks > bt.max_blocks) bt.max_blocks = split_blocks;
-    for (auto& il : bt.var)
-      for (int32_t sb = 0; sb < p->nsplit; ++sb) il.h_bands.push_back({p->h_split_bands[sb], (int32_t)split_blocks});
-  }
+  const bool edges = kind == 0 && p->nsplit > 0;
+  const int64_t split_blocks = edges ? ceil_div(p->n, native::block_valid((int)(p->native_split_e / 512))) : 0;
+  bt.max_blocks = split_blocks;
   for (int v = 0; v < 2; ++v) {
     auto& il = bt.var[v];
+    for (int32_t sb = 0; sb < p->nsplit && edges; ++sb) il.h_bands.push_back({p->h_split_bands[sb], (int32_t)split_blocks});
     std::vector<native::BlockBandT<T>> list;
-    int32_t group_first[NG] = {0, 0, 0, 0}, group_count[NG] = {0, 0, 0, 0};
-    for (int g = 0; g < NG; ++g) {
-      const int32_t first = (int32_t)list.size();
+    int32_t group_first[kBlockGroups], group_count[kBlockGroups];
+    for (int g = 0; g < kBlockGroups; ++g) {
+      group_first[g] = (int32_t)list.size();
       for (int32_t r = 0; r < rows; ++r) {
-        const bool is_long = long_ok(picks[r], v);
-        const int home = is_long ? native::kBlkLongWq : picks[r].wq;  // the group that takes this band
-        if (home != wqs[g]) continue;
-        native::BlockBandT<T> b;
-        memset(&b, 0, sizeof(b));
-        b.out_band = picks[r].band;
-        b.bank_row = r;
-        b.shift = (int32_t)picks[r].shift;
-        b.analytic = p->native_blk_analytic ? picks[r].analytic : 0;
-        const double grid = is_long ? 2.0 : 1.0;  // the band on the 8192-bin grid of a long block: twice the bins
-        const double kappa = grid * picks[r].kappa, cw = picks[r].cw / grid;
-        b.kappa_int = (int32_t)std::floor(kappa);
-        b.kappa_frac = (T)(kappa - std::floor(kappa));
-        b.cw = (T)cw;
-        b.amp = (T)(picks[r].amp / grid);
-        // weights >= 2^-30 of the peak: |cw dk| <= sqrt(30) (float64: 2^-52)
-        const double half = std::ceil(std::sqrt(drop_bits) / cw);
-        if (F64 && !b.analytic) {
-          set_error("block engine: float64 tables take analytic (Gaussian) bands only");
-          return QI_ERR_STATE;
-        }
-        // (float64 since round 5: `half` is then the 2^-52 half-width, the weight comes from the table -- bands of the 512- and
-        // 1024-sample reach groups; analytic = 2, an aliased spectrum, is not narrow)
-        if ((!F64 || (b.analytic == 1 && p->native_blk64_wtab && p->native_blk64_narrow)) && b.analytic && p->native_blk_narrow &&
-            2.0 * half + 2.0 <= 256.0) {
-          b.narrow = 1;
-          b.klo = is_long ? (int32_t)long_window(picks[r])
-                          : (int32_t)((((int64_t)std::llround(kappa) - 128) % native::kBlk + native::kBlk) % native::kBlk);
-          const int ba = b.klo >> 8;
-          b.rot_a[0] = (T)std::cos(2.0 * M_PI * ba / 16.0);
-          b.rot_a[1] = (T)std::sin(2.0 * M_PI * ba / 16.0);
-          b.rot_b[0] = (T)std::cos(2.0 * M_PI * ((ba + 1) & 15) / 16.0);
-          b.rot_b[1] = (T)std::sin(2.0 * M_PI * ((ba + 1) & 15) / 16.0);
-          b.rot8_a[0] = (T)std::cos(M_PI * ba / 16.0);  // exp(2 pi i 256 b / 8192)
-          b.rot8_a[1] = (T)std::sin(M_PI * ba / 16.0);
-          b.rot8_b[0] = (T)std::cos(M_PI * (ba + 1) / 16.0);
-          b.rot8_b[1] = (T)std::sin(M_PI * (ba + 1) / 16.0);
-        } else if (!F64 && b.analytic && p->native_blk_half && kappa - half - 1.0 >= 0.0 && kappa + half + 1.0 < (double)(native::kBlk / 2)) {
-          b.narrow = 2;  // every weight above 2^-30 of the peak lies in the lower half of the block spectrum
-        }
-        if (b.analytic && p->native_blk_fastw && b.amp > (T)0 && kappa - half - 1.0 >= 0.0 && kappa + half + 1.0 < (double)native::kBlk) {
-          b.nowrap = 1;
-          b.la = (T)std::log2(picks[r].amp / grid);
-        }
-        for (int k = 0; k < 4; ++k) {
-          // r^(2^k), r = exp(-2 pi i idx 256 / n), from the exact integer phase
-          const int64_t m = (int64_t)(((__int128)picks[r].shift * 256 * (1 << k)) % p->n);
-          const double ang = -2.0 * M_PI * (double)m / (double)p->n;
-          b.rot[2 * k] = (T)std::cos(ang);
-          b.rot[2 * k + 1] = (T)std::sin(ang);
-        }
-        {
-          const int64_t m1 = picks[r].shift % p->n;  // one sample: the odd sample of a long block's pair
-          b.rot1[0] = (T)std::cos(-2.0 * M_PI * (double)m1 / (double)p->n);
-          b.rot1[1] = (T)std::sin(-2.0 * M_PI * (double)m1 / (double)p->n);
-        }
-        list.push_back(b);
+        const bool is_long = !F64 && long_ok(p, picks[r], v);
+        if ((is_long ? native::kBlkLongWq : picks[r].wq) != kBlockGroupWq[g]) continue;  // another group takes this band
+        list.emplace_back();
+        QI_TRY(block_band_desc<T>(p, picks[r], r, is_long, &list.back()));
       }
-      group_first[g] = first;
-      group_count[g] = (int32_t)list.size() - first;
+      group_count[g] = (int32_t)list.size() - group_first[g];
       if (group_count[g] == 0) continue;
-      const int64_t nblocks = ceil_div(p->n, native::block_valid(wqs[g]));
+      const int64_t nblocks = ceil_div(p->n, native::block_valid(kBlockGroupWq[g]));
       if (nblocks > bt.max_blocks) bt.max_blocks = nblocks;
-      for (int32_t q = first; q < (int32_t)list.size(); ++q) {
+      for (int32_t q = group_first[g]; q < (int32_t)list.size(); ++q) {
         il.h_bands.push_back({list[q].out_band, (int32_t)nblocks});
-        il.h_route.push_back({list[q].out_band, wqs[g], list[q].analytic, list[q].narrow, list[q].nowrap});
+        il.h_route.push_back({list[q].out_band, kBlockGroupWq[g], list[q].analytic, list[q].narrow, list[q].nowrap});
       }
     }
-    std::vector<native::BlockItem> items;
-    for (int g = 0; g < NG; ++g) {
-      const int32_t first = group_first[g], count = group_count[g];
-      if (count == 0) continue;
-      // the group's bands are dealt to `nchunk` workgroups per block (each pays one forward transform of the block)
-      const int per_wg = v == 0 ? p->native_blk_bands : p->native_blk_bands_batch;
-      const int32_t nchunk = (int32_t)ceil_div(count, per_wg);
-      const int64_t nblocks = ceil_div(p->n, native::block_valid(wqs[g]));
-      if (tune_env("QI_NATIVE_VERBOSE"))
-        fprintf(stderr, "[qi plan] block table %d cut %d, reach <= %d%s: %d bands (%d analytic, %d narrow, %d half) in %d workgroups x %lld blocks\n", kind, v,
-                g == 3 ? 1024 : 256 * (wqs[g] & 15), g == 3 ? " (8192-sample blocks)" : "", count,
-                (int)std::count_if(list.begin() + first, list.begin() + first + count, [](const native::BlockBandT<T>& b) { return b.analytic != 0; }),
-                (int)std::count_if(list.begin() + first, list.begin() + first + count, [](const native::BlockBandT<T>& b) { return b.narrow == 1; }),
-                (int)std::count_if(list.begin() + first, list.begin() + first + count, [](const native::BlockBandT<T>& b) { return b.narrow == 2; }),
-                nchunk, (long long)nblocks);
-      for (int32_t c = 0; c < nchunk; ++c) {
-        const int32_t lo = first + (int32_t)((int64_t)count * c / nchunk);
-        const int32_t hi = first + (int32_t)((int64_t)count * (c + 1) / nchunk);
-        for (int64_t b = 0; b < nblocks; ++b) {
-          native::BlockItem it;
-          it.wq = wqs[g];
-          it.block = (int32_t)b;
-          it.band_first = lo;
-          it.band_count = hi - lo;
-          it.plane = il.nplanes;
-          it.stat_slot = 0;
-          items.push_back(it);
-        }
-        il.nplanes += 1;
-      }
+    il.h_items = block_cut_items<T>(p, kind, v, il, list, group_first, group_count, split_blocks);
+    if constexpr (F64) {
+      if (p->native_blk64_wtab && !list.empty()) QI_TRY(upload_table(&il.d_gauss_w, block_gauss_weights(list, demod)));
+      if (demod && !list.empty()) QI_TRY(upload_demod_tables(p, il, list));
     }
-    std::stable_sort(items.begin(), items.end(), [](const native::BlockItem& x, const native::BlockItem& y) {
-      const bool lx = x.wq == native::kBlkLongWq, ly = y.wq == native::kBlkLongWq;
-      return lx != ly ? lx : x.band_count > y.band_count;
-    });
-    for (size_t i = 0; i < items.size(); ++i) items[i].stat_slot = (int32_t)i;
-    il.nitems = (int32_t)items.size();
-    il.nlong = (int32_t)std::count_if(items.begin(), items.end(), [](const native::BlockItem& x) { return x.wq == native::kBlkLongWq; });
-    if (kind == 0 && p->nsplit > 0) {
-      // the edge items of the split bands ride at the end of the launch (light items: they fill its tail); each split
-      // band has a per-time plane and one partial slot per block like the other bands of the launch
-      // -- in the table for many records one item per block covers all of them (one plane, one launch of its own)
-      const int wq = (int)(p->native_split_e / 512);
-      il.edge_merged = (v == 1 && p->native_edge_merge != 0) || F64;  // (float64: always, k_block64_edge)
-      if (il.edge_merged) {
-        for (int64_t b = 0; b < split_blocks; ++b)
-          items.push_back({-wq, (int32_t)b, 0, p->nsplit, il.nplanes, (int32_t)items.size()});
-        il.nplanes += 1;
-      } else {
-        for (int32_t sb = 0; sb < p->nsplit; ++sb) {
-          for (int64_t b = 0; b < split_blocks; ++b)
-            items.push_back({-wq, (int32_t)b, sb, 0, il.nplanes, (int32_t)items.size()});
-          il.nplanes += 1;
-        }
-      }
-      il.nedge_items = (int32_t)items.size() - il.nitems;
-    }
-    il.h_items = items;
-    if (F64 && p->native_blk64_wtab && !list.empty()) {
-      // float64: the bands' real Gaussian filter weights, weight(k) = amp exp2(-(cw dk)^2) with dk = k - kappa wrapped to
-      // +-kBlk / 2 (Gabor banks: the aliases of the half-sample grid alternate in sign) -- block_bands' formula, in double
-      std::vector<double> gw(list.size() * (size_t)native::kBlk);
-      for (size_t q = 0; q < list.size(); ++q) {
-        const auto& b = list[q];
-        for (int k = 0; k < native::kBlk; ++k) {
-          if (b.analytic == 2) {  // an atom shorter than 2.75 samples: every alias that matters, alternating in sign
-            double acc = 0.0;
-            for (int m = -6; m <= 6; ++m) {
-              const double e = (double)b.cw * ((double)(k - b.kappa_int) - (double)b.kappa_frac + (double)native::kBlk * m);
-              acc += ((m & 1) && !demod ? -1.0 : 1.0) * std::exp2(-e * e);
-            }
-            gw[q * native::kBlk + k] = (double)b.amp * acc;
-            continue;
-          }
-          double dk = (double)(k - b.kappa_int) - (double)b.kappa_frac, amp = (double)b.amp;
-          if (dk > (double)(native::kBlk / 2)) {
-            dk -= (double)native::kBlk;
-            if (!demod) amp = -amp;
-          }
-          if (demod && dk < -(double)(native::kBlk / 2)) dk += (double)native::kBlk;
-          const double e = (double)b.cw * dk;
-          gw[q * native::kBlk + k] = amp * std::exp2(-e * e);
-        }
-      }
-      QI_HIP(hipMalloc((void**)&il.d_gauss_w, gw.size() * sizeof(double)));
-      QI_HIP(hipMemcpy(il.d_gauss_w, gw.data(), gw.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (F64 && demod && !list.empty()) {
-      // demodulation tables of the float64 Stockwell bands (exact integer phases, long double): per band exp(-2 pi i idx 256 i / n)
-      const long double two_pi = 6.283185307179586476925286766559005768L;
-      auto root = [&](int64_t m) {
-        const long double ang = -two_pi * (long double)(((m % p->n) + p->n) % p->n) / (long double)p->n;
-        return make_double2((double)cosl(ang), (double)sinl(ang));
-      };
-      std::vector<double2> pw(list.size() * 16);
-      for (size_t q = 0; q < list.size(); ++q)
-        for (int i = 0; i < 16; ++i) pw[q * 16 + i] = root((int64_t)(((__int128)list[q].shift * 256 * i) % p->n));
-      QI_HIP(hipMalloc((void**)&il.d_demod_pow, pw.size() * sizeof(double2)));
-      QI_HIP(hipMemcpy(il.d_demod_pow, pw.data(), pw.size() * sizeof(double2), hipMemcpyHostToDevice));
-      if (!p->d_demod_t1 && p->n >= 1024) {
-        std::vector<double2> t1((size_t)(p->n / 1024)), t2(1024);
-        for (int64_t j = 0; j < p->n / 1024; ++j) t1[(size_t)j] = root(1024 * j);
-        for (int64_t j = 0; j < 1024; ++j) t2[(size_t)j] = root(j);
-        QI_HIP(hipMalloc((void**)&p->d_demod_t1, t1.size() * sizeof(double2)));
-        QI_HIP(hipMemcpy(p->d_demod_t1, t1.data(), t1.size() * sizeof(double2), hipMemcpyHostToDevice));
-        QI_HIP(hipMalloc((void**)&p->d_demod_t2, t2.size() * sizeof(double2)));
-        QI_HIP(hipMemcpy(p->d_demod_t2, t2.data(), t2.size() * sizeof(double2), hipMemcpyHostToDevice));
-      }
-    }
-    QI_HIP(hipMalloc((void**)&il.d_bands, list.size() * sizeof(native::BlockBandT<T>)));
-    QI_HIP(hipMemcpy(il.d_bands, list.data(), list.size() * sizeof(native::BlockBandT<T>), hipMemcpyHostToDevice));
-    QI_HIP(hipMalloc((void**)&il.d_items, items.size() * sizeof(native::BlockItem)));
-    QI_HIP(hipMemcpy(il.d_items, items.data(), items.size() * sizeof(native::BlockItem), hipMemcpyHostToDevice));
+    QI_TRY(upload_table(&il.d_bands, list));
+    QI_TRY(upload_table(&il.d_items, il.h_items));
   }
   QI_HIP(hipStreamSynchronize(st));
   bt.ready = true;
@@ -643,28 +706,21 @@ int build_block_gabor(qi_plan* p, int kind, int32_t B, const std::vector<BlockPi
     set_error("workspace too small for the block-engine taps");
     return QI_ERR_NOMEM;
   }
-  const int wqs[3] = {1, 2, 4};
-  int32_t* d_ids = nullptr;
-  QI_HIP(hipMalloc((void**)&d_ids, picks.size() * sizeof(int32_t)));
-  int rc = QI_OK;
+  DeviceTemp<int32_t> d_ids;
+  QI_HIP(hipMalloc((void**)&d_ids.ptr, picks.size() * sizeof(int32_t)));
   size_t r = 0;
   // picks are ordered by group, so each group is one run of rows
-  for (int g = 0; g < 3 && rc == QI_OK; ++g) {
+  for (int wq : {1, 2, 4}) {
     std::vector<int32_t> ids;
     for (const auto& pk : picks)
-      if (pk.wq == wqs[g]) ids.push_back(pk.band);
+      if (pk.wq == wq) ids.push_back(pk.band);
     if (ids.empty()) continue;
-    if (hipMemcpy(d_ids + r, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-      set_error("hipMemcpy of block band ids failed");
-      rc = QI_ERR_HIP;
-      break;
-    }
-    rc = native::launch_block_taps_gabor(taps + r * native::kBlk, 256 * wqs[g], d_par, B, d_ids + r, (int)ids.size(), st);
+    QI_HIP(hipMemcpy(d_ids.ptr + r, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    QI_TRY(native::launch_block_taps_gabor(taps + r * native::kBlk, 256 * wq, d_par, B, d_ids.ptr + r, (int)ids.size(), st));
     r += ids.size();
   }
-  if (rc == QI_OK) rc = finish_block_table<T>(p, kind, 0, picks, taps, st);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(d_ids);
+  const int rc = finish_block_table<T>(p, kind, 0, picks, taps, st);
+  (void)hipStreamSynchronize(st);  // (the tap kernels read d_ids)
   return rc;
 }
 
@@ -691,32 +747,6 @@ int build_block_stx(qi_plan* p, const std::vector<BlockPick>& picks, const std::
   return finish_block_table<T>(p, 2, 1, picks, taps, st);
 }
 
-// Zoom engine level of a band with `len` occupied bins out of Lf (-1: not eligible): the coarsest grid
-// M_g = (Lf / 64) << g on which the band is oversampled at least 4 times.
-int zoom_class(const qi_plan* p, int table, int64_t Lf, int64_t len) {
-  if (!p->native_zoom || table == 3 || len <= 0 || Lf % native::kZoomD != 0) return -1;
-  const int64_t M0 = Lf / native::kZoomD;
-  if (!is_pow2(M0)) return -1;
-  // the coarse stage works in 4096-point planes: a short record starts at the first grid level that fills one
-  int g_min = 0;
-  while ((M0 << g_min) < native::kBlk) ++g_min;
-  for (int g = g_min; g < native::kZoomLevels; ++g) {
-    if (p->n % ((int64_t)native::kZoomD * native::zoom_steps(g) * 4) != 0) return -1;
-    if (native::kZoomOversample * len <= (M0 << g)) {
-      // (the finest grid costs more in the coarse stage than the two-pass kernels save -- where those exist; at other
-      // lengths it keeps the table off the hipFFT engine)
-      if (g > p->native_zoom_max_level && native_len_ok(Lf)) return -1;
-      // on the coarsest grid the band may be oversampled far more than 4 times: shorter interpolators (classes 5, 6)
-      if (g == 0 && p->native_zoom_short) {
-        if ((int64_t)native::zoom_design_oversampling(6) * len <= M0) return 6;
-        if ((int64_t)native::zoom_design_oversampling(5) * len <= M0) return 5;
-      }
-      return g;
-    }
-  }
-  return -1;
-}
-
 // Classify bands by spectrum support, allocate and fill one table.
 template <typename T>
 int make_native_table(qi_plan* p, int table, int circular, int64_t L, int32_t B, const std::vector<int32_t>& ids,
@@ -728,21 +758,18 @@ int make_native_table(qi_plan* p, int table, int circular, int64_t L, int32_t B,
   for (size_t q = 0; q < ids.size(); ++q) {
     native::BandDesc& d = bands[q];
     memset(&d, 0, sizeof(d));
-    const int64_t lo = (int64_t)sup[3 * q + 1], hi = (int64_t)sup[3 * q + 2];
-    const int64_t len = hi >= lo ? hi - lo + 1 : 0;
+    const int64_t len = support_len(&sup[3 * q]);
     d.out_band = ids[q];
     d.edge = edge_w.empty() ? 0 : edge_w[q];
     d.edge_slot = (int32_t)q;  // the edge list is in the order of `ids`
     d.add_row = add_row.empty() ? 0 : add_row[q];
-    const int zc = zoom_class(p, table, L, len);
-    if (zc >= 0 || (len > 0 && len <= narrow_limit(p, table, L))) {
-      d.mode = zc >= 0 ? 2 + zc : 0;  // 0: one-pass loader of pass 2; 2 + c: zoom engine, class c
-      d.k_lo = (int32_t)lo;
+    d.mode = band_mode(p, table, L, len);
+    if (d.mode != 1) {
+      d.k_lo = (int32_t)(int64_t)sup[3 * q + 1];
       d.k_len = (int32_t)len;
       d.src_off = compact;
       compact += len;
     } else {
-      d.mode = 1;
       d.bank_row = ngen++;
     }
   }
@@ -755,8 +782,148 @@ int make_native_table(qi_plan* p, int table, int circular, int64_t L, int32_t B,
   }
   if (compact > 0) QI_HIP(hipMalloc(&t.Hc, (size_t)compact * sizeof(cplx<T>)));
   if (ngen > 0) QI_HIP(hipMalloc(&t.Hfull, (size_t)ngen * L * sizeof(cplx<T>)));
-  QI_TRY(fill_native_bank<T>(p, t, circular, L, B, ids, bands, d_par, st));
+  QI_TRY(fill_native_bank<T>(p, table, circular, L, B, ids, bands, d_par, st));
   return upload_native_table(p, table, L, bands);
+}
+
+// ---- native bank -------------------------------------------------------------------------------------------------------
+struct GaborRoutes {
+  std::vector<BlockPick> picks;           // block engine
+  std::vector<int32_t> shorts, short_w;   // short atoms (table 3) and their reach in samples
+  std::vector<int32_t> keep;              // the bank's own table (zoom, float64 zoom, two-pass; split bands)
+};
+bool gabor_can_block(const qi_plan* p, int circular) {
+  return !circular && p->native_block && is_pow2(p->n) && p->n >= 4 * native::kBlk;
+}
+
+// Every band of a Gabor bank to the block engine, the short-atom table or the bank's own table, from its support
+// `sup` [B][3] and its parameters `h_par` [4][B].
+GaborRoutes classify_gabor_bands(const qi_plan* p, int bank, int64_t L, int32_t B, const std::vector<double>& sup,
+                                 const double* h_par) {
+  GaborRoutes out;
+  const int64_t n = p->n;
+  const int circular = bank == QI_BANK_ATOMS;
+  const bool f64 = p->d.dtype == QI_F64;
+  const bool can_short = !circular && p->native_short && native_len_ok(n) && is_pow2(n);
+  const bool can_block = gabor_can_block(p, circular);
+  for (int32_t j = 0; j < B; ++j) {
+    const int64_t len = support_len(&sup[3 * j]);
+    // taps with |x| <= w are above 2^-30 of the atom's peak: exp(-p_re x^2) >= 2^-30 (float64: 2^-52)
+    const double w = std::ceil(std::sqrt(drop_bits(f64) * M_LN2 / h_par[j])) + 1.0;
+    const int group = can_block ? block_group_of(w) : 0;
+    // (a band of the widest reach groups -- half of each 4096-sample block is overlap there -- goes to the zoom
+    // engine instead when its spectrum fits one of its grids)
+    // (float64: a band the float64 zoom takes stays there, unless it needs one of the finest grids)
+    const int z64 = z64_level(p, bank, L, len);
+    const bool zoom_first = (z64 >= 0 && !z64_level_for_block(p, z64)) ||
+                            (group > p->native_blk_maxwq && zoom_class(p, bank, L, len) >= 0);
+    bool to_block = group > 0 && !zoom_first, wide = band_mode(p, bank, L, len) == 1;
+    BlockPick pk{j, group, 0};
+    if (to_block) {
+      const double p_re = h_par[j], p_im = h_par[B + j], om = h_par[2 * B + j], am = h_par[3 * B + j];
+      const bool pure = p_im == 0.0 && p_re > 0.0 && om > 0.0 && om < M_PI;  // a pure Gabor atom, centre frequency inside (0, pi)
+      // at least 2.75 samples wide (no alias of its Gaussian spectrum above 1e-16): the Gaussian itself
+      if (pure && p_re <= 1.0 / (2.0 * 2.75 * 2.75)) pk.analytic = 1;
+      // float64, an atom SHORTER than 2.75 samples (the top band of an order-1 or order-2 table): its sampled spectrum is the
+      // Gaussian plus its aliases, sum over m of (-1)^m G(theta + 2 pi m) after the half-sample factor -- still real weights,
+      // which the plan-time weight table holds summed (analytic = 2: table only; float32 reads such a band's bank row)
+      else if (pure && f64 && p->native_blk64_wtab) pk.analytic = 2;
+      if (pk.analytic) gabor_gaussian(pk, p_re, om, am);
+      // (the float64 block kernels evaluate Gaussians only: any other band is a short atom if it can be, whatever its spectrum)
+      if (f64 && !pk.analytic) to_block = false, wide = true;
+    }
+    if (to_block) {
+      out.picks.push_back(pk);
+    } else if (can_short && wide && w <= 8192.0 && w < (double)n / 8) {
+      out.shorts.push_back(j);
+      out.short_w.push_back((int32_t)w);
+    } else {
+      out.keep.push_back(j);
+    }
+  }
+  return out;
+}
+
+// Bands left for the two-pass kernels because the reference cuts their atoms off at |x| = n / 2 (a spectrum with
+// 1 / k side lobes): with the last `e` samples before the cut tapered away the spectrum is narrow enough for the
+// zoom engine; what the taper removed is a pair of e-tap filters at lags +-n / 2 (k_block_edge), added back by the
+// zoom kernel.  The split bands' rows of `sup` are replaced by the tapered supports.
+int find_split_bands(qi_plan* p, int bank, int64_t L, int32_t B, const double* d_par, const std::vector<int32_t>& keep,
+                     std::vector<double>* sup, std::vector<int32_t>* split, hipStream_t st) {
+  const int64_t se = p->native_split_e;
+  if (!(se == 512 || se == 1024 || se == 2048) || p->n < 8 * se) return QI_OK;
+  // float64: "the zoom engine" is the float64 zoom
+  const bool f64 = p->d.dtype == QI_F64;
+  for (int32_t j : keep) {
+    const int64_t len = support_len(&(*sup)[3 * j]);
+    // (a band the one-pass loader of the two-pass kernels would take stays there only where those kernels exist)
+    const int mode = band_mode(p, bank, L, len);
+    if (f64 ? z64_level(p, bank, L, len) >= 0 : (mode >= 2 || (mode == 0 && native_len_ok(L)))) continue;
+    std::vector<double> part;
+    QI_TRY(analyse_support(p, 0, L, B, j, 1, d_par, &part, st, (double)se));
+    const int64_t tlen = support_len(part.data());
+    if (tune_env("QI_NATIVE_VERBOSE"))
+      fprintf(stderr, "[qi plan] band %d: support %lld bins as the reference cuts it, %lld bins tapered over %lld samples\n",
+              j, (long long)len, (long long)tlen, (long long)se);
+    if (f64 ? z64_level(p, bank, L, tlen) < 0 : zoom_class(p, bank, L, tlen) < 0) continue;
+    std::copy(part.begin(), part.end(), sup->begin() + 3 * j);
+    split->push_back(j);
+  }
+  return QI_OK;
+}
+
+// filter spectra of the edge pieces of the split bands: taps in float64, transformed, scaled by 1 / 4096
+template <typename T>
+int build_split_edges(qi_plan* p, int32_t B, const std::vector<int32_t>& split, const double* d_par, hipStream_t st) {
+  const size_t rows = split.size() * 2;
+  if (p->ws_bytes < rows * native::kBlk * sizeof(double2) + 4096) {
+    set_error("workspace too small for the taps of the split bands");
+    return QI_ERR_NOMEM;
+  }
+  double2* taps = reinterpret_cast<double2*>(p->ws);
+  QI_TRY(upload_table(&p->d_split_bands, split));
+  QI_TRY(native::launch_block_taps_edge(taps, (int)(p->native_split_e / 2), p->n, (double)p->native_split_e, d_par, B,
+                                        p->d_split_bands, (int)split.size(), st));
+  QI_TRY(fft_c2c<double>(p->fft, taps, native::kBlk, (int64_t)rows, HIPFFT_FORWARD, st));
+  QI_HIP(hipMalloc(&p->split_bank, rows * native::kBlk * sizeof(cplx<T>)));
+  QI_TRY(launch_bank_convert<T>(taps, static_cast<cplx<T>*>(p->split_bank), (int64_t)rows * native::kBlk, 0,
+                                1.0 / (double)native::kBlk, st));
+  QI_HIP(hipStreamSynchronize(st));
+  p->nsplit = (int32_t)split.size();
+  p->h_split_bands = split;
+  return QI_OK;
+}
+
+// Table 3: the short atoms in their circular (length n) form, and the list k_edge_fix corrects their edges from.
+template <typename T>
+int build_short_table(qi_plan* p, int32_t B, const std::vector<int32_t>& shorts, const std::vector<int32_t>& short_w,
+                      const double* d_par, const double* h_par, hipStream_t st) {
+  std::vector<double> sup_s((size_t)shorts.size() * 3);
+  size_t q = 0;
+  while (q < shorts.size()) {
+    size_t r = q + 1;
+    while (r < shorts.size() && shorts[r] == shorts[r - 1] + 1) ++r;
+    std::vector<double> part;
+    QI_TRY(analyse_support(p, 1, p->n, B, shorts[q], (int32_t)(r - q), d_par, &part, st));
+    std::copy(part.begin(), part.end(), sup_s.begin() + 3 * q);
+    q = r;
+  }
+  QI_TRY(make_native_table<T>(p, 3, 1, p->n, B, shorts, sup_s, short_w, d_par, st));
+  p->nat[3].nbands = B;
+  std::vector<native::EdgeBand> eb(shorts.size());
+  for (size_t i = 0; i < shorts.size(); ++i) {
+    const int32_t j = shorts[i];
+    eb[i].out_band = j;
+    eb[i].w = short_w[i];
+    eb[i].p_re = h_par[j];
+    eb[i].p_im = h_par[B + j];
+    eb[i].omega = h_par[2 * B + j];
+    eb[i].amp = h_par[3 * B + j];
+    if (short_w[i] > p->edge_wmax) p->edge_wmax = short_w[i];
+  }
+  QI_TRY(upload_table(&p->d_edge, eb));
+  p->nedge = (int32_t)eb.size();
+  return QI_OK;
 }
 
 // Native bank.  Every atom spectrum is analysed for its support: a narrow one keeps a compact window (one-pass
@@ -766,186 +933,33 @@ int make_native_table(qi_plan* p, int table, int circular, int64_t L, int32_t B,
 // samples -- the only ones where circular and linear differ -- are corrected by k_edge_fix.
 template <typename T>
 int build_native_bank(qi_plan* p, int bank, int32_t B, const double* d_par, const double* h_par, hipStream_t st) {
-  const int64_t n = p->n;
   const int circular = bank == QI_BANK_ATOMS;
-  const int64_t L = circular ? n : p->L;
+  const bool styx = bank == QI_BANK_STYX;
+  const int64_t L = circular ? p->n : p->L;
   std::vector<double> sup;
   QI_TRY(analyse_support(p, circular, L, B, 0, B, d_par, &sup, st));
-  std::vector<int32_t> keep, shorts, short_w;
-  std::vector<BlockPick> picks;
-  const bool can_short = !circular && p->native_short && native_len_ok(n) && is_pow2(n);
-  const bool can_block = !circular && p->native_block && is_pow2(n) && n >= 4 * native::kBlk;
-  for (int32_t j = 0; j < B; ++j) {
-    const int64_t lo = (int64_t)sup[3 * j + 1], hi = (int64_t)sup[3 * j + 2];
-    const int64_t len = hi >= lo ? hi - lo + 1 : 0;
-    // taps with |x| <= w are above 2^-30 of the atom's peak: exp(-p_re x^2) >= 2^-30 (float64: 2^-52)
-    const double w = std::ceil(std::sqrt((p->d.dtype == QI_F64 ? 52.0 : 30.0) * M_LN2 / h_par[j])) + 1.0;
-    // (a band of the widest reach groups -- half of each 4096-sample block is overlap there -- goes to the zoom
-    // engine instead when its spectrum fits one of its grids)
-    // (float64: a band the float64 zoom takes -- support within Lf / 16 bins -- stays there)
-    // (... its finest grid, Lf / 4 samples, oversamples it four times: at transform lengths below 2^19 the one-pass loader's
-    // limit is wider than that, and such a band belongs to the block engine)
-    // (... and not on one of its finest grids when the block engine can take the band: a band of 65 536 - 131 072 bins costs
-    // the float64 zoom 13.5 us per record -- a 2^19-point coarse transform and the LDS-window interpolation kernel --
-    // against 7.4 us on the block engine, measured at order 12 x 4 records: native_z64_block_from)
-    bool z64_first = p->d.dtype == QI_F64 && z64_table(p, bank) && len > 0 && len <= narrow_limit(p, bank, L) &&
-                     4 * len <= ((L / 64) << (p->native_z64_levels - 1));
-    if (z64_first && can_block && block_group_of(w) > 0 && 4 * len > ((L / 64) << (p->native_z64_block_from - 1))) z64_first = false;
-    if (can_block && block_group_of(w) > 0 && !z64_first &&
-        !(block_group_of(w) > p->native_blk_maxwq && zoom_class(p, bank, L, len) >= 0)) {
-      BlockPick pk{j, block_group_of(w), 0};
-      const double p_re = h_par[j], p_im = h_par[B + j], om = h_par[2 * B + j], am = h_par[3 * B + j];
-      // a pure Gabor atom at least 2.75 samples wide (no alias of its Gaussian spectrum above 1e-16) with its centre
-      // frequency inside (0, pi): its 4096-point filter spectrum is amp sqrt(pi / p) exp(-d^2 / 4p) exp(-i theta / 2)
-      if (p_im == 0.0 && p_re > 0.0 && p_re <= 1.0 / (2.0 * 2.75 * 2.75) && om > 0.0 && om < M_PI) {
-        pk.analytic = 1;
-        pk.kappa = om * (double)native::kBlk / (2.0 * M_PI);
-        pk.cw = (2.0 * M_PI / (double)native::kBlk) * std::sqrt(M_LOG2E / (4.0 * p_re));
-        pk.amp = am * std::sqrt(M_PI / p_re) / (double)native::kBlk;
-      }
-      // float64, an atom SHORTER than 2.75 samples (the top band of an order-1 or order-2 table): its sampled spectrum is the
-      // Gaussian plus its aliases, sum over m of (-1)^m G(theta + 2 pi m) after the half-sample factor -- still real weights,
-      // which the plan-time weight table holds summed (analytic = 2: table only; float32 reads such a band's bank row)
-      if (p->d.dtype == QI_F64 && !pk.analytic && p->native_blk64_wtab && p_im == 0.0 && p_re > 0.0 && om > 0.0 && om < M_PI) {
-        pk.analytic = 2;
-        pk.kappa = om * (double)native::kBlk / (2.0 * M_PI);
-        pk.cw = (2.0 * M_PI / (double)native::kBlk) * std::sqrt(M_LOG2E / (4.0 * p_re));
-        pk.amp = am * std::sqrt(M_PI / p_re) / (double)native::kBlk;
-      }
-      if (p->d.dtype == QI_F64 && !pk.analytic) {  // (the float64 block kernels evaluate Gaussians only)
-        if (can_short && w <= 8192.0 && w < (double)n / 8) {
-          shorts.push_back(j);
-          short_w.push_back((int32_t)w);
-        } else {
-          keep.push_back(j);
-        }
-        continue;
-      }
-      picks.push_back(pk);
-    } else if (can_short && zoom_class(p, bank, L, len) < 0 && !(len > 0 && len <= narrow_limit(p, bank, L)) && w <= 8192.0 &&
-               w < (double)n / 8) {
-      shorts.push_back(j);
-      short_w.push_back((int32_t)w);
-    } else {
-      keep.push_back(j);
-    }
+  GaborRoutes routes = classify_gabor_bands(p, bank, L, B, sup, h_par);
+  if (styx) {
+    release_styx_extras(p);
+    p->nat[3].release();
   }
-  // Bands left for the two-pass kernels because the reference cuts their atoms off at |x| = n / 2 (a spectrum with
-  // 1 / k side lobes): with the last `e` samples before the cut tapered away the spectrum is narrow enough for the
-  // zoom engine; what the taper removed is a pair of e-tap filters at lags +-n / 2 (k_block_edge), added back by the
-  // zoom kernel.
   std::vector<int32_t> split;
-  if (bank == QI_BANK_STYX) {
-    if (p->split_bank) (void)hipFree(p->split_bank);
-    if (p->d_split_bands) (void)hipFree(p->d_split_bands);
-    p->split_bank = nullptr;
-    p->d_split_bands = nullptr;
-    p->h_split_bands.clear();
-    p->nsplit = 0;
-  }
-  const int64_t se = p->native_split_e;
-  if (bank == QI_BANK_STYX && p->native_split && can_block && !picks.empty() &&  // (their edge items ride in the block launch)
-      (se == 512 || se == 1024 || se == 2048) && n >= 8 * se) {
-    // float64: "the zoom engine" is the float64 zoom, which takes a band whose support its finest grid oversamples four times
-    const bool z64 = p->d.dtype == QI_F64;
-    auto z64_takes = [&](int64_t len) {
-      return z64_table(p, bank) && len > 0 && len <= narrow_limit(p, bank, L) &&
-             4 * len <= ((L / 64) << (p->native_z64_levels - 1));
-    };
-    for (int32_t j : keep) {
-      const int64_t lo = (int64_t)sup[3 * j + 1], hi = (int64_t)sup[3 * j + 2];
-      const int64_t len = hi >= lo ? hi - lo + 1 : 0;
-      // (a band the one-pass loader of the two-pass kernels would take stays there only where those kernels exist)
-      if (z64 ? z64_takes(len)
-              : (zoom_class(p, bank, L, len) >= 0 || (len > 0 && len <= p->native_kmax && native_len_ok(L))))
-        continue;
-      std::vector<double> part;
-      QI_TRY(analyse_support(p, 0, L, B, j, 1, d_par, &part, st, (double)se));
-      const int64_t tlo = (int64_t)part[1], thi = (int64_t)part[2];
-      const int64_t tlen = thi >= tlo ? thi - tlo + 1 : 0;
-      if (tune_env("QI_NATIVE_VERBOSE"))
-        fprintf(stderr, "[qi plan] band %d: support %lld bins as the reference cuts it, %lld bins tapered over %lld samples\n",
-                j, (long long)len, (long long)tlen, (long long)se);
-      if (z64 ? !z64_takes(tlen) : zoom_class(p, bank, L, tlen) < 0) continue;
-      std::copy(part.begin(), part.end(), sup.begin() + 3 * j);
-      split.push_back(j);
-    }
-  }
+  if (styx && p->native_split && gabor_can_block(p, circular) && !routes.picks.empty())  // (their edge items ride in the block launch)
+    QI_TRY(find_split_bands(p, bank, L, B, d_par, routes.keep, &sup, &split, st));
   std::vector<double> sup_keep;
   std::vector<int32_t> add_row;
-  for (int32_t j : keep) {
+  for (int32_t j : routes.keep) {
     sup_keep.insert(sup_keep.end(), sup.begin() + 3 * j, sup.begin() + 3 * j + 3);
     const auto it = std::find(split.begin(), split.end(), j);
     add_row.push_back(it == split.end() ? 0 : (int32_t)(it - split.begin()) + 1);
   }
-  QI_TRY(make_native_table<T>(p, bank, circular, L, B, keep, sup_keep, {}, d_par, st, add_row));
-  if (!split.empty()) {
-    // filter spectra of the edge pieces: taps in float64, transformed, scaled by 1 / 4096
-    const size_t rows = split.size() * 2;
-    if (p->ws_bytes < rows * native::kBlk * sizeof(double2) + 4096) {
-      set_error("workspace too small for the taps of the split bands");
-      return QI_ERR_NOMEM;
-    }
-    double2* taps = reinterpret_cast<double2*>(p->ws);
-    QI_HIP(hipMalloc((void**)&p->d_split_bands, split.size() * sizeof(int32_t)));
-    int32_t* d_ids = p->d_split_bands;
-    int rc = hipMemcpy(d_ids, split.data(), split.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess
-                 ? QI_OK : QI_ERR_HIP;
-    if (rc == QI_OK)
-      rc = native::launch_block_taps_edge(taps, (int)(se / 2), n, (double)se, d_par, B, d_ids, (int)split.size(), st);
-    if (rc == QI_OK) rc = fft_c2c<double>(p->fft, taps, native::kBlk, (int64_t)rows, HIPFFT_FORWARD, st);
-    if (rc == QI_OK && hipMalloc(&p->split_bank, rows * native::kBlk * sizeof(cplx<T>)) != hipSuccess) rc = QI_ERR_NOMEM;
-    if (rc == QI_OK)
-      rc = launch_bank_convert<T>(taps, static_cast<cplx<T>*>(p->split_bank), (int64_t)rows * native::kBlk, 0,
-                                  1.0 / (double)native::kBlk, st);
-    (void)hipStreamSynchronize(st);
-    if (rc != QI_OK) {
-      if (rc == QI_ERR_HIP) set_error("building the edge pieces of the split bands failed");
-      return rc;
-    }
-    p->nsplit = (int32_t)split.size();
-    p->h_split_bands = split;
-  }
+  QI_TRY(make_native_table<T>(p, bank, circular, L, B, routes.keep, sup_keep, {}, d_par, st, add_row));
+  if (!split.empty()) QI_TRY(build_split_edges<T>(p, B, split, d_par, st));
   p->nat[bank].nbands = B;  // the table's panel has all B rows even when some are produced by table 3 / the block engine
-  if (bank == QI_BANK_STYX) {
-    std::stable_sort(picks.begin(), picks.end(), [](const BlockPick& x, const BlockPick& y) { return x.wq < y.wq; });
-    QI_TRY(build_block_gabor<T>(p, 0, B, picks, d_par, st));
-  }
-  if (bank == QI_BANK_STYX) {
-    p->nat[3].release();
-    if (p->d_edge) (void)hipFree(p->d_edge);
-    p->d_edge = nullptr;
-    p->nedge = 0;
-    p->edge_wmax = 0;
-    if (!shorts.empty()) {
-      // spectra of the circular (length n) form of the short atoms
-      std::vector<double> sup_s((size_t)shorts.size() * 3);
-      size_t q = 0;
-      while (q < shorts.size()) {
-        size_t r = q + 1;
-        while (r < shorts.size() && shorts[r] == shorts[r - 1] + 1) ++r;
-        std::vector<double> part;
-        QI_TRY(analyse_support(p, 1, n, B, shorts[q], (int32_t)(r - q), d_par, &part, st));
-        std::copy(part.begin(), part.end(), sup_s.begin() + 3 * q);
-        q = r;
-      }
-      QI_TRY(make_native_table<T>(p, 3, 1, n, B, shorts, sup_s, short_w, d_par, st));
-      p->nat[3].nbands = B;
-      std::vector<native::EdgeBand> eb(shorts.size());
-      for (size_t i = 0; i < shorts.size(); ++i) {
-        const int32_t j = shorts[i];
-        eb[i].out_band = j;
-        eb[i].w = short_w[i];
-        eb[i].p_re = h_par[j];
-        eb[i].p_im = h_par[B + j];
-        eb[i].omega = h_par[2 * B + j];
-        eb[i].amp = h_par[3 * B + j];
-        if (short_w[i] > p->edge_wmax) p->edge_wmax = short_w[i];
-      }
-      QI_HIP(hipMalloc((void**)&p->d_edge, eb.size() * sizeof(native::EdgeBand)));
-      QI_HIP(hipMemcpy(p->d_edge, eb.data(), eb.size() * sizeof(native::EdgeBand), hipMemcpyHostToDevice));
-      p->nedge = (int32_t)eb.size();
-    }
+  if (styx) {
+    std::stable_sort(routes.picks.begin(), routes.picks.end(), [](const BlockPick& x, const BlockPick& y) { return x.wq < y.wq; });
+    QI_TRY(build_block_gabor<T>(p, 0, B, routes.picks, d_par, st));
+    if (!routes.shorts.empty()) QI_TRY(build_short_table<T>(p, B, routes.shorts, routes.short_w, d_par, h_par, st));
   }
   return QI_OK;
 }
@@ -973,116 +987,141 @@ int build_bank(qi_plan* p, int bank, int32_t B, const double* d_par, hipStream_t
   return QI_OK;
 }
 
-// The Stockwell table of a plan: every band is assigned to the zoom / float64 zoom, block or two-pass engines from its
-// window (shift index, sigma -> coef); nat[2] and blk[2] are left ready, or empty when the hipFFT engine runs the table.
+// ---- Stockwell table -----------------------------------------------------------------------------------------------------
+struct StxRoutes {
+  std::vector<BlockPick> picks;             // block engine
+  std::vector<native::BandDesc> bands;      // zoom, float64 zoom, two-pass
+};
+
+// Every band to the zoom / float64 zoom, block or two-pass engines from its window (shift index, sigma -> coef).
+StxRoutes classify_stx_bands(const qi_plan* p, int32_t B, const int64_t* shift_index, const double* sigma,
+                             const std::vector<double>& coef) {
+  StxRoutes out;
+  const bool f64 = p->d.dtype == QI_F64;
+  const bool can_block = p->native_block && p->n >= 4 * native::kBlk;
+  for (int32_t j = 0; j < B; ++j) {
+    // the band's time-domain kernel is a Gaussian of standard deviation sigma_j samples (above 2^-30 of its peak
+    // within sqrt(60 ln 2) sigma); it is only that short if the frequency window has decayed before Nyquist
+    const double reach = std::ceil(std::sqrt(2.0 * drop_bits(f64) * M_LN2) * sigma[j]) + 1.0;
+    const int group = can_block && sigma[j] >= 2.75 ? block_group_of(reach) : 0;
+    // support of exp2(-(coef k)^2) above 2^-30: |k| <= kh = sqrt(30) / coef (float64: above 2^-50); 0 bins stands for a
+    // window as wide as the record, which no engine takes as a narrow one
+    const double kh = std::floor(std::sqrt(support_bits(p)) / coef[j]);
+    const int64_t len = 2 * kh + 1 < (double)p->n ? (int64_t)(2 * kh + 1) : 0;
+    // (a band of the float64 zoom's finest grids goes to the block engine when that can take it: native_z64_block_from)
+    const int z64 = z64_level(p, 2, p->n, len);
+    const bool zoom_first = (z64 >= 0 && !z64_level_for_block(p, z64)) ||
+                            (group > p->native_blk_maxwq && zoom_class(p, 2, p->n, len) >= 0);
+    if (group > 0 && !zoom_first) {
+      BlockPick pk{j, group, shift_index[j]};
+      pk.analytic = 1;
+      stx_gaussian(pk, p->n, sigma[j]);
+      out.picks.push_back(pk);
+      continue;
+    }
+    out.bands.emplace_back();
+    native::BandDesc& d = out.bands.back();
+    memset(&d, 0, sizeof(d));
+    d.shift = shift_index[j];
+    d.coef = coef[j];
+    d.out_band = j;
+    d.mode = band_mode(p, 2, p->n, len);
+    if (d.mode != 1) {
+      d.k_lo = -(int32_t)kh;
+      d.k_len = 2 * (int32_t)kh + 1;
+    }
+  }
+  return out;
+}
+
+// Stockwell bands that need the two-pass kernels at a length they do not run: if they are the last (at most four) rows of the
+// table, a pass of the hipFFT engine over those rows follows the native run (run_stx_leftover) and they leave `bands`.
+void take_stx_leftover(qi_plan* p, int32_t B, std::vector<native::BandDesc>* bands) {
+  p->stx_left_lo = -1;
+  p->stx_left_n = 0;
+  if (native_len_ok(p->n) || p->d.engine == QI_ENGINE_NATIVE) return;
+  int32_t lo = B, cnt = 0;
+  for (const auto& d : *bands)
+    if (d.mode == 1) {
+      ++cnt;
+      lo = d.out_band < lo ? d.out_band : lo;
+    }
+  // (the pass tiles the plan's scratch like the hipFFT engine: one record's spectrum, `cnt` rows and the partial sums
+  // of the whole table must fit -- else the whole table goes to the hipFFT engine, which tiles over bands)
+  const size_t row = (size_t)p->n * (p->d.dtype == QI_F64 ? sizeof(double2) : sizeof(float2));
+  const int64_t nblk_e = ceil_div(p->n, kEpiSpan);
+  const size_t part = align_up((size_t)B * nblk_e * 8) + align_up((size_t)B * nblk_e * 24);
+  const bool left_fits = p->ws_bytes >= part + 2048 + row * (size_t)(cnt + 1);
+  if (cnt > 0 && cnt <= 4 && lo == B - cnt && cnt < B && left_fits) {
+    bands->erase(std::remove_if(bands->begin(), bands->end(), [](const native::BandDesc& d) { return d.mode == 1; }), bands->end());
+    p->stx_left_lo = lo;
+    p->stx_left_n = cnt;
+  }
+}
+
+// The Stockwell table of a plan: nat[2] and blk[2] are left ready, or empty when the hipFFT engine runs the table.
 int build_stx_tables(qi_plan* p, int32_t B, const int64_t* shift_index, const double* sigma, const std::vector<double>& coef) {
-  if (native_wanted(p, 2)) {
-    // support of exp2(-(coef k)^2) above 2^-30: |k| <= sqrt(30) / coef (float64: above 2^-50)
-    const double cut = p->d.dtype == QI_F64 ? std::sqrt(50.0) : std::sqrt(30.0);
-    std::vector<native::BandDesc> bands;
-    std::vector<BlockPick> picks;
-    const bool can_block = p->native_block && p->n >= 4 * native::kBlk;
-    int32_t ngen = 0;
-    (void)ngen;
-    for (int32_t j = 0; j < B; ++j) {
-      // the band's time-domain kernel is a Gaussian of standard deviation sigma_j samples (above 2^-30 of its peak
-      // within sqrt(60 ln 2) sigma); it is only that short if the frequency window has decayed before Nyquist
-      const double reach = std::ceil(std::sqrt((p->d.dtype == QI_F64 ? 104.0 : 60.0) * M_LN2) * sigma[j]) + 1.0;
-      const double kh0 = std::floor(std::sqrt(30.0) / coef[j]);
-      const bool zoom_first = block_group_of(reach) > p->native_blk_maxwq && 2 * kh0 + 1 < (double)p->n &&
-                              zoom_class(p, 2, p->n, (int64_t)(2 * kh0 + 1)) >= 0;
-      const double kh64 = std::floor(cut / coef[j]);
-      bool z64_first = p->d.dtype == QI_F64 && z64_table(p, 2) && 2 * kh64 + 1 <= (double)narrow_limit(p, 2, p->n) &&
-                       2 * kh64 + 1 < (double)p->n && 4.0 * (2 * kh64 + 1) <= (double)((p->n / 64) << (p->native_z64_levels - 1));
-      // (a band of the float64 zoom's finest grids goes to the block engine when that can take it: native_z64_block_from)
-      if (z64_first && can_block && sigma[j] >= 2.75 && block_group_of(reach) > 0 &&
-          4.0 * (2 * kh64 + 1) > (double)((p->n / 64) << (p->native_z64_block_from - 1)))
-        z64_first = false;
-      if (can_block && sigma[j] >= 2.75 && block_group_of(reach) > 0 && !zoom_first && !z64_first) {
-        BlockPick pk{j, block_group_of(reach), shift_index[j]};
-        // the band's filter spectrum is the Gaussian window itself, centred on the band's shift index
-        pk.analytic = 1;
-        pk.kappa = (double)shift_index[j] * (double)native::kBlk / (double)p->n;
-        pk.cw = (2.0 * M_PI / (double)native::kBlk) * sigma[j] * std::sqrt(M_LOG2E / 2.0);
-        pk.amp = 1.0 / (double)native::kBlk;
-        picks.push_back(pk);
-        continue;
-      }
-      bands.emplace_back();
-      native::BandDesc& d = bands.back();
-      memset(&d, 0, sizeof(d));
-      d.shift = shift_index[j];
-      d.coef = coef[j];
-      d.out_band = j;
-      const double kh = std::floor(cut / coef[j]);
-      const int zc = 2 * kh + 1 < (double)p->n ? zoom_class(p, 2, p->n, (int64_t)(2 * kh + 1)) : -1;
-      if (zc >= 0 || (2 * kh + 1 <= (double)narrow_limit(p, 2, p->n) && 2 * kh + 1 < (double)p->n)) {
-        d.mode = zc >= 0 ? 2 + zc : 0;
-        d.k_lo = -(int32_t)kh;
-        d.k_len = 2 * (int32_t)kh + 1;
-      } else {
-        d.mode = 1;
-        ngen++;
-      }
-    }
-    p->stx_left_lo = -1;
-    p->stx_left_n = 0;
-    if (!native_len_ok(p->n) && p->d.engine != QI_ENGINE_NATIVE) {
-      // bands for the two-pass kernels at a length they do not run: if they are the last (at most four) rows of the table, a
-      // pass of the hipFFT engine over those rows follows the native run (run_stx_leftover)
-      int32_t lo = B, cnt = 0;
-      for (const auto& d : bands)
-        if (d.mode == 1) {
-          ++cnt;
-          lo = d.out_band < lo ? d.out_band : lo;
-        }
-      // (the pass tiles the plan's scratch like the hipFFT engine: one record's spectrum, `cnt` rows and the partial sums
-      // of the whole table must fit -- else the whole table goes to the hipFFT engine, which tiles over bands)
-      const size_t row = (size_t)p->n * (p->d.dtype == QI_F64 ? sizeof(double2) : sizeof(float2));
-      const int64_t nblk_e = ceil_div(p->n, kEpiSpan);
-      const size_t part = align_up((size_t)B * nblk_e * 8) + align_up((size_t)B * nblk_e * 24);
-      const bool left_fits = p->ws_bytes >= part + 2048 + row * (size_t)(cnt + 1);
-      if (cnt > 0 && cnt <= 4 && lo == B - cnt && cnt < B && left_fits) {
-        bands.erase(std::remove_if(bands.begin(), bands.end(), [](const native::BandDesc& d) { return d.mode == 1; }), bands.end());
-        p->stx_left_lo = lo;
-        p->stx_left_n = cnt;
-      }
-    }
-    bool two_pass_free = true;  // no band for pass 1 / pass 2 (their transform lengths are 2^20 and 2^21 only)
-    for (const auto& d : bands) two_pass_free = two_pass_free && d.mode >= 2;
-    // (float64: the float64 zoom takes its bands inside upload_native_table -- what it leaves is known afterwards)
-    const bool f64_maybe = p->d.dtype == QI_F64 && z64_table(p, 2);
-    if (native_len_ok(p->n) || two_pass_free || f64_maybe) {
-      int rc = upload_native_table(p, 2, p->n, bands);
-      if (rc == QI_OK && !native_len_ok(p->n) && !p->nat[2].h_rows.empty()) {
-        p->nat[2].release();  // bands are left for the two-pass kernels at a length they do not run: the hipFFT engine takes the table
-        p->blk[2].release();
-        p->stx_left_n = 0;
-        if (p->d.engine == QI_ENGINE_NATIVE) {
-          set_error("native engine: this Stockwell band table needs the two-pass kernels, which run 2^20 / 2^21 samples only");
-          return QI_ERR_UNSUPPORTED;
-        }
-        return QI_OK;
-      }
-      if (rc == QI_OK) {
-        p->nat[2].nbands = B;
-        rc = p->d.dtype == QI_F64 ? build_block_stx<double>(p, picks, coef, nullptr) : build_block_stx<float>(p, picks, coef, nullptr);
-      }
-      if (rc != QI_OK) {  // no half-built table: a ready table whose block bands have no producer would leave panel rows unwritten
-        p->nat[2].release();
-        p->blk[2].release();
-        p->stx_left_n = 0;
-        return rc;
-      }
-    } else if (p->d.engine == QI_ENGINE_NATIVE) {
-      set_error("native engine: this Stockwell band table needs the two-pass kernels, which run 2^20 / 2^21 samples only");
-      return QI_ERR_UNSUPPORTED;
-    }  // else: the hipFFT engine runs it (nat[2] stays empty)
-  } else if (p->d.engine == QI_ENGINE_NATIVE) {
+  if (!native_wanted(p, 2)) {
+    if (p->d.engine != QI_ENGINE_NATIVE) return QI_OK;
     set_error("native engine does not support the Stockwell transform at n = %lld", (long long)p->n);
     return QI_ERR_UNSUPPORTED;
   }
-  return QI_OK;
+  StxRoutes routes = classify_stx_bands(p, B, shift_index, sigma, coef);
+  take_stx_leftover(p, B, &routes.bands);
+  bool two_pass_free = true;  // no band for pass 1 / pass 2 (their transform lengths are 2^20 and 2^21 only)
+  for (const auto& d : routes.bands) two_pass_free = two_pass_free && d.mode >= 2;
+  // (float64: the float64 zoom takes its bands inside upload_native_table -- what it leaves is known afterwards)
+  bool native = native_len_ok(p->n) || two_pass_free || z64_table(p, 2);
+  int rc = QI_OK;
+  if (native) {
+    rc = upload_native_table(p, 2, p->n, routes.bands);
+    // bands left for the two-pass kernels at a length they do not run: the hipFFT engine takes the table
+    if (rc == QI_OK && !native_len_ok(p->n) && !p->nat[2].h_rows.empty()) native = false;
+  }
+  if (rc == QI_OK && native) {
+    p->nat[2].nbands = B;
+    rc = p->d.dtype == QI_F64 ? build_block_stx<double>(p, routes.picks, coef, nullptr) : build_block_stx<float>(p, routes.picks, coef, nullptr);
+  }
+  if (rc != QI_OK || !native) drop_stx_tables(p);
+  if (rc == QI_OK && !native && p->d.engine == QI_ENGINE_NATIVE) {
+    set_error("native engine: this Stockwell band table needs the two-pass kernels, which run 2^20 / 2^21 samples only");
+    return QI_ERR_UNSUPPORTED;
+  }
+  return rc;
+}
+
+// ---- what the C ABI shares with the table builds -------------------------------------------------------------------------
+void release_styx_extras(qi_plan* p) {
+  free_device(p->split_bank);
+  free_device(p->d_split_bands);
+  p->h_split_bands.clear();
+  p->nsplit = 0;
+  free_device(p->d_edge);
+  p->nedge = 0;
+  p->edge_wmax = 0;
+}
+void drop_gabor_tables(qi_plan* p, int bank) {
+  p->nat[bank].release();
+  if (bank != QI_BANK_STYX) return;
+  p->blk[0].release();
+  p->nat[3].release();
+  p->nsplit = 0;  // (the split and edge buffers stay until the next build of the bank releases them)
+}
+void drop_stx_tables(qi_plan* p) {
+  p->nat[2].release();
+  p->blk[2].release();
+  p->stx_left_n = 0;
+}
+void drop_band_slots(qi_plan* p, int kind) {
+  for (auto*& b : p->d_band_slots[kind]) free_device(b);
+}
+
+int upload_atom_params(int32_t B, const double* p_re, const double* p_im, const double* omega, const double* amp,
+                       std::vector<double>* host, DeviceTemp<double>* d_par) {
+  host->resize((size_t)4 * B);
+  const double* parts[4] = {p_re, p_im, omega, amp};
+  for (int k = 0; k < 4; ++k) memcpy(host->data() + (size_t)k * B, parts[k], B * sizeof(double));
+  return upload_table(&d_par->ptr, *host);
 }
 
 template int build_native_bank<float>(qi_plan*, int, int32_t, const double*, const double*, hipStream_t);
@@ -1092,3 +1131,4 @@ template int build_bank<double>(qi_plan*, int, int32_t, const double*, hipStream
 
 }  // namespace host
 }  // namespace qi
+

@@ -287,8 +287,7 @@ template int run_stx_leftover<double>(qi_plan*, const void*, int64_t, const qi_t
 // the edge items of the styx table keep their place at the end.
 int build_dual_items(qi_plan* p, int cut) {
   if (p->dual_valid[cut]) return QI_OK;
-  if (p->d_dual[cut]) (void)hipFree(p->d_dual[cut]);
-  p->d_dual[cut] = nullptr;
+  free_device(p->d_dual[cut]);
   p->n_dual[cut] = 0;
   std::map<std::pair<int32_t, int32_t>, std::pair<std::vector<native::BlockItem>, std::vector<native::BlockItem>>> at;
   std::vector<native::DualItem> dual, edge;
@@ -324,8 +323,7 @@ int build_dual_items(qi_plan* p, int cut) {
   p->n_dual_long[cut] = (int32_t)std::count_if(dual.begin(), dual.end(), [](const native::DualItem& x) { return x.wq == native::kBlkLongWq; });
   dual.insert(dual.end(), edge.begin(), edge.end());
   if (dual.empty()) return QI_OK;
-  QI_HIP(hipMalloc((void**)&p->d_dual[cut], dual.size() * sizeof(native::DualItem)));
-  QI_HIP(hipMemcpy(p->d_dual[cut], dual.data(), dual.size() * sizeof(native::DualItem), hipMemcpyHostToDevice));
+  QI_TRY(upload_table(&p->d_dual[cut], dual));
   p->n_dual[cut] = (int32_t)dual.size();
   p->dual_valid[cut] = true;
   return QI_OK;
@@ -726,9 +724,7 @@ int upload_band_slots(qi_plan* p, int kind, int cut, int64_t nblk_max, bool bloc
   for (const auto& z : p->nat[kind].h_zoom) slots[z.first] = (int32_t)native::zoom_groups(p->n, z.second);
   if (blocks)
     for (const auto& b : p->blk[kind].var[cut].h_bands) slots[b.first] = b.second;
-  QI_HIP(hipMalloc((void**)&p->d_band_slots[kind][cut], slots.size() * sizeof(int32_t)));
-  QI_HIP(hipMemcpy(p->d_band_slots[kind][cut], slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  return QI_OK;
+  return upload_table(&p->d_band_slots[kind][cut], slots);
 }
 
 // the zoom launch of table `kind` (narrow bands of the main table); stat_base, chunk_base: its first stat slot and plane;
@@ -767,7 +763,7 @@ native::ZoomArgs<float> zoom_args(const qi_plan* p, int kind, const ZoomRows& r,
     z.lvl_chunk0[g] = chunk0;
     z.lvl_nchunk[g] = r.nchunk[g];
     z.lvl_stat_base[g] = stat_base + r.stat_base[g];
-    z.lvl_weights[g] = p->d_zoom_w[g][0];  // (a lane's position in its window does not depend on the kind)
+    z.lvl_weights[g] = p->d_zoom_w[g];  // (a lane's position in its window does not depend on the kind)
     chunk0 += r.nchunk[g];
   }
   int first = 0;
