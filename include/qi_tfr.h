@@ -123,6 +123,14 @@ int64_t qi_plan_bands(const qi_plan* plan, int which /* qi_bank, or 2 for the ST
  * PASS2 or BLOCK on the native engine, INVERSE on the hipFFT engine); used to price a stage's algorithmic bytes. */
 int64_t qi_plan_stage_bands(const qi_plan* plan, int which, int stage);
 
+/* Forward transform of a float32 plan on the native engines (a read-only query).  When every native table set on the plan
+ * reads the record spectrum only near DC -- all bands on the zoom, block and split engines, no two-pass row, no short-atom
+ * sub-table, transform lengths 2^20 / 2^21 -- the forward transform forms only the bins (-Lf / 64, Lf / 64) of each
+ * table's Lf-point spectrum ("low-bins" path; qi_cwt, qi_stx and qi_cwt_stx of one plan always take the same path).
+ * Returns 0 when the plan runs the full transform (or table `which` is not set); otherwise the power of two K of table
+ * `which` with every bin its bands read inside (-K, K), K <= Lf / 64. */
+int64_t qi_plan_forward_low(const qi_plan* plan, int which /* as qi_plan_bands */);
+
 /* Which kernels produce row `band` of table `which` in a call of `records` records (a read-only query: tests and
  * diagnostics use it to tell which path a band takes; it changes nothing).  `records` means the records that go through
  * together: a call whose records do not fit the plan's scratch runs in tiles, and each tile takes the route of its own

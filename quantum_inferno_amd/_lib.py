@@ -77,6 +77,7 @@ PROTOTYPES = {
     "qi_plan_set_stx_bands": (_int, [_P, _i32, _I64, _D]),
     "qi_plan_bands": (_i64, [_P, _int]),
     "qi_plan_stage_bands": (_i64, [_P, _int, _int]),
+    "qi_plan_forward_low": (_i64, [_P, _int]),
     "qi_plan_band_route": (_int, [_P, _int, _i32, _i64, C.POINTER(BandRoute)]),
     "qi_plan_profile": (_int, [_P, _int]),
     "qi_plan_profile_read": (_int, [_P, _D, _I64, _i32]),

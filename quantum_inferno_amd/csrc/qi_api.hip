@@ -47,6 +47,7 @@ int qi_plan_create(qi_plan** plan, const qi_plan_desc* desc) {
     p->native_kmax = (int64_t)native::kMaxPrunedTerms * native::kN2;
   if (const char* e = tune_env("QI_NATIVE_DEBUG")) p->native_debug = atoi(e);
   if (const char* e = tune_env("QI_NATIVE_FWD")) p->native_fwd = atoi(e);
+  if (const char* e = tune_env("QI_NATIVE_FWD_LOW")) p->native_fwd_low = atoi(e);
 #ifdef QI_NATIVE_STAMPS
   if (tune_env("QI_NATIVE_STAMPS")) {
     if (hipMalloc((void**)&p->stamps, 65536 * 8 * sizeof(unsigned long long)) != hipSuccess) p->stamps = nullptr;
@@ -316,6 +317,11 @@ int64_t qi_plan_bands(const qi_plan* p, int which) {
   if (!p) return 0;
   if (which == QI_BANK_STYX || which == QI_BANK_ATOMS) return p->nb[which];
   return which == 2 ? p->nb_stx : 0;
+}
+
+int64_t qi_plan_forward_low(const qi_plan* p, int which) {
+  if (!p || which < 0 || which > 2 || !forward_low(p)) return 0;
+  return table_low_bins(p, which);
 }
 
 int64_t qi_plan_stage_bands(const qi_plan* p, int which, int stage) {

@@ -1409,7 +1409,7 @@ __device__ __forceinline__ void zoom_coarse_plane_gather(const ZoomArgs<T>& a, c
   const BandDesc bd = load_uniform(a.bands + *as_const(a.plane_band + plane_i));
   const uint32_t tau1 = plane_i - (uint32_t)bd.edge;
   const int64_t ch = blockIdx.z;
-  const cplx<T>* __restrict__ X = a.X + ch * (a.Lf << a.x_shift);
+  const cplx<T>* __restrict__ X = a.X + ch * ((int64_t)a.x_mask + 1);
   cplx<T> v[16];
 #ifdef QI_NATIVE_DEBUG
   if (a.debug & 256) {

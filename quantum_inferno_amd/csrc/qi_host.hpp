@@ -264,6 +264,9 @@ struct qi_plan {
     std::vector<int32_t> h_row_mode;                  // ... 0 one-pass loader, 1 general (same order)
     std::vector<int32_t> h_z64;                       // panel rows of the float64 zoom bands, in the order of d_z64
     int32_t nzoom = 0, zoom_count[native::kZoomClasses] = {0, 0, 0, 0, 0, 0, 0};
+    // record-spectrum bins the zoom bands read (signed, modulo Lf; a Stockwell row reads k + shift, negative near DC):
+    // the most negative and the most positive one (x_lo > x_hi: no zoom band)
+    int64_t x_lo = 0, x_hi = -1;
     int64_t zoom_planes = 0;  // 4096-sample planes of coarse storage per record
     int zoom_max_level = 0;
     // float64 zoom (qi_zoom64.hip): the narrow-spectrum bands of a float64 table, by coarse-grid level
@@ -405,6 +408,7 @@ struct qi_plan {
   int64_t native_kmax = 12288;  // widest spectrum support handled by the one-pass (pruned) loader
   int native_debug = 0;
   int native_fwd = 1;          // forward transform of the records on the native kernels (0: hipFFT)
+  int native_fwd_low = 1;      // ... only the bins near DC when nothing reads the others (forward_low); 0: always every bin
   int native_wgs = 256;        // workgroups a pass-2 launch should have at least (band chunks are sized for it)
   unsigned long long* stamps = nullptr;  // diagnostic builds: phase cycle counters of the last pass-2 launch
   unsigned long long* blk_stamps = nullptr;  // idem, last block launch
@@ -439,6 +443,11 @@ constexpr int kZoomListOrder[native::kZoomClasses] = {6, 5, 0, 1, 2, 3, 4};
 // ---- qi_plan_build.hip: the tables of a plan ---------------------------------------------------------------------------
 bool native_len_ok(int64_t Lf);
 bool native_wanted(const qi_plan* p, int kind);
+// Low-bins forward transform (native::fwd_low_bins): a property of the plan's tables.  table_low_bins: the power of two K
+// with every spectrum read of table `kind` in (-K, K), or 0 when the table needs the whole spectrum; forward_low: every
+// native table set on the plan allows it, so qi_cwt, qi_stx and qi_cwt_stx all take the same forward path.
+int64_t table_low_bins(const qi_plan* p, int kind);
+bool forward_low(const qi_plan* p);
 int batch_from(const qi_plan* p);
 // nothing half-built stays behind: a ready table without its block / split producers would leave panel rows unwritten
 void release_styx_extras(qi_plan* p);  // the split and short-atom (edge) members of the styx bank

@@ -6,11 +6,9 @@ namespace qi {
 static thread_local char g_err[512] = "";
 
 // Development switches (QI_NATIVE_*, QI_STFT_FUSED: engine ablations and launch-geometry experiments)
-// are read only when QI_TUNE is set in the environment: a production process never consults them.
-const char* tune_env(const char* name) {
-  static const bool on = std::getenv("QI_TUNE") != nullptr;
-  return on ? std::getenv(name) : nullptr;
-}
+// are read only when QI_TUNE is set in the environment: a production process never consults them.  (QI_TUNE itself is
+// looked up on every call, so a test can switch a plan it creates without a process of its own.)
+const char* tune_env(const char* name) { return std::getenv("QI_TUNE") != nullptr ? std::getenv(name) : nullptr; }
 
 void set_error(const char* fmt, ...) {
   va_list ap;

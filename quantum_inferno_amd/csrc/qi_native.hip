@@ -314,8 +314,12 @@ __device__ __forceinline__ void rows_fft1024(cplx<T>* buf, const cplx<T>* tw, cp
 // ---- pass 1 (wide bands, and the forward transform of the records) -------------------------------------------------
 // Rows are G consecutive k2; the transform runs over k1 (N1 = 1024 NPH points) and the result, multiplied by the
 // pass twiddle W_Lf^(k2 t1), is written transposed, imdT[t1][k2], in runs of G consecutive k2 (128 bytes).
-template <typename T, class C, int SRC, int NPH>
+// LOW (forward transform, SRC 2): only the rows t1 <= N1 / 2 are written, fwd_low_rows(N1) rows per record -- the
+// outputs c1 >= 9 of a thread's last radix-16 step are never used, so their butterflies are eliminated, and c1 = 8 is
+// kept by the one thread that holds t1 = N1 / 2.
+template <typename T, class C, int SRC, int NPH, bool LOW = false>
 __global__ void __launch_bounds__(C::TH) k_pass1(RowArgs<T> a) {
+  static_assert(!LOW || SRC == 2, "the low-bins variant is the forward transform's");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cplx<T>* buf = reinterpret_cast<cplx<T>*>(smem);
   cplx<T>* tw = buf + C::BUF;
@@ -349,7 +353,8 @@ __global__ void __launch_bounds__(C::TH) k_pass1(RowArgs<T> a) {
   // transposed intermediate imdT[r][k2]: one row of 1024 values per time residue.  The linear kind's pass 2 works
   // on residues t1 = r - 1 (r = 0 is t1 = -1 == N1 - 1 with the pass twiddle taken at -1): columns are stored at
   // r = (t1 + 1) mod N1 so that pass 2 reads whole rows.
-  cplx<T>* __restrict__ dst = a.imd + ((int64_t)ch * a.imd_slots + bd.gen_slot) * a.Lf + k2;
+  cplx<T>* __restrict__ dst = LOW ? a.imd + (int64_t)ch * fwd_low_rows(a.N1) * kN2 + k2
+                                  : a.imd + ((int64_t)ch * a.imd_slots + bd.gen_slot) * a.Lf + k2;
   const uint32_t roll = a.neg_last_row ? 1u : 0u, cmask = (uint32_t)a.N1 - 1u;
 #ifdef QI_NATIVE_STAMPS
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -371,12 +376,13 @@ __global__ void __launch_bounds__(C::TH) k_pass1(RowArgs<T> a) {
     unit_root_t<T>((k2 * (uint32_t)(NPH * (d2 + 16 * c2) + ph)) & mask, a.two_over_len, &wr, &wi);
     unit_root_t<T>((k2 * (uint32_t)(64 * NPH)) & mask, a.two_over_len, &sr, &si);
 #pragma unroll
-    for (int c1 = 0; c1 < 16; ++c1) {
+    for (int c1 = 0; c1 < (LOW ? 9 : 16); ++c1) {
       const cplx<T> z = u[brev(c1, 4)];
       const uint32_t t1 = (uint32_t)(NPH * (d2 + 16 * c2 + 64 * c1)) + (uint32_t)ph;
       if (c1 == 15 && a.neg_last_row && t1 == cmask)  // t1 = N1 - 1 is used by pass 2 as t1 = -1
         unit_root_t<T>((0u - k2) & mask, a.two_over_len, &wr, &wi);
       const T cr = (T)wr, ci = (T)wi;
+      if (LOW && c1 == 8 && t1 != (uint32_t)a.N1 / 2u) break;  // (the last kept row, t1 = N1 / 2)
       if (!QI_DBG(1)) dst[(size_t)((t1 + roll) & cmask) * kN2] = mk<T>(z.x * cr - z.y * ci, z.x * ci + z.y * cr);
       const double nr = wr * sr - wi * si;
       wi = wr * si + wi * sr;
@@ -416,6 +422,65 @@ __global__ void __launch_bounds__(C::TH) k_fwd2(RowArgs<T> a, cplx<T>* __restric
     const cplx<T> z = u[brev(c1, 4)];
     dst[(size_t)c1 * tstep] = mk<T>(z.x, -z.y);
   }
+}
+
+// Low-bins second pass (see fwd_low_bins): rows are G consecutive f1 <= N1 / 2 of the halved intermediate.  Step 1 of the
+// row transform is the full one; of step 2 only the outputs f2 = d + 16 c with c = 0 and c = 63 are formed -- thread (d, sel,
+// row g) of the first half of the workgroup folds the radix-4 over q for c2 = 0 / 3 as rows_fft1024_regs does and sums the
+// sixteen terms with W_64^(63 a1) = conj(W_64^a1) (c = 63) or 1 (c = 0); the other butterflies are gone.  Bin j = f1 + N1 f2
+// (f2 taken in [-16, 16)) goes to Xlow[j & (2K - 1)] and, for 0 < f1 < N1 / 2, its conjugate to bin -j: every bin of
+// (-K, K) is written exactly once (the rows f1 = 0 and N1 / 2 hold both signs themselves).
+template <typename T, class C>
+__global__ void __launch_bounds__(C::TH) k_fwd2_low(RowArgs<T> a, cplx<T>* __restrict__ Xlow) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cplx<T>* buf = reinterpret_cast<cplx<T>*>(smem);
+  cplx<T>* tw = buf + C::BUF;
+  const int tid = threadIdx.x;
+  const int64_t ch = blockIdx.z;
+  const uint32_t row0 = blockIdx.x * C::G, half = (uint32_t)a.N1 / 2u;
+  const int g1 = tid / 64, a1 = tid % 64;
+  fill_step_twiddles<T, C>(tw);
+  cplx<T> v[16];
+  if (row0 + g1 <= half) {
+    load_imd_direct<T>(v, a.imd + ch * fwd_low_rows(a.N1) * kN2, row0 + g1, a1);
+  } else {
+#pragma unroll
+    for (int b = 0; b < 16; ++b) v[b] = mk<T>(T(0), T(0));
+  }
+  __syncthreads();  // step twiddles ready
+  fft_reg<T, 16, 1>(v);
+#pragma unroll
+  for (int d = 1; d < 16; ++d) v[brev(d, 4)] = cmul(v[brev(d, 4)], tw[d * 64 + a1]);
+#pragma unroll
+  for (int d = 0; d < 16; ++d) buf[a1 * C::SA + d * C::G + g1] = v[brev(d, 4)];
+  __syncthreads();
+  if (tid >= C::TH / 2) return;
+  const int d2 = tid / (2 * C::G), sel = (tid / C::G) & 1, g2 = tid % C::G;
+  const uint32_t f1 = row0 + g2;
+  if (f1 > half) return;
+  const cplx<T>* __restrict__ col = buf + d2 * C::G + g2;
+  cplx<T> u[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const cplx<T> t0 = col[q * C::SA], t1 = col[(q + 16) * C::SA], t2 = col[(q + 32) * C::SA], t3 = col[(q + 48) * C::SA];
+    if (sel) {  // c2 = 3: W_4^(3 q') = 1, -i, -1, i
+      const cplx<T> u02 = mk<T>(t0.x - t2.x, t0.y - t2.y), u13 = mk<T>(t1.x - t3.x, t1.y - t3.y);
+      const cplx<T> w = tw[C::NR + 16 + q];  // W_64^q
+      u[q] = cmul(mk<T>(u02.x + u13.y, u02.y - u13.x), mk<T>(w.x, -w.y));
+    } else {
+      u[q] = mk<T>((t0.x + t2.x) + (t1.x + t3.x), (t0.y + t2.y) + (t1.y + t3.y));
+    }
+  }
+#pragma unroll
+  for (int s = 8; s >= 1; s >>= 1)
+#pragma unroll
+    for (int q = 0; q < s; ++q) u[q] = mk<T>(u[q].x + u[q + s].x, u[q].y + u[q + s].y);
+  const cplx<T> z = u[0];
+  const uint32_t lmask = (uint32_t)fwd_low_len(a.Lf) - 1u;
+  const int32_t j = (int32_t)f1 + (int32_t)a.N1 * (sel ? d2 - kFwdLowF2 : d2);
+  cplx<T>* __restrict__ dst = Xlow + ch * fwd_low_len(a.Lf);
+  dst[(uint32_t)j & lmask] = mk<T>(z.x, -z.y);  // X = conj(IDFT(x))
+  if (f1 != 0u && f1 != half) dst[(uint32_t)(-j) & lmask] = z;
 }
 
 // ---- pass 2 (every band) ---------------------------------------------------------------------------------------------
@@ -906,9 +971,9 @@ static int launch_lds(Kern kern, size_t lds, const RowArgs<T>& a, dim3 grid, int
   return QI_OK;
 }
 
-template <typename T, class C, int SRC, int NPH>
+template <typename T, class C, int SRC, int NPH, bool LOW = false>
 static int launch_p1(const RowArgs<T>& a, dim3 grid, hipStream_t st) {
-  return launch_lds(k_pass1<T, C, SRC, NPH>, C::LDS_BYTES, a, grid, C::TH, st);
+  return launch_lds(k_pass1<T, C, SRC, NPH, LOW>, C::LDS_BYTES, a, grid, C::TH, st);
 }
 template <typename T, class C, int KIND, bool COEF, bool BITS>
 static int launch_p2v(const RowArgs<T>& a, dim3 grid, hipStream_t st) {
@@ -947,20 +1012,20 @@ int launch_pass1<double>(const RowArgs<double>& a, int kind, int64_t n_channels,
 }
 
 // forward transform of n_channels real records (a.sig) into Xout [C][Lf], through a.imd (one slot per channel)
-template <typename T, class C1>
-static int launch_forward_cfg(const RowArgs<T>& a0, cplx<T>* Xout, int64_t n_channels, hipStream_t st) {
-  using C2 = C1;
+template <typename T, class C1, bool LOW>
+static int launch_forward_p1(const RowArgs<T>& a0, int64_t n_channels, hipStream_t st) {
   RowArgs<T> a = a0;
   a.phase_split = a.N1 == 2048 && (a.N2 / C1::G) * n_channels < 256 ? 1 : 0;
   dim3 g1((unsigned)(a.N2 / C1::G), a.phase_split ? 2u : 1u, (unsigned)n_channels);
-  if (a.N1 == 1024)
-    QI_TRY((launch_p1<T, C1, 2, 1>(a, g1, st)));
-  else if (a.N1 == 2048)
-    QI_TRY((launch_p1<T, C1, 2, 2>(a, g1, st)));
-  else {
-    set_error("native forward transform supports N1 = 1024 or 2048, got %lld", (long long)a.N1);
-    return QI_ERR_UNSUPPORTED;
-  }
+  if (a.N1 == 1024) return launch_p1<T, C1, 2, 1, LOW>(a, g1, st);
+  if (a.N1 == 2048) return launch_p1<T, C1, 2, 2, LOW>(a, g1, st);
+  set_error("native forward transform supports N1 = 1024 or 2048, got %lld", (long long)a.N1);
+  return QI_ERR_UNSUPPORTED;
+}
+template <typename T, class C1>
+static int launch_forward_cfg(const RowArgs<T>& a, cplx<T>* Xout, int64_t n_channels, hipStream_t st) {
+  using C2 = C1;
+  QI_TRY((launch_forward_p1<T, C1, false>(a, n_channels, st)));
   auto kern = k_fwd2<T, C2>;
   QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(kern), C2::LDS_BYTES));
   dim3 g2((unsigned)(a.N1 / C2::G), 1, (unsigned)n_channels);
@@ -968,15 +1033,40 @@ static int launch_forward_cfg(const RowArgs<T>& a0, cplx<T>* Xout, int64_t n_cha
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
-template <>
-int launch_forward<float>(const RowArgs<float>& a, float2* Xout, int64_t n_channels, hipStream_t st) {
-  // few records: 8-row workgroups, twice as many of them (a launch of 16-row workgroups would leave most CUs idle)
-  if (n_channels * (a.N2 / 16) < 256) return launch_forward_cfg<float, Cfg<float, 8>>(a, Xout, n_channels, st);
-  return launch_forward_cfg<float, Cfg<float, 16>>(a, Xout, n_channels, st);
+// the low-bins pair (fwd_low_bins): pass 1 as above with half its stores, pass 2 over fwd_low_rows(N1) rows
+template <typename T, class C2>
+static int launch_fwd2_low(const RowArgs<T>& a, cplx<T>* Xlow, int64_t n_channels, hipStream_t st) {
+  auto kern = k_fwd2_low<T, C2>;
+  QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(kern), C2::LDS_BYTES));
+  dim3 g2((unsigned)ceil_div(fwd_low_rows(a.N1), C2::G), 1, (unsigned)n_channels);
+  kern<<<g2, C2::TH, C2::LDS_BYTES, st>>>(a, Xlow);
+  QI_LAUNCH_CHECK();
+  return QI_OK;
 }
-// float64 (round 4): the same two launches in double instead of hipFFT's five passes over the padded records
 template <>
-int launch_forward<double>(const RowArgs<double>& a, double2* Xout, int64_t n_channels, hipStream_t st) {
+int launch_forward<float>(const RowArgs<float>& a, float2* Xout, int64_t n_channels, hipStream_t st, bool low) {
+  // few records: 8-row workgroups, twice as many of them (a launch of 16-row workgroups would leave most CUs idle)
+  const bool few = n_channels * (a.N2 / 16) < 256;
+  if (!low) {
+    if (few) return launch_forward_cfg<float, Cfg<float, 8>>(a, Xout, n_channels, st);
+    return launch_forward_cfg<float, Cfg<float, 16>>(a, Xout, n_channels, st);
+  }
+  if (few) QI_TRY((launch_forward_p1<float, Cfg<float, 8>, true>(a, n_channels, st)));
+  else QI_TRY((launch_forward_p1<float, Cfg<float, 16>, true>(a, n_channels, st)));
+  // the second pass has half the rows: the row count per workgroup that still gives the chip a round of workgroups
+  const int64_t rows = fwd_low_rows(a.N1) * n_channels;
+  if (rows >= 256 * 16) return launch_fwd2_low<float, Cfg<float, 16>>(a, Xout, n_channels, st);
+  if (rows >= 256 * 8) return launch_fwd2_low<float, Cfg<float, 8>>(a, Xout, n_channels, st);
+  return launch_fwd2_low<float, Cfg<float, 4>>(a, Xout, n_channels, st);
+}
+// float64 (round 4): the same two launches in double instead of hipFFT's five passes over the padded records; always the
+// full transform (the float64 zoom reads X through its own kernels)
+template <>
+int launch_forward<double>(const RowArgs<double>& a, double2* Xout, int64_t n_channels, hipStream_t st, bool low) {
+  if (low) {
+    set_error("the low-bins forward transform is float32 only");
+    return QI_ERR_UNSUPPORTED;
+  }
   return launch_forward_cfg<double, Cfg<double, 8>>(a, Xout, n_channels, st);
 }
 

@@ -62,8 +62,18 @@ struct RowArgs {
 
 template <typename T>
 int launch_pass1(const RowArgs<T>& a, int kind, int64_t n_channels, hipStream_t st);
+// Low-bins forward transform (float32): a call whose tables read the record spectrum only near DC (zoom gather) gets just
+// the bins (-K, K), K = kFwdLowF2 * N1 = Lf / 64, in a compact array Xlow[C][2K] indexed by bin & (2K - 1).  Pass 1 writes
+// only the rows f1 <= N1 / 2 of the intermediate (the record is real: row N1 - f1 is the conjugate of row f1 times a unit
+// root), pass 2 forms of each row only the outputs f2 < kFwdLowF2 and f2 >= 1024 - kFwdLowF2 and writes every bin with
+// its Hermitian mirror.
+constexpr int kFwdLowF2 = 16;
+constexpr int64_t fwd_low_bins(int64_t Lf) { return Lf / kN2 * kFwdLowF2; }       // K
+constexpr int64_t fwd_low_len(int64_t Lf) { return 2 * fwd_low_bins(Lf); }        // elements of Xlow per record
+constexpr int64_t fwd_low_rows(int64_t N1) { return N1 / 2 + 1; }                 // rows of the intermediate per record
+// low: Xout is Xlow [C][fwd_low_len(Lf)] and a.imd holds fwd_low_rows(N1) rows per record
 template <typename T>
-int launch_forward(const RowArgs<T>& a, cplx<T>* Xout, int64_t n_channels, hipStream_t st);
+int launch_forward(const RowArgs<T>& a, cplx<T>* Xout, int64_t n_channels, hipStream_t st, bool low = false);
 template <typename T>
 int launch_pass2(const RowArgs<T>& a, int kind, int rows_per_group, int nchunk, int64_t n_channels, hipStream_t st);
 // one short-atom band of the styx bank evaluated circularly (see k_edge_fix)
@@ -228,8 +238,9 @@ struct ZoomArgs {
   int32_t lvl_first[kZoomClasses], lvl_count[kZoomClasses], lvl_chunk0[kZoomClasses], lvl_nchunk[kZoomClasses];
   int64_t lvl_stat_base[kZoomClasses];
   const float* lvl_weights[kZoomClasses];  // [taps][64] interpolation weights of the lanes, per class
-  const cplx<T>* X;        // [C][Lf << x_shift] spectra of the records
+  const cplx<T>* X;        // [C][x_mask + 1] spectra of the records: bin k of Lf at (k << x_shift) & x_mask
   int32_t x_shift;         // 1: X is the spectrum of the records zero-padded to twice Lf (bin k of Lf = bin 2k)
+  uint32_t x_mask;         // (Lf << x_shift) - 1, or the compact low-bins array's length - 1 (fwd_low_len)
   const cplx<T>* Hc;       // compact bank (Gabor kinds)
   cplx<T>* split_part;     // [C][split_rows][n]: the split bands (BandDesc::add_row) leave their samples here, see k_zoom
   int32_t split_rows;

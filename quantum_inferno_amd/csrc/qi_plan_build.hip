@@ -11,6 +11,29 @@ namespace host {
 
 bool native_len_ok(int64_t Lf) { return Lf == (1ll << 20) || Lf == (1ll << 21); }
 
+// low-bins forward transform: the rule (see qi_host.hpp).  Evaluated from the tables on every run, so replacing a table
+// re-evaluates it.
+int64_t table_low_bins(const qi_plan* p, int kind) {
+  const auto& t = p->nat[kind];
+  if (!t.ready || p->d.dtype != QI_F32 || !p->native_fwd || !p->native_fwd_low || !native_len_ok(t.Lf)) return 0;
+  // the two-pass kernels and the short-atom sub-table read the spectrum as a whole array
+  if (!t.h_rows.empty() || (kind == 0 && p->nat[3].ready && p->nedge > 0)) return 0;
+  const int64_t kmax = native::fwd_low_bins(t.Lf);  // what the pruned second pass forms: Lf / 64 (2K = Lf / 32 <= Lf / 8)
+  int64_t K = 1;
+  while (K <= kmax && !(t.x_lo > -K && t.x_hi < K)) K *= 2;
+  return K <= kmax ? K : 0;
+}
+bool forward_low(const qi_plan* p) {
+  if (p->d.dtype != QI_F32) return false;
+  bool any = false;
+  for (int kind = 0; kind < 3; ++kind) {
+    if (!p->nat[kind].ready) continue;
+    if (table_low_bins(p, kind) == 0) return false;
+    any = true;
+  }
+  return any;
+}
+
 // does this plan run transform `kind` (0 styx bank, 1 atoms bank, 2 Stockwell) on the native engine?
 bool native_wanted(const qi_plan* p, int kind) {
   if (p->d.engine == QI_ENGINE_HIPFFT) return false;
@@ -133,7 +156,7 @@ double2 unit_root(int64_t m, int64_t N, bool negative) {
 
 // ---- the band lists of a table -----------------------------------------------------------------------------------------
 // Bands marked for the zoom engine (mode 2 + class) leave `bands`, ordered by class.
-int upload_zoom_list(qi_plan* p, qi_plan::NativeTable& t, int64_t Lf, std::vector<native::BandDesc>& bands) {
+int upload_zoom_list(qi_plan* p, qi_plan::NativeTable& t, int64_t Lf, std::vector<native::BandDesc>& bands, bool stx) {
   std::vector<native::BandDesc> rest;
   std::vector<std::vector<native::BandDesc>> by_level(native::kZoomClasses);
   for (const auto& d : bands) {
@@ -161,6 +184,18 @@ int upload_zoom_list(qi_plan* p, qi_plan::NativeTable& t, int64_t Lf, std::vecto
   t.h_zoom.clear();
   t.zoom_planes = 0;
   t.zoom_max_level = 0;
+  t.x_lo = 0;
+  t.x_hi = -1;
+  for (const auto& lvl : by_level)
+    for (const auto& d : lvl) {  // bins zoom_gather_value reads: k (+ shift), k in [k_lo, k_lo + k_len)
+      const int64_t lo = d.k_lo + (stx ? d.shift : 0), hi = lo + d.k_len - 1;
+      if (t.x_lo > t.x_hi) {
+        t.x_lo = lo;
+        t.x_hi = hi;
+      }
+      t.x_lo = lo < t.x_lo ? lo : t.x_lo;
+      t.x_hi = hi > t.x_hi ? hi : t.x_hi;
+    }
   for (int g = 0; g < native::kZoomClasses; ++g) t.zoom_count[g] = (int32_t)by_level[g].size();
   for (int gi = 0; gi < native::kZoomClasses; ++gi) {
     // list order: the short-interpolator classes first, next to the 10-tap class of their grid, so that a call with
@@ -355,7 +390,7 @@ int upload_native_table(qi_plan* p, int kind, int64_t Lf, std::vector<native::Ba
     for (const auto& d : bands)
       fprintf(stderr, "[qi plan] table %d (Lf = %lld) band %d: %s, support [%d, +%d)\n", kind, (long long)Lf, d.out_band,
               d.mode == 0 ? "one-pass loader" : (d.mode == 1 ? "two-pass" : "zoom"), d.k_lo, d.k_len);
-  QI_TRY(upload_zoom_list(p, t, Lf, bands));
+  QI_TRY(upload_zoom_list(p, t, Lf, bands, kind == 2));
   if (z64_table(p, kind)) QI_TRY(upload_z64_list(p, t, kind, Lf, bands));
   return upload_two_pass_groups(p, t, Lf, bands);
 }

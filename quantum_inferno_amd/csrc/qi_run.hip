@@ -469,9 +469,10 @@ struct Arena {  // the plan's scratch, handed out front to back in regions of Ct
 
 // forward stage: spectra of ct records of n samples, zero-padded to Lf, into s.X (native kernels staged through one slot of
 // the intermediate, or pack + hipFFT) and, for the short-atom table, their even bins into s.Xn
+// low: only the bins (-K, K) into the compact array (native::fwd_low_bins; forward_low(p) holds, so no short-atom table)
 template <typename T>
-int launch_spectra(qi_plan* p, const T* sig, int64_t n, int64_t Lf, bool shorts, bool have_spectra, const Scratch<T>& s,
-                   int64_t ct, hipStream_t st) {
+int launch_spectra(qi_plan* p, const T* sig, int64_t n, int64_t Lf, bool shorts, bool have_spectra, bool low,
+                   const Scratch<T>& s, int64_t ct, hipStream_t st) {
   p->prof.begin(st, QI_STAGE_FORWARD);
   if (have_spectra) {
     // X already holds the zero-padded spectra of these records
@@ -486,7 +487,7 @@ int launch_spectra(qi_plan* p, const T* sig, int64_t n, int64_t Lf, bool shorts,
     f.sig = sig;
     f.two_over_len = (float)(2.0 / (double)Lf);
     f.debug = 0;
-    QI_TRY(native::launch_forward<T>(f, s.X, ct, st));
+    QI_TRY(native::launch_forward<T>(f, s.X, ct, st, low));
   } else {
     QI_TRY(launch_pack_pad<T>(sig, s.X, ct, n, Lf, st));
     QI_TRY(fft_c2c<T>(p->fft, s.X, Lf, ct, HIPFFT_FORWARD, st));
@@ -744,6 +745,7 @@ native::ZoomArgs<float> zoom_args(const qi_plan* p, int kind, const ZoomRows& r,
   z.plane_band = zt.d_zoom_plane_band;
   z.X = s.X;
   z.x_shift = x_shift ? 1 : 0;
+  z.x_mask = (uint32_t)((forward_low(p) ? native::fwd_low_len(zt.Lf) : zt.Lf) << z.x_shift) - 1u;
   z.Hc = static_cast<const cplx<T>*>(zt.Hc);
   z.coarse = s.zoom;
   z.stx = kind == 2 ? 1 : 0;
@@ -908,9 +910,17 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
                p->nat[kind].h_rows.empty() && !shorts;
   const int32_t nsplit = kind == 0 ? p->nsplit : 0;  // split bands: the zoom launch hands its part to the block launch
   ScratchBytes e = scratch_bytes<T>(p, n, B, nbk, stat_slots, chunk_total, shorts, time_via_part, out->coef != nullptr, nsplit);
-  e.x = (size_t)(share ? 2 * Lf0 : Lf0) * sizeof(cplx<T>);
+  // low-bins forward transform (a property of the plan: qi_cwt, qi_stx and both halves of qi_cwt_stx agree): X is the
+  // compact array of the bins near DC, and the forward transform stages through half a slot of the intermediate
+  const bool low = forward_low(p);
+  const int64_t x_len = low ? native::fwd_low_len(Lf0) : Lf0;
+  const int64_t fwd_imd = low ? native::fwd_low_rows(Lf0 / native::kN2) * native::kN2 : Lf0;
+  if (tune_env("QI_NATIVE_VERBOSE"))
+    fprintf(stderr, "[qi run] forward transform of table %d (Lf = %lld): %s, bins read (-%lld, %lld)\n", kind, (long long)Lf0,
+            low ? "low bins" : "every bin", (long long)table_low_bins(p, kind), (long long)table_low_bins(p, kind));
+  e.x = (size_t)(share ? 2 * x_len : x_len) * sizeof(cplx<T>);
   // (the forward transform of the records stages through one slot of the intermediate)
-  e.imd = (size_t)(tp.imd_elems < Lf0 ? Lf0 : tp.imd_elems) * sizeof(cplx<T>);
+  e.imd = (size_t)(tp.imd_elems < fwd_imd ? fwd_imd : tp.imd_elems) * sizeof(cplx<T>);
   e.zoom = zoom ? (size_t)zt.zoom_planes * native::kBlk * sizeof(cplx<T>) : 0;
   const size_t per_chan = e.per_record();
   if (probe) {
@@ -964,7 +974,7 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
     const TileOut<T> v = tile_out<T>(out, c0, B, n, time_via_part ? s.time_part : nullptr, s.part_band, s.part_stat, nbk,
                                      stat_slots, chunk_total);
     if (shorts) QI_HIP(hipMemsetAsync(s.parts0, 0, s.parts_bytes, st));
-    QI_TRY(launch_spectra<T>(p, sig_t, n, Lf0, shorts, share, s, ct, st));
+    QI_TRY(launch_spectra<T>(p, sig_t, n, Lf0, shorts, share, low, s, ct, st));
     QI_TRY(launch_two_pass<T>(p, tp, v, s, G, tp.nblk_max, /*diag=*/true, ct, st));
     if (zoom)
       QI_TRY(launch_zoom_stage(p, zoom_args(p, kind, zr, v, s, share, nsplit, p2_stats + blk_stats, chunk_z0), zt.zoom_max_level,
@@ -1207,7 +1217,7 @@ int run_native64(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tf
     const TileOut<T> v = tile_out<T>(out, c0, B, n, time_via_part ? s.time_part : nullptr, s.part_band, s.part_stat, nbk,
                                      stat_slots, chunk_total);
     if (clear_parts) QI_HIP(hipMemsetAsync(s.parts0, 0, s.parts_bytes, st));
-    QI_TRY(launch_spectra<T>(p, sig_t, n, Lf, shorts, false, s, ct, st));
+    QI_TRY(launch_spectra<T>(p, sig_t, n, Lf, shorts, false, /*low=*/false, s, ct, st));
     QI_TRY(launch_two_pass<T>(p, tp, v, s, G, nblk, /*diag=*/false, ct, st));
     QI_TRY(launch_z64_stage(p, kind, zr, v, s, nsplit, nblk, tp.chunk_total, ct, st));
     if (blocks)

@@ -40,7 +40,7 @@ __device__ __forceinline__ void zoom_gather_plane(const ZoomArgs<T>& a, const ui
   const int32_t kappa0 = (int32_t)(blockIdx.x * 256 + threadIdx.x);
   const uint32_t tau1 = plane - (uint32_t)bd.edge;
   const int64_t ch = blockIdx.z;
-  const cplx<T>* __restrict__ X = a.X + ch * (a.Lf << a.x_shift);
+  const cplx<T>* __restrict__ X = a.X + ch * ((int64_t)a.x_mask + 1);
   a.coarse[((int64_t)ch * a.planes + bd.edge) * kBlk + (int32_t)tau1 * kBlk + kappa0] =
       zoom_gather_value<T, STX>(a, bd, tau1, kappa0, X);
 }

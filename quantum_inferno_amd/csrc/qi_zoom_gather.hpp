@@ -21,7 +21,6 @@ __device__ __forceinline__ cplx<T> zoom_gather_value(const ZoomArgs<T>& a, const
   const int32_t M = (int32_t)((a.Lf / kZoomD) << bd.edge_slot), P = M / kBlk;
   const int32_t kc = STX ? 0 : bd.k_lo + bd.k_len / 2;
   const int32_t ks_lo = bd.k_lo - kc, ks_hi = ks_lo + bd.k_len;  // support in baseband bins
-  const uint32_t lmask = (uint32_t)a.Lf - 1u;
   cplx<T> acc = mk<T>(T(0), T(0));
   // the occupied baseband bins congruent to kappa0 modulo 4096: ks = ks0, ks0 + 4096, ... < ks_hi
   const int32_t ks0 = ks_lo + ((kappa0 - ks_lo) & (kBlk - 1));
@@ -31,12 +30,12 @@ __device__ __forceinline__ cplx<T> zoom_gather_value(const ZoomArgs<T>& a, const
     const int32_t k = kc + ks;
     cplx<T> y;
     if (STX) {
-      const cplx<T> x = X[((uint32_t)(k + (int32_t)bd.shift) & lmask) << a.x_shift];
+      const cplx<T> x = X[((uint32_t)(k + (int32_t)bd.shift) << a.x_shift) & a.x_mask];
       const T g0 = (T)bd.coef * (T)k;
       const T g = exp2_t(-g0 * g0) * a.inv_len;
       y = mk<T>(x.x * g, x.y * g);
     } else {
-      y = cmul(X[((uint32_t)k & lmask) << a.x_shift], a.Hc[bd.src_off + (k - bd.k_lo)]);  // k < 0: bins modulo Lf
+      y = cmul(X[((uint32_t)k << a.x_shift) & a.x_mask], a.Hc[bd.src_off + (k - bd.k_lo)]);  // k < 0: bins modulo the array
     }
     float sr, cr;
     sincospif(2.0f * (float)((r * tau1) & (uint32_t)(P - 1)) / (float)P, &sr, &cr);
@@ -60,7 +59,6 @@ __device__ __forceinline__ void zoom_gather16(const ZoomArgs<T>& a, const BandDe
   const int32_t M = (int32_t)((a.Lf / kZoomD) << bd.edge_slot), P = M / kBlk;
   const int32_t kc = STX ? 0 : bd.k_lo + bd.k_len / 2;
   const int32_t ks_lo = bd.k_lo - kc, ks_hi = ks_lo + bd.k_len;
-  const uint32_t lmask = (uint32_t)a.Lf - 1u;
   const int nterm = (bd.k_len + kBlk - 1) / kBlk;  // terms of the element whose first bin is the support's first
   int32_t ks0[16];
 #pragma unroll
@@ -94,9 +92,9 @@ __device__ __forceinline__ void zoom_gather16(const ZoomArgs<T>& a, const BandDe
         h[q] = mk<T>(T(0), T(0));
         if (on[q]) {
           if (STX) {
-            x[q] = X[((uint32_t)(k + (int32_t)bd.shift) & lmask) << a.x_shift];
+            x[q] = X[((uint32_t)(k + (int32_t)bd.shift) << a.x_shift) & a.x_mask];
           } else {
-            x[q] = X[((uint32_t)k & lmask) << a.x_shift];
+            x[q] = X[((uint32_t)k << a.x_shift) & a.x_mask];
             h[q] = a.Hc[bd.src_off + (k - bd.k_lo)];
           }
         }

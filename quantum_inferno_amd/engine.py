@@ -233,6 +233,11 @@ class TfrPlan:
         k = _lib.STAGES.index(stage)
         return [int(self._lib.qi_plan_stage_bands(self._handle, which, k)) for which in (0, 1, 2)]
 
+    def forward_low(self, which):
+        """0 when the plan's native runs form the whole record spectrum; otherwise (low-bins forward transform) the power
+        of two K with every spectrum bin table `which` reads inside (-K, K) (qi_plan_forward_low)."""
+        return int(self._lib.qi_plan_forward_low(self._handle, which))
+
     def band_route(self, which, band, records=1):
         """(stage name, cls, run_cls, flags) of the kernels that produce row `band` of table `which` in a call of
         `records` records (qi_plan_band_route; the flag bits are _lib.ROUTE_*)."""
