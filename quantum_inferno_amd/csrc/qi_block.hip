@@ -143,12 +143,53 @@ __device__ __forceinline__ void mul_powers16(cplx<T> (&v)[16], cplx<T> w) {
   v[brev(15, 4)] = cmul(v[brev(15, 4)], cmul(p8, p7));
 }
 
-// 4096-point transform of the workgroup's block.  Entry: v[b] = in[tid + 256 b]; exit: v[brev(c)] = out[tid + 256 c].
-// `w` = W4096^tid (inverse sign), `tw256[m]` = W256^m (inverse sign); DIR = -1 conjugates both.
-// Column order: the thread of lane L in wave wv owns column col = 64 wv + (L < 32 ? 2 L : 2 (L - 32) + 1) on entry
-// and on exit, i.e. lanes L and L + 32 hold ADJACENT samples -- after one v_permlane32_swap per register pair a lane
-// holds two adjacent outputs and stores them as 16 bytes (the epilogue is store-issue bound: half the store
-// instructions).  `w` = W4096^col.
+// The column of fft4096 that thread `tid` owns, on entry and on exit: lanes L and L + 32 of a wave hold ADJACENT samples --
+// after one v_permlane32_swap per register pair a lane holds two adjacent outputs and stores them as 16 bytes (the epilogue
+// is store-issue bound: half the store instructions).  Every kernel here computes it once and hands it down.
+__device__ __forceinline__ int fft4096_col(int tid) {
+  const int lane = tid & (kWave - 1);
+  return (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
+}
+
+// Workgroup set-up of fft4096: fills this thread's entry of tw256 and returns its w = W4096^col (both inverse sign).  The
+// float64 kernels' table is [W256 | the entropy logarithm's table, read by block_bands and edge_item]; `log2tab` = false
+// leaves the second part out.
+template <typename T>
+__device__ __forceinline__ cplx<T> fft4096_setup(cplx<T>* __restrict__ tw256, int tid, int col, bool log2tab = true) {
+  T s, c;
+  if constexpr (sizeof(T) == 8) {
+    sincospi((double)tid * (2.0 / 256.0), &s, &c);
+    tw256[tid] = mk<T>(c, s);
+    if (log2tab && tid < 128) tw256[256 + tid] = mk<T>(kLog2Tab[tid][0], kLog2Tab[tid][1]);
+    sincospi((double)col * (2.0 / 4096.0), &s, &c);
+  } else {
+    sincospif((float)tid * (2.0f / 256.0f), &s, &c);
+    tw256[tid] = mk<T>(c, s);
+    sincospif((float)col * (2.0f / 4096.0f), &s, &c);
+  }
+  return mk<T>(c, s);
+}
+// the long kernels' W8192^col
+template <typename T>
+__device__ __forceinline__ cplx<T> long_setup_w8(int col) {
+  float s, c;
+  sincospif((float)col * (2.0f / 8192.0f), &s, &c);
+  return mk<T>((T)c, (T)s);
+}
+
+// Runs `...` with WQ a compile-time constant: the reach group wq of an item (1, 2, else 4: taps within 256 WQ samples).
+// A macro, not a function that takes a callable: through a callable's extra inlining level the __restrict__ parameters of
+// the item functions become alias scopes that the direct call does not get, the optimiser hoists more across the band loop
+// and the float64 kernels, which sit at 256 registers, pay 170-230 bytes of scratch per lane for it.
+#define QI_WITH_REACH(wq, ...)                             \
+  switch (wq) {                                            \
+    case 1: { constexpr int WQ = 1; __VA_ARGS__; } break;  \
+    case 2: { constexpr int WQ = 2; __VA_ARGS__; } break;  \
+    default: { constexpr int WQ = 4; __VA_ARGS__; } break; \
+  }
+
+// 4096-point transform of the workgroup's block.  Entry: v[b] = in[col + 256 b]; exit: v[brev(c)] = out[col + 256 c],
+// col = fft4096_col(tid).  `w` = W4096^col (inverse sign), `tw256[m]` = W256^m (inverse sign); DIR = -1 conjugates both.
 template <typename T, int DIR>
 __device__ __forceinline__ void fft4096_tail(cplx<T> (&v)[16], cplx<T>* __restrict__ buf,
                                              const cplx<T>* __restrict__ tw256, int tid, int col);
@@ -254,6 +295,73 @@ __device__ __forceinline__ void fft4096_tail(cplx<T> (&v)[16], cplx<T>* __restri
   fft_reg<T, 16, DIR>(v);  // over k0 -> q0
 }
 
+// The wave sums of the pending band (`sums`: complete once a barrier has passed) into its slot of a.part_band, by thread 0.
+template <typename T>
+__device__ __forceinline__ void flush_band_sum(const BlockArgs<T>& a, int64_t ch, int64_t blk, int pending, const double* sums,
+                                               int tid) {
+  if (pending >= 0 && tid == 0) {
+    double r = 0.0;
+    for (int q = 0; q < kBlkThreads / kWave; ++q) r += sums[q];
+    a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + blk] = r;
+  }
+}
+
+// Workgroup maximum / sum / sum of the waves' r0 / r1 / r2 through buf (free: a barrier has passed since its last reader);
+// thread 0 writes them to statistics slot `stat_slot` -- `follows`: the slot already holds earlier bands and is added to --
+// and the sum r1 to a.part_band[band_slot] (band_slot >= 0: edge_item, whose one band has no wave sums to flush).
+template <typename T>
+__device__ __forceinline__ void reduce_stats(const BlockArgs<T>& a, cplx<T>* __restrict__ buf, double r0, double r1, double r2,
+                                             int64_t ch, int32_t stat_slot, int tid, bool follows = false, int64_t band_slot = -1) {
+  constexpr int NW = kBlkThreads / kWave;
+  if (!a.part_stat && band_slot < 0) return;  // (the same for the whole workgroup)
+  const int lane = tid & (kWave - 1), wv = tid / kWave;
+  double* fin = reinterpret_cast<double*>(buf);
+  if (lane == 0) {
+    fin[wv] = r0;
+    fin[NW + wv] = r1;
+    fin[2 * NW + wv] = r2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double m = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int q = 0; q < NW; ++q) {
+      m = fin[q] > m ? fin[q] : m;
+      s1 += fin[NW + q];
+      s2 += fin[2 * NW + q];
+    }
+    if (band_slot >= 0 && a.part_band) a.part_band[band_slot] = s1;
+    if (a.part_stat) {
+      double* o = a.part_stat + ((int64_t)ch * a.stat_stride + a.stat_base + stat_slot) * 3;
+      o[0] = follows ? (o[0] > m ? o[0] : m) : m;
+      o[1] = follows ? o[1] + s1 : s1;
+      o[2] = follows ? o[2] + s2 : s2;
+    }
+  }
+}
+
+// Gaussian weight of bin k of band bd: amp exp2(-(cw (k - kappa))^2).  `fold`: the filter spectrum wraps around the 4096 bins
+// -- k is taken to the alias within kBlk / 2 of kappa; on the Gabor banks' half-integer sample grid (!DEMOD) the aliases
+// alternate in sign.
+template <typename T, bool DEMOD>
+__device__ __forceinline__ T gauss_weight(const BlockBandT<T>& bd, int k, bool fold) {
+  T dk = (T)(k - bd.kappa_int) - (T)bd.kappa_frac;
+  T amp = (T)bd.amp;
+  if (fold && dk > (T)(kBlk / 2)) {
+    dk -= (T)kBlk;
+    if (!DEMOD) amp = -amp;
+  }
+  if (DEMOD && fold && dk < -(T)(kBlk / 2)) dk += (T)kBlk;
+  const T e = (T)bd.cw * dk;
+  return amp * fast_exp2(-e * e);
+}
+// The same where no alias matters (bd.nowrap): exp2(la - (cw (k - kappa))^2) straight from the bin index -- kf = k - kappa_int
+// is an exact float, the fractional part of kappa enters through the fused multiply-add.
+template <typename T>
+__device__ __forceinline__ T gauss_weight_nowrap(const BlockBandT<T>& bd, T kf) {
+  const T e = fma_t((T)bd.cw, kf, -(T)bd.cw * (T)bd.kappa_frac);
+  return fast_exp2(fma_t(-e, e, (T)bd.la));
+}
+
 // Spectrum of record samples [t0, t0 + 4096) (CIRC: the record wraps -- Stockwell; else it is zero outside -- the
 // reference's zero padding), in natural order: S[c] = bin col + 256 c.
 template <typename T, bool CIRC>
@@ -289,12 +397,11 @@ template <typename T, int WQ, bool DEMOD, bool COEF, bool BITS, bool EDGE = fals
 __device__ __forceinline__ void block_bands(const BlockArgs<T>& a, int32_t blk_i, int32_t band_first, int32_t band_count,
                                             int32_t plane, int32_t stat_slot, cplx<T> (&S)[16], cplx<T>* __restrict__ buf,
                                             const cplx<T>* __restrict__ tw256, double (*s_red)[kBlkThreads / kWave],
-                                            cplx<T> w, int edge_piece = 0) {
+                                            cplx<T> w, int col, int edge_piece = 0) {
   static_assert(!EDGE || !DEMOD, "split bands belong to the styx table");
-  constexpr int W = 256 * WQ, V = kBlk - 2 * W, NOUT = 16 - 2 * WQ, NW = kBlkThreads / kWave;
+  constexpr int W = 256 * WQ, V = kBlk - 2 * W, NOUT = 16 - 2 * WQ;
   constexpr bool F64 = sizeof(T) == 8;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  const int col = kWave * wv + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // the column this thread owns
   const int64_t blk = blk_i, ch = blockIdx.z;
   const int64_t n = a.n;
 #ifdef QI_NATIVE_STAMPS
@@ -343,19 +450,11 @@ __device__ __forceinline__ void block_bands(const BlockArgs<T>& a, int32_t blk_i
       const cplx<T> x = pick_pair16<T>(S, __builtin_amdgcn_readfirstlane(bd.klo >> 8), first);
       T r;
       if constexpr (F64) {
-        // (float64: the plan-time weight table holds this bin's weight -- block_bands' formula in double, aliases and signs
+        // (float64: the plan-time weight table holds this bin's weight -- gauss_weight's formula in double, aliases and signs
         // included; `narrow` is set there only when every weight above 2^-52 of the peak lies inside the 256-bin window)
         r = a.gauss_w[(int64_t)(band_first + jj) * kBlk + k];
       } else {
-        T dk = (T)(k - bd.kappa_int) - (T)bd.kappa_frac;
-        T amp = (T)bd.amp;
-        if (dk > (T)(kBlk / 2)) {
-          dk -= (T)kBlk;
-          if (!DEMOD) amp = -amp;  // half-integer sample grid: the aliases alternate in sign
-        }
-        if (DEMOD && dk < -(T)(kBlk / 2)) dk += (T)kBlk;
-        const T e = (T)bd.cw * dk;
-        r = amp * fast_exp2(-e * e);
+        r = gauss_weight<T, DEMOD>(bd, k, true);
       }
       cplx<T> wq = w;
       asm volatile("" : "+v"(wq.x), "+v"(wq.y));
@@ -381,13 +480,10 @@ __device__ __forceinline__ void block_bands(const BlockArgs<T>& a, int32_t blk_i
       // lower eight values of a thread, and the upper eight are taken as zero)
       const bool lower = bd.narrow == 2;
       if (bd.nowrap) {
-        // no alias of the filter spectrum matters: weight(k) = exp2(la - (cw (k - kappa))^2) straight from the bin index
-        // (k - kappa_int is an exact float; the fractional part of kappa enters through the fused multiply-add)
-        const T kf0 = (T)(col - bd.kappa_int), cwf = -(T)bd.cw * (T)bd.kappa_frac, cw = (T)bd.cw, la = (T)bd.la;
+        const T kf0 = (T)(col - bd.kappa_int);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
-          const T e = fma_t(cw, kf0 + (T)(256 * b), cwf);
-          const T r = fast_exp2(fma_t(-e, e, la));
+          const T r = gauss_weight_nowrap<T>(bd, kf0 + (T)(256 * b));
           v[b] = mk<T>(S[b].x * r, S[b].y * r);
         }
         if (lower) {
@@ -396,43 +492,26 @@ __device__ __forceinline__ void block_bands(const BlockArgs<T>& a, int32_t blk_i
         } else {
 #pragma unroll
           for (int b = 8; b < 16; ++b) {
-            const T e = fma_t(cw, kf0 + (T)(256 * b), cwf);
-            const T r = fast_exp2(fma_t(-e, e, la));
+            const T r = gauss_weight_nowrap<T>(bd, kf0 + (T)(256 * b));
             v[b] = mk<T>(S[b].x * r, S[b].y * r);
           }
         }
       } else {
 #pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        T dk = (T)(col + 256 * b - bd.kappa_int) - (T)bd.kappa_frac;
-        T amp = (T)bd.amp;
-        if (!lower && dk > (T)(kBlk / 2)) {
-          dk -= (T)kBlk;
-          if (!DEMOD) amp = -amp;  // half-integer sample grid: the aliases alternate in sign
-        }
-        if (DEMOD && !lower && dk < -(T)(kBlk / 2)) dk += (T)kBlk;
-        const T e = (T)bd.cw * dk;
-        const T r = amp * fast_exp2(-e * e);
-        v[b] = mk<T>(S[b].x * r, S[b].y * r);
-      }
-      if (lower) {
-#pragma unroll
-        for (int b = 8; b < 16; ++b) v[b] = mk<T>(T(0), T(0));
-      } else {
-#pragma unroll
-        for (int b = 8; b < 16; ++b) {
-          T dk = (T)(col + 256 * b - bd.kappa_int) - (T)bd.kappa_frac;
-          T amp = (T)bd.amp;
-          if (dk > (T)(kBlk / 2)) {
-            dk -= (T)kBlk;
-            if (!DEMOD) amp = -amp;
-          }
-          if (DEMOD && dk < -(T)(kBlk / 2)) dk += (T)kBlk;
-          const T e = (T)bd.cw * dk;
-          const T r = amp * fast_exp2(-e * e);
+        for (int b = 0; b < 8; ++b) {
+          const T r = gauss_weight<T, DEMOD>(bd, col + 256 * b, !lower);
           v[b] = mk<T>(S[b].x * r, S[b].y * r);
         }
-      }
+        if (lower) {
+#pragma unroll
+          for (int b = 8; b < 16; ++b) v[b] = mk<T>(T(0), T(0));
+        } else {
+#pragma unroll
+          for (int b = 8; b < 16; ++b) {
+            const T r = gauss_weight<T, DEMOD>(bd, col + 256 * b, true);
+            v[b] = mk<T>(S[b].x * r, S[b].y * r);
+          }
+        }
       }
     } else {
       const cplx<T>* __restrict__ H =
@@ -450,11 +529,7 @@ __device__ __forceinline__ void block_bands(const BlockArgs<T>& a, int32_t blk_i
     }
     if ((EDGE || bd.narrow != 1) && !QI_BDBG(4)) fft4096<T, 1>(v, buf, tw256, w, tid, col);
     QI_BSTAMP(3);
-    if (pending >= 0 && tid == 0) {
-      double r = 0.0;
-      for (int q = 0; q < NW; ++q) r += s_red[par ^ 1][q];
-      a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + blk] = r;
-    }
+    flush_band_sum(a, ch, blk, pending, s_red[par ^ 1], tid);
 
     cplx<T> ph = mk<T>(T(1), T(0));
     if (DEMOD && !F64) {
@@ -579,32 +654,8 @@ __device__ __forceinline__ void block_bands(const BlockArgs<T>& a, int32_t blk_i
   }
   const double r0 = wave_max((double)mx), r1 = wave_sum((double)tot), r2 = wave_sum(plogp);
   __syncthreads();  // the last band's wave sums are visible; buf is free
-  if (pending >= 0 && tid == 0) {
-    double r = 0.0;
-    for (int q = 0; q < NW; ++q) r += s_red[par ^ 1][q];
-    a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + blk] = r;
-  }
-  if (a.part_stat) {
-    double* fin = reinterpret_cast<double*>(buf);
-    if (lane == 0) {
-      fin[wv] = r0;
-      fin[NW + wv] = r1;
-      fin[2 * NW + wv] = r2;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double m = 0.0, s1 = 0.0, s2 = 0.0;
-      for (int q = 0; q < NW; ++q) {
-        m = fin[q] > m ? fin[q] : m;
-        s1 += fin[NW + q];
-        s2 += fin[2 * NW + q];
-      }
-      double* o = a.part_stat + ((int64_t)ch * a.stat_stride + a.stat_base + stat_slot) * 3;
-      o[0] = m;
-      o[1] = s1;
-      o[2] = s2;
-    }
-  }
+  flush_band_sum(a, ch, blk, pending, s_red[par ^ 1], tid);
+  reduce_stats(a, buf, r0, r1, r2, ch, stat_slot, tid);
 }
 
 // One work item: block `it.block` of the reach group WQ (taps within W = 256 WQ samples), bands
@@ -613,14 +664,12 @@ __device__ __forceinline__ void block_bands(const BlockArgs<T>& a, int32_t blk_i
 template <typename T, int WQ, bool DEMOD, bool COEF, bool BITS>
 __device__ __forceinline__ void block_item(const BlockArgs<T>& a, const BlockItem& it, cplx<T>* __restrict__ buf,
                                            const cplx<T>* __restrict__ tw256, double (*s_red)[kBlkThreads / kWave],
-                                           cplx<T> w) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
+                                           cplx<T> w, int col) {
   cplx<T> S[16];
   block_forward<T, DEMOD>(a.sig + (int64_t)blockIdx.z * a.n, a.n, (int64_t)it.block * (kBlk - 512 * WQ) - 256 * WQ, S, buf, tw256,
-                          w, tid, col);
+                          w, threadIdx.x, col);
   block_bands<T, WQ, DEMOD, COEF, BITS>(a, it.block, it.band_first, it.band_count, it.plane, it.stat_slot, S, buf, tw256,
-                                        s_red, w);
+                                        s_red, w, col);
 }
 
 
@@ -670,10 +719,9 @@ template <typename T, bool DEMOD, bool COEF, bool BITS>
 __device__ __forceinline__ void long_bands(const BlockArgs<T>& a, int32_t blk_i, int32_t band_first, int32_t band_count,
                                            int32_t plane, int32_t stat_slot, cplx<T> (&S)[16], cplx<T>* __restrict__ buf,
                                            const cplx<T>* __restrict__ tw256, double (*s_red)[kBlkThreads / kWave],
-                                           cplx<T> w, cplx<T> w8) {
-  constexpr int W = 1024, V = kBlkLongValid, NOUT = 12, C0 = 2, NW = kBlkThreads / kWave;  // pairs c = 2 .. 13 of a thread are kept
+                                           cplx<T> w, cplx<T> w8, int col) {
+  constexpr int W = 1024, V = kBlkLongValid, NOUT = 12, C0 = 2;  // pairs c = 2 .. 13 of a thread are kept
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  const int col = kWave * wv + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
   const int64_t blk = blk_i, ch = blockIdx.z, n = a.n;
   const int64_t t0 = blk * V - W;  // record samples [t0, t0 + 8192), outputs [t0 + W, t0 + W + V)
   if (!DEMOD) {
@@ -698,9 +746,7 @@ __device__ __forceinline__ void long_bands(const BlockArgs<T>& a, int32_t blk_i,
     const int k = (bd.klo + kres) & (kBlk - 1);  // (the band lies in the lower half of the 8192-bin grid)
     const bool first = (k >> 8) == (bd.klo >> 8);
     const cplx<T> x = pick_pair16<T>(S, __builtin_amdgcn_readfirstlane(bd.klo >> 8), first);
-    const T dk = (T)(k - bd.kappa_int) - (T)bd.kappa_frac;
-    const T e = (T)bd.cw * dk;
-    const T r = (T)bd.amp * fast_exp2(-e * e);
+    const T r = gauss_weight<T, DEMOD>(bd, k, false);
     const cplx<T> y = mk<T>(x.x * r, x.y * r);
     cplx<T> wq = w, wq8 = w8;
     asm volatile("" : "+v"(wq.x), "+v"(wq.y), "+v"(wq8.x), "+v"(wq8.y));
@@ -734,11 +780,7 @@ __device__ __forceinline__ void long_bands(const BlockArgs<T>& a, int32_t blk_i,
       for (int i = 0; i < NOUT; ++i) ze[i] = v[brev(i + C0, 4)];
       sparse_head16<T>(v, cmul(y, tw_odd), om);  // odd output samples: Y[k] W_8192^k
       fft4096_tail<T, 1>(v, buf, tw256, tid, col);
-      if (pending >= 0 && tid == 0) {
-        double rs = 0.0;
-        for (int q = 0; q < NW; ++q) rs += s_red[par ^ 1][q];
-        a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + blk] = rs;
-      }
+      flush_band_sum(a, ch, blk, pending, s_red[par ^ 1], tid);
       auto finish_band = [&](auto guard) {  // guard: the block reaches past the end of the record (see block_bands)
       constexpr bool GUARD = decltype(guard)::value;
       cplx<T> seed = ph, rcur = ph;
@@ -799,63 +841,37 @@ __device__ __forceinline__ void long_bands(const BlockArgs<T>& a, int32_t blk_i,
   }
   const double r0 = wave_max((double)mx), r1 = wave_sum((double)tot), r2 = wave_sum(plogp);
   __syncthreads();  // the last band's wave sums are visible; buf is free
-  if (pending >= 0 && tid == 0) {
-    double rs = 0.0;
-    for (int q = 0; q < NW; ++q) rs += s_red[par ^ 1][q];
-    a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + blk] = rs;
-  }
-  if (a.part_stat) {
-    double* fin = reinterpret_cast<double*>(buf);
-    if (lane == 0) {
-      fin[wv] = r0;
-      fin[NW + wv] = r1;
-      fin[2 * NW + wv] = r2;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double m = 0.0, s1 = 0.0, s2 = 0.0;
-      for (int q = 0; q < NW; ++q) {
-        m = fin[q] > m ? fin[q] : m;
-        s1 += fin[NW + q];
-        s2 += fin[2 * NW + q];
-      }
-      double* o = a.part_stat + ((int64_t)ch * a.stat_stride + a.stat_base + stat_slot) * 3;
-      o[0] = m;
-      o[1] = s1;
-      o[2] = s2;
-    }
-  }
+  flush_band_sum(a, ch, blk, pending, s_red[par ^ 1], tid);
+  reduce_stats(a, buf, r0, r1, r2, ch, stat_slot, tid);
 }
 
 template <typename T, bool DEMOD, bool COEF, bool BITS>
 __device__ __forceinline__ void long_item(const BlockArgs<T>& a, const BlockItem& it, cplx<T>* __restrict__ buf,
                                           const cplx<T>* __restrict__ tw256, double (*s_red)[kBlkThreads / kWave], cplx<T> w,
-                                          cplx<T> w8) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
+                                          cplx<T> w8, int col) {
   cplx<T> S[16];
   block_forward8<T, DEMOD>(a.sig + (int64_t)blockIdx.z * a.n, a.n, (int64_t)it.block * kBlkLongValid - 1024, S, buf, tw256, w, w8,
-                           tid, col);
-  long_bands<T, DEMOD, COEF, BITS>(a, it.block, it.band_first, it.band_count, it.plane, it.stat_slot, S, buf, tw256, s_red, w, w8);
+                           threadIdx.x, col);
+  long_bands<T, DEMOD, COEF, BITS>(a, it.block, it.band_first, it.band_count, it.plane, it.stat_slot, S, buf, tw256, s_red, w, w8,
+                                   col);
 }
 
 // joint launch: the Stockwell bands and the styx bands of the same long block (see dual_item)
 template <typename T, bool COEF, bool BITS>
 __device__ __forceinline__ void long_dual_item(const BlockArgs<T>& a0, const BlockArgs<T>& a2, const DualItem& it,
                                                cplx<T>* __restrict__ buf, const cplx<T>* __restrict__ tw256,
-                                               double (*s_red)[kBlkThreads / kWave], cplx<T> w, cplx<T> w8) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
+                                               double (*s_red)[kBlkThreads / kWave], cplx<T> w, cplx<T> w8, int col) {
+  const int tid = threadIdx.x;
   const int64_t n = a0.n, t0 = (int64_t)it.block * kBlkLongValid - 1024;
   const bool inside = t0 >= 0 && t0 + kBlkLong <= n;
   const T* sig = a0.sig + (int64_t)blockIdx.z * n;
   cplx<T> S[16];
   if (it.count2 > 0 || inside) block_forward8<T, true>(sig, n, t0, S, buf, tw256, w, w8, tid, col);
   if (it.count2 > 0)
-    long_bands<T, true, COEF, BITS>(a2, it.block, it.first2, it.count2, it.plane2, it.slot2, S, buf, tw256, s_red, w, w8);
+    long_bands<T, true, COEF, BITS>(a2, it.block, it.first2, it.count2, it.plane2, it.slot2, S, buf, tw256, s_red, w, w8, col);
   if (it.count0 > 0) {
     if (!inside) block_forward8<T, false>(sig, n, t0, S, buf, tw256, w, w8, tid, col);
-    long_bands<T, false, COEF, BITS>(a0, it.block, it.first0, it.count0, it.plane0, it.slot0, S, buf, tw256, s_red, w, w8);
+    long_bands<T, false, COEF, BITS>(a0, it.block, it.first0, it.count0, it.plane0, it.slot0, S, buf, tw256, s_red, w, w8, col);
   }
 }
 
@@ -865,19 +881,18 @@ __device__ __forceinline__ void long_dual_item(const BlockArgs<T>& a0, const Blo
 template <typename T, int WQ, bool COEF, bool BITS>
 __device__ __forceinline__ void dual_item(const BlockArgs<T>& a0, const BlockArgs<T>& a2, const DualItem& it,
                                           cplx<T>* __restrict__ buf, const cplx<T>* __restrict__ tw256,
-                                          double (*s_red)[kBlkThreads / kWave], cplx<T> w) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
+                                          double (*s_red)[kBlkThreads / kWave], cplx<T> w, int col) {
+  const int tid = threadIdx.x;
   const int64_t n = a0.n, t0 = (int64_t)it.block * (kBlk - 512 * WQ) - 256 * WQ;
   const bool inside = t0 >= 0 && t0 + kBlk <= n;
   const T* sig = a0.sig + (int64_t)blockIdx.z * n;
   cplx<T> S[16];
   if (it.count2 > 0 || inside) block_forward<T, true>(sig, n, t0, S, buf, tw256, w, tid, col);
   if (it.count2 > 0)
-    block_bands<T, WQ, true, COEF, BITS>(a2, it.block, it.first2, it.count2, it.plane2, it.slot2, S, buf, tw256, s_red, w);
+    block_bands<T, WQ, true, COEF, BITS>(a2, it.block, it.first2, it.count2, it.plane2, it.slot2, S, buf, tw256, s_red, w, col);
   if (it.count0 > 0) {
     if (!inside) block_forward<T, false>(sig, n, t0, S, buf, tw256, w, tid, col);
-    block_bands<T, WQ, false, COEF, BITS>(a0, it.block, it.first0, it.count0, it.plane0, it.slot0, S, buf, tw256, s_red, w);
+    block_bands<T, WQ, false, COEF, BITS>(a0, it.block, it.first0, it.count0, it.plane0, it.slot0, S, buf, tw256, s_red, w, col);
   }
 }
 
@@ -889,10 +904,9 @@ __device__ __forceinline__ void dual_item(const BlockArgs<T>& a0, const BlockArg
 // with two pieces): added to instead of written.
 template <typename T, int WQ, bool COEF, bool BITS>
 __device__ __forceinline__ void edge_item(const BlockArgs<T>& a, const BlockItem& it, cplx<T>* __restrict__ buf,
-                                          const cplx<T>* __restrict__ tw256, cplx<T> w, bool follows = false) {
-  constexpr int W = 256 * WQ, V = kBlk - 2 * W, NOUT = 16 - 2 * WQ, NW = kBlkThreads / kWave;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  const int col = kWave * wv + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // fft4096's column order
+                                          const cplx<T>* __restrict__ tw256, cplx<T> w, int col, bool follows = false) {
+  constexpr int W = 256 * WQ, V = kBlk - 2 * W, NOUT = 16 - 2 * WQ;
+  const int tid = threadIdx.x;
   const int64_t n = a.n, ch = blockIdx.z, blk = it.block;
   const int sb = it.band_first, out_band = a.edge_band[sb];
   const int64_t t0 = blk * V - W;  // outputs [t0 + W, t0 + W + V)
@@ -953,28 +967,7 @@ __device__ __forceinline__ void edge_item(const BlockArgs<T>& a, const BlockItem
   }
   const double r0 = wave_max((double)mx), r1 = wave_sum((double)rowacc), r2 = wave_sum((double)pl);
   __syncthreads();  // buf is free
-  double* fin = reinterpret_cast<double*>(buf);
-  if (lane == 0) {
-    fin[wv] = r0;
-    fin[NW + wv] = r1;
-    fin[2 * NW + wv] = r2;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double m = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int q = 0; q < NW; ++q) {
-      m = fin[q] > m ? fin[q] : m;
-      s1 += fin[NW + q];
-      s2 += fin[2 * NW + q];
-    }
-    if (a.part_band) a.part_band[((int64_t)ch * a.panel_bands + out_band) * a.nblk + blk] = s1;
-    if (a.part_stat) {
-      double* o = a.part_stat + ((int64_t)ch * a.stat_stride + a.stat_base + it.stat_slot) * 3;
-      o[0] = follows ? (o[0] > m ? o[0] : m) : m;
-      o[1] = follows ? o[1] + s1 : s1;
-      o[2] = follows ? o[2] + s2 : s2;
-    }
-  }
+  reduce_stats(a, buf, r0, r1, r2, ch, it.stat_slot, tid, follows, ((int64_t)ch * a.panel_bands + out_band) * a.nblk + blk);
 }
 
 // The same for ALL split bands of an output block (it.band_first ... + it.band_count): the block's far piece is read and
@@ -989,10 +982,9 @@ __device__ __forceinline__ void edge_item(const BlockArgs<T>& a, const BlockItem
 template <typename T, int WQ, bool COEF, bool BITS, int PATH = 0>
 __device__ __forceinline__ void edge_block_item(const BlockArgs<T>& a, const BlockItem& it, cplx<T>* __restrict__ buf,
                                                 const cplx<T>* __restrict__ tw256, double (*s_red)[kBlkThreads / kWave],
-                                                cplx<T> w) {
+                                                cplx<T> w, int col) {
   constexpr int W = 256 * WQ, V = kBlk - 2 * W;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  const int col = kWave * wv + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // fft4096's column order
+  const int tid = threadIdx.x;
   const int64_t n = a.n, t0 = (int64_t)it.block * V - W;
   const int64_t in_p[2] = {t0 + (n / 2 - W), t0 - (n / 2 - W)};
   const bool has_p[2] = {!(in_p[0] >= n || in_p[0] + kBlk <= 0), !(in_p[1] >= n || in_p[1] + kBlk <= 0)};
@@ -1001,7 +993,7 @@ __device__ __forceinline__ void edge_block_item(const BlockArgs<T>& a, const Blo
       for (int32_t q = 0; q < it.band_count; ++q) {
         const BlockItem one{it.wq, it.block, it.band_first + q, 0, it.plane, it.stat_slot};
         if (q > 0) __syncthreads();  // the previous band's statistics have left the exchange buffer
-        edge_item<T, WQ, COEF, BITS>(a, one, buf, tw256, w, q > 0);
+        edge_item<T, WQ, COEF, BITS>(a, one, buf, tw256, w, col, q > 0);
       }
     }
     return;
@@ -1020,7 +1012,7 @@ __device__ __forceinline__ void edge_block_item(const BlockArgs<T>& a, const Blo
 #pragma unroll
   for (int b = 0; b < 16; ++b) Sn[b] = S[brev(b, 4)];
   block_bands<T, WQ, false, COEF, BITS, true>(a, it.block, it.band_first, it.band_count, it.plane, it.stat_slot, Sn, buf, tw256,
-                                              s_red, w, piece);
+                                              s_red, w, col, piece);
 }
 
 #ifndef QI_BLK_EDGE_WAVES
@@ -1033,13 +1025,8 @@ __global__ void __launch_bounds__(kBlkThreads, QI_BLK_EDGE_WAVES) k_block_edge(B
   __shared__ cplx<T> buf[kBlkBuf];
   __shared__ cplx<T> tw256[256];
   __shared__ double s_red[2][kBlkThreads / kWave];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
-  float sn, cs;
-  sincospif((float)tid * (2.0f / 256.0f), &sn, &cs);
-  tw256[tid] = mk<T>((T)cs, (T)sn);
-  sincospif((float)col * (2.0f / 4096.0f), &sn, &cs);
-  const cplx<T> w = mk<T>((T)cs, (T)sn);
+  const int tid = threadIdx.x, col = fft4096_col(tid);
+  const cplx<T> w = fft4096_setup<T>(tw256, tid, col);
   BlockItem it;
   if (items) {
     it = load_uniform(items + blockIdx.x);
@@ -1047,11 +1034,7 @@ __global__ void __launch_bounds__(kBlkThreads, QI_BLK_EDGE_WAVES) k_block_edge(B
     const DualItem d = load_uniform(dual + blockIdx.x);
     it = BlockItem{d.wq, d.block, d.first0, d.count0, d.plane0, d.slot0};
   }
-  switch (-it.wq) {
-    case 1: edge_block_item<T, 1, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-    case 2: edge_block_item<T, 2, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-    default: edge_block_item<T, 4, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-  }
+  QI_WITH_REACH(-it.wq, edge_block_item<T, WQ, COEF, BITS>(a, it, buf, tw256, s_red, w, col));
 }
 
 template <typename T, bool DEMOD, bool COEF, bool BITS>
@@ -1059,37 +1042,15 @@ __global__ void __launch_bounds__(kBlkThreads, QI_BLK_WAVES) k_block(BlockArgs<T
   __shared__ cplx<T> buf[kBlkBuf];
   __shared__ cplx<T> tw256[256];
   __shared__ double s_red[2][kBlkThreads / kWave];
-  const int tid = threadIdx.x;
-  {
-    float s, c;
-    sincospif((float)tid * (2.0f / 256.0f), &s, &c);
-    tw256[tid] = mk<T>((T)c, (T)s);
-  }
-  cplx<T> w;
-  {
-    float s, c;
-    const int lane = tid & (kWave - 1);
-    const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // block_item's column order
-    sincospif((float)col * (2.0f / 4096.0f), &s, &c);
-    w = mk<T>((T)c, (T)s);
-  }
+  const int tid = threadIdx.x, col = fft4096_col(tid);
+  const cplx<T> w = fft4096_setup<T>(tw256, tid, col);
   const BlockItem it = load_uniform(a.items + blockIdx.x);
   if (it.wq < 0) {
     // edge item of a split band (styx bank): light items at the end of the list, they fill the tail of the launch
-    if constexpr (!DEMOD) {
-      switch (-it.wq) {
-        case 1: edge_item<T, 1, COEF, BITS>(a, it, buf, tw256, w); break;
-        case 2: edge_item<T, 2, COEF, BITS>(a, it, buf, tw256, w); break;
-        default: edge_item<T, 4, COEF, BITS>(a, it, buf, tw256, w); break;
-      }
-    }
+    if constexpr (!DEMOD) QI_WITH_REACH(-it.wq, edge_item<T, WQ, COEF, BITS>(a, it, buf, tw256, w, col));
     return;
   }
-  switch (it.wq) {
-    case 1: block_item<T, 1, DEMOD, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-    case 2: block_item<T, 2, DEMOD, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-    default: block_item<T, 4, DEMOD, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-  }
+  QI_WITH_REACH(it.wq, block_item<T, WQ, DEMOD, COEF, BITS>(a, it, buf, tw256, s_red, w, col));
 }
 
 // float64 records (run_native64): the same band items in double arithmetic -- Gaussian filter spectra in registers, no
@@ -1102,26 +1063,10 @@ __global__ void __launch_bounds__(kBlkThreads, 2) k_block64(BlockArgs<double> a)
   double2* buf = reinterpret_cast<double2*>(smem64);
   double2* tw256 = buf + kBlkBuf;
   __shared__ double s_red[2][kBlkThreads / kWave];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // block_item's column order
-  {
-    double s, c;
-    sincospi((double)tid * (2.0 / 256.0), &s, &c);
-    tw256[tid] = make_double2(c, s);
-    if (tid < 128) tw256[256 + tid] = make_double2(kLog2Tab[tid][0], kLog2Tab[tid][1]);  // (block_bands' entropy logarithm)
-  }
-  double2 w;
-  {
-    double s, c;
-    sincospi((double)col * (2.0 / 4096.0), &s, &c);
-    w = make_double2(c, s);
-  }
+  const int tid = threadIdx.x, col = fft4096_col(tid);
+  const double2 w = fft4096_setup<double>(tw256, tid, col);
   const BlockItem it = load_uniform(a.items + blockIdx.x);
-  switch (it.wq) {
-    case 1: block_item<double, 1, DEMOD, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-    case 2: block_item<double, 2, DEMOD, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-    default: block_item<double, 4, DEMOD, COEF, BITS>(a, it, buf, tw256, s_red, w); break;
-  }
+  QI_WITH_REACH(it.wq, block_item<double, WQ, DEMOD, COEF, BITS>(a, it, buf, tw256, s_red, w, col));
 }
 
 // the split bands of a float64 styx table: one edge item per block (edge_block_item), always a launch of its own (PATH 2:
@@ -1132,20 +1077,10 @@ __global__ void __launch_bounds__(kBlkThreads, 2) k_block64_edge(BlockArgs<doubl
   double2* buf = reinterpret_cast<double2*>(smem64);
   double2* tw256 = buf + kBlkBuf;
   __shared__ double s_red[2][kBlkThreads / kWave];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
-  double s, c;
-  sincospi((double)tid * (2.0 / 256.0), &s, &c);
-  tw256[tid] = make_double2(c, s);
-  if (tid < 128) tw256[256 + tid] = make_double2(kLog2Tab[tid][0], kLog2Tab[tid][1]);
-  sincospi((double)col * (2.0 / 4096.0), &s, &c);
-  const double2 w = make_double2(c, s);
+  const int tid = threadIdx.x, col = fft4096_col(tid);
+  const double2 w = fft4096_setup<double>(tw256, tid, col);
   const BlockItem it = load_uniform(items + blockIdx.x);
-  switch (-it.wq) {
-    case 1: edge_block_item<double, 1, COEF, BITS, PATH>(a, it, buf, tw256, s_red, w); break;
-    case 2: edge_block_item<double, 2, COEF, BITS, PATH>(a, it, buf, tw256, s_red, w); break;
-    default: edge_block_item<double, 4, COEF, BITS, PATH>(a, it, buf, tw256, s_red, w); break;
-  }
+  QI_WITH_REACH(-it.wq, edge_block_item<double, WQ, COEF, BITS, PATH>(a, it, buf, tw256, s_red, w, col));
 }
 
 // ---- float64 zoom, coarse stage in LDS (round 4) ---------------------------------------------------------------------
@@ -1229,14 +1164,13 @@ __device__ __forceinline__ void z64_gather16(const Z64Args& a, const BandDesc& b
   sincospi(2.0 * (double)(((uint32_t)col * tau1) & ((uint32_t)M - 1u)) / (double)M, &sf, &cf);
   const double2 e0 = make_double2(cf, sf);
   sincospi(2.0 * (double)((256u * tau1) & ((uint32_t)M - 1u)) / (double)M, &sf, &cf);
-  const double2 s1 = make_double2(cf, sf), s2 = cmul(s1, s1), s4 = cmul(s2, s2), s8 = cmul(s4, s4);
+  const double2 s1 = make_double2(cf, sf);
   double2 pw = e0;
 #pragma unroll
   for (int b = 0; b < 16; ++b) {  // (Gray-code-free walk: pw(b) from pw(b - lowbit(b)) needs sixteen live values; b -> b + 1 by s1,
     v[b] = cmul(v[b], pw);        //  fifteen roundings deep, is far inside the float64 tolerance and holds one)
     pw = cmul(pw, s1);
   }
-  (void)s2; (void)s4; (void)s8;
 }
 
 template <bool STX>
@@ -1244,8 +1178,7 @@ __global__ void __launch_bounds__(kBlkThreads, 2) k_z64_coarse(Z64Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem64[];
   double2* buf = reinterpret_cast<double2*>(smem64);
   double2* tw256 = buf + kBlkBuf;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // fft4096's column order
+  const int tid = threadIdx.x, col = fft4096_col(tid);
   const int32_t P = (int32_t)(a.M / kBlk);
   // Consecutive workgroups go to consecutive XCDs; the P planes of a band fill the same 128-byte lines of its coarse array
   // (sample tau = P tau2 + tau1, 16 bytes each) and gather the same bins: consecutive planes sit behind ONE L2 -- workgroup
@@ -1258,17 +1191,7 @@ __global__ void __launch_bounds__(kBlkThreads, 2) k_z64_coarse(Z64Args a) {
   const int64_t ch = blockIdx.y;
   double2 v[16];
   z64_gather16<STX>(a, bd, tau1, col, a.X + ch * a.Lf, v);
-  {
-    double s, c;
-    sincospi((double)tid * (2.0 / 256.0), &s, &c);
-    tw256[tid] = make_double2(c, s);
-  }
-  double2 w;
-  {
-    double s, c;
-    sincospi((double)col * (2.0 / 4096.0), &s, &c);
-    w = make_double2(c, s);
-  }
+  const double2 w = fft4096_setup<double>(tw256, tid, col, false);  // (no entropy here)
   fft4096<double, 1>(v, buf, tw256, w, tid, col);
   double2* __restrict__ z = a.Z + ((int64_t)ch * a.nbands + band) * (a.M + 2 * kZ64Pad) + kZ64Pad;
 #pragma unroll
@@ -1288,16 +1211,9 @@ __global__ void __launch_bounds__(kBlkThreads, QI_BLK_LONG_WAVES) k_block_long(B
   __shared__ cplx<T> buf[kBlkBuf];
   __shared__ cplx<T> tw256[256];
   __shared__ double s_red[2][kBlkThreads / kWave];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
-  float s, c;
-  sincospif((float)tid * (2.0f / 256.0f), &s, &c);
-  tw256[tid] = mk<T>((T)c, (T)s);
-  sincospif((float)col * (2.0f / 4096.0f), &s, &c);
-  const cplx<T> w = mk<T>((T)c, (T)s);
-  sincospif((float)col * (2.0f / 8192.0f), &s, &c);
-  const cplx<T> w8 = mk<T>((T)c, (T)s);
-  long_item<T, DEMOD, COEF, BITS>(a, load_uniform(items + blockIdx.x), buf, tw256, s_red, w, w8);
+  const int tid = threadIdx.x, col = fft4096_col(tid);
+  const cplx<T> w = fft4096_setup<T>(tw256, tid, col), w8 = long_setup_w8<T>(col);
+  long_item<T, DEMOD, COEF, BITS>(a, load_uniform(items + blockIdx.x), buf, tw256, s_red, w, w8, col);
 }
 template <typename T, bool COEF, bool BITS>
 __global__ void __launch_bounds__(kBlkThreads, QI_BLK_LONG_WAVES) k_block_long_dual(BlockArgs<T> a0, BlockArgs<T> a2,
@@ -1305,16 +1221,9 @@ __global__ void __launch_bounds__(kBlkThreads, QI_BLK_LONG_WAVES) k_block_long_d
   __shared__ cplx<T> buf[kBlkBuf];
   __shared__ cplx<T> tw256[256];
   __shared__ double s_red[2][kBlkThreads / kWave];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);
-  float s, c;
-  sincospif((float)tid * (2.0f / 256.0f), &s, &c);
-  tw256[tid] = mk<T>((T)c, (T)s);
-  sincospif((float)col * (2.0f / 4096.0f), &s, &c);
-  const cplx<T> w = mk<T>((T)c, (T)s);
-  sincospif((float)col * (2.0f / 8192.0f), &s, &c);
-  const cplx<T> w8 = mk<T>((T)c, (T)s);
-  long_dual_item<T, COEF, BITS>(a0, a2, load_uniform(items + blockIdx.x), buf, tw256, s_red, w, w8);
+  const int tid = threadIdx.x, col = fft4096_col(tid);
+  const cplx<T> w = fft4096_setup<T>(tw256, tid, col), w8 = long_setup_w8<T>(col);
+  long_dual_item<T, COEF, BITS>(a0, a2, load_uniform(items + blockIdx.x), buf, tw256, s_red, w, w8, col);
 }
 
 template <typename T, bool COEF, bool BITS>
@@ -1323,37 +1232,17 @@ __global__ void __launch_bounds__(kBlkThreads, QI_BLK_WAVES) k_block_dual(BlockA
   __shared__ cplx<T> buf[kBlkBuf];
   __shared__ cplx<T> tw256[256];
   __shared__ double s_red[2][kBlkThreads / kWave];
-  const int tid = threadIdx.x;
-  {
-    float s, c;
-    sincospif((float)tid * (2.0f / 256.0f), &s, &c);
-    tw256[tid] = mk<T>((T)c, (T)s);
-  }
-  cplx<T> w;
-  {
-    float s, c;
-    const int lane = tid & (kWave - 1);
-    const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // block_bands' column order
-    sincospif((float)col * (2.0f / 4096.0f), &s, &c);
-    w = mk<T>((T)c, (T)s);
-  }
+  const int tid = threadIdx.x, col = fft4096_col(tid);
+  const cplx<T> w = fft4096_setup<T>(tw256, tid, col);
   const DualItem it = load_uniform(items + blockIdx.x);
 #ifdef QI_NATIVE_STAMPS
   const unsigned long long wall0 = __builtin_amdgcn_s_memrealtime();  // (100 MHz) the launch's dispatch timeline
 #endif
   if (it.wq < 0) {
     const BlockItem e{it.wq, it.block, it.first0, it.count0, it.plane0, it.slot0};
-    switch (-it.wq) {
-      case 1: edge_item<T, 1, COEF, BITS>(a0, e, buf, tw256, w); break;
-      case 2: edge_item<T, 2, COEF, BITS>(a0, e, buf, tw256, w); break;
-      default: edge_item<T, 4, COEF, BITS>(a0, e, buf, tw256, w); break;
-    }
+    QI_WITH_REACH(-it.wq, edge_item<T, WQ, COEF, BITS>(a0, e, buf, tw256, w, col));
   } else {
-    switch (it.wq) {
-      case 1: dual_item<T, 1, COEF, BITS>(a0, a2, it, buf, tw256, s_red, w); break;
-      case 2: dual_item<T, 2, COEF, BITS>(a0, a2, it, buf, tw256, s_red, w); break;
-      default: dual_item<T, 4, COEF, BITS>(a0, a2, it, buf, tw256, s_red, w); break;
-    }
+    QI_WITH_REACH(it.wq, dual_item<T, WQ, COEF, BITS>(a0, a2, it, buf, tw256, s_red, w, col));
   }
 #ifdef QI_NATIVE_STAMPS
   if (a0.stamps && tid == 0) {
@@ -1378,23 +1267,12 @@ template <typename T>
 __device__ __forceinline__ void zoom_coarse_plane(cplx<T>* __restrict__ plane0) {
   __shared__ cplx<T> buf[kBlkBuf];
   __shared__ cplx<T> tw256[256];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // fft4096's column order
+  const int tid = threadIdx.x, col = fft4096_col(tid);
   cplx<T>* __restrict__ plane = plane0 + col;
   cplx<T> v[16];
 #pragma unroll
   for (int b = 0; b < 16; ++b) v[b] = plane[256 * b];
-  {
-    float s, c;
-    sincospif((float)tid * (2.0f / 256.0f), &s, &c);
-    tw256[tid] = mk<T>((T)c, (T)s);
-  }
-  cplx<T> w;
-  {
-    float s, c;
-    sincospif((float)col * (2.0f / 4096.0f), &s, &c);
-    w = mk<T>((T)c, (T)s);
-  }
+  const cplx<T> w = fft4096_setup<T>(tw256, tid, col);
   fft4096<T, 1>(v, buf, tw256, w, tid, col);
 #pragma unroll
   for (int c = 0; c < 16; ++c) plane[256 * c] = v[brev(c, 4)];
@@ -1404,8 +1282,7 @@ __device__ __forceinline__ void zoom_coarse_plane(cplx<T>* __restrict__ plane0) 
 template <typename T, bool STX, int NF>
 __device__ __forceinline__ void zoom_coarse_plane_gather(const ZoomArgs<T>& a, const uint32_t plane_i,
                                                          cplx<T>* __restrict__ buf, cplx<T>* __restrict__ tw256) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int col = (tid & ~(kWave - 1)) + (lane < 32 ? 2 * lane : 2 * (lane - 32) + 1);  // fft4096's column order
+  const int tid = threadIdx.x, col = fft4096_col(tid);
   const BandDesc bd = load_uniform(a.bands + *as_const(a.plane_band + plane_i));
   const uint32_t tau1 = plane_i - (uint32_t)bd.edge;
   const int64_t ch = blockIdx.z;
@@ -1418,17 +1295,7 @@ __device__ __forceinline__ void zoom_coarse_plane_gather(const ZoomArgs<T>& a, c
   } else
 #endif
   zoom_gather16<T, STX, NF>(a, bd, tau1, col, X, v);
-  {
-    float s, c;
-    sincospif((float)tid * (2.0f / 256.0f), &s, &c);
-    tw256[tid] = mk<T>((T)c, (T)s);
-  }
-  cplx<T> w;
-  {
-    float s, c;
-    sincospif((float)col * (2.0f / 4096.0f), &s, &c);
-    w = mk<T>((T)c, (T)s);
-  }
+  const cplx<T> w = fft4096_setup<T>(tw256, tid, col);
 #ifdef QI_NATIVE_DEBUG
   if (!(a.debug & 512))
 #endif
@@ -1580,11 +1447,18 @@ __global__ void k_block_rotate_rows(double2* __restrict__ rows) {
 
 template <typename T, bool DEMOD>
 int launch_block_v(const BlockArgs<T>& a, dim3 grid, hipStream_t st) {
-  const bool coef = a.coef != nullptr, bits = a.bits != nullptr;
-  if (coef && bits) k_block<T, DEMOD, true, true><<<grid, kBlkThreads, 0, st>>>(a);
-  else if (coef) k_block<T, DEMOD, true, false><<<grid, kBlkThreads, 0, st>>>(a);
-  else if (bits) k_block<T, DEMOD, false, true><<<grid, kBlkThreads, 0, st>>>(a);
-  else k_block<T, DEMOD, false, false><<<grid, kBlkThreads, 0, st>>>(a);
+  with_panels(a.coef != nullptr, a.bits != nullptr, [&](auto C, auto B) {
+    k_block<T, DEMOD, C.value, B.value><<<grid, kBlkThreads, 0, st>>>(a);
+  });
+  QI_LAUNCH_CHECK();
+  return QI_OK;
+}
+
+// a float64 kernel (72 KB of dynamic LDS): the permission for that much and the launch
+template <typename... P, typename... A>
+int launch_lds64(void (*kern)(P...), dim3 grid, hipStream_t st, const A&... args) {
+  QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(kern), kBlk64Lds));
+  kern<<<grid, kBlkThreads, kBlk64Lds, st>>>(args...);
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
@@ -1597,20 +1471,10 @@ static int launch_block_long(const BlockArgs<float>& a, int demod, const BlockIt
                              hipStream_t st) {
   if (nitems <= 0) return QI_OK;
   dim3 grid((unsigned)nitems, 1, (unsigned)n_channels);
-  const bool coef = a.coef != nullptr, bits = a.bits != nullptr;
-#define QI_LONG(D, C, B) k_block_long<float, D, C, B><<<grid, kBlkThreads, 0, st>>>(a, items)
-  if (demod) {
-    if (coef && bits) QI_LONG(true, true, true);
-    else if (coef) QI_LONG(true, true, false);
-    else if (bits) QI_LONG(true, false, true);
-    else QI_LONG(true, false, false);
-  } else {
-    if (coef && bits) QI_LONG(false, true, true);
-    else if (coef) QI_LONG(false, true, false);
-    else if (bits) QI_LONG(false, false, true);
-    else QI_LONG(false, false, false);
-  }
-#undef QI_LONG
+  with_panels(a.coef != nullptr, a.bits != nullptr, [&](auto C, auto B) {
+    if (demod) k_block_long<float, true, C.value, B.value><<<grid, kBlkThreads, 0, st>>>(a, items);
+    else k_block_long<float, false, C.value, B.value><<<grid, kBlkThreads, 0, st>>>(a, items);
+  });
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
@@ -1618,14 +1482,10 @@ static int launch_block_long(const BlockArgs<float>& a, int demod, const BlockIt
 static int launch_block_long_dual(const BlockArgs<float>& a0, const BlockArgs<float>& a2, const DualItem* items, int32_t nitems,
                                   int64_t n_channels, hipStream_t st) {
   if (nitems <= 0) return QI_OK;
-  const bool coef = a0.coef != nullptr, bits = a0.bits != nullptr;
   dim3 grid((unsigned)nitems, 1, (unsigned)n_channels);
-#define QI_LONG2(C, B) k_block_long_dual<float, C, B><<<grid, kBlkThreads, 0, st>>>(a0, a2, items)
-  if (coef && bits) QI_LONG2(true, true);
-  else if (coef) QI_LONG2(true, false);
-  else if (bits) QI_LONG2(false, true);
-  else QI_LONG2(false, false);
-#undef QI_LONG2
+  with_panels(a0.coef != nullptr, a0.bits != nullptr, [&](auto C, auto B) {
+    k_block_long_dual<float, C.value, B.value><<<grid, kBlkThreads, 0, st>>>(a0, a2, items);
+  });
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
@@ -1634,12 +1494,10 @@ static int launch_block_long_dual(const BlockArgs<float>& a0, const BlockArgs<fl
 static int launch_block_edge(const BlockArgs<float>& a, const BlockItem* items, const DualItem* dual, int32_t count,
                              int64_t n_channels, hipStream_t st) {
   if (count <= 0) return QI_OK;
-  const bool coef = a.coef != nullptr, bits = a.bits != nullptr;
   dim3 grid((unsigned)count, 1, (unsigned)n_channels);
-  if (coef && bits) k_block_edge<float, true, true><<<grid, kBlkThreads, 0, st>>>(a, items, dual);
-  else if (coef) k_block_edge<float, true, false><<<grid, kBlkThreads, 0, st>>>(a, items, dual);
-  else if (bits) k_block_edge<float, false, true><<<grid, kBlkThreads, 0, st>>>(a, items, dual);
-  else k_block_edge<float, false, false><<<grid, kBlkThreads, 0, st>>>(a, items, dual);
+  with_panels(a.coef != nullptr, a.bits != nullptr, [&](auto C, auto B) {
+    k_block_edge<float, C.value, B.value><<<grid, kBlkThreads, 0, st>>>(a, items, dual);
+  });
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
@@ -1663,19 +1521,14 @@ int launch_block<float>(const BlockArgs<float>& a, int demod, int64_t n_channels
 
 template <bool DEMOD>
 static int launch_block64_v(const BlockArgs<double>& a, dim3 grid, hipStream_t st) {
-  const bool coef = a.coef != nullptr, bits = a.bits != nullptr;
-#define QI_B64(C, B)                                                                                   \
-  do {                                                                                                 \
-    QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(&k_block64<DEMOD, C, B>), kBlk64Lds));      \
-    k_block64<DEMOD, C, B><<<grid, kBlkThreads, kBlk64Lds, st>>>(a);                                   \
-  } while (0)
-  if (coef && bits) QI_B64(true, true);
-  else if (coef) QI_B64(true, false);
-  else if (bits) QI_B64(false, true);
-  else QI_B64(false, false);
-#undef QI_B64
-  QI_LAUNCH_CHECK();
-  return QI_OK;
+  return with_panels(a.coef != nullptr, a.bits != nullptr,
+                     [&](auto C, auto B) { return launch_lds64(&k_block64<DEMOD, C.value, B.value>, grid, st, a); });
+}
+// the split bands' blocks of kind PATH (see k_block64_edge)
+template <int PATH>
+static int launch_block64_edge(const BlockArgs<double>& a, dim3 grid, const BlockItem* items, hipStream_t st) {
+  return with_panels(a.coef != nullptr, a.bits != nullptr,
+                     [&](auto C, auto B) { return launch_lds64(&k_block64_edge<C.value, B.value, PATH>, grid, st, a, items); });
 }
 template <>
 int launch_block<double>(const BlockArgs<double>& a, int demod, int64_t n_channels, hipStream_t st, hipStream_t side, hipEvent_t fork,
@@ -1685,7 +1538,6 @@ int launch_block<double>(const BlockArgs<double>& a, int demod, int64_t n_channe
     set_error("block engine: float64 tables have no long blocks, and their split bands one edge item per block");
     return QI_ERR_STATE;
   }
-  const bool coef = a.coef != nullptr, bits = a.bits != nullptr;
   const BlockItem* items = a.items + a.nitems;
   // the blocks around the middle of the record see both far pieces: items [mid_lo, mid_hi] of the (block-ordered) edge list,
   // a small launch of the band-by-band kernel; every other block goes through the one-piece kernel
@@ -1700,18 +1552,6 @@ int launch_block<double>(const BlockArgs<double>& a, int demod, int64_t n_channe
       }
     }
   }
-#define QI_E64(C, B, PATH, GRID, ITEMS, STREAM)                                                         \
-  do {                                                                                                  \
-    QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(&k_block64_edge<C, B, PATH>), kBlk64Lds));   \
-    k_block64_edge<C, B, PATH><<<GRID, kBlkThreads, kBlk64Lds, STREAM>>>(a, ITEMS);                     \
-  } while (0)
-#define QI_E64_ALL(PATH, GRID, ITEMS, STREAM)                          \
-  do {                                                                 \
-    if (coef && bits) QI_E64(true, true, PATH, GRID, ITEMS, STREAM);   \
-    else if (coef) QI_E64(true, false, PATH, GRID, ITEMS, STREAM);     \
-    else if (bits) QI_E64(false, true, PATH, GRID, ITEMS, STREAM);     \
-    else QI_E64(false, false, PATH, GRID, ITEMS, STREAM);              \
-  } while (0)
   const bool mids = mid_hi >= mid_lo;
   const bool beside = mids && side && fork && join && a.nitems > 0;  // the two-piece items beside the band items
   if (mids) {
@@ -1721,8 +1561,7 @@ int launch_block<double>(const BlockArgs<double>& a, int demod, int64_t n_channe
       QI_HIP(hipEventRecord(fork, st));
       QI_HIP(hipStreamWaitEvent(side, fork, 0));
     }
-    QI_E64_ALL(1, grid_mid, items + mid_lo, ms);
-    QI_LAUNCH_CHECK();
+    QI_TRY(launch_block64_edge<1>(a, grid_mid, items + mid_lo, ms));
     if (beside) QI_HIP(hipEventRecord(join, side));
   }
   // (whatever fails below: the caller's stream still waits for the side stream's launch -- its rows and partial slots must
@@ -1737,11 +1576,8 @@ int launch_block<double>(const BlockArgs<double>& a, int demod, int64_t n_channe
   }
   if (a.nedge_items > 0) {
     dim3 grid((unsigned)a.nedge_items, 1, (unsigned)n_channels);
-    QI_E64_ALL(2, grid, items, st);
-    QI_LAUNCH_CHECK();
+    QI_TRY(launch_block64_edge<2>(a, grid, items, st));
   }
-#undef QI_E64_ALL
-#undef QI_E64
   return QI_OK;
 }
 
@@ -1753,15 +1589,7 @@ int launch_z64_coarse(const Z64Args& a, int64_t n_channels, hipStream_t st) {
     return QI_ERR_UNSUPPORTED;
   }
   dim3 grid((unsigned)(8 * ceil_div(a.nbands * P, 8)), (unsigned)n_channels, 1);
-  if (a.kind == 2) {
-    QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(&k_z64_coarse<true>), kBlk64Lds));
-    k_z64_coarse<true><<<grid, kBlkThreads, kBlk64Lds, st>>>(a);
-  } else {
-    QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(&k_z64_coarse<false>), kBlk64Lds));
-    k_z64_coarse<false><<<grid, kBlkThreads, kBlk64Lds, st>>>(a);
-  }
-  QI_LAUNCH_CHECK();
-  return QI_OK;
+  return launch_lds64(a.kind == 2 ? &k_z64_coarse<true> : &k_z64_coarse<false>, grid, st, a);
 }
 
 template <>
@@ -1781,19 +1609,17 @@ int launch_block_dual<float>(const BlockArgs<float>& a0, const BlockArgs<float>&
   const int32_t own = a0.edge_merged ? (n_edge < nitems ? n_edge : nitems) : 0;
   if (nitems - own > 0) {
     dim3 grid((unsigned)(nitems - own), 1, (unsigned)n_channels);
-    if (coef && bits) k_block_dual<float, true, true><<<grid, kBlkThreads, 0, st>>>(a0, a2, items);
-    else if (coef) k_block_dual<float, true, false><<<grid, kBlkThreads, 0, st>>>(a0, a2, items);
-    else if (bits) k_block_dual<float, false, true><<<grid, kBlkThreads, 0, st>>>(a0, a2, items);
-    else k_block_dual<float, false, false><<<grid, kBlkThreads, 0, st>>>(a0, a2, items);
+    with_panels(coef, bits, [&](auto C, auto B) {
+      k_block_dual<float, C.value, B.value><<<grid, kBlkThreads, 0, st>>>(a0, a2, items);
+    });
     QI_LAUNCH_CHECK();
   }
   return launch_block_edge(a0, nullptr, items + (nitems - own), own, n_channels, st);
 }
 
 template <>
-int launch_zoom_coarse<float>(const ZoomArgs<float>& a, int max_level, int64_t n_channels, hipStream_t st) {
+int launch_zoom_coarse<float>(const ZoomArgs<float>& a, int64_t n_channels, hipStream_t st) {
   if (a.nbands <= 0) return QI_OK;
-  (void)max_level;
   dim3 grid((unsigned)a.planes, 1, (unsigned)n_channels);  // every plane of every band is one 4096-point transform
   k_zoom_coarse<float><<<grid, kBlkThreads, 0, st>>>(a);
   QI_LAUNCH_CHECK();

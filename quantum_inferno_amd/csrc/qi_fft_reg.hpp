@@ -1,5 +1,6 @@
 // Register-resident FFT building blocks shared by the native engines (qi_native.hip, qi_block.hip).
 #pragma once
+#include <type_traits>
 #include <utility>
 
 #include "qi_common.hpp"
@@ -16,6 +17,16 @@
 namespace qi {
 namespace native {
 namespace {
+
+// The panels a launch writes (coefficients, bit depths) as compile-time constants: calls f(std::bool_constant<coef>{},
+// std::bool_constant<bits>{}) -- a generic lambda that names the kernel instantiation -- and returns what it returns.
+template <typename F>
+inline auto with_panels(bool coef, bool bits, F&& f) {
+  if (coef && bits) return f(std::true_type{}, std::true_type{});
+  if (coef) return f(std::true_type{}, std::false_type{});
+  if (bits) return f(std::false_type{}, std::true_type{});
+  return f(std::false_type{}, std::false_type{});
+}
 
 // cos / sin of 2 pi k / 64, exact at the quadrant points so that trivial twiddles fold away
 constexpr double kCos64[33] = {1.0, 0.9951847266721969, 0.9807852804032304, 0.9569403357322088, 0.9238795325112867,

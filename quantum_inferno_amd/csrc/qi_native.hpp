@@ -262,9 +262,9 @@ struct ZoomArgs {
 };
 int64_t zoom_groups(int64_t n, int level);  // workgroups along time (partial slots per band, stat slots per chunk)
 template <typename T>
-int launch_zoom_gather(const ZoomArgs<T>& a, int max_level, int64_t n_channels, hipStream_t st);  // folded baseband bins, then
+int launch_zoom_gather(const ZoomArgs<T>& a, int64_t n_channels, hipStream_t st);  // folded baseband bins, then
 template <typename T>
-int launch_zoom_coarse(const ZoomArgs<T>& a, int max_level, int64_t n_channels, hipStream_t st);  // their 4096-point transforms, in place (qi_block.hip)
+int launch_zoom_coarse(const ZoomArgs<T>& a, int64_t n_channels, hipStream_t st);  // their 4096-point transforms, in place (qi_block.hip)
 template <typename T>
 int launch_zoom(const ZoomArgs<T>& a, int64_t n_channels, hipStream_t st);
 // qi_cwt_stx: gather / coarse stage of the styx table (a0) and the Stockwell table (a2) in one launch each
@@ -356,6 +356,8 @@ int launch_z64_fine(const Z64FineArgs& a, int64_t n_channels, hipStream_t st);
 void z64_fine_weights(int cls, double* w /*[z64f_win(cls)][64]*/);
 
 void zoom_weights(int level, int lane_off, float* w /*[zoom_taps(level)][64]*/);
+// the interpolator solve behind the three weight tables above (qi_zoom.hip)
+void chebyshev_taps(int N, long double band, long double x, long double* out /*[N], N <= 16*/);
 
 template <typename T>
 int launch_time_reduce(const T* part, T* out, int64_t C, int64_t n, int nchunk, const T* edge_time, int64_t wmax,

@@ -334,8 +334,8 @@ int launch_zoom_all(qi_plan* p, const native::ZoomArgs<float>& z, int64_t ct, hi
   if (p->native_gather_fused > 0 && ct >= p->native_gather_fused) {
     QI_TRY(native::launch_zoom_coarse_gather<float>(z, ct, st));
   } else {
-    QI_TRY(native::launch_zoom_gather<float>(z, 0, ct, st));
-    QI_TRY(native::launch_zoom_coarse<float>(z, 0, ct, st));
+    QI_TRY(native::launch_zoom_gather<float>(z, ct, st));
+    QI_TRY(native::launch_zoom_coarse<float>(z, ct, st));
   }
   p->prof.end(QI_STAGE_ZOOM_COARSE, st);
   p->prof.begin(st, QI_STAGE_ZOOM);
@@ -781,7 +781,7 @@ native::ZoomArgs<float> zoom_args(const qi_plan* p, int kind, const ZoomRows& r,
 // zoom stage of a tile.  defer (the CWT half of a joint tile, native_fuse > 2): the Stockwell run of qi_cwt_stx launches
 // them with its own; finish (the Stockwell half): the launches the CWT run left, jointly with this table's where the
 // tiles match.
-int launch_zoom_stage(qi_plan* p, const native::ZoomArgs<float>& z, int max_level, FusedCarry* defer, FusedCarry* finish,
+int launch_zoom_stage(qi_plan* p, const native::ZoomArgs<float>& z, FusedCarry* defer, FusedCarry* finish,
                       int64_t ct, hipStream_t st) {
   using T = float;
   if (defer) {
@@ -801,8 +801,8 @@ int launch_zoom_stage(qi_plan* p, const native::ZoomArgs<float>& z, int max_leve
   } else if (gfused) {
     QI_TRY(native::launch_zoom_coarse_gather<T>(z, ct, st));
   } else {
-    QI_TRY(native::launch_zoom_gather<T>(z, max_level, ct, st));
-    QI_TRY(native::launch_zoom_coarse<T>(z, max_level, ct, st));
+    QI_TRY(native::launch_zoom_gather<T>(z, ct, st));
+    QI_TRY(native::launch_zoom_coarse<T>(z, ct, st));
   }
   p->prof.end(QI_STAGE_ZOOM_COARSE, st);
   p->prof.begin(st, QI_STAGE_ZOOM);
@@ -977,7 +977,7 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
     QI_TRY(launch_spectra<T>(p, sig_t, n, Lf0, shorts, share, low, s, ct, st));
     QI_TRY(launch_two_pass<T>(p, tp, v, s, G, tp.nblk_max, /*diag=*/true, ct, st));
     if (zoom)
-      QI_TRY(launch_zoom_stage(p, zoom_args(p, kind, zr, v, s, share, nsplit, p2_stats + blk_stats, chunk_z0), zt.zoom_max_level,
+      QI_TRY(launch_zoom_stage(p, zoom_args(p, kind, zr, v, s, share, nsplit, p2_stats + blk_stats, chunk_z0),
                                deferring && p->native_fuse > 2 ? defer : nullptr, finishing ? finish : nullptr, ct, st));
     if (finishing && finish->has_zoom) {  // (this table has no zoom band, or another tiling: the deferred launches alone)
       QI_TRY(launch_zoom_all(p, finish->zoom, finish->ct, st));

@@ -259,11 +259,9 @@ __global__ void __launch_bounds__(kZoomThreads) k_zoom2(ZoomArgs<T> a0, ZoomArgs
 
 template <typename T, bool PHASOR>
 int launch_zoom_v(const ZoomArgs<T>& a, dim3 grid, hipStream_t st) {
-  const bool coef = a.coef != nullptr, bits = a.bits != nullptr;
-  if (coef && bits) k_zoom<T, PHASOR, true, true><<<grid, kZoomThreads, 0, st>>>(a);
-  else if (coef) k_zoom<T, PHASOR, true, false><<<grid, kZoomThreads, 0, st>>>(a);
-  else if (bits) k_zoom<T, PHASOR, false, true><<<grid, kZoomThreads, 0, st>>>(a);
-  else k_zoom<T, PHASOR, false, false><<<grid, kZoomThreads, 0, st>>>(a);
+  with_panels(a.coef != nullptr, a.bits != nullptr, [&](auto C, auto B) {
+    k_zoom<T, PHASOR, C.value, B.value><<<grid, kZoomThreads, 0, st>>>(a);
+  });
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
@@ -275,9 +273,8 @@ int64_t zoom_groups(int64_t n, int level) {
 }
 
 template <>
-int launch_zoom_gather<float>(const ZoomArgs<float>& a, int max_level, int64_t n_channels, hipStream_t st) {
+int launch_zoom_gather<float>(const ZoomArgs<float>& a, int64_t n_channels, hipStream_t st) {
   if (a.nbands <= 0) return QI_OK;
-  (void)max_level;
   dim3 grid((unsigned)(kBlk / 256), (unsigned)a.planes, (unsigned)n_channels);
   if (a.stx) k_zoom_gather<float, true><<<grid, 256, 0, st>>>(a);
   else k_zoom_gather<float, false><<<grid, 256, 0, st>>>(a);
@@ -340,18 +337,47 @@ int launch_zoom2<float>(const ZoomArgs<float>& a0, const ZoomArgs<float>& a2, in
   }
   dim3 grid((unsigned)(g0 > g2 ? g0 : g2), (unsigned)(r0 + r2), (unsigned)n_channels);
   const bool sdesc = n_channels >= 4;  // (see zoom_level)
-#define QI_ZOOM2(C, B)                                                                  \
-  do {                                                                                  \
-    if (sdesc) k_zoom2<float, C, B, true><<<grid, kZoomThreads, 0, st>>>(a0, a2, r0);   \
-    else k_zoom2<float, C, B, false><<<grid, kZoomThreads, 0, st>>>(a0, a2, r0);        \
-  } while (0)
-  if (coef && bits) QI_ZOOM2(true, true);
-  else if (coef) QI_ZOOM2(true, false);
-  else if (bits) QI_ZOOM2(false, true);
-  else QI_ZOOM2(false, false);
-#undef QI_ZOOM2
+  with_panels(coef, bits, [&](auto C, auto B) {
+    if (sdesc) k_zoom2<float, C.value, B.value, true><<<grid, kZoomThreads, 0, st>>>(a0, a2, r0);
+    else k_zoom2<float, C.value, B.value, false><<<grid, kZoomThreads, 0, st>>>(a0, a2, r0);
+  });
   QI_LAUNCH_CHECK();
   return QI_OK;
+}
+
+// N <= 16 taps (nodes -N/2 + 1 .. N/2) of the interpolator to the fraction x in [0, 1) that is exact for the tones at the
+// N / 2 Chebyshev nodes of the band [-band, band] (radians per coarse sample); out[c] belongs to node c - N/2 + 1.  Solved in
+// long double; the float64 engine's tables (qi_zoom64.hip) come from here, too.
+void chebyshev_taps(int N, long double band, long double x, long double* out) {
+  const int half = N / 2;
+  const long double pi = 3.14159265358979323846264338327950288L;
+  long double M[16][17];
+  for (int k = 0; k < half; ++k) {
+    const long double om = band * std::cos((long double)(2 * k + 1) * pi / (long double)(2 * N));
+    for (int c = 0; c < N; ++c) {
+      const long double node = (long double)(c - half + 1);
+      M[k][c] = std::cos(om * node);
+      M[half + k][c] = std::sin(om * node);
+    }
+    M[k][N] = std::cos(om * x);
+    M[half + k][N] = std::sin(om * x);
+  }
+  for (int i = 0; i < N; ++i) {  // Gauss-Jordan with partial pivoting
+    int piv = i;
+    for (int r = i + 1; r < N; ++r)
+      if (std::fabs((double)M[r][i]) > std::fabs((double)M[piv][i])) piv = r;
+    if (piv != i)
+      for (int c = 0; c <= N; ++c) std::swap(M[i][c], M[piv][c]);
+    const long double d = M[i][i];
+    for (int c = 0; c <= N; ++c) M[i][c] /= d;
+    for (int r = 0; r < N; ++r) {
+      if (r == i) continue;
+      const long double f = M[r][i];
+      if (f == 0.0L) continue;
+      for (int c = 0; c <= N; ++c) M[r][c] -= f * M[i][c];
+    }
+  }
+  for (int c = 0; c < N; ++c) out[c] = M[c][N];
 }
 
 // Interpolation weights of lane L for window sample j of a wave-step of class `cls`: the lane sits pos = L / D coarse
@@ -362,39 +388,6 @@ int launch_zoom2<float>(const ZoomArgs<float>& a0, const ZoomArgs<float>& a2, in
 // weights, solved in long double.  Worst-case error of a unit tone anywhere in the band, float32 weights included:
 // 9e-8 (N = 10, r = 4), 6e-7 (N = 6, r = 8), 3e-7 (N = 4, r = 32); the 12-tap Kaiser-windowed sinc it replaces: 6e-7.
 // Layout [tap][lane].
-// N taps (nodes -N/2 + 1 .. N/2) of the interpolator to the fraction x in [0, 1) that is exact at the Chebyshev nodes of
-// the band [-band, band] (radians per coarse sample); out[c] belongs to node c - N/2 + 1
-static void interp_taps(int N, long double band, long double x, long double* out) {
-  const int half = N / 2;
-  long double M[10][11];
-  for (int k = 0; k < half; ++k) {
-    const long double om = band * std::cos((long double)(2 * k + 1) * 3.14159265358979323846264338327950288L / (long double)(2 * N));
-    for (int c = 0; c < N; ++c) {
-      const long double node = (long double)(c - half + 1);
-      M[k][c] = std::cos(om * node);
-      M[half + k][c] = std::sin(om * node);
-    }
-    M[k][N] = std::cos(om * x);
-    M[half + k][N] = std::sin(om * x);
-  }
-  for (int c = 0; c < N; ++c) {  // Gauss-Jordan with partial pivoting
-    int piv = c;
-    for (int r = c + 1; r < N; ++r)
-      if (std::fabs((double)M[r][c]) > std::fabs((double)M[piv][c])) piv = r;
-    if (piv != c)
-      for (int k = 0; k <= N; ++k) std::swap(M[c][k], M[piv][k]);
-    const long double d = M[c][c];
-    for (int k = 0; k <= N; ++k) M[c][k] /= d;
-    for (int r = 0; r < N; ++r) {
-      if (r == c) continue;
-      const long double f = M[r][c];
-      if (f != 0.0L)
-        for (int k = 0; k <= N; ++k) M[r][k] -= f * M[c][k];
-    }
-  }
-  for (int c = 0; c < N; ++c) out[c] = M[c][N];
-}
-
 void zoom_weights(int cls, int lane_off, float* w) {
   const int taps = zoom_taps(cls), N = zoom_ntap(cls), half = N / 2;
   const long double D = (long double)(kZoomD >> zoom_grid(cls));
@@ -404,7 +397,7 @@ void zoom_weights(int cls, int lane_off, float* w) {
     const int q = (int)std::floor((double)pos);
     const long double x = pos - (long double)q;
     long double t[10];
-    interp_taps(N, band, x, t);
+    chebyshev_taps(N, band, x, t);
     for (int j = 0; j < taps; ++j) w[j * kWave + lane] = 0.0f;
     for (int c = 0; c < N; ++c) {
       const int j = (half - 1) + q + (c - half + 1);

@@ -685,40 +685,6 @@ int launch_z64_fine(const Z64FineArgs& a, int64_t n_channels, hipStream_t st) {
   return QI_OK;
 }
 
-// N taps (nodes -N/2 + 1 .. N/2) of the interpolator to the fraction x in [0, 1) that is exact for the tones at the N / 2
-// Chebyshev nodes of the band [-band, band] (radians per coarse sample); solved in long double
-static void z64_taps(int N, long double band, long double x, long double* out) {
-  const int half = N / 2;
-  const long double pi = 3.14159265358979323846264338327950288L;
-  long double M[16][17];
-  for (int k = 0; k < half; ++k) {
-    const long double om = band * std::cos((long double)(2 * k + 1) * pi / (long double)(2 * N));
-    for (int c = 0; c < N; ++c) {
-      const long double node = (long double)(c - half + 1);
-      M[k][c] = std::cos(om * node);
-      M[half + k][c] = std::sin(om * node);
-    }
-    M[k][N] = std::cos(om * x);
-    M[half + k][N] = std::sin(om * x);
-  }
-  for (int i = 0; i < N; ++i) {  // Gauss-Jordan with partial pivoting
-    int piv = i;
-    for (int r = i + 1; r < N; ++r)
-      if (std::fabs((double)M[r][i]) > std::fabs((double)M[piv][i])) piv = r;
-    if (piv != i)
-      for (int c = 0; c <= N; ++c) std::swap(M[i][c], M[piv][c]);
-    const long double d = M[i][i];
-    for (int c = 0; c <= N; ++c) M[i][c] /= d;
-    for (int r = 0; r < N; ++r) {
-      if (r == i) continue;
-      const long double f = M[r][i];
-      if (f == 0.0L) continue;
-      for (int c = 0; c <= N; ++c) M[r][c] -= f * M[i][c];
-    }
-  }
-  for (int c = 0; c < N; ++c) out[c] = M[c][N];
-}
-
 // weights of the lanes for class `cls`, layout [window sample j][lane]: lane sits q = lane / D coarse intervals after the
 // window's reference sample (index N / 2 - 1) at the fraction x = (lane mod D) / D; its N taps are window samples q .. q + N - 1
 void z64_fine_weights(int cls, double* w) {
@@ -727,7 +693,7 @@ void z64_fine_weights(int cls, double* w) {
   for (int lane = 0; lane < kWave; ++lane) {
     const int q = lane >> log2d;
     long double t[16];
-    z64_taps(N, band, (long double)(lane & (D - 1)) / (long double)D, t);
+    chebyshev_taps(N, band, (long double)(lane & (D - 1)) / (long double)D, t);
     for (int j = 0; j < WL; ++j) w[j * kWave + lane] = (j >= q && j - q < N) ? (double)t[j - q] : 0.0;
   }
 }
@@ -735,39 +701,13 @@ void z64_fine_weights(int cls, double* w) {
 // weights[phase][tap] of coarse step D = 1 << log2d: the 16-tap interpolator at x = phase / D that is exact for the
 // tones at the Chebyshev nodes of [-pi / 4, pi / 4] (the same design as zoom_weights, solved in long double)
 void z64_weights(int log2d, double* w) {
-  constexpr int N = kZ64Taps, half = N / 2;
+  constexpr int N = kZ64Taps;
   const int D = 1 << log2d;
-  const long double pi = 3.14159265358979323846264338327950288L;
-  const long double band = pi / 4.0L;
+  const long double band = 3.14159265358979323846264338327950288L / 4.0L;
   for (int ph = 0; ph < D; ++ph) {
-    const long double x = (long double)ph / (long double)D;
-    long double M[N][N + 1];
-    for (int k = 0; k < half; ++k) {
-      const long double om = band * std::cos((long double)(2 * k + 1) * pi / (long double)(2 * N));
-      for (int c = 0; c < N; ++c) {
-        const long double node = (long double)(c - half + 1);
-        M[k][c] = std::cos(om * node);
-        M[half + k][c] = std::sin(om * node);
-      }
-      M[k][N] = std::cos(om * x);
-      M[half + k][N] = std::sin(om * x);
-    }
-    for (int i = 0; i < N; ++i) {  // Gauss-Jordan with partial pivoting
-      int piv = i;
-      for (int r = i + 1; r < N; ++r)
-        if (std::fabs((double)M[r][i]) > std::fabs((double)M[piv][i])) piv = r;
-      if (piv != i)
-        for (int c = 0; c <= N; ++c) std::swap(M[i][c], M[piv][c]);
-      const long double d = M[i][i];
-      for (int c = 0; c <= N; ++c) M[i][c] /= d;
-      for (int r = 0; r < N; ++r) {
-        if (r == i) continue;
-        const long double f = M[r][i];
-        if (f == 0.0L) continue;
-        for (int c = 0; c <= N; ++c) M[r][c] -= f * M[i][c];
-      }
-    }
-    for (int c = 0; c < N; ++c) w[ph * N + c] = (double)M[c][N];
+    long double t[N];
+    chebyshev_taps(N, band, (long double)ph / (long double)D, t);
+    for (int c = 0; c < N; ++c) w[ph * N + c] = (double)t[c];
   }
 }
 
