@@ -283,6 +283,24 @@ int qi_shannon_tdr(int dtype, int device, const void* sig, int64_t n_channels, i
 int qi_shannon_fft(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, void* spectrum, void* angle,
                    void* marginal, void* scratch, int64_t scratch_bytes, qi_stream stream);
 
+/* ---- pooling along time (utilities/sampling.py) -------------------------------------------------------------------- */
+typedef enum { QI_POOL_NTH = 0, QI_POOL_AVERAGE = 1, QI_POOL_MAX = 2, QI_POOL_MIN = 3, QI_POOL_MEDIAN = 4 } qi_pool_method;
+typedef enum { QI_POOL_REAL = 0,     /* real in  -> real out                                   */
+               QI_POOL_COMPLEX = 1,  /* complex in -> complex out; NTH and AVERAGE only        */
+               QI_POOL_POWER = 2     /* complex in -> real out, of P = power_scale * |z|^2     */ } qi_pool_input;
+
+/* columns of the result: ceil(n / factor) for NTH, floor(n / factor) otherwise (sampling.py:106-120: the tail that does
+ * not fill a window is dropped, except for "nth"); negative qi_status for factor < 2, n < 1 or an unknown method.  Host only. */
+int64_t qi_pool_columns(int64_t n, int64_t factor, int method);
+
+/* utilities.sampling.subsample_2d / subsample (sampling.py:14-50,87-120) on a device panel in [rows][n] -> out [rows][columns],
+ * both C-contiguous; rows = channels * bands.  power_scale: 0 is read as 1 (QI_POOL_POWER only).  One kernel launch, no
+ * atomics: the average accumulates in float64 in a fixed order and is rounded once, the other methods return input values
+ * (the median of an even window the mean of its two middle values, in the input precision).  MEDIAN sorts each window in
+ * LDS and takes factor <= 4096 (QI_ERR_UNSUPPORTED above); a result of 0 columns is a successful no-op. */
+int qi_pool_panel(int dtype, int device, const void* in, int input_kind, int64_t rows, int64_t n, int64_t factor,
+                  int method, double power_scale, void* out, qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

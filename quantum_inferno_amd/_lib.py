@@ -13,6 +13,9 @@ QI_BANK_STYX, QI_BANK_ATOMS, QI_TABLE_STX = 0, 1, 2
 QI_ENGINE_AUTO, QI_ENGINE_HIPFFT, QI_ENGINE_NATIVE = 0, 1, 2
 STAGES = ("forward", "multiply", "inverse", "epilogue", "pass1", "pass2", "block", "zoom", "zoom_coarse")
 # qi_band_route.flags (QI_ROUTE_* of include/qi_tfr.h)
+QI_POOL_NTH, QI_POOL_AVERAGE, QI_POOL_MAX, QI_POOL_MIN, QI_POOL_MEDIAN = 0, 1, 2, 3, 4
+QI_POOL_REAL, QI_POOL_COMPLEX, QI_POOL_POWER = 0, 1, 2
+POOL_MEDIAN_MAX = 4096  # longest window the median sorts (qi_pool_panel)
 ROUTE_NOWRAP, ROUTE_SPLIT, ROUTE_BEHIND, ROUTE_F64_ZOOM = 16, 32, 256, 512
 
 
@@ -102,6 +105,8 @@ PROTOTYPES = {
     "qi_shannon_scratch_bytes": (_i64, [_int, _i64, _i64]),
     "qi_shannon_tdr": (_int, [_int, _int, _P, _i64, _i64, _P, _P, _P, _i64, _P]),
     "qi_shannon_fft": (_int, [_int, _int, _P, _i64, _i64, _P, _P, _P, _P, _i64, _P]),
+    "qi_pool_columns": (_i64, [_i64, _i64, _int]),
+    "qi_pool_panel": (_int, [_int, _int, _P, _int, _i64, _i64, _i64, _int, _dbl, _P, _P]),
 }
 
 _lib = None

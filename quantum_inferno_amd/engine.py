@@ -161,6 +161,7 @@ class TfrPlan:
         )
         _lib.check(self._lib.qi_plan_create(C.byref(self._handle), C.byref(desc)))
         self.freq = {}  # bank name -> host band centre frequencies
+        self._stage = None  # staging panel of pooled(), kept between calls
 
     # -- sizing -------------------------------------------------------------------------------
     @staticmethod
@@ -352,7 +353,46 @@ class TfrPlan:
     def stx(self, sig, coef=True, bits=False, reductions=False, power_scale=1.0, eps=0.0, out=None, reduced_out=None):
         return self._run(_lib.QI_TABLE_STX, sig, coef, bits, reductions, power_scale, eps, out, reduced_out)
 
+    def pooled(self, which, sig, factor, method="average", quantity="power", power_scale=1.0, eps=0.0, tile_bytes=1 << 30):
+        """Transform `which` (QI_BANK_STYX, QI_BANK_ATOMS or QI_TABLE_STX) of records [C, n], pooled along time in windows of
+        `factor` samples (utilities.sampling.subsample_2d's methods): -> device tensor [C, B, columns], real, in the plan's
+        precision.  quantity "power": power_scale * |z|^2 of the coefficients; "bits": log2(|z| + eps).  The full panel never
+        reaches the caller: the records go through in tiles of max(1, tile_bytes // (B n element size)) records, each tile's
+        panel lands in a staging tensor the plan keeps between calls (close() drops it) and is pooled into its slice of the
+        result by one kernel (qi_pool_panel) on the same stream.  Nothing is synchronised on the host."""
+        from .utilities.sampling import _METHOD_CODE, pool_rows
+
+        if quantity not in ("power", "bits"):
+            raise ValueError(f'quantity must be "power" or "bits", got {quantity!r}')
+        if method not in _METHOD_CODE:
+            raise ValueError(f"method must be one of {sorted(_METHOD_CODE)}, got {method!r}")
+        sig = self._signal(sig)
+        f_hz = self.freq.get(which)
+        if f_hz is None:
+            raise _lib.QiError("band table not set on this plan")
+        n_ch, n_b = sig.shape[0], len(f_hz)
+        cols = int(self._lib.qi_pool_columns(self.n, int(factor), _METHOD_CODE[method]))
+        if cols < 0:
+            _lib.check(cols)
+        power = quantity == "power"
+        sdtype = _complex_of(self.rdtype) if power else self.rdtype
+        per_record = n_b * self.n * torch.empty((), dtype=sdtype).element_size()
+        tile = min(n_ch, max(1, int(tile_bytes) // per_record))
+        if self._stage is None or self._stage.numel() < tile * per_record:
+            self._stage = None  # (released before the larger one is made)
+            self._stage = torch.empty(tile * per_record, dtype=torch.uint8, device=self.device)
+        stage = self._stage[: tile * per_record].view(sdtype).view(tile, n_b, self.n)
+        result = torch.empty((n_ch, n_b, cols), dtype=self.rdtype, device=self.device)
+        for c0 in range(0, n_ch, tile):
+            c1 = min(n_ch, c0 + tile)
+            panel = stage[: c1 - c0]
+            res = TfrResult(frequency_hz=f_hz, coef=panel if power else None, bits=None if power else panel)
+            self._run(which, sig[c0:c1], power, not power, False, power_scale, eps, out=res)
+            pool_rows(panel, factor, method, _lib.QI_POOL_POWER if power else _lib.QI_POOL_REAL, power_scale, out=result[c0:c1])
+        return result
+
     def close(self):
+        self._stage = None
         if getattr(self, "_handle", None) is not None and self._handle.value:
             self._lib.qi_plan_destroy(self._handle)
             self._handle = C.c_void_p()
