@@ -56,7 +56,8 @@ typedef enum {
 
 /* FFT engine behind a plan */
 typedef enum {
-  QI_ENGINE_AUTO = 0,   /* native kernels when n is a supported power of two, else hipFFT */
+  QI_ENGINE_AUTO = 0,   /* native kernels when n is a supported power of two (the small-record engine at
+                           2^10 .. 2^13 samples, see qi_plan_band_route), else hipFFT */
   QI_ENGINE_HIPFFT = 1, /* batched hipFFT + hand-written multiply / epilogue kernels      */
   QI_ENGINE_NATIVE = 2  /* hand-written LDS FFT passes with fused multiply and epilogue   */
 } qi_engine;
@@ -120,7 +121,8 @@ int qi_plan_set_stx_bands(qi_plan* plan, int32_t n_bands, const int64_t* shift_i
 
 int64_t qi_plan_bands(const qi_plan* plan, int which /* qi_bank, or 2 for the STX table */);
 /* Bands of table `which` whose coefficients are produced by the kernels of profiling stage `stage` (qi_stage below:
- * PASS2 or BLOCK on the native engine, INVERSE on the hipFFT engine); used to price a stage's algorithmic bytes. */
+ * PASS2 or BLOCK on the native engine, SMALL on the small-record engine -- the table's whole band count --, INVERSE on the
+ * hipFFT engine); used to price a stage's algorithmic bytes. */
 int64_t qi_plan_stage_bands(const qi_plan* plan, int which, int stage);
 
 /* Forward transform of a float32 plan on the native engines (a read-only query).  When every native table set on the plan
@@ -135,13 +137,20 @@ int64_t qi_plan_forward_low(const qi_plan* plan, int which /* as qi_plan_bands *
  * diagnostics use it to tell which path a band takes; it changes nothing).  `records` means the records that go through
  * together: a call whose records do not fit the plan's scratch runs in tiles, and each tile takes the route of its own
  * record count.
- *   stage    qi_stage below: ZOOM, BLOCK, PASS2, or INVERSE (the hipFFT engine: the whole table, or the pass behind
+ *   stage    qi_stage below: ZOOM, BLOCK, PASS2, SMALL, or INVERSE (the hipFFT engine: the whole table, or the pass behind
  *            the native run)
+ *            SMALL: the small-record engine runs the whole table.  Size rule: the plan is QI_ENGINE_AUTO, n is a power of two
+ *            with 2^10 <= n <= 2^13 (and below the length from which zoom / block are tried), and the L complex values of the
+ *            table's transform -- L = 2n for QI_BANK_STYX, n for QI_BANK_ATOMS and the STX table -- fit 128 KiB: every float32
+ *            table; every float64 table but QI_BANK_STYX at n = 2^13, which stays on the hipFFT engine.  A call whose
+ *            workspace cannot hold one record's scratch (a spectrum row, the reduction slots, the per-time planes) runs on the
+ *            hipFFT engine, whose tables such a plan keeps.
  *   cls      ZOOM, float32: the band's class 0..6 in the table, after small classes have joined their neighbours
  *            (0..4 coarse-grid level with the 10-tap interpolator, 5 / 6 the 6- / 4-tap classes of level 0);
  *            ZOOM, float64: the coarse-grid level 0..4;  BLOCK: reach group 1, 2, 4, or 8 (8192-sample long blocks)
  *   run_cls  ZOOM, float32: the class the band runs as in this call (classes 5 and 6 run as 0 in calls of few
  *            records); ZOOM, float64: the class of the fine kernel, or -1 (k_z64_interp);  otherwise = cls
+ *            (SMALL: cls = run_cls = log2 L, flags = 0)
  *   flags    QI_ROUTE_* bits */
 typedef struct {
   int32_t stage, cls, run_cls, flags;
@@ -169,7 +178,9 @@ typedef enum {
                          /* epilogue in one kernel)                                                             */
   QI_STAGE_ZOOM = 7,     /* native engine: narrow-band panels, interpolation kernel (one span per launch)       */
   QI_STAGE_ZOOM_COARSE = 8, /* native engine: baseband gather + batched coarse inverse FFT of the zoom bands     */
-  QI_STAGE_COUNT = 9
+  QI_STAGE_SMALL = 9,    /* small-record engine: spectrum product, in-LDS inverse transform and fused epilogue of  */
+                         /* every band in one kernel (its forward launch is timed as FORWARD, its tail as EPILOGUE) */
+  QI_STAGE_COUNT = 10
 } qi_stage;
 /* enable: 0 off; low 16 bits: 1 every stage, otherwise a mask with bit (stage + 1) set for each stage to time (every
  * recorded event is a small bubble in the stream, so a caller that wants one stage asks for that one); high 16 bits:

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("QI_TFR_LIB") or os.path.join(_HERE, "libqi_tfr.so")  
 QI_F32, QI_F64 = 0, 1
 QI_BANK_STYX, QI_BANK_ATOMS, QI_TABLE_STX = 0, 1, 2
 QI_ENGINE_AUTO, QI_ENGINE_HIPFFT, QI_ENGINE_NATIVE = 0, 1, 2
-STAGES = ("forward", "multiply", "inverse", "epilogue", "pass1", "pass2", "block", "zoom", "zoom_coarse")
+STAGES = ("forward", "multiply", "inverse", "epilogue", "pass1", "pass2", "block", "zoom", "zoom_coarse", "small")
 # qi_band_route.flags (QI_ROUTE_* of include/qi_tfr.h)
 QI_POOL_NTH, QI_POOL_AVERAGE, QI_POOL_MAX, QI_POOL_MIN, QI_POOL_MEDIAN = 0, 1, 2, 3, 4
 QI_POOL_REAL, QI_POOL_COMPLEX, QI_POOL_POWER = 0, 1, 2

@@ -94,6 +94,13 @@ int qi_plan_create(qi_plan** plan, const qi_plan_desc* desc) {
     delete p;
     return QI_ERR_HIP;
   }
+  if (const char* e = tune_env("QI_SMALL_CHUNK_BANDS")) p->small_chunk_bands = atoi(e);
+  if (const char* e = tune_env("QI_SMALL_JOINT")) p->small_joint = atoi(e);
+  if (build_small_twiddles(p) != QI_OK) {
+    free_device(p->ws);
+    delete p;
+    return QI_ERR_HIP;
+  }
   *plan = p;
   return QI_OK;
 }
@@ -169,6 +176,7 @@ int qi_plan_destroy(qi_plan* p) {
   for (auto*& b : p->bank) free_device(b);
   free_device(p->d_stx_idx);
   free_device(p->d_stx_coef);
+  free_device(p->small_tw);
   free_device(p->ws);
   delete p;
   return QI_OK;
@@ -327,6 +335,7 @@ int64_t qi_plan_forward_low(const qi_plan* p, int which) {
 int64_t qi_plan_stage_bands(const qi_plan* p, int which, int stage) {
   if (!p || which < 0 || which > 2) return 0;
   const int64_t total = qi_plan_bands(p, which);
+  if (on_small(p, which)) return stage == QI_STAGE_SMALL ? total : 0;
   if (!p->nat[which].ready) return stage == QI_STAGE_INVERSE ? total : 0;
   int64_t blk = 0;
   if (which != 1 && p->blk[which].ready) blk = p->blk[which].rows;
@@ -346,6 +355,12 @@ int qi_plan_band_route(const qi_plan* p, int which, int32_t band, int64_t record
   QI_REQUIRE(records > 0, "records must be positive");
   *route = qi_band_route{QI_STAGE_INVERSE, 0, 0, 0};
   const auto& t = p->nat[which];
+  if (on_small(p, which)) {  // the small-record engine runs the whole table: cls = log2 of its transform length
+    int32_t lg = 0;
+    while (((int64_t)1 << lg) < (which == 0 ? p->L : p->n)) ++lg;
+    *route = qi_band_route{QI_STAGE_SMALL, lg, lg, 0};
+    return QI_OK;
+  }
   if (!t.ready) return QI_OK;  // the hipFFT engine runs the whole table
   if (which == 2 && p->stx_left_n > 0 && band >= p->stx_left_lo && band < p->stx_left_lo + p->stx_left_n) {
     route->flags = QI_ROUTE_BEHIND;
@@ -416,6 +431,12 @@ int qi_plan_profile_read(qi_plan* p, double* stage_ms, int64_t* stage_launches, 
   return QI_OK;
 }
 
+// One table on the small-record engine; *ran = false when the workspace does not hold one record (then the hipFFT engine runs it)
+static int small_one(qi_plan* p, int kind, const void* sig, int64_t C, const qi_tfr_out* out, hipStream_t st, bool* ran) {
+  return p->d.dtype == QI_F64 ? run_small<double>(p, 1, &kind, &out, sig, C, st, ran)
+                              : run_small<float>(p, 1, &kind, &out, sig, C, st, ran);
+}
+
 int qi_cwt(qi_plan* p, int bank, const void* sig, int64_t C, const qi_tfr_out* out, qi_stream stream) {
   QI_REQUIRE(p && sig && out, "null argument");
   QI_REQUIRE(bank == QI_BANK_STYX || bank == QI_BANK_ATOMS, "bad bank %d", bank);
@@ -423,6 +444,11 @@ int qi_cwt(qi_plan* p, int bank, const void* sig, int64_t C, const qi_tfr_out* o
   DeviceGuard g(p->d.device);
   const Kind k = bank == QI_BANK_STYX ? Kind::Linear : Kind::Circular;
   p->prof.unchain();
+  if (on_small(p, bank)) {
+    bool ran = false;
+    QI_TRY(small_one(p, bank, sig, C, out, (hipStream_t)stream, &ran));
+    if (ran) return QI_OK;
+  }
   if (p->nat[bank].ready)
     return p->d.dtype == QI_F64 ? run_native64(p, bank, sig, C, out, (hipStream_t)stream)
                                 : run_native<float>(p, bank, sig, C, out, (hipStream_t)stream);
@@ -435,6 +461,11 @@ int qi_stx(qi_plan* p, const void* sig, int64_t C, const qi_tfr_out* out, qi_str
   QI_REQUIRE(C > 0, "n_channels must be positive");
   DeviceGuard g(p->d.device);
   p->prof.unchain();
+  if (on_small(p, 2)) {
+    bool ran = false;
+    QI_TRY(small_one(p, 2, sig, C, out, (hipStream_t)stream, &ran));
+    if (ran) return QI_OK;
+  }
   if (p->nat[2].ready) {
     int rc = p->d.dtype == QI_F64 ? run_native64(p, 2, sig, C, out, (hipStream_t)stream)
                                   : run_native<float>(p, 2, sig, C, out, (hipStream_t)stream);
@@ -468,6 +499,18 @@ int qi_cwt_stx(qi_plan* p, int bank, const void* sig, int64_t C, const qi_tfr_ou
   p->carry.has_zoom = false;
   QI_REQUIRE(C > 0, "n_channels must be positive");
   hipStream_t st = (hipStream_t)stream;
+  if (p->small_joint > 0 && on_small(p, bank) && on_small(p, 2)) {
+    // both tables on the small-record engine: one forward launch forms the 2n-point and the n-point spectra of every record
+    // (each by the code of its own call, so the results are those of qi_cwt then qi_stx bit for bit), one tail launch
+    DeviceGuard g0(p->d.device);
+    const int kinds[2] = {bank, 2};
+    const qi_tfr_out* outs[2] = {out_cwt, out_stx};
+    bool ran = false;
+    p->prof.unchain();
+    QI_TRY(p->d.dtype == QI_F64 ? run_small<double>(p, 2, kinds, outs, sig, C, st, &ran)
+                                : run_small<float>(p, 2, kinds, outs, sig, C, st, &ran));
+    if (ran) return QI_OK;
+  }
   if (fuse) {
     // Joint launches need the scratch of both transforms of a tile side by side: the records go through in tiles of
     // as many as fit (the scratch per record depends a little on the tile's size -- rows of the zoom launch --, so the

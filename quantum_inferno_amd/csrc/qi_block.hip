@@ -121,28 +121,6 @@ __device__ __forceinline__ void long_rotate(cplx<T> (&S)[16], cplx<T> r0, std::i
   ((S[Cs] = mul_tw64<T, Cs, -1>(cmul(S[Cs], r0))), ...);
 }
 
-// v[brev(q)] *= w^q, q = 1..15, powers by products of w, w^2, w^4, w^8 (depth <= 4 roundings)
-template <typename T>
-__device__ __forceinline__ void mul_powers16(cplx<T> (&v)[16], cplx<T> w) {
-  const cplx<T> p1 = w, p2 = cmul(p1, p1), p4 = cmul(p2, p2), p8 = cmul(p4, p4);
-  const cplx<T> p3 = cmul(p2, p1), p5 = cmul(p4, p1), p6 = cmul(p4, p2), p7 = cmul(p4, p3);
-  v[brev(1, 4)] = cmul(v[brev(1, 4)], p1);
-  v[brev(2, 4)] = cmul(v[brev(2, 4)], p2);
-  v[brev(3, 4)] = cmul(v[brev(3, 4)], p3);
-  v[brev(4, 4)] = cmul(v[brev(4, 4)], p4);
-  v[brev(5, 4)] = cmul(v[brev(5, 4)], p5);
-  v[brev(6, 4)] = cmul(v[brev(6, 4)], p6);
-  v[brev(7, 4)] = cmul(v[brev(7, 4)], p7);
-  v[brev(8, 4)] = cmul(v[brev(8, 4)], p8);
-  v[brev(9, 4)] = cmul(v[brev(9, 4)], cmul(p8, p1));
-  v[brev(10, 4)] = cmul(v[brev(10, 4)], cmul(p8, p2));
-  v[brev(11, 4)] = cmul(v[brev(11, 4)], cmul(p8, p3));
-  v[brev(12, 4)] = cmul(v[brev(12, 4)], cmul(p8, p4));
-  v[brev(13, 4)] = cmul(v[brev(13, 4)], cmul(p8, p5));
-  v[brev(14, 4)] = cmul(v[brev(14, 4)], cmul(p8, p6));
-  v[brev(15, 4)] = cmul(v[brev(15, 4)], cmul(p8, p7));
-}
-
 // The column of fft4096 that thread `tid` owns, on entry and on exit: lanes L and L + 32 of a wave hold ADJACENT samples --
 // after one v_permlane32_swap per register pair a lane holds two adjacent outputs and stores them as 16 bytes (the epilogue
 // is store-issue bound: half the store instructions).  Every kernel here computes it once and hands it down.

@@ -94,6 +94,28 @@ __device__ __forceinline__ void mul_w64_powers(cplx<T> (&v)[32], std::integer_se
   ((v[brev(Cs, 5)] = mul_tw64<T, Cs, 1>(v[brev(Cs, 5)])), ...);
 }
 
+// v[brev(q)] *= w^q, q = 1..15, powers by products of w, w^2, w^4, w^8 (depth <= 4 roundings)
+template <typename T>
+__device__ __forceinline__ void mul_powers16(cplx<T> (&v)[16], cplx<T> w) {
+  const cplx<T> p1 = w, p2 = cmul(p1, p1), p4 = cmul(p2, p2), p8 = cmul(p4, p4);
+  const cplx<T> p3 = cmul(p2, p1), p5 = cmul(p4, p1), p6 = cmul(p4, p2), p7 = cmul(p4, p3);
+  v[brev(1, 4)] = cmul(v[brev(1, 4)], p1);
+  v[brev(2, 4)] = cmul(v[brev(2, 4)], p2);
+  v[brev(3, 4)] = cmul(v[brev(3, 4)], p3);
+  v[brev(4, 4)] = cmul(v[brev(4, 4)], p4);
+  v[brev(5, 4)] = cmul(v[brev(5, 4)], p5);
+  v[brev(6, 4)] = cmul(v[brev(6, 4)], p6);
+  v[brev(7, 4)] = cmul(v[brev(7, 4)], p7);
+  v[brev(8, 4)] = cmul(v[brev(8, 4)], p8);
+  v[brev(9, 4)] = cmul(v[brev(9, 4)], cmul(p8, p1));
+  v[brev(10, 4)] = cmul(v[brev(10, 4)], cmul(p8, p2));
+  v[brev(11, 4)] = cmul(v[brev(11, 4)], cmul(p8, p3));
+  v[brev(12, 4)] = cmul(v[brev(12, 4)], cmul(p8, p4));
+  v[brev(13, 4)] = cmul(v[brev(13, 4)], cmul(p8, p5));
+  v[brev(14, 4)] = cmul(v[brev(14, 4)], cmul(p8, p6));
+  v[brev(15, 4)] = cmul(v[brev(15, 4)], cmul(p8, p7));
+}
+
 // exp(+2 pi i m / Lf) for an exact integer phase m in [0, Lf), Lf = 2^p <= 2^24: the float argument
 // 2 m / Lf is exact, so the seeds are accurate to single precision whatever the size of m
 __device__ __forceinline__ void unit_root(uint32_t m, float two_over_len, double* c, double* s) {

@@ -361,6 +361,11 @@ struct qi_plan {
   // Nyquist bins -- the native run leaves them out and a pass of the hipFFT engine over just these rows follows it
   // (run_stx_leftover); any other case hands the whole table to the hipFFT engine as before
   int32_t stx_left_lo = -1, stx_left_n = 0;
+  // small-record engine (qi_small.hip): power-of-two records of 2^10 .. 2^13 samples below native_min_log2n on an AUTO plan, per table
+  // when its transform (2n points for the styx bank, n otherwise) fits the LDS; reads the hipFFT engine's tables
+  void* small_tw = nullptr;    // exp(2 pi i k / 2n), k < n / 8, in the plan's precision (float64 values rounded once); null: no table is small
+  int small_chunk_bands = 2;   // bands per workgroup (band chunk): the chunk count is a property of the table and the workspace, never of the call
+  int small_joint = 2;         // qi_cwt_stx with both tables small: 0 two separate runs, 1 one forward launch for both, 2 and one tail launch
   int native_min_log2n = 14;    // shortest power-of-two record the zoom / block engines are tried on (below: the hipFFT engine).
                                 // float32: 2^14 (round 5: 54 / 69 us per call against 97 / 230 on the hipFFT engine at orders 3 / 12);
                                 // float64: 2^15 (at 2^14 the float64 zoom's small grids go through hipFFT launch by launch: slower)
@@ -464,6 +469,12 @@ int build_bank(qi_plan* p, int bank, int32_t B, const double* d_par, hipStream_t
 // the Stockwell table of a plan (native classification, block picks; nat[2] / blk[2]); `sigma`, `shift_index`: host [B]
 int build_stx_tables(qi_plan* p, int32_t B, const int64_t* shift_index, const double* sigma, const std::vector<double>& coef);
 
+// the small-record engine's rule: does table `kind` (0 styx bank, 1 atoms bank, 2 Stockwell) of this plan run on it?  (A
+// property of the plan alone; on_small: ... and the table is set)
+bool small_wanted(const qi_plan* p, int kind);
+bool on_small(const qi_plan* p, int kind);
+int build_small_twiddles(qi_plan* p);
+
 // ---- qi_run.hip: launch sequences ----------------------------------------------------------------------------------------
 template <typename T>
 int run_transform(qi_plan* p, Kind kind, const void* sig_v, int64_t C, const qi_tfr_out* out, hipStream_t st);
@@ -472,6 +483,11 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
                bool may_share = false, FusedCarry* defer = nullptr, FusedCarry* finish = nullptr, size_t* probe = nullptr);
 template <typename T>
 int run_stx_leftover(qi_plan* p, const void* sig, int64_t C, const qi_tfr_out* out, hipStream_t st);
+// The small-record engine on one table, or on two tables of the same records (qi_cwt_stx: one forward launch for both).
+// *ran = false, nothing launched: the workspace does not hold one record's scratch -- the caller runs the hipFFT engine.
+template <typename T>
+int run_small(qi_plan* p, int njobs, const int* kinds, const qi_tfr_out* const* outs, const void* sig_v, int64_t C, hipStream_t st,
+              bool* ran);
 int run_native64(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_out* out, hipStream_t st);
 int flush_carry(qi_plan* p, FusedCarry* c, hipStream_t st);
 

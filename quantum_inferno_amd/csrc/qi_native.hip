@@ -1175,6 +1175,7 @@ int launch_tail2(const TailCall<T>& t0, const TailCall<T>& t1, hipStream_t st) {
   return QI_OK;
 }
 template int launch_tail2<float>(const TailCall<float>&, const TailCall<float>&, hipStream_t);
+template int launch_tail2<double>(const TailCall<double>&, const TailCall<double>&, hipStream_t);
 template int launch_tail<float>(const TailCall<float>&, hipStream_t);
 template int launch_tail<double>(const TailCall<double>&, hipStream_t);
 template int launch_time_reduce<float>(const float*, float*, int64_t, int64_t, int, const float*, int64_t, hipStream_t);

@@ -359,6 +359,36 @@ void zoom_weights(int level, int lane_off, float* w /*[zoom_taps(level)][64]*/);
 // the interpolator solve behind the three weight tables above (qi_zoom.hip)
 void chebyshev_taps(int N, long double band, long double x, long double* out /*[N], N <= 16*/);
 
+// ---- small-record engine (qi_small.hip): transforms that fit the LDS of one CU, one workgroup per (band chunk, record) ----
+constexpr int kSmallMinLog2 = 10, kSmallMaxLog2 = 14;  // transform lengths L = 2^10 .. 2^14 ...
+constexpr size_t kSmallLdsBytes = 128 * 1024;          // ... whose L complex values fit this much LDS
+bool small_len_ok(int64_t L, size_t elem_bytes);
+template <typename T>
+struct SmallArgs {
+  const cplx<T>* X;         // [ct][L] spectra of the records
+  const cplx<T>* H;         // [B][L] atom spectra (1 / L folded in); null: the Stockwell table below
+  const int64_t* stx_idx;   // [B] shift indices
+  const double* stx_coef;   // [B] window coefficients (qi_plan::d_stx_coef)
+  const cplx<T>* tw;        // exp(2 pi i k / (L << tw_shift)), k < (L << tw_shift) / 16
+  int32_t tw_shift;
+  int32_t kind;             // 0 styx bank, 1 atoms bank, 2 Stockwell
+  int32_t n, L, off;        // panel sample t = Y[(t + off) mod L], t < n
+  int32_t B, nchunk;        // bands of the table; workgroups (band chunks) per record
+  int32_t chunk_total;      // per-time planes per record in time_part (= nchunk, or 1: the output row itself)
+  cplx<T>* coef;            // [ct][B][n] or null
+  T* bits;
+  T* time_part;             // [ct][chunk_total][n] or null
+  double* part_band;        // [ct][B] or null: a workgroup sees the whole row of a band
+  double* part_stat;        // [ct][nchunk][3] or null
+  T power_scale, eps;
+};
+template <typename T>
+int launch_small_band(const SmallArgs<T>& a, int64_t ct, hipStream_t st);
+// spectra of ct records of n samples: zero-padded to 2n points into X2 and / or of n points into X1 (null: not formed), one launch
+template <typename T>
+int launch_small_forward(const T* sig, cplx<T>* X2, cplx<T>* X1, const cplx<T>* tw, int64_t tw_len, int64_t n, int64_t ct,
+                         hipStream_t st);
+
 template <typename T>
 int launch_time_reduce(const T* part, T* out, int64_t C, int64_t n, int nchunk, const T* edge_time, int64_t wmax,
                        hipStream_t st);

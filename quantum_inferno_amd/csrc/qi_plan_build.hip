@@ -46,6 +46,32 @@ bool native_wanted(const qi_plan* p, int kind) {
   return kind != 1 && is_pow2(p->n) && p->n >= ((int64_t)1 << p->native_min_log2n) && Lf <= (1ll << 26);
 }
 
+// ---- small-record engine: the rule and the twiddle table ---------------------------------------------------------------
+bool small_wanted(const qi_plan* p, int kind) {
+  if (p->d.engine != QI_ENGINE_AUTO || !p->small_tw || !is_pow2(p->n)) return false;
+  if (p->n < (1 << 10) || p->n > (1 << 13) || p->n >= ((int64_t)1 << p->native_min_log2n)) return false;
+  return native::small_len_ok(kind == 0 ? p->L : p->n, p->d.dtype == QI_F64 ? sizeof(double2) : sizeof(float2));
+}
+bool on_small(const qi_plan* p, int kind) {
+  const int32_t bands = kind == 2 ? p->nb_stx : p->nb[kind];
+  return bands > 0 && !p->nat[kind].ready && small_wanted(p, kind);
+}
+// exp(2 pi i k / 2n), k < n / 8: what the passes of an n- or 2n-point transform load (their other factors are products)
+int build_small_twiddles(qi_plan* p) {
+  const int64_t n = p->n;
+  if (p->d.engine != QI_ENGINE_AUTO || !is_pow2(n) || n < (1 << 10) || n > (1 << 13)) return QI_OK;
+  const int64_t len = 2 * n, count = len / 16;
+  std::vector<double2> w((size_t)count);
+  for (int64_t k = 0; k < count; ++k) {
+    const double ph = 2.0 * M_PI * (double)k / (double)len;
+    w[(size_t)k] = make_double2(std::cos(ph), std::sin(ph));
+  }
+  if (p->d.dtype == QI_F64) return upload_table(reinterpret_cast<double2**>(&p->small_tw), w);
+  std::vector<float2> wf((size_t)count);
+  for (int64_t k = 0; k < count; ++k) wf[(size_t)k] = make_float2((float)w[(size_t)k].x, (float)w[(size_t)k].y);
+  return upload_table(reinterpret_cast<float2**>(&p->small_tw), wf);
+}
+
 // Widest spectrum support (bins) of a band that keeps a compact bank row: the one-pass loader's limit, or -- float64 with
 // the float64 zoom engine, which then takes every such band -- the widest band its finest grid (Lf / 4 samples) still
 // oversamples four times.

@@ -1,5 +1,5 @@
 // Launch sequences of the engines: the hipFFT engine (any length), the native float32 engines (two-pass, zoom, block,
-// joint launches of qi_cwt_stx) and the float64 native path.
+// joint launches of qi_cwt_stx), the float64 native path and the small-record engine.
 #include "qi_host.hpp"
 
 using namespace qi;
@@ -1234,6 +1234,121 @@ int run_native64(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tf
   return QI_OK;
 }
 
+// ---- the small-record engine (qi_small.hip) -----------------------------------------------------------------------------
+// Per table of a run: forward launch, band launch (nchunk workgroups per record, each with the band's whole row), tail.
+// Scratch per record: one spectrum row, one partial per band, three statistics per chunk and -- when the per-time sums are
+// wanted and there is more than one chunk -- one per-time plane per chunk.
+template <typename T>
+struct SmallJob {
+  int kind = 0;
+  const qi_tfr_out* out = nullptr;
+  int64_t L = 0, B = 0, off = 0;
+  const cplx<T>* H = nullptr;
+  int nchunk = 1;
+  bool planes = false;
+  size_t bytes(const qi_plan* p, int64_t ct) const {
+    return align_up((size_t)L * sizeof(cplx<T>) * ct) + align_up((size_t)B * 8 * ct) + align_up((size_t)nchunk * 24 * ct) +
+           (planes ? align_up((size_t)nchunk * p->n * sizeof(T) * ct) : 0);
+  }
+};
+
+template <typename T>
+int run_small(qi_plan* p, int njobs, const int* kinds, const qi_tfr_out* const* outs, const void* sig_v, int64_t C, hipStream_t st,
+              bool* ran) {
+  const int64_t n = p->n;
+  const T* sig = static_cast<const T*>(sig_v);
+  *ran = false;
+  SmallJob<T> job[2];
+  size_t per_record = 0;
+  for (int q = 0; q < njobs; ++q) {
+    SmallJob<T>& jb = job[q];
+    jb.kind = kinds[q];
+    jb.out = outs[q];
+    jb.L = jb.kind == 0 ? p->L : n;
+    jb.B = jb.kind == 2 ? p->nb_stx : p->nb[jb.kind];
+    jb.off = jb.kind == 0 ? (n - 1) / 2 : jb.kind == 1 ? n / 2 : 0;  // (run_transform's constants)
+    jb.H = jb.kind == 2 ? nullptr : static_cast<const cplx<T>*>(p->bank[jb.kind]);
+    if (jb.B <= 0) {
+      set_error("plan has no band table for this transform");
+      return QI_ERR_STATE;
+    }
+    // band chunks: small_chunk_bands bands each, fewer (down to one: no planes at all) only when the workspace cannot hold
+    // the planes -- the count depends on the table, the workspace and the outputs asked for, never on the records of the call
+    jb.nchunk = (int)ceil_div(jb.B, p->small_chunk_bands > 0 ? p->small_chunk_bands : 1);
+    for (;;) {
+      jb.planes = jb.out->power_time && jb.nchunk > 1;
+      if (jb.bytes(p, 1) <= p->ws_bytes || jb.nchunk == 1) break;
+      jb.nchunk = (jb.nchunk + 1) / 2;
+    }
+    per_record += jb.bytes(p, 1);
+  }
+  if (per_record > p->ws_bytes) return QI_OK;  // (not even one record: the caller's fallback)
+  int64_t Ct = (int64_t)(p->ws_bytes / per_record);
+  if (Ct > C) Ct = C;
+  *ran = true;
+  const bool joint_tail = njobs == 2 && p->small_joint > 1;
+  for (int64_t c0 = 0; c0 < C; c0 += Ct) {
+    const int64_t ct = C - c0 < Ct ? C - c0 : Ct;
+    QI_LAYOUT_BEGIN(p, "small-engine tile", false);
+    Arena ar{p, p->ws, ct, "small", false};
+    cplx<T>* X[2] = {nullptr, nullptr};
+    TileOut<T> v[2];
+    for (int q = 0; q < njobs; ++q) {
+      const SmallJob<T>& jb = job[q];
+      X[q] = ar.carve<cplx<T>>((size_t)jb.L * sizeof(cplx<T>));
+      double* part_band = ar.carve<double>((size_t)jb.B * 8);
+      double* part_stat = ar.carve<double>((size_t)jb.nchunk * 24);
+      T* planes = jb.planes ? ar.carve<T>((size_t)jb.nchunk * n * sizeof(T)) : nullptr;
+      v[q] = tile_out<T>(jb.out, c0, jb.B, n, planes, part_band, part_stat, 1, jb.nchunk, jb.planes ? jb.nchunk : 1);
+    }
+    // forward: the zero-padded 2n-point spectra for the styx bank, the n-point spectra for the other tables -- one launch
+    cplx<T>*X2 = nullptr, *X1 = nullptr;
+    for (int q = 0; q < njobs; ++q) (job[q].kind == 0 ? X2 : X1) = X[q];
+    p->prof.begin(st, QI_STAGE_FORWARD);
+    QI_TRY(native::launch_small_forward<T>(sig + c0 * n, X2, X1, static_cast<const cplx<T>*>(p->small_tw), 2 * n, n, ct, st));
+    p->prof.end(QI_STAGE_FORWARD, st);
+    native::TailCall<T> tc[2];
+    for (int q = 0; q < njobs; ++q) {
+      const SmallJob<T>& jb = job[q];
+      native::SmallArgs<T> a{};
+      a.X = X[q];
+      a.H = jb.H;
+      a.stx_idx = p->d_stx_idx;
+      a.stx_coef = p->d_stx_coef;
+      a.tw = static_cast<const cplx<T>*>(p->small_tw);
+      a.tw_shift = jb.L == 2 * n ? 0 : 1;
+      a.kind = jb.kind;
+      a.n = (int32_t)n;
+      a.L = (int32_t)jb.L;
+      a.off = (int32_t)jb.off;
+      a.B = (int32_t)jb.B;
+      a.nchunk = jb.nchunk;
+      a.chunk_total = v[q].chunk_total;
+      v[q].fill_panel(a);
+      a.time_part = v[q].time_part;
+      a.part_band = v[q].part_band;
+      a.part_stat = v[q].part_stat;
+      p->prof.begin(st, QI_STAGE_SMALL);
+      QI_TRY(native::launch_small_band<T>(a, ct, st));
+      p->prof.end(QI_STAGE_SMALL, st);
+      tc[q] = tail_call<T>(v[q], ct, nullptr);
+    }
+    p->prof.begin(st, QI_STAGE_EPILOGUE);
+    auto sums = [](const native::TailCall<T>& t) { return t.part_band || t.part_stat; };
+    if (joint_tail && job[0].planes && job[1].planes && sums(tc[0]) && sums(tc[1])) {
+      QI_TRY(native::launch_tail2<T>(tc[0], tc[1], st));
+    } else {
+      for (int q = 0; q < njobs; ++q)
+        if (job[q].planes || sums(tc[q])) QI_TRY(launch_reductions<T>(tc[q], job[q].planes, true, st));
+    }
+    p->prof.end(QI_STAGE_EPILOGUE, st);
+    p->prof.unchain();
+  }
+  return QI_OK;
+}
+
+template int run_small<float>(qi_plan*, int, const int*, const qi_tfr_out* const*, const void*, int64_t, hipStream_t, bool*);
+template int run_small<double>(qi_plan*, int, const int*, const qi_tfr_out* const*, const void*, int64_t, hipStream_t, bool*);
 template int run_transform<float>(qi_plan*, Kind, const void*, int64_t, const qi_tfr_out*, hipStream_t);
 template int run_transform<double>(qi_plan*, Kind, const void*, int64_t, const qi_tfr_out*, hipStream_t);
 template int run_native<float>(qi_plan*, int, const void*, int64_t, const qi_tfr_out*, hipStream_t, bool, FusedCarry*, FusedCarry*,
