@@ -312,6 +312,21 @@ int64_t qi_pool_columns(int64_t n, int64_t factor, int method);
 int qi_pool_panel(int dtype, int device, const void* in, int input_kind, int64_t rows, int64_t n, int64_t factor,
                   int method, double power_scale, void* out, qi_stream stream);
 
+/* A column range of a complex device panel in [rows][row_stride], pooled as subsample_2d pools it (sampling.py:87-120:
+ * "average" and "max" of P = power_scale * |z|^2; 0 is read as 1) and summed as the transforms' reductions sum it
+ * (tfr_info.py:203-236: the entropy of a panel from sum P and sum P log2 P), all from ONE read of the range: the columns
+ * [first, first + windows * factor) of every row, any `first`, any factor >= 2.  mean_out, max_out: real [rows][out_stride],
+ * one value per window (the average accumulated in float64 and rounded once, the maximum an input value); sums_out: float64
+ * [rows][3] = {max P, sum P, sum P log2 P} over the range, 0 log2 0 = 0.  Any of the three may be NULL.  No atomics, a fixed
+ * order of summation: the same call gives the same bits.  windows = 0 is a successful no-op.  With sums_out and few rows the
+ * per-row sums are finished by a second small launch from a 196 KB buffer the library keeps per (device, stream). */
+int qi_pool_strip(int dtype, int device, const void* in, int64_t rows, int64_t row_stride, int64_t first, int64_t factor,
+                  int64_t windows, double power_scale, void* mean_out, void* max_out, int64_t out_stride, void* sums_out,
+                  qi_stream stream);
+/* qi_pool_strip's sums [records][bands][3] -> a transform's statistics [records][4] = {max over bands, sum, sum, 0}
+ * (qi_tfr_out.stats), float64, in a fixed order. */
+int qi_pool_strip_stats(int device, const void* sums, int64_t records, int64_t bands, void* stats, qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,8 @@ PROTOTYPES = {
     "qi_shannon_fft": (_int, [_int, _int, _P, _i64, _i64, _P, _P, _P, _P, _i64, _P]),
     "qi_pool_columns": (_i64, [_i64, _i64, _int]),
     "qi_pool_panel": (_int, [_int, _int, _P, _int, _i64, _i64, _i64, _int, _dbl, _P, _P]),
+    "qi_pool_strip": (_int, [_int, _int, _P, _i64, _i64, _i64, _i64, _i64, _dbl, _P, _P, _i64, _P, _P]),
+    "qi_pool_strip_stats": (_int, [_int, _P, _i64, _i64, _P, _P]),
 }
 
 _lib = None

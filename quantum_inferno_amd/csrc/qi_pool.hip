@@ -8,7 +8,14 @@
 // The median sorts its windows in LDS (k_pool_median, factor <= 4096); "nth" is a gather (k_pool_nth).
 // Averages accumulate in float64 in a fixed order (no atomics) and are rounded once; max / min / median / nth return
 // input values.  The power of a complex panel is formed as the engines' epilogues form it (qi_device.hpp: norm2, mul_rn).
+// qi_pool_strip (k_pool_strip, further down) pools a column range of a complex panel's power: the average and the maximum
+// of every window and the range's {max P, sum P, sum P log2 P} per row from ONE read -- what a streamed record keeps of a
+// chunk (stream.py: the range a chunk owns).
+#include <algorithm>
+#include <map>
+#include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "qi_host.hpp"
 #include "qi_device.hpp"
@@ -274,6 +281,234 @@ inline unsigned pool_grid(int64_t work_per_group_units) {
   return (unsigned)(work_per_group_units > kPoolGridMax ? kPoolGridMax : (work_per_group_units < 1 ? 1 : work_per_group_units));
 }
 
+// ---- strips: the windows of a column range and the additive sums of that range, from one read -------------------------
+// A row's range [first, first + windows f) is cut into S segments of G consecutive windows; a workgroup takes a segment:
+//   kStripLane   f < 64       a thread per window, element loads (the plain path)
+//   kStripWave   f <= 1024    a wave per window, the waves take the segment's windows in turn; loads as k_pool_win
+//   kStripBlock  larger       the workgroup per window, one after the other
+// Every lane folds its elements into the window's sum (float64) and maximum and into its share of the segment's
+// {maximum, sum P, sum P log2 P}; a window is finished by the wave reduction (kStripBlock: then the waves in index order),
+// the segment's triple the same way at the end.  With S = 1 the triple is the row's; otherwise it goes to `part`
+// [rows][S][3] and k_strip_fold adds the segments up, lanes striding over them, then the wave: a fixed order throughout.
+enum { kStripLane = 0, kStripWave = 1, kStripBlock = 2 };
+constexpr int64_t kStripUnits = 4096;            // segments a launch aims at
+constexpr int64_t kStripSlots = 2 * kStripUnits;  // triples of the partials buffer: rows S < rows + kStripUnits, and S > 1 only for rows < kStripUnits
+
+__device__ __forceinline__ double strip_plog2p(float p, const double (*)[2]) { return (double)native::plog2p(p); }
+__device__ __forceinline__ double strip_plog2p(double p, const double (*tab)[2]) { return native::plog2p_flat(p, tab); }
+
+template <typename T>
+struct StripLane {
+  double a;  // sum of P over the lane's elements of this window
+  T m;       // their maximum
+  double l;  // sum of P log2 P over the lane's elements of the segment
+  __device__ __forceinline__ void take(cplx<T> z, T scale, const double (*tab)[2]) {
+    const T p = pool_value(z, scale);
+    a += (double)p;
+    m = p > m ? p : m;
+    l += strip_plog2p(p, tab);
+  }
+};
+
+template <typename T, int MODE>
+__global__ void __launch_bounds__(kPoolThreads) k_pool_strip(const cplx<T>* __restrict__ in, int64_t rows, int64_t stride,
+                                                             int64_t first, int64_t f, int64_t windows, int64_t G, int64_t S,
+                                                             T scale, T* __restrict__ mean, T* __restrict__ mx, int64_t ostride,
+                                                             double* __restrict__ part) {
+  using In = cplx<T>;
+  constexpr int V = 16 / (int)sizeof(In);
+  using Vec = PoolVec<In, V>;
+  constexpr bool kTab = std::is_same<T, double>::value;  // the float64 logarithm reads its table from LDS (log2_pos)
+  __shared__ double ltab[kTab ? 128 : 1][2];
+  __shared__ double sa[kPoolWaves], sl[kPoolWaves];
+  __shared__ T sm[kPoolWaves];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  if constexpr (kTab) {
+    (&ltab[0][0])[threadIdx.x] = (&native::kLog2Tab[0][0])[threadIdx.x];  // 256 threads, 128 x 2 entries
+    __syncthreads();
+  }
+  const T low = -(T)__builtin_huge_val();
+  const int nt = MODE == kStripBlock ? kPoolThreads : kWave;
+  const int t = MODE == kStripBlock ? (int)threadIdx.x : lane;
+  for (int64_t u = blockIdx.x; u < rows * S; u += gridDim.x) {  // (uniform over the workgroup)
+    const int64_t row = u / S, w0 = (u - row * S) * G;
+    const int64_t w1 = w0 + G < windows ? w0 + G : windows;
+    const In* base = in + row * stride + first;  // first + w1 f <= first + windows f <= stride
+    StripLane<T> x{0.0, low, 0.0};
+    double ra = 0.0;  // the lane's share of the segment: sum and maximum (x.l runs on over the windows)
+    T rm = low;
+    if (MODE == kStripLane) {
+      for (int64_t w = w0 + threadIdx.x; w < w1; w += kPoolThreads) {
+        const In* src = base + w * f;
+        x.a = 0.0;
+        x.m = low;
+        for (int64_t i = 0; i < f; ++i) x.take(src[i], scale, ltab);
+        if (mean) mean[row * ostride + w] = (T)(x.a / (double)f);
+        if (mx) mx[row * ostride + w] = x.m;
+        ra += x.a;
+        rm = x.m > rm ? x.m : rm;
+      }
+    } else {
+      for (int64_t w = w0 + (MODE == kStripBlock ? 0 : wv); w < w1; w += (MODE == kStripBlock ? 1 : kPoolWaves)) {
+        const In* src = base + w * f;
+        int64_t hd = (int64_t)(((16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15) / sizeof(In));
+        if (hd > f) hd = f;
+        const int64_t nv = (f - hd) / V, tl = hd + nv * V;
+        x.a = 0.0;
+        x.m = low;
+        if (t < hd) x.take(src[t], scale, ltab);
+        const Vec* vp = reinterpret_cast<const Vec*>(src + hd);
+        auto take_vec = [&](const Vec& v) {
+#pragma unroll
+          for (int q = 0; q < V; ++q) x.take(v.e[q], scale, ltab);
+        };
+        // four, then two, then one load in flight per lane; the lane's elements are folded in ascending order either way
+        int64_t i = t;
+        for (; i + 3 * nt < nv; i += 4 * nt) {
+          const Vec v0 = vp[i], v1 = vp[i + nt], v2 = vp[i + 2 * nt], v3 = vp[i + 3 * nt];
+          take_vec(v0);
+          take_vec(v1);
+          take_vec(v2);
+          take_vec(v3);
+        }
+        if (i + nt < nv) {
+          const Vec v0 = vp[i], v1 = vp[i + nt];
+          take_vec(v0);
+          take_vec(v1);
+          i += 2 * nt;
+        }
+        if (i < nv) take_vec(vp[i]);
+        if (tl + t < f) x.take(src[tl + t], scale, ltab);
+        ra += x.a;
+        rm = x.m > rm ? x.m : rm;
+        if (MODE == kStripWave) {  // (the loop is uniform over the wave: every lane is here)
+          if (mean) {
+            const double a = wave_sum(x.a);
+            if (lane == 0) mean[row * ostride + w] = (T)(a / (double)f);
+          }
+          if (mx) {
+            const T m = wave_max(x.m);
+            if (lane == 0) mx[row * ostride + w] = m;
+          }
+        } else if (mean || mx) {  // (uniform over the workgroup)
+          const double a = wave_sum(x.a);
+          const T m = wave_max(x.m);
+          if (lane == 0) {
+            sa[wv] = a;
+            sm[wv] = m;
+          }
+          __syncthreads();
+          if (threadIdx.x == 0) {
+            double r = sa[0];
+            T q = sm[0];
+            for (int k = 1; k < kPoolWaves; ++k) {
+              r += sa[k];
+              q = sm[k] > q ? sm[k] : q;
+            }
+            if (mean) mean[row * ostride + w] = (T)(r / (double)f);
+            if (mx) mx[row * ostride + w] = q;
+          }
+          __syncthreads();
+        }
+      }
+    }
+    if (part) {  // (uniform; the loops above have reconverged)
+      const double a = wave_sum(ra), l = wave_sum(x.l);
+      const T m = wave_max(rm);
+      if (lane == 0) {
+        sa[wv] = a;
+        sl[wv] = l;
+        sm[wv] = m;
+      }
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double r = sa[0], g = sl[0];
+        T q = sm[0];
+        for (int k = 1; k < kPoolWaves; ++k) {
+          r += sa[k];
+          g += sl[k];
+          q = sm[k] > q ? sm[k] : q;
+        }
+        part[u * 3 + 0] = (double)q;
+        part[u * 3 + 1] = r;
+        part[u * 3 + 2] = g;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// out[g][0 .. 2] = {max, sum, sum} over the `per` consecutive triples of group g, out[g][3 .. width - 1] = 0: a wave per
+// group, lanes striding over the triples, then the wave
+__global__ void __launch_bounds__(kPoolThreads) k_strip_fold(const double* __restrict__ part, int64_t groups, int64_t per,
+                                                             double* __restrict__ out, int width) {
+  const int lane = threadIdx.x & (kWave - 1);
+  for (int64_t g = (int64_t)blockIdx.x * kPoolWaves + threadIdx.x / kWave; g < groups; g += (int64_t)gridDim.x * kPoolWaves) {
+    double m = -__builtin_huge_val(), s = 0.0, l = 0.0;
+    for (int64_t i = lane; i < per; i += kWave) {
+      const double* p = part + (g * per + i) * 3;
+      m = p[0] > m ? p[0] : m;
+      s += p[1];
+      l += p[2];
+    }
+    m = wave_max(m);  // (the loop over g is uniform over the wave)
+    s = wave_sum(s);
+    l = wave_sum(l);
+    if (lane == 0) {
+      out[g * width + 0] = m;
+      out[g * width + 1] = s;
+      out[g * width + 2] = l;
+      for (int k = 3; k < width; ++k) out[g * width + k] = 0.0;
+    }
+  }
+}
+
+// The partials of a strip launch with S > 1: one buffer of kStripSlots triples per (device, stream), made at the first such
+// call and kept (196 KB).  Launches of one stream run in order, so they share it; other streams have their own.
+std::mutex g_strip_mutex;
+std::map<std::pair<int, hipStream_t>, double*> g_strip_part;
+
+int strip_partials(int device, hipStream_t st, double** out) {
+  std::lock_guard<std::mutex> lock(g_strip_mutex);
+  double*& p = g_strip_part[{device, st}];
+  if (!p) QI_HIP(hipMalloc((void**)&p, (size_t)kStripSlots * 3 * sizeof(double)));
+  *out = p;
+  return QI_OK;
+}
+
+template <typename T>
+int launch_strip(int device, const void* in_, int64_t rows, int64_t stride, int64_t first, int64_t f, int64_t windows,
+                 double power_scale, void* mean, void* mx, int64_t ostride, double* sums, hipStream_t st) {
+  const T scale = (T)host::power_scale_or_default(power_scale);
+  const int mode = f < kPoolSegMax ? kStripLane : (f <= kPoolWaveMax ? kStripWave : kStripBlock);
+  const int64_t gmin = mode == kStripLane ? kPoolThreads : (mode == kStripWave ? kPoolWaves : 1);
+  const int64_t G = std::max(gmin, ceil_div(rows * windows, kStripUnits));
+  const int64_t S = ceil_div(windows, G);
+  double* part = sums;
+  if (sums && S > 1) {
+    QI_REQUIRE(rows * S <= kStripSlots, "strip partials: %lld segments", (long long)(rows * S));
+    const int rc = strip_partials(device, st, &part);
+    if (rc != QI_OK) return rc;
+  }
+  const auto* in = static_cast<const cplx<T>*>(in_);
+  const unsigned grid = pool_grid(rows * S);
+  if (mode == kStripLane)
+    k_pool_strip<T, kStripLane><<<grid, kPoolThreads, 0, st>>>(in, rows, stride, first, f, windows, G, S, scale, (T*)mean, (T*)mx,
+                                                               ostride, part);
+  else if (mode == kStripWave)
+    k_pool_strip<T, kStripWave><<<grid, kPoolThreads, 0, st>>>(in, rows, stride, first, f, windows, G, S, scale, (T*)mean, (T*)mx,
+                                                               ostride, part);
+  else
+    k_pool_strip<T, kStripBlock><<<grid, kPoolThreads, 0, st>>>(in, rows, stride, first, f, windows, G, S, scale, (T*)mean, (T*)mx,
+                                                                ostride, part);
+  QI_LAUNCH_CHECK();
+  if (sums && S > 1) {
+    k_strip_fold<<<pool_grid(ceil_div(rows, kPoolWaves)), kPoolThreads, 0, st>>>(part, rows, S, sums, 3);
+    QI_LAUNCH_CHECK();
+  }
+  return QI_OK;
+}
+
 template <typename T, int KIND, int OP>
 int launch_pool_windows(const void* in_, int64_t rows, int64_t n, int64_t f, int64_t cols, T scale, void* out_,
                         hipStream_t st) {
@@ -377,6 +612,36 @@ int qi_pool_panel(int dtype, int device, const void* in, int input_kind, int64_t
   DeviceGuard g(device);
   return dtype == QI_F64 ? pool_dispatch<double>(in, input_kind, rows, n, factor, cols, method, power_scale, out, (hipStream_t)stream)
                          : pool_dispatch<float>(in, input_kind, rows, n, factor, cols, method, power_scale, out, (hipStream_t)stream);
+}
+
+int qi_pool_strip(int dtype, int device, const void* in, int64_t rows, int64_t row_stride, int64_t first, int64_t factor,
+                  int64_t windows, double power_scale, void* mean_out, void* max_out, int64_t out_stride, void* sums_out,
+                  qi_stream stream) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(in, "null argument");
+  QI_REQUIRE(rows >= 1 && row_stride >= 1, "bad panel shape");
+  QI_REQUIRE(factor >= 2, "pooling factor %lld: 2 or more", (long long)factor);
+  QI_REQUIRE(first >= 0 && windows >= 0 && first <= row_stride && windows <= (row_stride - first) / factor,
+             "%lld windows of %lld columns from column %lld do not fit a row of %lld", (long long)windows, (long long)factor,
+             (long long)first, (long long)row_stride);
+  QI_REQUIRE(!(mean_out || max_out) || out_stride >= windows, "output rows of %lld columns for %lld windows",
+             (long long)out_stride, (long long)windows);
+  if (windows == 0 || !(mean_out || max_out || sums_out)) return QI_OK;  // nothing to write
+  DeviceGuard g(device);
+  return dtype == QI_F64 ? launch_strip<double>(device, in, rows, row_stride, first, factor, windows, power_scale, mean_out, max_out,
+                                                out_stride, static_cast<double*>(sums_out), (hipStream_t)stream)
+                         : launch_strip<float>(device, in, rows, row_stride, first, factor, windows, power_scale, mean_out, max_out,
+                                               out_stride, static_cast<double*>(sums_out), (hipStream_t)stream);
+}
+
+int qi_pool_strip_stats(int device, const void* sums, int64_t records, int64_t bands, void* stats, qi_stream stream) {
+  QI_REQUIRE(sums && stats, "null argument");
+  QI_REQUIRE(records >= 1 && bands >= 1, "bad shape");
+  DeviceGuard g(device);
+  k_strip_fold<<<pool_grid(ceil_div(records, kPoolWaves)), kPoolThreads, 0, (hipStream_t)stream>>>(
+      static_cast<const double*>(sums), records, bands, static_cast<double*>(stats), 4);
+  QI_LAUNCH_CHECK();
+  return QI_OK;
 }
 
 }  // extern "C"

@@ -94,6 +94,7 @@ class TfrResult:
     stats: Optional[torch.Tensor] = None  # [C, 4] float64: max P, sum P, sum P log2 P, 0
     power_scale: float = 1.0
     reduced: Optional[torch.Tensor] = None  # float64 buffer the three reductions are views of (dist.reduced_slots)
+    pooled: Optional[dict] = None  # method -> [C, B, windows] pooled power strips (TfrPlan.pooled_strip, stream.py)
 
     @property
     def max_power(self):
@@ -353,6 +354,29 @@ class TfrPlan:
     def stx(self, sig, coef=True, bits=False, reductions=False, power_scale=1.0, eps=0.0, out=None, reduced_out=None):
         return self._run(_lib.QI_TABLE_STX, sig, coef, bits, reductions, power_scale, eps, out, reduced_out)
 
+    def _staged_panels(self, which, sig, power, power_scale, eps, tile_bytes):
+        """The tile loop of pooled() and pooled_strip(): the records [C, n] go through transform `which` in tiles of
+        max(1, tile_bytes // (B n element size)) records; each tile's panel (coefficients if `power`, else bits) lands in the
+        staging tensor the plan keeps between calls (close() drops it).  Yields (first record, end record, panel
+        [records, B, n]) after the tile's launches are queued; the panel is overwritten by the next tile."""
+        f_hz = self.freq.get(which)
+        if f_hz is None:
+            raise _lib.QiError("band table not set on this plan")
+        n_ch, n_b = sig.shape[0], len(f_hz)
+        sdtype = _complex_of(self.rdtype) if power else self.rdtype
+        per_record = n_b * self.n * torch.empty((), dtype=sdtype).element_size()
+        tile = min(n_ch, max(1, int(tile_bytes) // per_record))
+        if self._stage is None or self._stage.numel() < tile * per_record:
+            self._stage = None  # (released before the larger one is made)
+            self._stage = torch.empty(tile * per_record, dtype=torch.uint8, device=self.device)
+        stage = self._stage[: tile * per_record].view(sdtype).view(tile, n_b, self.n)
+        for c0 in range(0, n_ch, tile):
+            c1 = min(n_ch, c0 + tile)
+            panel = stage[: c1 - c0]
+            res = TfrResult(frequency_hz=f_hz, coef=panel if power else None, bits=None if power else panel)
+            self._run(which, sig[c0:c1], power, not power, False, power_scale, eps, out=res)
+            yield c0, c1, panel
+
     def pooled(self, which, sig, factor, method="average", quantity="power", power_scale=1.0, eps=0.0, tile_bytes=1 << 30):
         """Transform `which` (QI_BANK_STYX, QI_BANK_ATOMS or QI_TABLE_STX) of records [C, n], pooled along time in windows of
         `factor` samples (utilities.sampling.subsample_2d's methods): -> device tensor [C, B, columns], real, in the plan's
@@ -375,21 +399,49 @@ class TfrPlan:
         if cols < 0:
             _lib.check(cols)
         power = quantity == "power"
-        sdtype = _complex_of(self.rdtype) if power else self.rdtype
-        per_record = n_b * self.n * torch.empty((), dtype=sdtype).element_size()
-        tile = min(n_ch, max(1, int(tile_bytes) // per_record))
-        if self._stage is None or self._stage.numel() < tile * per_record:
-            self._stage = None  # (released before the larger one is made)
-            self._stage = torch.empty(tile * per_record, dtype=torch.uint8, device=self.device)
-        stage = self._stage[: tile * per_record].view(sdtype).view(tile, n_b, self.n)
         result = torch.empty((n_ch, n_b, cols), dtype=self.rdtype, device=self.device)
-        for c0 in range(0, n_ch, tile):
-            c1 = min(n_ch, c0 + tile)
-            panel = stage[: c1 - c0]
-            res = TfrResult(frequency_hz=f_hz, coef=panel if power else None, bits=None if power else panel)
-            self._run(which, sig[c0:c1], power, not power, False, power_scale, eps, out=res)
+        for c0, c1, panel in self._staged_panels(which, sig, power, power_scale, eps, tile_bytes):
             pool_rows(panel, factor, method, _lib.QI_POOL_POWER if power else _lib.QI_POOL_REAL, power_scale, out=result[c0:c1])
         return result
+
+    def pooled_strip(self, which, sig, factor, first, windows, methods=("average",), power_scale=1.0, tile_bytes=1 << 30):
+        """The part of a pooled power panel that lies in the column range [first, first + windows factor) of transform `which`
+        of records [C, n], and the additive reductions of that range -- what a streamed record keeps of the range a chunk
+        owns (stream.owned_windows).  -> (strips, power_band, stats): strips {method: [C, B, windows]} in the plan's
+        precision for methods out of ("average", "max"); power_band [C, B] float64, the sum of P = power_scale |z|^2 over
+        the range; stats [C, 4] float64 = {max P, sum P, sum P log2 P, 0} over the range, as TfrResult.stats.  Tiles and
+        staging tensor as pooled(); per tile one transform into the stage and ONE kernel (qi_pool_strip) that reads the range
+        once for every output; the statistics are folded over the bands on the device (qi_pool_strip_stats).  Nothing is
+        synchronised on the host."""
+        methods = tuple(methods)
+        if not methods or any(m not in ("average", "max") for m in methods) or len(set(methods)) != len(methods):
+            raise ValueError(f'methods must be a subset of ("average", "max"), got {methods!r}')
+        factor, first, windows = int(factor), int(first), int(windows)
+        if factor < 2:
+            raise ValueError(f"pooling factor {factor}: 2 or more")
+        if first < 0 or windows < 0 or first + windows * factor > self.n:
+            raise ValueError(f"{windows} windows of {factor} samples from sample {first} do not fit a record of {self.n}")
+        sig = self._signal(sig)
+        f_hz = self.freq.get(which)
+        if f_hz is None:
+            raise _lib.QiError("band table not set on this plan")
+        n_ch, n_b = sig.shape[0], len(f_hz)
+        strips = {m: torch.empty((n_ch, n_b, windows), dtype=self.rdtype, device=self.device) for m in methods}
+        sums = torch.zeros((n_ch, n_b, 3), dtype=torch.float64, device=self.device)
+        stats = torch.zeros((n_ch, 4), dtype=torch.float64, device=self.device)
+        if windows == 0 or n_ch == 0:
+            return strips, sums[:, :, 1].contiguous(), stats
+        code = _lib.QI_F64 if self.rdtype == torch.float64 else _lib.QI_F32
+        mean, peak = strips.get("average"), strips.get("max")
+        for c0, c1, panel in self._staged_panels(which, sig, True, power_scale, 0.0, tile_bytes):
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.qi_pool_strip(code, self.device.index, _lib.ptr(panel), (c1 - c0) * n_b, self.n, first, factor,
+                                                   windows, float(power_scale), _lib.ptr(None if mean is None else mean[c0:c1]),
+                                                   _lib.ptr(None if peak is None else peak[c0:c1]), windows, _lib.ptr(sums[c0:c1]),
+                                                   self._stream()))
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qi_pool_strip_stats(self.device.index, _lib.ptr(sums), n_ch, n_b, _lib.ptr(stats), self._stream()))
+        return strips, sums[:, :, 1].contiguous(), stats
 
     def close(self):
         self._stage = None

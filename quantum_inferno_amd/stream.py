@@ -8,7 +8,14 @@ carries).  The records stay on the HOST (a NumPy array or memmap: 1024 x 69.12 M
 copy of item k + 1 runs on a copy stream while item k is transformed, so PCIe (8 MB per record and chunk, ~0.2 ms) hides
 behind the transforms (~6 ms per record and chunk in float64).  Only the REDUCED product of a chunk is kept -- no panel
 is ever stored (coef=False): per-band power, per-time power, max / total / entropy sums.  Items are dealt to ranks by
-`dist.shard` (one process per GPU, no data-path collective; the reduced products are gathered as in dist.py)."""
+`dist.shard` (one process per GPU, no data-path collective; the reduced products are gathered as in dist.py).
+
+With hop < chunk the chunks overlap, so those per-chunk sums count most of the record twice, and no chunk product is a
+picture of the record.  `StreamPipeline(pooled=factor)` closes both: every pooling window of `factor` samples of the
+RECORD is owned by exactly one chunk (`owned_windows`), an item keeps the pooled power strips and the sums of the range
+its chunk owns (`TfrPlan.pooled_strip`: the chunk's panel goes through a staging tensor on the device, tile by tile), and
+`PooledRecord` puts the strips side by side and adds the sums up: a display-resolution panel, band powers and entropy of
+the whole record."""
 from dataclasses import dataclass
 from typing import Iterator, List, Optional, Tuple
 
@@ -30,6 +37,33 @@ def chunk_starts(n_total: int, chunk: int, hop: int) -> np.ndarray:
     if starts[-1] + chunk < n_total:
         starts = np.append(starts, n_total - chunk)
     return starts
+
+
+def owned_windows(n_total: int, chunk: int, hop: int, factor: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Which chunk owns which pooling windows of a record: -> (starts [K], edges [K + 1]), int64.  The windows are
+    [w factor, (w + 1) factor) in record time for w < n_total // factor (the ragged tail is dropped, as subsample_2d drops
+    it); chunk i (starting at starts[i] = chunk_starts(...)[i]) owns the samples [edges[i], edges[i + 1]): edges[0] = 0,
+    edges[K] = (n_total // factor) factor, and between two chunks the edge is the middle of their overlap, rounded down
+    to a window boundary -- the owned range stays away from the chunk ends, where a transform of the chunk differs most
+    from one of the record.  Chunk i's first window is edges[i] // factor, its window count (edges[i + 1] - edges[i]) //
+    factor, its offset inside the chunk edges[i] - starts[i] (any value: the last chunk is flush with the record end).
+    ValueError when a window lies in no single chunk (hop == chunk with a factor that does not divide the hop, or an
+    overlap shorter than about two windows)."""
+    factor = int(factor)
+    if factor < 2:
+        raise ValueError(f"pooling factor {factor}: 2 or more")
+    starts = chunk_starts(n_total, chunk, hop)
+    k = len(starts)
+    edges = np.empty(k + 1, dtype=np.int64)
+    edges[0] = 0
+    edges[k] = (n_total // factor) * factor
+    mid = (starts[1:] + starts[:-1] + chunk) // 2
+    edges[1:k] = (mid // factor) * factor
+    # (mid <= n_total and mid <= starts[i - 1] + chunk: the edges rise and end inside the chunk before them)
+    if np.any(edges[:k] < starts):
+        raise ValueError(f"pooling factor {factor}: some window of {factor} samples lies in no single chunk of {chunk} samples "
+                         f"(hop {hop}); the overlap chunk - hop must hold about two windows, or the factor divide the hop")
+    return starts, edges
 
 
 def iter_chunks(sig, chunk: int, hop: int, first_chunk: int = 0) -> Iterator[Tuple[int, int, torch.Tensor]]:
@@ -96,6 +130,44 @@ class StreamItem:
     start: int          # first sample of the chunk
     cwt: Optional[engine.TfrResult]
     stx: Optional[engine.TfrResult]
+    window0: Optional[int] = None  # pooled=factor: first pooling window of the record that this chunk owns ...
+    windows: Optional[int] = None  # ... and how many (owned_windows)
+
+
+class PooledRecord:
+    """Assembles the items of a `StreamPipeline(pooled=factor)` run into the pooled panel and the reductions of the whole
+    record set: `add(item, "cwt")` puts the item's strips at [first_channel : first_channel + channels, :, window0 :
+    window0 + windows], adds its band powers, sum P and sum P log2 P, and keeps the larger maximum.  `panel[method]` is
+    the [n_channels, n_bands, n_windows] panel (n_windows = n_total // factor), `result()` a TfrResult of the whole record
+    (power_band, stats -> total_power, entropy_bits, power_per_band_bits()).  One assembler per transform.
+
+    Strips carry their own position, so a rank that owns only some of the items fills only its part: the columns nobody
+    added stay NaN and the sums hold what was added.  Combining the assemblers of several ranks (the panel parts side by
+    side, the sums added, the maxima compared) is not built here."""
+
+    def __init__(self, n_channels, n_bands, n_windows, methods=("average",), dtype=torch.float32, device=None):
+        self.methods = tuple(methods)
+        self.panel = {m: torch.full((n_channels, n_bands, n_windows), float("nan"), dtype=dtype, device=device) for m in self.methods}
+        self.power_band = torch.zeros((n_channels, n_bands), dtype=torch.float64, device=device)
+        self.stats = torch.zeros((n_channels, 4), dtype=torch.float64, device=device)
+        self.frequency_hz = None
+        self.power_scale = 1.0
+
+    def add(self, item: "StreamItem", which: str = "cwt"):
+        res = {"cwt": item.cwt, "stx": item.stx}[which]
+        if res is None or res.pooled is None or item.windows is None:
+            raise ValueError(f"item {item.index} carries no pooled {which} strips (StreamPipeline(pooled=factor))")
+        ch = slice(item.first_channel, item.first_channel + item.channels)
+        for m in self.methods:
+            self.panel[m][ch, :, item.window0 : item.window0 + item.windows] = res.pooled[m]
+        self.power_band[ch] += res.power_band
+        self.stats[ch, 1:3] += res.stats[:, 1:3]
+        self.stats[ch, 0] = torch.maximum(self.stats[ch, 0], res.stats[:, 0])
+        self.frequency_hz, self.power_scale = res.frequency_hz, res.power_scale
+
+    def result(self) -> engine.TfrResult:
+        return engine.TfrResult(frequency_hz=self.frequency_hz, power_band=self.power_band, stats=self.stats,
+                                power_scale=self.power_scale, pooled=self.panel)
 
 
 class StreamPipeline:
@@ -108,11 +180,18 @@ class StreamPipeline:
 
     `host_records`: NumPy array / memmap [channels, n_total] (any real dtype; converted to the plan's on the way into
     the pinned buffer).  Every yielded item owns its reduced products.  keep_time=False: the per-time power of a chunk
-    (8 MB per record in float64) is neither kept nor computed (`reductions="band"`: band powers, maximum, total, entropy)."""
+    (8 MB per record in float64) is neither kept nor computed (`reductions="band"`: band powers, maximum, total, entropy).
+
+    pooled=factor: every item keeps, per transform, what the range its chunk OWNS contributes to the record (owned_windows;
+    a ValueError of that rule is raised here): `item.cwt.pooled[method]` [channels, bands, item.windows], the strips of the
+    record's pooled power panel from window `item.window0` on (pooled_methods out of "average", "max"), and `power_band` /
+    `stats` over the owned range only, so that they add up over the items of a record (`PooledRecord`); `power_time` is
+    None.  Each transform then stores its panel in the plan's staging tensor, tile by tile (TfrPlan.pooled_strip)."""
 
     def __init__(self, plan: engine.TfrPlan, host_records, hop: int, block: int = 16, transforms=("cwt", "stx"),
-                 power_scale: float = 1.0, keep_time: bool = True):
+                 power_scale: float = 1.0, keep_time: bool = True, pooled: Optional[int] = None, pooled_methods=("average",)):
         self.plan, self.hop, self.block = plan, int(hop), int(block)
+        self.pooled, self.pooled_methods = (None if pooled is None else int(pooled)), tuple(pooled_methods)
         # an ndarray / memmap, or any object with a 2-D `shape` that answers [channel slice, sample slice] with an array
         # (a rank of the 24 h job materialises only the records it owns)
         self.sig = host_records if hasattr(host_records, "shape") and hasattr(host_records, "__getitem__") else np.asarray(host_records)
@@ -126,6 +205,10 @@ class StreamPipeline:
         # (no per-time power kept: it is not computed either -- no per-time planes written or summed, round 5)
         self._reductions = True if keep_time else "band"
         self.items = work_items(self.sig.shape[0], self.block, self.sig.shape[1], plan.n, self.hop)
+        if self.pooled is not None:
+            if not self.pooled_methods or any(m not in ("average", "max") for m in self.pooled_methods):
+                raise ValueError(f'pooled_methods must be a subset of ("average", "max"), got {self.pooled_methods!r}')
+            self._starts, self._edges = owned_windows(self.sig.shape[1], plan.n, self.hop, self.pooled)
         np_dtype = np.float64 if plan.rdtype == torch.float64 else np.float32
         # (a plan on the CPU exists only as the stand-in of bench.py --stub: the item walk without streams or pinning)
         self._gpu = torch.device(plan.device).type == "cuda"
@@ -178,7 +261,15 @@ class StreamPipeline:
                 compute.wait_event(self._copied[j])
             x = self._dev[j][:cb]
             res = {}
-            if self.transforms == ("cwt", "stx"):
+            if self.pooled is not None:
+                e0, e1 = int(self._edges[chunk]), int(self._edges[chunk + 1])
+                w0, nw = e0 // self.pooled, (e1 - e0) // self.pooled
+                for t in self.transforms:
+                    strips, band, stats = self.plan.pooled_strip(engine._lib.QI_BANK_STYX if t == "cwt" else engine._lib.QI_TABLE_STX,
+                                                                 x, self.pooled, e0 - s, nw, self.pooled_methods, self.power_scale)
+                    res[t] = engine.TfrResult(frequency_hz=self.plan.freq[engine._lib.QI_BANK_STYX if t == "cwt" else engine._lib.QI_TABLE_STX],
+                                              power_band=band, stats=stats, power_scale=self.power_scale, pooled=strips)
+            elif self.transforms == ("cwt", "stx"):
                 key = ("both", cb)
                 self._out[key] = self.plan.cwt_stx(x, coef=False, reductions=self._reductions, power_scale=self.power_scale,
                                                    out=self._out.get(key))
@@ -196,6 +287,9 @@ class StreamPipeline:
             # waits for every item before asking for the next (round 3 staged first: the GPU idled through the gather)
             if k + 1 < len(mine):
                 self._stage(j ^ 1, mine[k + 1])
+            if self.pooled is not None:  # (pooled_strip's outputs are new tensors: the item owns them)
+                yield StreamItem(first_item + k, c0, cb, chunk, s, res.get("cwt"), res.get("stx"), w0, nw)
+                continue
             kept = {t: self._keep(r) for t, r in res.items()}
             yield StreamItem(first_item + k, c0, cb, chunk, s, kept.get("cwt"), kept.get("stx"))
 
