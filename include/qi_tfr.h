@@ -327,6 +327,23 @@ int qi_pool_strip(int dtype, int device, const void* in, int64_t rows, int64_t r
  * (qi_tfr_out.stats), float64, in a fixed order. */
 int qi_pool_strip_stats(int device, const void* sums, int64_t records, int64_t bands, void* stats, qi_stream stream);
 
+/* ---- STFT with the plan transforms' outputs --------------------------------------------------------------------------
+ * qi_stft's transform (styx_fft.stft_complex_pow2 / stft_from_sig) into a qi_tfr_out: any of coef (= Z [C][nfft/2+1][n_seg])
+ * and bits may be NULL -- no panel is stored then --, and the reductions of P = power_scale |Z|^2 come from the kernel that forms the
+ * coefficients: power_band [C][nfft/2+1] float64 (sum over the segments), power_time [C][n_seg] in the record's precision
+ * (sum over the bins), stats [C][4] float64 {max P, sum P, sum P log2 P, 0} (tfr_info.py:65-94,203-236, whose 2-D entropy
+ * classes are named after this transform).  power_band and stats come together; power_time may be NULL beside them.  All
+ * five NULL is QI_ERR_ARG.  No atomics, fixed orders of summation: a record's reductions are the same bits alone and in a
+ * batch, with both panels stored and with none.  With coef and bits only the call is qi_stft.  eps as in qi_stft.
+ * Power-of-two nfft of 64 .. 4096 (float64: .. 2048) run one fused kernel and a small tail; other lengths form the panel
+ * with hipFFT (in `coef`, or in scratch) and reduce it with the hipFFT engine's epilogue.
+ * scratch: caller-owned device buffer of qi_stft_out_scratch_bytes() for the same want_coef = (coef != NULL). */
+int64_t qi_stft_out_scratch_bytes(int dtype, int64_t n_channels, int64_t n, int64_t seg, int64_t hop, int64_t nfft,
+                                  int want_coef, int want_bits);
+int qi_stft_out(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, const void* window, int64_t seg,
+                int64_t hop, int64_t nfft, double scale, const qi_tfr_out* out, void* scratch, int64_t scratch_bytes,
+                qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

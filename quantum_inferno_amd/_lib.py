@@ -90,6 +90,8 @@ PROTOTYPES = {
     "qi_stft_segments": (_i64, [_i64, _i64, _i64]),
     "qi_stft_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
     "qi_stft": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _i64, _dbl, _P, _P, _dbl, _P, _i64, _P]),
+    "qi_stft_out_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _int, _int]),
+    "qi_stft_out": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _i64, _dbl, C.POINTER(TfrOut), _P, _i64, _P]),
     "qi_welch_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
     "qi_welch": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _i64, _dbl, _P, _P, _i64, _P]),
     "qi_power_marginals": (_int, [_int, _int, _P, _i64, _i64, _i64, _P, _P, _P, _P, _i64, _P]),

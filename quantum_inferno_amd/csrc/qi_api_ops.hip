@@ -33,6 +33,77 @@ int stft_impl(int device, const void* sig, int64_t C, int64_t n, const void* win
                                   (T)qi::host::eps_or_default(eps), st);
 }
 
+// Scratch of qi_stft_out: [0] the three-kernel path's frames and spectra (qi_stft_scratch_bytes) | [1] the panel when the
+// caller keeps none | [2] band partials | [3] statistics partials -- [2] and [3] hold either engine's: per segment group of
+// the fused kernel, or per kEpiSpan columns of k_epilogue.
+struct StftOutLayout {
+  size_t panel, part_band, part_stat, total;
+};
+StftOutLayout stft_out_layout(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft, bool want_coef) {
+  const int64_t nseg = qi_stft_segments(n, seg, hop), nf = nfft / 2 + 1;
+  const size_t e = dtype == QI_F64 ? 8 : 4;
+  int64_t slots = ceil_div(nseg, kEpiSpan);
+  if (stft_fused_supported(dtype, seg, hop, nfft)) slots = std::max(slots, stft_fused_groups(dtype, nfft, nseg));
+  StftOutLayout l;
+  l.panel = align_up((size_t)C * nseg * nfft * e) + align_up((size_t)C * nseg * nf * 2 * e);
+  l.part_band = l.panel + (want_coef ? 0 : align_up((size_t)C * nf * nseg * 2 * e));
+  l.part_stat = l.part_band + align_up((size_t)C * slots * nf * 8);
+  l.total = l.part_stat + align_up((size_t)C * slots * 24);
+  return l;
+}
+
+template <typename T>
+int stft_out_impl(int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop, int64_t nfft,
+                  double scale, const qi_tfr_out* out, char* scratch, hipStream_t st) {
+  const int dtype = sizeof(T) == 8 ? QI_F64 : QI_F32;
+  const int64_t nseg = qi_stft_segments(n, seg, hop), nf = nfft / 2 + 1;
+  const double eps = qi::host::eps_or_default(out->eps);
+  const StftOutLayout l = stft_out_layout(dtype, C, n, seg, hop, nfft, out->coef != nullptr);
+  cplx<T>* Z = static_cast<cplx<T>*>(out->coef);
+  T* bits = static_cast<T*>(out->bits);
+  double* part_band = reinterpret_cast<double*>(scratch + l.part_band);
+  double* part_stat = reinterpret_cast<double*>(scratch + l.part_stat);
+  const bool reduce = out->power_band != nullptr;
+  static const bool fused_off = tune_env("QI_STFT_FUSED") && atoi(tune_env("QI_STFT_FUSED")) == 0;
+  if (!fused_off && stft_fused_supported(dtype, seg, hop, nfft)) {
+    const StftReduce red{part_band, part_stat, out->power_time, static_cast<double*>(out->power_band),
+                         static_cast<double*>(out->stats), qi::host::power_scale_or_default(out->power_scale)};
+    const int rc = launch_stft_fused<T>(static_cast<const T*>(sig), static_cast<const T*>(window), Z, bits, C, n, seg, hop, nfft,
+                                        nseg, seg / 2, scale, eps, st, nullptr, nullptr, reduce ? &red : nullptr);
+    if (rc != QI_ERR_UNSUPPORTED) return rc;  // (a device with less LDS than the tile needs: the three-kernel path below)
+  }
+  // frames -> hipFFT -> transpose into the caller's panel or the scratch one, then the hipFFT engine's reduction kernels on it
+  T* frames = reinterpret_cast<T*>(scratch);
+  cplx<T>* F = reinterpret_cast<cplx<T>*>(scratch + align_up((size_t)C * nseg * nfft * sizeof(T)));
+  if (!Z) Z = reinterpret_cast<cplx<T>*>(scratch + l.panel);
+  QI_TRY(launch_stft_frames<T>(static_cast<const T*>(sig), static_cast<const T*>(window), frames, C, n, seg, hop, nfft, nseg,
+                               seg / 2, st));
+  {
+    std::lock_guard<std::mutex> lk(g_stft_mu);
+    QI_TRY(fft_r2c<T>(g_stft_fft[device], frames, F, nfft, C * nseg, st));
+  }
+  QI_TRY(launch_stft_transpose<T>(F, Z, bits, C, nseg, nf, (T)scale, (T)eps, st));
+  if (!reduce) return QI_OK;
+  const int64_t nblk = ceil_div(nseg, kEpiSpan);
+  EpiArgs<T> a{};
+  a.Y = Z;
+  a.L = a.n = nseg;
+  a.off = 0;
+  a.Ct = C;
+  a.Bt = a.B = nf;
+  a.j0 = 0;
+  a.power_time = static_cast<T*>(out->power_time);
+  a.part_band = part_band;
+  a.part_stat = part_stat;
+  a.tile_b = 0;
+  a.ntile_b = 1;
+  a.power_scale = (T)qi::host::power_scale_or_default(out->power_scale);
+  a.eps = (T)eps;
+  QI_TRY(launch_epilogue<T>(a, st));
+  return launch_finalize(part_band, part_stat, static_cast<double*>(out->power_band), static_cast<double*>(out->stats), C, nf,
+                         nblk, nblk, st);
+}
+
 template <typename T>
 int welch_impl(int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop,
                int64_t nfft, double scale, void* pxx, char* scratch, hipStream_t st) {
@@ -146,6 +217,29 @@ int qi_stft(int dtype, int device, const void* sig, int64_t C, int64_t n, const 
                                              (char*)scratch, (hipStream_t)stream)
                          : stft_impl<float>(device, sig, C, n, window, seg, hop, nfft, scale, Z, bits, eps,
                                             (char*)scratch, (hipStream_t)stream);
+}
+
+int64_t qi_stft_out_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft, int want_coef,
+                                  int want_bits) {
+  (void)want_bits;  // (the bits panel is never formed in scratch)
+  if (C <= 0 || nfft < seg || qi_stft_segments(n, seg, hop) <= 0) return 0;
+  return (int64_t)stft_out_layout(dtype, C, n, seg, hop, nfft, want_coef != 0).total;
+}
+
+int qi_stft_out(int dtype, int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop,
+                int64_t nfft, double scale, const qi_tfr_out* out, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_REQUIRE(sig && window && out && scratch, "null argument");
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(C > 0 && n > 0 && seg > 0 && hop > 0 && hop <= seg && nfft >= seg, "bad STFT geometry");
+  QI_REQUIRE(out->coef || out->bits || out->power_band || out->power_time || out->stats, "nothing to produce");
+  QI_REQUIRE((out->power_band != nullptr) == (out->stats != nullptr), "power_band and stats come together");
+  QI_REQUIRE(!out->power_time || out->power_band, "power_time needs power_band and stats");
+  QI_REQUIRE(scratch_bytes >= qi_stft_out_scratch_bytes(dtype, C, n, seg, hop, nfft, out->coef != nullptr, out->bits != nullptr),
+             "scratch too small");
+  DeviceGuard g(device);
+  return dtype == QI_F64
+             ? stft_out_impl<double>(device, sig, C, n, window, seg, hop, nfft, scale, out, (char*)scratch, (hipStream_t)stream)
+             : stft_out_impl<float>(device, sig, C, n, window, seg, hop, nfft, scale, out, (char*)scratch, (hipStream_t)stream);
 }
 
 int64_t qi_welch_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {

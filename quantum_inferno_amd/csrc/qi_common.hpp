@@ -165,10 +165,21 @@ struct StftSliding {
 };
 // fused STFT (qi_stft_fused.hip): frames, transform and [frequency][time] store in one kernel
 bool stft_fused_supported(int dtype, int64_t seg, int64_t hop, int64_t nfft);
+// reductions of the panel from the fused kernel's registers (qi_stft_out): part_band [C][groups][nfft / 2 + 1] and part_stat
+// [C][groups][3] doubles of scratch, groups = stft_fused_groups(); power_band [C][nfft / 2 + 1] and stats [C][4] float64,
+// power_time [C][nseg] in the record's precision or null.  Z and bits may then be null (no panel is stored).
+struct StftReduce {
+  double *part_band, *part_stat;
+  void* power_time;
+  double *power_band, *stats;
+  double power_scale;
+};
+// segment groups (workgroups) per record of a fused launch; 0: the transform length has no fused shape
+int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg);
 template <typename T>
 int launch_stft_fused(const T* sig, const T* win, cplx<T>* Z, T* bits, int64_t C, int64_t n, int64_t seg, int64_t hop,
                       int64_t nfft, int64_t nseg, int64_t lead, double scale, double eps, hipStream_t st,
-                      double* welch_part = nullptr, const StftSliding* sliding = nullptr);
+                      double* welch_part = nullptr, const StftSliding* sliding = nullptr, const StftReduce* red = nullptr);
 // fused inverse of the ShortTimeFFT-convention transform (QI_ERR_UNSUPPORTED, with no error text, where it does not apply)
 template <typename T>
 int launch_istft_fused(const cplx<T>* S, const T* dual, T* out, int64_t C, int64_t seg, int64_t hop, int64_t nfft, int64_t first,

@@ -78,7 +78,79 @@ struct StftFusedArgs {
   int32_t pad_mode, detrend, real_kind;
   int64_t roll;
   int32_t dbg;  // -DQI_STFT_DBG builds: timing ablations (1: no panel stores, 2: no transforms, 4: no record loads, 8: no bits)
+  // reductions form (qi_stft_out): P = power_scale |X|^2 of the coefficient as stored.  red_band [C][ngroups][nfft / 2 + 1]
+  // sums of P over a group's segments, red_stat [C][ngroups][3] {max P, sum P, sum P log2 P} of a group, power_time [C][nseg]
+  // in the record's precision (may be null)
+  double* red_band;
+  double* red_stat;
+  void* power_time;
+  double power_scale;
 };
+
+// The untangling's complex product (z - conj z') w of the reductions form's PLAIN walk in one fixed instruction form per
+// precision: the one the compiler gives `cmul` in the PLAIN walk of qi_stft (a multiply and a fused multiply-add per part;
+// which product of the imaginary part is the fused one differs between float and double), so that the coefficients are
+// qi_stft's bit for bit and do not depend on what else an instantiation computes -- left to the compiler, the float32 form
+// without stores kept its multiplies unfused and its sums differed from the form with stores in the last bits.
+// (tests/test_gpu_stft_reduced.py holds both equalities at every transform length.)
+__device__ __forceinline__ float2 untangle_mul(float2 a, float2 b) {
+  return make_float2(fmaf(a.x, b.x, -__fmul_rn(a.y, b.y)), fmaf(a.x, b.y, __fmul_rn(a.y, b.x)));
+}
+__device__ __forceinline__ double2 untangle_mul(double2 a, double2 b) {
+  return make_double2(fma(a.x, b.x, -__dmul_rn(a.y, b.y)), fma(a.y, b.x, __dmul_rn(a.x, b.y)));
+}
+
+// LDS of the reductions form's tail, laid over the tiles once they are dead: one double per thread | [3][waves] doubles
+constexpr size_t kStftRedLds = (size_t)(kStftThreads + 3 * (kStftThreads / kWave)) * sizeof(double);
+
+// Sum over the 2^lg adjacent lanes of an aligned group (lg <= 4: inside one DPP row of sixteen lanes) in a fixed order --
+// the first steps of wave_sum; every lane of the group gets the total.  The whole wave is active.
+__device__ __forceinline__ double group_sum(double v, int lg) {
+  if (lg > 0) v += dpp_mov<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  if (lg > 1) v += dpp_mov<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  if (lg > 2) v += dpp_mov<0x141>(v);  // row_half_mirror
+  if (lg > 3) v += dpp_mov<0x140>(v);  // row_mirror
+  return v;
+}
+
+// Tail of the reductions form.  A thread holds, for its segment g = tid & (G - 1) and its share of the bins, pt = sum P,
+// mx = max P and pl = sum P log2 P.  power_time[c][m0 + g] = the S = threads / G shares of segment g added in index order
+// (through LDS, in float64, rounded once); the group's {max, sum, sum} entry by the wave reductions and one thread.
+template <typename T>
+__device__ __forceinline__ void stft_red_tail(unsigned char* lds_raw, const StftFusedArgs& a, int64_t c, int64_t grp, int64_t m0,
+                                              T pt, T mx, double pl) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  constexpr int NW = kStftThreads / kWave;
+  double* __restrict__ red = reinterpret_cast<double*>(lds_raw);
+  double* __restrict__ fin = red + kStftThreads;  // [3][NW]
+  __syncthreads();  // every thread has read its last coefficient: the tiles' LDS is free
+  red[tid] = (double)pt;
+  const double r0 = wave_max((double)mx), r1 = wave_sum((double)pt), r2 = wave_sum(pl);
+  if (lane == 0) {
+    fin[wv] = r0;
+    fin[NW + wv] = r1;
+    fin[2 * NW + wv] = r2;
+  }
+  __syncthreads();
+  if (tid < a.G && m0 + tid < a.nseg && a.power_time) {
+    double s = 0.0;
+    for (int q = tid; q < kStftThreads; q += a.G) s += red[q];
+    static_cast<T*>(a.power_time)[c * a.nseg + m0 + tid] = (T)s;
+  }
+  if (tid == kStftThreads - 1) {
+    double m = 0.0, s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      m = fin[w] > m ? fin[w] : m;
+      s1 += fin[NW + w];
+      s2 += fin[2 * NW + w];
+    }
+    double* __restrict__ o = a.red_stat + ((size_t)c * a.ngroups + (size_t)grp) * 3;
+    o[0] = m;
+    o[1] = s1;
+    o[2] = s2;
+  }
+}
 
 // dynamic LDS: data [G][R (C + 1) + 1] complex | twiddles [M + 1] complex (exp(-2 pi i k / (2 M)))
 //
@@ -90,7 +162,12 @@ struct StftFusedArgs {
 // PLAIN: the styx_fft product (zero extension, both panels, log2 bits, no slice rotation) with its loops specialised:
 // whole segments come in as aligned pairs, a thread of the store pass keeps its segment and walks the bins with running
 // addresses.  The general form serves Welch and the ShortTimeFFT convention.
-template <typename T, int LOG2R, int LOG2C, bool PLAIN>
+//
+// RED: the reductions form (qi_stft_out) of either store loop: the power marginals and the entropy sums of the panel from
+// the coefficients in registers, the panel stores compile-time optional (WZ, WB).  Consecutive lanes hold consecutive segments
+// of one bin, so the sum over a group's segments is group_sum over G adjacent lanes; no thread leaves before the tail (a
+// segment past the last one is a tile of zeros: P = 0, nothing stored).  No atomics: every partial has one writer.
+template <typename T, int LOG2R, int LOG2C, bool PLAIN, bool RED = false, bool WZ = true, bool WB = true>
 __global__ void QI_STFT_BOUNDS k_stft_fused(const T* __restrict__ sig, const T* __restrict__ win,
                                                             const cplx<T>* __restrict__ twg, cplx<T>* __restrict__ Z,
                                                             T* __restrict__ bits, StftFusedArgs a) {
@@ -111,11 +188,15 @@ __global__ void QI_STFT_BOUNDS k_stft_fused(const T* __restrict__ sig, const T* 
 
   // exp(-i pi k / M), k = 0..M: requested first, left in LDS after the segments (one round trip, not one per sweep)
   constexpr int NT = (M + kStftThreads) / kStftThreads;
+  // (the reductions form fetches them after the segments instead: NT complex registers fewer while the pair loader holds its
+  // three half segments and the window -- what keeps its 2048-point float32 instantiation at two workgroups per CU)
   cplx<T> twv[NT];
+  if constexpr (!RED) {
 #pragma unroll
-  for (int i = 0; i < NT; ++i) {
-    const int k = tid + i * kStftThreads;
-    twv[i] = k <= M ? twg[k] : mk<T>(T(0), T(0));
+    for (int i = 0; i < NT; ++i) {
+      const int k = tid + i * kStftThreads;
+      twv[i] = k <= M ? twg[k] : mk<T>(T(0), T(0));
+    }
   }
   // segments: one wave per segment (mean by wave shuffles, no workgroup barrier)
   constexpr int NW = kStftThreads / kWave, NP = (M + kWave - 1) / kWave;
@@ -234,7 +315,11 @@ __global__ void QI_STFT_BOUNDS k_stft_fused(const T* __restrict__ sig, const T* 
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     const int k = tid + i * kStftThreads;
-    if (k <= M) tw[k] = twv[i];
+    if constexpr (RED) {
+      if (k <= M) tw[k] = twg[k];
+    } else {
+      if (k <= M) tw[k] = twv[i];
+    }
   }
   __syncthreads();
 
@@ -281,7 +366,52 @@ __global__ void QI_STFT_BOUNDS k_stft_fused(const T* __restrict__ sig, const T* 
   // Z[k] = row k mod R, column k / R.  Consecutive threads take consecutive segments of one bin.
   const int nf = M + 1, lg = a.log2g;
   const T scale = (T)a.scale, eps = (T)a.eps;
-  if constexpr (PLAIN) {
+  if constexpr (PLAIN && RED) {
+    // the PLAIN walk (segment and tile fixed, the bins k and M - k together) in sweeps every thread takes part in
+    const int g = tid & (G - 1), S = kStftThreads >> lg, ks = tid >> lg;
+    const int64_t m = m0 + g, grp = item % a.ngroups;
+    const bool live = m < a.nseg;
+    const cplx<T>* __restrict__ d = data + (size_t)g * TILE;
+    const T hs = T(0.5) * scale, ps = (T)a.power_scale;
+    double* __restrict__ pband = a.red_band + ((size_t)c * a.ngroups + (size_t)grp) * nf;
+    const int64_t step = (int64_t)S * a.nseg;
+    int64_t ia = (c * nf + ks) * a.nseg + m, ib = (c * nf + (M - ks)) * a.nseg + m;
+    T pt = T(0), mx = T(0);
+    double pl = 0.0;
+    for (int k0 = 0; k0 <= M / 2; k0 += S, ia += step, ib -= step) {
+      const int k = k0 + ks;
+      const bool on = k <= M / 2;
+      T pa = T(0), pb = T(0);
+      if (on) {
+        const int ka = k, kb = (M - k) & (M - 1);
+        const cplx<T> za = d[(ka & (R - 1)) * RS + (ka >> LOG2R)], zb = d[(kb & (R - 1)) * RS + (kb >> LOG2R)];
+        const cplx<T> w = tw[k];
+        const T A = za.x + zb.x, B = za.y - zb.y;
+        const cplx<T> wo = untangle_mul(mk<T>(za.x - zb.x, za.y + zb.y), w);
+        const cplx<T> X = mk<T>(hs * (A + wo.y), hs * (B - wo.x)), Y = mk<T>(hs * (A - wo.y), hs * (-B - wo.x));
+        if (live) {
+          if constexpr (WZ) Z[ia] = X;
+          if constexpr (WB) bits[ia] = log2_t(sqrt_t(X.x * X.x + X.y * X.y) + eps);
+          if (2 * k != M) {
+            if constexpr (WZ) Z[ib] = Y;
+            if constexpr (WB) bits[ib] = log2_t(sqrt_t(Y.x * Y.x + Y.y * Y.y) + eps);
+          }
+        }
+        pa = mul_rn(ps, norm2(X.x, X.y));
+        if (2 * k != M) pb = mul_rn(ps, norm2(Y.x, Y.y));
+      }
+      const double sa = group_sum((double)pa, lg), sb = group_sum((double)pb, lg);
+      if (on && g == 0) {
+        pband[k] = sa;
+        if (2 * k != M) pband[M - k] = sb;
+      }
+      pt += pa + pb;
+      mx = native::max_t(mx, native::max_t(pa, pb));
+      pl += (double)native::plog2p(pa) + (double)native::plog2p(pb);
+    }
+    stft_red_tail<T>(lds_raw, a, c, grp, m0, pt, mx, pl);
+    return;
+  } else if constexpr (PLAIN) {
     // thread = (bin k0 of a sweep of S = threads / G bins, segment g): its segment, its tile and its place in a row stay;
     // bins advance by S, the panel addresses by S rows
     const int g = tid & (G - 1), S = kStftThreads >> lg;
@@ -324,6 +454,46 @@ __global__ void QI_STFT_BOUNDS k_stft_fused(const T* __restrict__ sig, const T* 
         *bq = log2_t(sqrt_t(Y.x * Y.x + Y.y * Y.y) + eps);
       }
     }
+    return;
+  }
+  if constexpr (RED) {
+    // the general walk (one bin of one segment per step; zero extension, no slice rotation, log2 bits) in sweeps every thread
+    // takes part in: 256 is a multiple of G, so a thread keeps its segment
+    const int g = tid & (G - 1), S = kStftThreads >> lg, ks = tid >> lg;
+    const int64_t m = m0 + g, grp = item % a.ngroups;
+    const bool live = m < a.nseg;
+    const cplx<T>* __restrict__ d = data + (size_t)g * TILE;
+    const T ps = (T)a.power_scale;
+    double* __restrict__ pband = a.red_band + ((size_t)c * a.ngroups + (size_t)grp) * nf;
+    T pt = T(0), mx = T(0);
+    double pl = 0.0;
+    for (int k0 = 0; k0 < nf; k0 += S) {
+      const int k = k0 + ks;
+      const bool on = k < nf;
+      T p = T(0);
+      if (on) {
+        const int ka = k & (M - 1), kb = (M - k) & (M - 1);
+        const cplx<T> za = d[(ka & (R - 1)) * RS + (ka >> LOG2R)], zb = d[(kb & (R - 1)) * RS + (kb >> LOG2R)];
+        const cplx<T> e = mk<T>(T(0.5) * (za.x + zb.x), T(0.5) * (za.y - zb.y));
+        const cplx<T> o = mk<T>(T(0.5) * (za.x - zb.x), T(0.5) * (za.y + zb.y));
+        const cplx<T> wo = cmul(o, tw[k]);
+        cplx<T> X = mk<T>(e.x + wo.y, e.y - wo.x);
+        X.x *= scale;
+        X.y *= scale;
+        if (live) {
+          const int64_t at = (c * nf + k) * a.nseg + m;
+          if constexpr (WZ) Z[at] = X;
+          if constexpr (WB) bits[at] = log2_t(sqrt_t(X.x * X.x + X.y * X.y) + eps);
+        }
+        p = mul_rn(ps, norm2(X.x, X.y));
+      }
+      const double sp = group_sum((double)p, lg);
+      if (on && g == 0) pband[k] = sp;
+      pt += p;
+      mx = native::max_t(mx, p);
+      pl += (double)native::plog2p(p);
+    }
+    stft_red_tail<T>(lds_raw, a, c, grp, m0, pt, mx, pl);
     return;
   }
   if (a.welch_part) {
@@ -517,6 +687,34 @@ __global__ void k_welch_reduce(const double* __restrict__ part, T* __restrict__ 
   pxx[c * nf + f] = (T)(acc / (double)nseg) * scale2 * (paired ? T(2) : T(1));
 }
 
+// Tail of the reductions form: power_band[c][f] = the groups' partial sums added in index order (blocks x < gridDim.x - 1);
+// stats[c] = {max, sum, sum, 0} of the groups' entries, in index order too (the last block of a record, one thread)
+__global__ void __launch_bounds__(256) k_stft_reduce(const double* __restrict__ part_band, const double* __restrict__ part_stat,
+                                                     double* __restrict__ power_band, double* __restrict__ stats, int ngroups,
+                                                     int nf) {
+  const int64_t c = blockIdx.y;
+  if (blockIdx.x == gridDim.x - 1) {
+    if (threadIdx.x != 0) return;
+    const double* __restrict__ p = part_stat + (size_t)c * ngroups * 3;
+    double m = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int g = 0; g < ngroups; ++g) {
+      m = p[3 * g] > m ? p[3 * g] : m;
+      s1 += p[3 * g + 1];
+      s2 += p[3 * g + 2];
+    }
+    stats[c * 4 + 0] = m;
+    stats[c * 4 + 1] = s1;
+    stats[c * 4 + 2] = s2;
+    stats[c * 4 + 3] = 0.0;
+    return;
+  }
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  double acc = 0.0;
+  for (int g = 0; g < ngroups; ++g) acc += part_band[((size_t)c * ngroups + g) * nf + f];
+  power_band[c * nf + f] = acc;
+}
+
 }  // namespace
 
 // M = R x C per transform length (R <= C <= 64: register transforms of at most 64 points; float64 keeps to 32)
@@ -571,13 +769,35 @@ static int stft_twiddles(int64_t M, const cplx<T>** out) {
 
 static thread_local int32_t g_last_ngroups = 0;  // segment groups per record of this thread's last launch (Welch partials)
 
+// segments per workgroup of a forward launch: two workgroups per CU
+static int stft_launch_group(int64_t M, int lr, int lc, size_t esz) {
+  size_t budget = 80 * 1024;
+  if (const char* e = tune_env("QI_STFT_LDS_KB")) budget = (size_t)atoi(e) * 1024;
+  return stft_fused_group(M, lr, lc, esz, budget);
+}
+
+int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg) {
+  int lr, lc;
+  const int64_t M = nfft / 2;
+  if (!(dtype == QI_F64 ? stft_shape<double>(M, &lr, &lc) : stft_shape<float>(M, &lr, &lc))) return 0;
+  const int G = stft_launch_group(M, lr, lc, dtype == QI_F64 ? sizeof(double2) : sizeof(float2));
+  return G < 1 ? 0 : ceil_div(nseg, G);
+}
+
+template <typename T, int LR, int LC, bool PLAIN, bool WZ, bool WB>
+static int launch_stft_red(const T* sig, const T* win, const cplx<T>* twg, cplx<T>* Z, T* bits, const StftFusedArgs& a, dim3 grid,
+                           size_t lds, hipStream_t st) {
+  QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(&k_stft_fused<T, LR, LC, PLAIN, true, WZ, WB>), lds));
+  k_stft_fused<T, LR, LC, PLAIN, true, WZ, WB><<<grid, kStftThreads, lds, st>>>(sig, win, twg, Z, bits, a);
+  QI_LAUNCH_CHECK();
+  return QI_OK;
+}
+
 template <typename T, int LR, int LC>
 static int launch_stft_shape(const T* sig, const T* win, cplx<T>* Z, T* bits, int64_t C, int64_t nseg, StftFusedArgs a,
-                             hipStream_t st) {
+                             hipStream_t st, const StftReduce* red) {
   const int64_t M = 1ll << (LR + LC);
-  size_t budget = 80 * 1024;  // two workgroups per CU
-  if (const char* e = tune_env("QI_STFT_LDS_KB")) budget = (size_t)atoi(e) * 1024;
-  const int G = stft_fused_group(M, LR, LC, sizeof(cplx<T>), budget);
+  const int G = stft_launch_group(M, LR, LC, sizeof(cplx<T>));
   if (G < 1) {
     set_error("fused STFT: a transform of %lld points does not fit the LDS tile", (long long)(2 * M));
     return QI_ERR_UNSUPPORTED;
@@ -586,19 +806,36 @@ static int launch_stft_shape(const T* sig, const T* win, cplx<T>* Z, T* bits, in
   a.log2g = 0;
   while ((1 << a.log2g) < G) ++a.log2g;
   const size_t tile = ((size_t)1 << LR) * (((size_t)1 << LC) + 1) + 1;
-  const size_t lds = ((size_t)G * tile + M + 1) * sizeof(cplx<T>);
+  size_t lds = ((size_t)G * tile + M + 1) * sizeof(cplx<T>);
   const cplx<T>* twg = nullptr;
   QI_TRY(stft_twiddles<T>(M, &twg));
-  // the product's own call (styx_fft: zeros beyond the record, both panels, log2 bits) runs the specialised loops
-  const bool plain = Z && bits && !a.welch_part && a.pad_mode == 0 && a.real_kind == 0 && a.roll == 0;
-  const void* fn = plain ? reinterpret_cast<const void*>(&k_stft_fused<T, LR, LC, true>)
-                         : reinterpret_cast<const void*>(&k_stft_fused<T, LR, LC, false>);
-  QI_TRY(allow_dynamic_lds(fn, lds));
   a.ngroups = (int32_t)ceil_div(nseg, G);
   g_last_ngroups = a.ngroups;
   a.nitems = (int64_t)a.ngroups * C;
   a.per_xcd = (int32_t)ceil_div(a.nitems, 8);
   dim3 grid((unsigned)(8 * a.per_xcd));
+  if (red) {
+    // both panels or none: the PLAIN walk (its coefficients and bits are qi_stft's); one panel: the general walk
+    if (lds < kStftRedLds) lds = kStftRedLds;
+    a.red_band = red->part_band;
+    a.red_stat = red->part_stat;
+    a.power_time = red->power_time;
+    a.power_scale = red->power_scale;
+    if (Z && bits) QI_TRY((launch_stft_red<T, LR, LC, true, true, true>(sig, win, twg, Z, bits, a, grid, lds, st)));
+    else if (Z) QI_TRY((launch_stft_red<T, LR, LC, false, true, false>(sig, win, twg, Z, bits, a, grid, lds, st)));
+    else if (bits) QI_TRY((launch_stft_red<T, LR, LC, false, false, true>(sig, win, twg, Z, bits, a, grid, lds, st)));
+    else QI_TRY((launch_stft_red<T, LR, LC, true, false, false>(sig, win, twg, Z, bits, a, grid, lds, st)));
+    const int nf = (int)(M + 1);
+    dim3 gr((unsigned)(ceil_div(nf, 256) + 1), (unsigned)C);
+    k_stft_reduce<<<gr, 256, 0, st>>>(red->part_band, red->part_stat, red->power_band, red->stats, a.ngroups, nf);
+    QI_LAUNCH_CHECK();
+    return QI_OK;
+  }
+  // the product's own call (styx_fft: zeros beyond the record, both panels, log2 bits) runs the specialised loops
+  const bool plain = Z && bits && !a.welch_part && a.pad_mode == 0 && a.real_kind == 0 && a.roll == 0;
+  const void* fn = plain ? reinterpret_cast<const void*>(&k_stft_fused<T, LR, LC, true>)
+                         : reinterpret_cast<const void*>(&k_stft_fused<T, LR, LC, false>);
+  QI_TRY(allow_dynamic_lds(fn, lds));
   if (plain)
     k_stft_fused<T, LR, LC, true><<<grid, kStftThreads, lds, st>>>(sig, win, twg, Z, bits, a);
   else
@@ -610,8 +847,11 @@ static int launch_stft_shape(const T* sig, const T* win, cplx<T>* Z, T* bits, in
 template <typename T>
 int launch_stft_fused(const T* sig, const T* win, cplx<T>* Z, T* bits, int64_t C, int64_t n, int64_t seg, int64_t hop,
                       int64_t nfft, int64_t nseg, int64_t lead, double scale, double eps, hipStream_t st,
-                      double* welch_part, const StftSliding* sl) {
+                      double* welch_part, const StftSliding* sl, const StftReduce* red) {
   StftFusedArgs a;
+  a.red_band = a.red_stat = nullptr;
+  a.power_time = nullptr;
+  a.power_scale = 1.0;
   a.welch_part = welch_part;
   a.pad_mode = sl ? sl->pad_mode : 0;
   a.detrend = sl ? sl->detrend : 1;
@@ -635,14 +875,14 @@ int launch_stft_fused(const T* sig, const T* win, cplx<T>* Z, T* bits, int64_t C
     return QI_ERR_UNSUPPORTED;
   }
   switch (lr * 8 + lc) {  // M = 32 ... 2048 (float64: ... 1024)
-    case 2 * 8 + 3: return launch_stft_shape<T, 2, 3>(sig, win, Z, bits, C, nseg, a, st);
-    case 3 * 8 + 3: return launch_stft_shape<T, 3, 3>(sig, win, Z, bits, C, nseg, a, st);
-    case 3 * 8 + 4: return launch_stft_shape<T, 3, 4>(sig, win, Z, bits, C, nseg, a, st);
-    case 4 * 8 + 4: return launch_stft_shape<T, 4, 4>(sig, win, Z, bits, C, nseg, a, st);
-    case 4 * 8 + 5: return launch_stft_shape<T, 4, 5>(sig, win, Z, bits, C, nseg, a, st);
-    case 5 * 8 + 5: return launch_stft_shape<T, 5, 5>(sig, win, Z, bits, C, nseg, a, st);
+    case 2 * 8 + 3: return launch_stft_shape<T, 2, 3>(sig, win, Z, bits, C, nseg, a, st, red);
+    case 3 * 8 + 3: return launch_stft_shape<T, 3, 3>(sig, win, Z, bits, C, nseg, a, st, red);
+    case 3 * 8 + 4: return launch_stft_shape<T, 3, 4>(sig, win, Z, bits, C, nseg, a, st, red);
+    case 4 * 8 + 4: return launch_stft_shape<T, 4, 4>(sig, win, Z, bits, C, nseg, a, st, red);
+    case 4 * 8 + 5: return launch_stft_shape<T, 4, 5>(sig, win, Z, bits, C, nseg, a, st, red);
+    case 5 * 8 + 5: return launch_stft_shape<T, 5, 5>(sig, win, Z, bits, C, nseg, a, st, red);
     case 5 * 8 + 6:
-      if constexpr (sizeof(T) == 4) return launch_stft_shape<T, 5, 6>(sig, win, Z, bits, C, nseg, a, st);
+      if constexpr (sizeof(T) == 4) return launch_stft_shape<T, 5, 6>(sig, win, Z, bits, C, nseg, a, st, red);
       break;
     default: break;
   }
@@ -651,16 +891,18 @@ int launch_stft_fused(const T* sig, const T* win, cplx<T>* Z, T* bits, int64_t C
 }
 
 template int launch_stft_fused<float>(const float*, const float*, float2*, float*, int64_t, int64_t, int64_t, int64_t,
-                                      int64_t, int64_t, int64_t, double, double, hipStream_t, double*, const StftSliding*);
+                                      int64_t, int64_t, int64_t, double, double, hipStream_t, double*, const StftSliding*,
+                                      const StftReduce*);
 template int launch_stft_fused<double>(const double*, const double*, double2*, double*, int64_t, int64_t, int64_t, int64_t,
-                                       int64_t, int64_t, int64_t, double, double, hipStream_t, double*, const StftSliding*);
+                                       int64_t, int64_t, int64_t, double, double, hipStream_t, double*, const StftSliding*,
+                                       const StftReduce*);
 
 // Welch power spectrum on the fused kernel: partial sums per segment group in `part` ([C][groups][nfft / 2 + 1] doubles,
 // groups <= nseg), then the mean over the segments with scipy's one-sided "spectrum" weights
 template <typename T>
 int launch_welch_fused(const T* sig, const T* win, T* pxx, double* part, int64_t C, int64_t n, int64_t seg, int64_t hop,
                        int64_t nfft, int64_t nseg, double scale2, hipStream_t st) {
-  QI_TRY(launch_stft_fused<T>(sig, win, nullptr, nullptr, C, n, seg, hop, nfft, nseg, 0, 1.0, 0.0, st, part, nullptr));
+  QI_TRY(launch_stft_fused<T>(sig, win, nullptr, nullptr, C, n, seg, hop, nfft, nseg, 0, 1.0, 0.0, st, part, nullptr, nullptr));
   const int nf = (int)(nfft / 2 + 1);
   dim3 g((unsigned)ceil_div(nf, 256), (unsigned)C);
   k_welch_reduce<T><<<g, 256, 0, st>>>(part, pxx, g_last_ngroups, nseg, nf, (T)scale2);

@@ -123,6 +123,32 @@ class TfrResult:
         return b - b.max(dim=1, keepdim=True).values
 
 
+def reduced_views(n_ch, n_b, n, rdtype, device, reductions=True, reduced_out=None):
+    """(reduced, power_band [C, B] f64, power_time [C, n], stats [C, 4] f64) of one transform: views into ONE float64 buffer
+    for the whole reduced product (the message of dist.gather_reduced; layout dist.reduced_slots), new or the caller's
+    `reduced_out` (e.g. a slice of one buffer for several transforms).  reductions="band": band powers and statistics only,
+    no per-time marginal -- the kernels then write (and the tails read) no per-time planes at all, what a streaming job that
+    keeps no per-time power asks for (stream.py); that form has no gather layout (reduced is None)."""
+    from .dist import reduced_slots
+
+    if reductions == "band":
+        if reduced_out is not None:
+            raise ValueError('reductions="band" has no gather layout: reduced_out does not apply')
+        small = torch.empty(n_ch * (n_b + 4), dtype=torch.float64, device=device)
+        return None, small[: n_ch * n_b].view(n_ch, n_b), None, small[n_ch * n_b :].view(n_ch, 4)
+    slots = reduced_slots(n_ch, n_b, n, rdtype)
+    if reduced_out is not None:
+        if reduced_out.dtype != torch.float64 or reduced_out.numel() != slots or not reduced_out.is_contiguous():
+            raise ValueError(f"reduced_out must be a contiguous float64 tensor of {slots} elements")
+        reduced = reduced_out
+    else:
+        reduced = torch.empty(slots, dtype=torch.float64, device=device)
+    o1 = reduced.numel() - n_ch * (n_b + 4)
+    o2 = o1 + n_ch * n_b
+    return (reduced, reduced[o1:o2].view(n_ch, n_b), reduced[:o1].view(rdtype)[: n_ch * n].view(n_ch, n),
+            reduced[o2:].view(n_ch, 4))
+
+
 def styx_bank_tables(order, n, fs, dictionary_type="norm"):
     """Host float64 tables of the styx_cwt Gabor bank (styx_cwt.py:29-40,68-144):
     returns (f_hz, p_re, p_im, omega, amp, scale)."""
@@ -281,32 +307,8 @@ class TfrPlan:
             if bits:
                 res.bits = torch.empty((n_ch, n_b, self.n), dtype=self.rdtype, device=dev)
             if reductions:
-                # one buffer for the whole reduced product (the message of dist.gather_reduced); the three outputs
-                # are views into it
-                from .dist import reduced_slots
-
-                slots = reduced_slots(n_ch, n_b, self.n, self.rdtype)
-                if reductions == "band":
-                    # band powers and statistics only, no per-time marginal: the kernels then write (and the tail reads) no
-                    # per-time planes at all -- what a streaming job that keeps no per-time power asks for (stream.py)
-                    if reduced_out is not None:
-                        raise ValueError('reductions="band" has no gather layout: reduced_out does not apply')
-                    small = torch.empty(n_ch * (n_b + 4), dtype=torch.float64, device=dev)
-                    res.power_band = small[: n_ch * n_b].view(n_ch, n_b)
-                    res.stats = small[n_ch * n_b :].view(n_ch, 4)
-                    slots = None
-                elif reduced_out is not None:  # caller-provided slice (e.g. of one buffer for several transforms)
-                    if reduced_out.dtype != torch.float64 or reduced_out.numel() != slots or not reduced_out.is_contiguous():
-                        raise ValueError(f"reduced_out must be a contiguous float64 tensor of {slots} elements")
-                    res.reduced = reduced_out
-                else:
-                    res.reduced = torch.empty(slots, dtype=torch.float64, device=dev)
-                if slots is not None:
-                    o1 = res.reduced.numel() - n_ch * (n_b + 4)
-                    o2 = o1 + n_ch * n_b
-                    res.power_time = res.reduced[:o1].view(self.rdtype)[: n_ch * self.n].view(n_ch, self.n)
-                    res.power_band = res.reduced[o1:o2].view(n_ch, n_b)
-                    res.stats = res.reduced[o2:].view(n_ch, 4)
+                res.reduced, res.power_band, res.power_time, res.stats = reduced_views(
+                    n_ch, n_b, self.n, self.rdtype, dev, reductions, reduced_out)
         desc = _lib.TfrOut(
             coef=_lib.ptr(res.coef),
             bits=_lib.ptr(res.bits),

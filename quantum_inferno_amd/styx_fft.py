@@ -46,7 +46,41 @@ def stft_segment_points(frequency_sample_rate_hz, band_order_nth, center_frequen
     return 2 ** get_num_points(frequency_sample_rate_hz, duration_s, "ceil", "log2")
 
 
-def _stft_windowed(sig_wf, fs, window64, segment_points, overlap_points, nfft_points, extra_scale=1.0, want_bits=False):
+def _stft_out(lib, sig, window, seg, hop, nfft, scale, res, scratch=None):
+    """qi_stft_out on a [C, n] device tensor into the buffers of `res` (a TfrResult: any of coef, bits, the reductions);
+    `scratch`: a kept buffer of qi_stft_out_scratch_bytes for this request, or None."""
+    n_ch, n = sig.shape
+    dev = sig.device
+    code = _lib.QI_F64 if sig.dtype == torch.float64 else _lib.QI_F32
+    nbytes = int(lib.qi_stft_out_scratch_bytes(code, n_ch, n, seg, hop, nfft, res.coef is not None, res.bits is not None))
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    desc = _lib.TfrOut(coef=_lib.ptr(res.coef), bits=_lib.ptr(res.bits), power_band=_lib.ptr(res.power_band),
+                       power_time=_lib.ptr(res.power_time), stats=_lib.ptr(res.stats), power_scale=float(res.power_scale),
+                       eps=float(get_epsilon()))
+    with torch.cuda.device(dev):
+        _lib.check(lib.qi_stft_out(code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(window), seg, hop, nfft, scale,
+                                   C.byref(desc), _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(dev)))
+    return res
+
+
+def _stft_result(frequency_hz, n_ch, n_f, n_seg, rdtype, dev, coef, bits, reductions, power_scale, reduced_out=None):
+    """New output buffers of one qi_stft_out request; the reductions as TfrPlan lays them out (engine.reduced_views)."""
+    res = engine.TfrResult(frequency_hz=frequency_hz, power_scale=power_scale)
+    if coef:
+        res.coef = torch.empty((n_ch, n_f, n_seg), dtype=engine._complex_of(rdtype), device=dev)
+    if bits:
+        res.bits = torch.empty((n_ch, n_f, n_seg), dtype=rdtype, device=dev)
+    if reductions:
+        res.reduced, res.power_band, res.power_time, res.stats = engine.reduced_views(
+            n_ch, n_f, n_seg, rdtype, dev, reductions, reduced_out)
+    return res
+
+
+def _stft_windowed(sig_wf, fs, window64, segment_points, overlap_points, nfft_points, extra_scale=1.0, want_bits=False,
+                   _reduce=None):
+    """_reduce: None, or the options of a reduced product -- dict(coef=True, bits=want_bits, reductions=True,
+    power_scale=1.0) -- and the return value is then (frequency_hz, time_s, TfrResult) with device tensors [C, ...]."""
     lib = _lib.require_gpu()
     sig, was_numpy, was_1d = engine.as_signal(sig_wf)
     n_ch, n = sig.shape
@@ -64,6 +98,14 @@ def _stft_windowed(sig_wf, fs, window64, segment_points, overlap_points, nfft_po
     win_d = torch.from_numpy(np.ascontiguousarray(win)).to(dev)
     n_seg = int(lib.qi_stft_segments(n, seg, hop))
     n_f = nfft // 2 + 1
+    padded = n + 2 * (seg // 2)
+    padded += (-(padded - seg) % hop) % seg
+    time_s = np.arange(seg / 2, padded - seg / 2 + 1, hop) / float(fs) - (seg / 2) / fs
+    freq_hz = np.fft.rfftfreq(nfft, 1 / fs)
+    if _reduce is not None:
+        res = _stft_result(freq_hz, n_ch, n_f, n_seg, sig.dtype, dev, _reduce.get("coef", True), _reduce.get("bits", want_bits),
+                           _reduce.get("reductions", True), _reduce.get("power_scale", 1.0))
+        return freq_hz, time_s, _stft_out(lib, sig, win_d, seg, hop, nfft, scale, res)
     cdt = torch.complex128 if f64 else torch.complex64
     z = torch.empty((n_ch, n_f, n_seg), dtype=cdt, device=dev)
     bits = torch.empty((n_ch, n_f, n_seg), dtype=sig.dtype, device=dev) if want_bits else None
@@ -75,10 +117,6 @@ def _stft_windowed(sig_wf, fs, window64, segment_points, overlap_points, nfft_po
             lib.qi_stft(code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale, _lib.ptr(z),
                         _lib.ptr(bits), float(get_epsilon()), _lib.ptr(scratch), scratch_bytes, _lib.stream_ptr(dev))
         )
-    padded = n + 2 * (seg // 2)
-    padded += (-(padded - seg) % hop) % seg
-    time_s = np.arange(seg / 2, padded - seg / 2 + 1, hop) / float(fs) - (seg / 2) / fs
-    freq_hz = np.fft.rfftfreq(nfft, 1 / fs)
     return freq_hz, time_s, engine.finish(z, was_numpy, was_1d), engine.finish(bits, was_numpy, was_1d)
 
 
@@ -126,6 +164,7 @@ class StftPlan:
         padded += (-(padded - self.seg) % self.hop) % self.seg
         self.time_s = np.arange(self.seg / 2, padded - self.seg / 2 + 1, self.hop) / float(self.fs) - (self.seg / 2) / self.fs
         self.frequency_hz = np.fft.rfftfreq(self.nfft, 1 / self.fs)
+        self._reduced, self._out_scratch = {}, None  # buffers of `reduce`, made on its first call
 
     @property
     def points(self):
@@ -143,6 +182,31 @@ class StftPlan:
                                   _lib.stream_ptr(self.device))
             )
         return self.z, self.bits
+
+    def reduce(self, sig, coef=False, bits=False, reductions=True, power_scale=1.0, reduced_out=None):
+        """The reduced product of the transform -- power_band [C, n_f] and stats [C, 4] float64, power_time [C, n_seg]
+        (reductions="band": without it) of P = power_scale |Z|^2 -- from the kernel that forms the coefficients, with the
+        panels (`coef`, `bits`: the buffers `run` fills) stored only when asked for (qi_stft_out).  The three reductions are
+        views into one dist.reduced_slots(C, n_f, n_seg) buffer, as TfrPlan's are, kept between calls like the plan's other
+        buffers (or `reduced_out`)."""
+        if sig.shape != (self.channels, self.n) or sig.dtype != self.rdtype or not sig.is_cuda:
+            raise ValueError(f"signal must be a [{self.channels}, {self.n}] {self.rdtype} CUDA tensor")
+        res = engine.TfrResult(frequency_hz=self.frequency_hz, power_scale=power_scale, coef=self.z if coef else None,
+                               bits=self.bits if bits else None)
+        if reductions:
+            key = "band" if reductions == "band" else "all"
+            views = None if reduced_out is not None else self._reduced.get(key)
+            if views is None:
+                views = engine.reduced_views(self.channels, self.n_f, self.n_seg, self.rdtype, self.device, reductions, reduced_out)
+                if reduced_out is None:
+                    self._reduced[key] = views
+            res.reduced, res.power_band, res.power_time, res.stats = views
+        if self._out_scratch is None:  # one scratch for `run` and every form of `reduce` (the form without a panel asks for most)
+            nbytes = int(self._lib.qi_stft_out_scratch_bytes(self.code, self.channels, self.n, self.seg, self.hop, self.nfft, 0, 0))
+            if nbytes > self.scratch.numel():
+                self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._out_scratch = self.scratch
+        return _stft_out(self._lib, sig, self.window, self.seg, self.hop, self.nfft, self.scale, res, self._out_scratch)
 
 
 def stft_complex_pow2(
@@ -206,6 +270,31 @@ def stft_from_sig(
         want_bits=True,
     )
     return z, bits, t, f
+
+
+def stft_reductions_from_sig(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    band_order_nth: float,
+    center_frequency_hz: float = None,
+    octaves_below_center: int = 4,
+    power_scale: float = 1.0,
+):
+    """The reduced product of stft_from_sig's panel (same segments, window and scale) without the panel: the marginals
+    and entropy sums of P = power_scale |stft_complex|^2 (tfr_info.py:82-94,203-236) from the transform kernel itself.
+    sig_wf: [n] or [C, n], NumPy or CUDA tensor.
+    :return: TfrResult (device tensors power_band [C, n_f], power_time [C, n_seg], stats [C, 4]), time_stft_s,
+        frequency_stft_hz"""
+    seg = stft_segment_points(frequency_sample_rate_hz, band_order_nth, center_frequency_hz, octaves_below_center)
+    n = sig_wf.shape[-1] if hasattr(sig_wf, "shape") else len(sig_wf)
+    if n < seg:
+        raise ValueError(f"Signal length: {n} is less than time_fft_nd: {seg}")
+    window = tukey_window_periodic(seg, 1.0)
+    f, t, res = _stft_windowed(
+        sig_wf, frequency_sample_rate_hz, window, seg, seg // 2, seg, extra_scale=2 * np.sqrt(np.pi) / seg,
+        _reduce=dict(coef=False, bits=False, power_scale=power_scale),
+    )
+    return res, t, f
 
 
 def welch_power_pow2(
