@@ -344,6 +344,31 @@ int qi_stft_out(int dtype, int device, const void* sig, int64_t n_channels, int6
                 int64_t hop, int64_t nfft, double scale, const qi_tfr_out* out, void* scratch, int64_t scratch_bytes,
                 qi_stream stream);
 
+/* ---- zero-phase IIR filtering (styx_fft.py:60-149 butter_bandpass / butter_highpass / butter_lowpass: scipy.signal.filtfilt;
+ * utilities/picker.py:56-76 apply_bandpass: scipy.signal.sosfiltfilt) ----------------------------------------------------
+ * Per record: x[k] <- x[k] * taper[k] when a taper is given (the product formed in float64 and rounded to the record's
+ * type); the odd extension [2 x[0] - x[edge] .. 2 x[0] - x[1], x, 2 x[n-1] - x[n-2] .. 2 x[n-1] - x[n-1-edge]] in the
+ * record's type; then in float64 the recurrence over the extension from the state zi * ext[0], the recurrence over the
+ * reversed result from the state zi * (its last value), and out[k] = the second pass's value at extended position edge + k.
+ *   QI_IIR_BA  (N = order):  y = b0 x + z0;  z_i = (b_{i+1} x + z_{i+1}) - a_{i+1} y  (i < N - 1);  z_{N-1} = b_N x - a_N y
+ *   QI_IIR_SOS (per sample through the sections in order):  xn = b0 xc + z0;  z0 = (b1 xc - a1 xn) + z1;  z1 = b2 xc - a2 xn;  xc = xn
+ * Every product and sum is rounded on its own (no fused multiply-add), in this order: scipy.signal.lfilter's / sosfilt's,
+ * so a float64 result is SciPy's bit for bit for the same tables.
+ * sig [C][n] in dtype (device), any n > edge >= 0; taper [n] float64 (device) or NULL; out [C][n] float64 whatever the
+ * dtype (the reference returns float64 for float32 records too).  coef, zi: HOST float64 --
+ *   QI_IIR_BA:  coef [2][order + 1] = b then a, zi [order] (scipy.signal.lfilter_zi); sections = 1, 1 <= order <= 16
+ *   QI_IIR_SOS: coef [sections][6] = b0 b1 b2 a0 a1 a2, zi [sections][2] (sosfilt_zi); order = 2, 1 <= sections <= 16
+ * with a0 = 1 in every section (QI_ERR_ARG otherwise).  edge: samples of extension at each end (filtfilt's padlen:
+ * 3 max(len(a), len(b)); sosfiltfilt's: 3 (2 sections + 1 - min(#(b2 == 0), #(a2 == 0)))).
+ * scratch: caller-owned device buffer of qi_filtfilt_scratch_bytes() (the forward pass's n + 2 edge values per record),
+ * aligned to 8 bytes.  Two kernel launches (forward, backward), no atomics; the same call gives the same bits.  One lane
+ * per record: a call of fewer than 64 records takes as long as one of 64 (a record is sequential in time). */
+typedef enum { QI_IIR_BA = 0, QI_IIR_SOS = 1 } qi_iir_form;
+int64_t qi_filtfilt_scratch_bytes(int64_t n_channels, int64_t n, int64_t edge);
+int qi_filtfilt(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, const void* taper, int form,
+                int32_t sections, int32_t order, const double* coef, const double* zi, int64_t edge, void* out,
+                void* scratch, int64_t scratch_bytes, qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ STAGES = ("forward", "multiply", "inverse", "epilogue", "pass1", "pass2", "block
 # qi_band_route.flags (QI_ROUTE_* of include/qi_tfr.h)
 QI_POOL_NTH, QI_POOL_AVERAGE, QI_POOL_MAX, QI_POOL_MIN, QI_POOL_MEDIAN = 0, 1, 2, 3, 4
 QI_POOL_REAL, QI_POOL_COMPLEX, QI_POOL_POWER = 0, 1, 2
+QI_IIR_BA, QI_IIR_SOS = 0, 1
+IIR_MAX = 16  # largest order of the (b, a) form, most second-order sections (qi_filtfilt)
 POOL_MEDIAN_MAX = 4096  # longest window the median sorts (qi_pool_panel)
 ROUTE_NOWRAP, ROUTE_SPLIT, ROUTE_BEHIND, ROUTE_F64_ZOOM = 16, 32, 256, 512
 
@@ -111,6 +113,8 @@ PROTOTYPES = {
     "qi_pool_panel": (_int, [_int, _int, _P, _int, _i64, _i64, _i64, _int, _dbl, _P, _P]),
     "qi_pool_strip": (_int, [_int, _int, _P, _i64, _i64, _i64, _i64, _i64, _dbl, _P, _P, _i64, _P, _P]),
     "qi_pool_strip_stats": (_int, [_int, _P, _i64, _i64, _P, _P]),
+    "qi_filtfilt_scratch_bytes": (_i64, [_i64, _i64, _i64]),
+    "qi_filtfilt": (_int, [_int, _int, _P, _i64, _i64, _P, _int, _i32, _i32, _D, _D, _i64, _P, _P, _i64, _P]),
 }
 
 _lib = None

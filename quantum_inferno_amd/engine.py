@@ -583,6 +583,69 @@ def gabor_atoms(n, p_re, p_im, omega, amp, device=None, x=None):
     return out
 
 
+_IIR_FORMS = {"ba": _lib.QI_IIR_BA, "sos": _lib.QI_IIR_SOS, _lib.QI_IIR_BA: _lib.QI_IIR_BA, _lib.QI_IIR_SOS: _lib.QI_IIR_SOS}
+
+
+def zero_phase_filter(sig, form, coef, zi, edge, taper=None):
+    """Zero-phase IIR filter of records [n] or [C, n] (qi_filtfilt): scipy.signal.filtfilt's / sosfiltfilt's result for
+    the same tables, float64 whatever the records' type.  form "ba": coef [2, order + 1] = (b, a) with a[0] = 1, zi [order]
+    (iir_design.lfilter_zi), order <= 16; form "sos": coef [sections, 6], zi [sections, 2] (iir_design.sosfilt_zi), at most
+    16 sections.  edge: samples of odd extension at each end (iir_design.filtfilt_edge / sosfiltfilt_edge); a record must
+    be longer.  taper: [n] float64 multiplied into every record first (NumPy or a tensor), or None.  NumPy in -> NumPy
+    out, CUDA tensor in -> CUDA tensor out on the current stream, nothing synchronised.  One lane per record: fewer than
+    64 records take as long as 64."""
+    if form not in _IIR_FORMS:
+        raise ValueError(f'form must be "ba" or "sos", got {form!r}')
+    code = _IIR_FORMS[form]
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    zi = np.ascontiguousarray(zi, dtype=np.float64)
+    if code == _lib.QI_IIR_BA:
+        if coef.ndim != 2 or coef.shape[0] != 2 or not 2 <= coef.shape[1] <= _lib.IIR_MAX + 1:
+            raise ValueError(f"coef must be [2, order + 1] with order 1 .. {_lib.IIR_MAX}, got shape {coef.shape}")
+        sections, order = 1, coef.shape[1] - 1
+        if zi.shape != (order,):
+            raise ValueError(f"zi must hold {order} values, got shape {zi.shape}")
+        if coef[1, 0] != 1.0:
+            raise ValueError("a[0] must be 1: normalise the coefficients")
+    else:
+        if coef.ndim != 2 or coef.shape[1] != 6 or not 1 <= coef.shape[0] <= _lib.IIR_MAX:
+            raise ValueError(f"coef must be [sections, 6] with 1 .. {_lib.IIR_MAX} sections, got shape {coef.shape}")
+        sections, order = coef.shape[0], 2
+        if zi.shape != (sections, 2):
+            raise ValueError(f"zi must be [{sections}, 2], got shape {zi.shape}")
+        if not (coef[:, 3] == 1.0).all():
+            raise ValueError("sos[:, 3] should be all ones")
+    edge = int(edge)
+    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"signal must be 1-D [n] or 2-D [channels, n], got shape {shape}")
+    n = shape[-1]
+    if edge < 0 or n <= edge:
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
+    if taper is not None and tuple(taper.shape) != (n,):
+        raise ValueError(f"taper must hold {n} values, got shape {tuple(taper.shape)}")
+    lib = _lib.require_gpu()
+    x, was_numpy, was_1d = as_signal(sig)
+    dev = x.device
+    n_ch = x.shape[0]
+    out = torch.empty((n_ch, n), dtype=torch.float64, device=dev)
+    if n_ch == 0:
+        return finish(out, was_numpy, was_1d)
+    if taper is not None:
+        if not isinstance(taper, torch.Tensor):
+            taper = torch.from_numpy(np.ascontiguousarray(taper, dtype=np.float64))
+        taper = taper.to(device=dev, dtype=torch.float64).contiguous()
+    nbytes = int(lib.qi_filtfilt_scratch_bytes(n_ch, n, edge))
+    if nbytes < 0:
+        _lib.check(nbytes)
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.qi_filtfilt(_lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32, dev.index, _lib.ptr(x), n_ch, n,
+                                   _lib.ptr(taper), code, sections, order, coef.ctypes.data_as(_lib._D), zi.ctypes.data_as(_lib._D),
+                                   edge, _lib.ptr(out), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)))
+    return finish(out, was_numpy, was_1d)
+
+
 # What the reference-signature wrappers hand back to NumPy callers for float32 records.  The reference returns
 # complex128 panels (float64 bits) whatever the record's dtype (styx_cwt.py:195-198, styx_stx.py:228,
 # cwt_atoms.py:408): "reference" computes in float32 and widens on the way out, so a drop-in caller sees the

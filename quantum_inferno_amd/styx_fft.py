@@ -46,6 +46,52 @@ def stft_segment_points(frequency_sample_rate_hz, band_order_nth, center_frequen
     return 2 ** get_num_points(frequency_sample_rate_hz, duration_s, "ceil", "log2")
 
 
+def _butter_filtfilt(sig_wf, filter_order, wn, btype, tukey_alpha):
+    """Shared body of butter_bandpass / butter_highpass / butter_lowpass: signal.butter(output="ba"), the symmetric Tukey
+    taper and signal.filtfilt of the reference, on every row of sig_wf (engine.zero_phase_filter)."""
+    from .utilities import iir_design
+    from .utilities.short_time_fft import tukey_window_symmetric
+
+    if np.ndim(sig_wf) not in (1, 2):
+        raise ValueError(f"signal must be 1-D [n] or 2-D [channels, n], got shape {tuple(np.shape(sig_wf))}")
+    b, a = iir_design.butter_ba(filter_order, wn, btype)
+    edge = iir_design.filtfilt_edge(b, a)
+    n = np.shape(sig_wf)[-1]
+    iir_design.check_length(n, edge)
+    return engine.zero_phase_filter(sig_wf, "ba", np.stack([b, a]), iir_design.lfilter_zi(b, a), edge,
+                                    taper=tukey_window_symmetric(n, tukey_alpha))
+
+
+def butter_bandpass(sig_wf, frequency_sample_rate_hz: float, frequency_cut_low_hz, frequency_cut_high_hz, filter_order: int = 4,
+                    tukey_alpha: float = 0.5):
+    """Zero-phase Butterworth band-pass of a Tukey-tapered record (ref styx_fft.py:60-90); a [C, n] input filters every
+    row.  A high cut-off at or above Nyquist is replaced by half of Nyquist, with the reference's warning.
+    -> float64, NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    nyquist = 0.5 * frequency_sample_rate_hz
+    edge_low = frequency_cut_low_hz / nyquist
+    edge_high = frequency_cut_high_hz / nyquist
+    if edge_high >= 1:
+        print(f"Warning: Frequency cutoff {frequency_cut_high_hz} greater than Nyquist {nyquist} Hz, using half Nyquist")
+        edge_high = 0.5  # Half of nyquist
+    return _butter_filtfilt(sig_wf, filter_order, [edge_low, edge_high], "bandpass", tukey_alpha)
+
+
+def butter_highpass(sig_wf, frequency_sample_rate_hz: float, frequency_cut_low_hz, filter_order: int = 4, tukey_alpha: float = 0.5):
+    """Zero-phase Butterworth high-pass of a Tukey-tapered record (ref styx_fft.py:93-120); see butter_bandpass."""
+    edge_low = frequency_cut_low_hz / (0.5 * frequency_sample_rate_hz)
+    if edge_low >= 1:
+        raise ValueError(f"Frequency cutoff {frequency_cut_low_hz} is greater than Nyquist {0.5*frequency_sample_rate_hz}")
+    return _butter_filtfilt(sig_wf, filter_order, [edge_low], "highpass", tukey_alpha)
+
+
+def butter_lowpass(sig_wf, frequency_sample_rate_hz: float, frequency_cut_high_hz, filter_order: int = 4, tukey_alpha: float = 0.5):
+    """Zero-phase Butterworth low-pass of a Tukey-tapered record (ref styx_fft.py:123-149); see butter_bandpass."""
+    edge_high = frequency_cut_high_hz / (0.5 * frequency_sample_rate_hz)
+    if edge_high >= 1:
+        raise ValueError(f"Frequency cutoff {frequency_cut_high_hz} is greater than Nyquist {0.5*frequency_sample_rate_hz}")
+    return _butter_filtfilt(sig_wf, filter_order, [edge_high], "lowpass", tukey_alpha)
+
+
 def _stft_out(lib, sig, window, seg, hop, nfft, scale, res, scratch=None):
     """qi_stft_out on a [C, n] device tensor into the buffers of `res` (a TfrResult: any of coef, bits, the reductions);
     `scratch`: a kept buffer of qi_stft_out_scratch_bytes for this request, or None."""
