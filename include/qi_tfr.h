@@ -369,6 +369,25 @@ int qi_filtfilt(int dtype, int device, const void* sig, int64_t n_channels, int6
                 int32_t sections, int32_t order, const double* coef, const double* zi, int64_t edge, void* out,
                 void* scratch, int64_t scratch_bytes, qi_stream stream);
 
+/* ---- zero-phase decimation (utilities/sampling.py:123-146 decimate_timeseries / decimate_timeseries_collection:
+ * scipy.signal.decimate(x, q, zero_phase=True) = sosfiltfilt with the order-8 Chebyshev type I sections, then every q-th sample) ----
+ * Per record, ALL in the record's type T (SciPy casts the sections to it; no float64 intermediate for a float32 record):
+ * the odd extension by `edge` samples, the QI_IIR_SOS recurrence above over the extension from the state zi * ext[0], the
+ * same over the reversed result from the state zi * (its last value), every product and sum rounded on its own in T; then
+ * out[c] = the second pass's value at extended position edge + c q, c = 0 .. qi_decimate_columns(n, q) - 1.  For the same
+ * tables the result is SciPy's bit for bit in float32 and in float64; in float64 it is qi_filtfilt's every q-th sample.
+ * sig [C][n] in dtype (device), any n > edge >= 0, any q >= 1; out [C][ceil(n / q)] in dtype (device).  sos [sections][6]
+ * = b0 b1 b2 a0 a1 a2 with a0 = 1, zi [sections][2]: HOST arrays in dtype (float for QI_F32, double for QI_F64),
+ * 1 <= sections <= 16.  scratch: caller-owned device buffer of qi_decimate_scratch_bytes() (the forward pass's
+ * n + 2 edge values per record in dtype: QI_F32 needs half of QI_F64); sig, out and scratch aligned to the size of dtype.
+ * Two kernel launches, no atomics; the backward pass stores only the kept samples, adjacent lanes adjacent columns.
+ * qi_decimate_columns: ceil(n / q), negative qi_status for n < 1 or q < 1.  Both size queries are host only. */
+int64_t qi_decimate_columns(int64_t n, int64_t q);
+int64_t qi_decimate_scratch_bytes(int dtype, int64_t n_channels, int64_t n, int64_t edge);
+int qi_decimate(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, int64_t q, int32_t sections,
+                const void* sos, const void* zi, int64_t edge, void* out, void* scratch, int64_t scratch_bytes,
+                qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

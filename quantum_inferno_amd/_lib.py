@@ -115,6 +115,9 @@ PROTOTYPES = {
     "qi_pool_strip_stats": (_int, [_int, _P, _i64, _i64, _P, _P]),
     "qi_filtfilt_scratch_bytes": (_i64, [_i64, _i64, _i64]),
     "qi_filtfilt": (_int, [_int, _int, _P, _i64, _i64, _P, _int, _i32, _i32, _D, _D, _i64, _P, _P, _i64, _P]),
+    "qi_decimate_columns": (_i64, [_i64, _i64]),
+    "qi_decimate_scratch_bytes": (_i64, [_int, _i64, _i64, _i64]),
+    "qi_decimate": (_int, [_int, _int, _P, _i64, _i64, _i64, _i32, _P, _P, _i64, _P, _P, _i64, _P]),
 }
 
 _lib = None

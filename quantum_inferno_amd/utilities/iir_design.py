@@ -3,14 +3,16 @@ styx_fft.butter_* (styx_fft.py:60-149: signal.butter(output="ba") + signal.filtf
 (picker.py:56-76: butter(output="sos") + sosfiltfilt), restated operation by operation so that the tables come out as
 SciPy's bits: analog prototype, pre-warp, band transform and bilinear transform on (zeros, poles, gain), then the
 polynomial coefficients or the second-order sections in SciPy's default pairing ("nearest").  The filter itself runs on
-the device (engine.zero_phase_filter, qi_filtfilt)."""
+the device (engine.zero_phase_filter, qi_filtfilt).  The same steps from the Chebyshev type I prototype give the sections of
+scipy.signal.decimate's anti-alias filter (utilities.sampling.decimate_*: cheby1_sos, decimator; engine.zero_phase_decimate,
+qi_decimate), in float64 or cast to float32 as SciPy casts them for a float32 record."""
 import numpy as np
 
 BTYPES = ("lowpass", "highpass", "bandpass")
 
 
-def _butter_zpk(order, wn, btype):
-    """Digital Butterworth (zeros, poles, gain); wn in units of Nyquist."""
+def _check_design(order, wn, btype):
+    """-> (order, wn [1] or [2]) of a digital design request; wn in units of Nyquist."""
     if btype not in BTYPES:
         raise ValueError(f"btype must be one of {BTYPES}, got {btype!r}")
     if int(order) != order or order < 1:
@@ -23,11 +25,35 @@ def _butter_zpk(order, wn, btype):
         raise ValueError("Digital filter critical frequencies must be 0 < Wn < 1")
     if wn.size > 1 and not wn[0] < wn[1]:
         raise ValueError("Wn[0] must be less than Wn[1]")
+    return order, wn
+
+
+def _butter_zpk(order, wn, btype):
+    """Digital Butterworth (zeros, poles, gain); wn in units of Nyquist."""
+    order, wn = _check_design(order, wn, btype)
     # analog prototype: poles on the unit circle, the middle one exactly real
     m = np.arange(-order + 1, order, 2)
     p = -np.exp(1j * np.pi * m / (2 * order))
-    z = np.array([])
-    k = 1
+    return _to_digital(np.array([]), p, 1, wn, btype)
+
+
+def _cheby1_zpk(order, rp, wn, btype):
+    """Digital Chebyshev type I (zeros, poles, gain) with rp decibels of pass-band ripple; wn in units of Nyquist."""
+    order, wn = _check_design(order, wn, btype)
+    # analog prototype (scipy.signal.cheb1ap): poles on an ellipse, an even order has a DC gain of -rp dB
+    eps = np.sqrt(10 ** (0.1 * rp) - 1.0)
+    mu = 1.0 / order * np.arcsinh(1 / eps)
+    m = np.arange(-order + 1, order, 2)
+    theta = np.pi * m / (2 * order)
+    p = -np.sinh(mu + 1j * theta)
+    k = np.prod(-p, axis=0).real
+    if order % 2 == 0:
+        k = k / np.sqrt(1 + eps * eps)
+    return _to_digital(np.array([]), p, k, wn, btype)
+
+
+def _to_digital(z, p, k, wn, btype):
+    """An analog low-pass prototype (cut-off 1 rad/s) -> the digital filter of the band wn: pre-warp, band transform, bilinear."""
     fs = 2.0
     warped = 2 * fs * np.tan(np.pi * wn / fs)
     degree = len(p) - len(z)
@@ -194,6 +220,25 @@ def butter_sos(order, wn, btype):
     return _zpk2sos(*_butter_zpk(order, wn, btype))
 
 
+def cheby1_sos(order, rp, wn, btype="lowpass"):
+    """scipy.signal.cheby1(order, rp, wn, btype, output="sos"): [sections][6] = b0 b1 b2 1 a1 a2, wn in units of Nyquist."""
+    return _zpk2sos(*_cheby1_zpk(order, rp, wn, btype))
+
+
+DECIMATE_ORDER, DECIMATE_RIPPLE_DB = 8, 0.05  # scipy.signal.decimate's defaults for ftype="iir", which the reference keeps
+
+
+def decimator(q, dtype=np.float64):
+    """(sos, zi, edge) of scipy.signal.decimate(x, q, zero_phase=True) for records of `dtype` (float32 or float64): the
+    order-8 Chebyshev type I low-pass of 0.05 dB ripple at 0.8 / q of Nyquist, designed in float64 and cast to the
+    records' type as SciPy casts it; zi evaluated in that type; edge = 27 samples of extension (4 sections)."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"records are filtered in float32 or float64, got {dtype}")
+    sos = np.asarray(cheby1_sos(DECIMATE_ORDER, DECIMATE_RIPPLE_DB, 0.8 / q), dtype=dtype)
+    return sos, sosfilt_zi(sos), sosfiltfilt_edge(sos)
+
+
 def lfilter_zi(b, a):
     """Steady-state delays of the transposed direct form II for a unit step (scipy.signal.lfilter_zi)."""
     b = np.atleast_1d(b)
@@ -220,7 +265,7 @@ def lfilter_zi(b, a):
 
 
 def sosfilt_zi(sos):
-    """scipy.signal.sosfilt_zi: [sections][2]."""
+    """scipy.signal.sosfilt_zi: [sections][2], in the sections' type (float32 sections give SciPy's float32 values)."""
     sos = _validate_sos(sos)
     zi = np.empty((sos.shape[0], 2), dtype=sos.dtype)
     scale = 1.0
@@ -233,7 +278,8 @@ def sosfilt_zi(sos):
 
 
 def _validate_sos(sos):
-    sos = np.atleast_2d(np.asarray(sos, dtype=np.float64))
+    sos = np.asarray(sos)
+    sos = np.atleast_2d(sos if sos.dtype == np.float32 else sos.astype(np.float64))  # float32 sections are not widened
     if sos.ndim != 2 or sos.shape[1] != 6:
         raise ValueError("sos array must be shape (n_sections, 6)")
     if not (sos[:, 3] == 1).all():

@@ -2,14 +2,26 @@
 n-th sample, or the average / median / max / min of each window of `subsample_factor` samples.  The work is one kernel of
 the library (qi_pool_panel) on the device: NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out, float32 and float64
 (complex64 / complex128 for "nth" and "average") kept.  A leading channel axis is accepted: [C, n] records, [C, B, n]
-panels.  There is no CPU fallback.  The reference's SciPy resamplers (decimate_*, resample_*) are not part of this."""
+panels.
+
+Decimation (mirror of sampling.py:123-146, scipy.signal.decimate(x, q, zero_phase=True)): decimate_timeseries for one
+record [n], decimate_timeseries_collection for records [C, n] along axis 1.  The anti-alias filter -- order-8 Chebyshev
+type I, 0.05 dB ripple, cut-off 0.8 / q of Nyquist, as second-order sections -- is designed on the host in NumPy
+(iir_design.decimator); the zero-phase filter and the every-q-th store are two launches of the library (qi_decimate), in
+the record's own precision as in SciPy: float32 records are filtered and returned in float32, float64 in float64, anything
+else (integers, float16) as float64.  A record must be 28 samples or longer.
+
+There is no CPU fallback.  The reference's FFT resamplers (resample_with_sample_rate, resample_uneven_timeseries) are
+not part of this, nor are decimate's other parameters (the reference fixes ftype, n and zero_phase)."""
+import operator
 import warnings
 from typing import Tuple
 
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, engine
+from . import iir_design
 
 SUBSAMPLE_METHODS = ["average", "median", "max", "min", "nth"]
 _METHOD_CODE = {"nth": _lib.QI_POOL_NTH, "average": _lib.QI_POOL_AVERAGE, "max": _lib.QI_POOL_MAX, "min": _lib.QI_POOL_MIN,
@@ -84,3 +96,33 @@ def subsample_2d(array, subsample_factor: int, method: str = "nth"):
     if np.ndim(array) not in (2, 3):
         raise ValueError(f"array must be [bands, n] or [channels, bands, n], got shape {tuple(np.shape(array))}")
     return _pool(array, subsample_factor, method, "array")
+
+
+def _decimate(records, decimation_factor, ndim, what):
+    """Shared body of decimate_timeseries / decimate_timeseries_collection: SciPy's argument handling, the design on the
+    host, then engine.zero_phase_decimate."""
+    q = operator.index(decimation_factor)  # TypeError for a factor that is no integer, as scipy.signal.decimate
+    if q < 1:
+        raise ValueError(f"decimation_factor must be a positive integer, got {q}")
+    shape = tuple(records.shape) if isinstance(records, torch.Tensor) else np.shape(records)
+    if len(shape) != ndim:
+        raise ValueError(f"{what} must be {ndim}-D, got shape {shape}")
+    dtype = records.dtype if isinstance(records, torch.Tensor) else np.asarray(records).dtype
+    real = np.float32 if dtype in (torch.float32, np.float32) else np.float64
+    sos, zi, edge = iir_design.decimator(q, real)
+    iir_design.check_length(shape[-1], edge)
+    return engine.zero_phase_decimate(records, q, sos, zi, edge)
+
+
+def decimate_timeseries(timeseries, decimation_factor: int):
+    """Decimate a time series [n] by the given factor as scipy.signal.decimate(timeseries, decimation_factor,
+    zero_phase=True) does (sampling.py:123-133); the time series must be 28 samples or longer.
+    -> decimated signal [ceil(n / decimation_factor)]"""
+    return _decimate(timeseries, decimation_factor, 1, "timeseries")
+
+
+def decimate_timeseries_collection(timeseries_collection, decimation_factor: int):
+    """Decimate a collection [C, n] of time series with the same sample rate at once, along axis 1 (sampling.py:136-146);
+    each must be 28 samples or longer.
+    -> decimated signals [C, ceil(n / decimation_factor)]"""
+    return _decimate(timeseries_collection, decimation_factor, 2, "timeseries_collection")
