@@ -433,8 +433,7 @@ int qi_plan_profile_read(qi_plan* p, double* stage_ms, int64_t* stage_launches, 
 
 // One table on the small-record engine; *ran = false when the workspace does not hold one record (then the hipFFT engine runs it)
 static int small_one(qi_plan* p, int kind, const void* sig, int64_t C, const qi_tfr_out* out, hipStream_t st, bool* ran) {
-  return p->d.dtype == QI_F64 ? run_small<double>(p, 1, &kind, &out, sig, C, st, ran)
-                              : run_small<float>(p, 1, &kind, &out, sig, C, st, ran);
+  return by_dtype(p->d.dtype, [&](auto t) { return run_small<decltype(t)>(p, 1, &kind, &out, sig, C, st, ran); });
 }
 
 int qi_cwt(qi_plan* p, int bank, const void* sig, int64_t C, const qi_tfr_out* out, qi_stream stream) {
@@ -449,11 +448,10 @@ int qi_cwt(qi_plan* p, int bank, const void* sig, int64_t C, const qi_tfr_out* o
     QI_TRY(small_one(p, bank, sig, C, out, (hipStream_t)stream, &ran));
     if (ran) return QI_OK;
   }
-  if (p->nat[bank].ready)
+  if (p->nat[bank].ready)  // (two engines, not one template: the float64 native run has its own launch sequence)
     return p->d.dtype == QI_F64 ? run_native64(p, bank, sig, C, out, (hipStream_t)stream)
                                 : run_native<float>(p, bank, sig, C, out, (hipStream_t)stream);
-  return p->d.dtype == QI_F64 ? run_transform<double>(p, k, sig, C, out, (hipStream_t)stream)
-                              : run_transform<float>(p, k, sig, C, out, (hipStream_t)stream);
+  return by_dtype(p->d.dtype, [&](auto t) { return run_transform<decltype(t)>(p, k, sig, C, out, (hipStream_t)stream); });
 }
 
 int qi_stx(qi_plan* p, const void* sig, int64_t C, const qi_tfr_out* out, qi_stream stream) {
@@ -467,15 +465,13 @@ int qi_stx(qi_plan* p, const void* sig, int64_t C, const qi_tfr_out* out, qi_str
     if (ran) return QI_OK;
   }
   if (p->nat[2].ready) {
-    int rc = p->d.dtype == QI_F64 ? run_native64(p, 2, sig, C, out, (hipStream_t)stream)
+    int rc = p->d.dtype == QI_F64 ? run_native64(p, 2, sig, C, out, (hipStream_t)stream)  // (two engines, as in qi_cwt)
                                   : run_native<float>(p, 2, sig, C, out, (hipStream_t)stream);
     if (rc == QI_OK && p->stx_left_n > 0)  // the rows no native engine takes at this length: the hipFFT engine's pass over them
-      rc = p->d.dtype == QI_F64 ? run_stx_leftover<double>(p, sig, C, out, (hipStream_t)stream)
-                                : run_stx_leftover<float>(p, sig, C, out, (hipStream_t)stream);
+      rc = by_dtype(p->d.dtype, [&](auto t) { return run_stx_leftover<decltype(t)>(p, sig, C, out, (hipStream_t)stream); });
     return rc;
   }
-  return p->d.dtype == QI_F64 ? run_transform<double>(p, Kind::Stockwell, sig, C, out, (hipStream_t)stream)
-                              : run_transform<float>(p, Kind::Stockwell, sig, C, out, (hipStream_t)stream);
+  return by_dtype(p->d.dtype, [&](auto t) { return run_transform<decltype(t)>(p, Kind::Stockwell, sig, C, out, (hipStream_t)stream); });
 }
 
 // the outputs of records [c0, ...) of a call whose panels have B bands
@@ -507,8 +503,7 @@ int qi_cwt_stx(qi_plan* p, int bank, const void* sig, int64_t C, const qi_tfr_ou
     const qi_tfr_out* outs[2] = {out_cwt, out_stx};
     bool ran = false;
     p->prof.unchain();
-    QI_TRY(p->d.dtype == QI_F64 ? run_small<double>(p, 2, kinds, outs, sig, C, st, &ran)
-                                : run_small<float>(p, 2, kinds, outs, sig, C, st, &ran));
+    QI_TRY(by_dtype(p->d.dtype, [&](auto t) { return run_small<decltype(t)>(p, 2, kinds, outs, sig, C, st, &ran); }));
     if (ran) return QI_OK;
   }
   if (fuse) {

@@ -9,28 +9,60 @@ extern "C" int64_t qi_stft_segments(int64_t n, int64_t seg, int64_t hop);
 
 namespace {
 
+// ---- the STFT family's two engines: the fused kernels (qi_stft_fused.hip), or frames -> hipFFT -> finish ----------------
+// the fused kernels switched off (development switch, read once per process)
+bool stft_fused_off() {
+  static const bool off = tune_env("QI_STFT_FUSED") && atoi(tune_env("QI_STFT_FUSED")) == 0;
+  return off;
+}
+
+// `fused` where the fused kernels take the geometry; when it answers QI_ERR_UNSUPPORTED (a device with less LDS per workgroup
+// than the tile needs, an inverse whose halo leaves no hop to own) and everywhere else the three-kernel sequence `hipfft`
+template <typename Fused, typename Hipfft>
+int fused_or_hipfft(bool takes, Fused&& fused, Hipfft&& hipfft) {
+  if (!stft_fused_off() && takes) {
+    const int rc = fused();
+    if (rc != QI_ERR_UNSUPPORTED) return rc;
+  }
+  return hipfft();
+}
+
+// Scratch of the three-kernel sequence: [C][rows][nfft] reals (frames, or the inverse's slices) | [C][rows][nfft / 2 + 1]
+// spectra.  The byte counts a caller is told and the pointers the sequences use both come from here.
+struct FftScratch {
+  size_t frames = 0, spectra, total;  // byte offsets of the two regions, and the size
+  FftScratch(int dtype, int64_t C, int64_t rows, int64_t nfft) {
+    const size_t e = dtype == QI_F64 ? 8 : 4;
+    spectra = align_up((size_t)C * rows * nfft * e);
+    total = spectra + align_up((size_t)C * rows * (nfft / 2 + 1) * 2 * e);
+  }
+};
+
+// a transform (fft_r2c, fft_c2r) on the plan cache the plan-less entry points share per device, under its mutex
+template <typename Transform>
+int locked_fft(int device, Transform&& transform) {
+  std::lock_guard<std::mutex> lk(g_stft_mu);
+  return transform(g_stft_fft[device]);
+}
+
+// `frames` fills the real rows, hipFFT transforms them, `finish` consumes the spectra
+template <typename T, typename Frames, typename Finish>
+int via_hipfft(int device, char* scratch, int64_t C, int64_t rows, int64_t nfft, hipStream_t st, Frames&& frames, Finish&& finish) {
+  const FftScratch l(sizeof(T) == 8 ? QI_F64 : QI_F32, C, rows, nfft);
+  T* re = reinterpret_cast<T*>(scratch + l.frames);
+  cplx<T>* F = reinterpret_cast<cplx<T>*>(scratch + l.spectra);
+  QI_TRY(frames(re));
+  QI_TRY(locked_fft(device, [&](FftCache& fc) { return fft_r2c<T>(fc, re, F, nfft, C * rows, st); }));
+  return finish(F);
+}
+
+// qi_stft / qi_stft_out on the three-kernel sequence: frames -> hipFFT -> transpose into the panels
 template <typename T>
-int stft_impl(int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop,
-                     int64_t nfft, double scale, void* Z, void* bits, double eps, char* scratch, hipStream_t st) {
-  const int64_t nseg = qi_stft_segments(n, seg, hop);
-  const int64_t nf = nfft / 2 + 1;
-  static const bool fused_off = tune_env("QI_STFT_FUSED") && atoi(tune_env("QI_STFT_FUSED")) == 0;
-  if (!fused_off && stft_fused_supported(sizeof(T) == 8 ? QI_F64 : QI_F32, seg, hop, nfft)) {  // one kernel: segments, transform and store from LDS
-    const int rc = launch_stft_fused<T>(static_cast<const T*>(sig), static_cast<const T*>(window), static_cast<cplx<T>*>(Z),
-                                        static_cast<T*>(bits), C, n, seg, hop, nfft, nseg, seg / 2, scale,
-                                        qi::host::eps_or_default(eps), st);
-    if (rc != QI_ERR_UNSUPPORTED) return rc;  // (a device with less LDS per workgroup than the tile needs: the three-kernel path below)
-  }
-  T* frames = reinterpret_cast<T*>(scratch);
-  cplx<T>* F = reinterpret_cast<cplx<T>*>(scratch + align_up((size_t)C * nseg * nfft * sizeof(T)));
-  QI_TRY(launch_stft_frames<T>(static_cast<const T*>(sig), static_cast<const T*>(window), frames, C, n, seg, hop,
-                               nfft, nseg, seg / 2, st));
-  {
-    std::lock_guard<std::mutex> lk(g_stft_mu);
-    QI_TRY(fft_r2c<T>(g_stft_fft[device], frames, F, nfft, C * nseg, st));
-  }
-  return launch_stft_transpose<T>(F, static_cast<cplx<T>*>(Z), static_cast<T*>(bits), C, nseg, nf, (T)scale,
-                                  (T)qi::host::eps_or_default(eps), st);
+int stft_hipfft(int device, const StftRequest& rq, const T* sig, const T* window, cplx<T>* Z, T* bits, char* scratch, hipStream_t st) {
+  return via_hipfft<T>(
+      device, scratch, rq.C, rq.nseg, rq.nfft, st,
+      [&](T* frames) { return launch_stft_frames<T>(sig, window, frames, rq.C, rq.n, rq.seg, rq.hop, rq.nfft, rq.nseg, rq.lead, st); },
+      [&](cplx<T>* F) { return launch_stft_transpose<T>(F, Z, bits, rq.C, rq.nseg, rq.nfft / 2 + 1, (T)rq.scale, (T)rq.eps, st); });
 }
 
 // Scratch of qi_stft_out: [0] the three-kernel path's frames and spectra (qi_stft_scratch_bytes) | [1] the panel when the
@@ -45,148 +77,65 @@ StftOutLayout stft_out_layout(int dtype, int64_t C, int64_t n, int64_t seg, int6
   int64_t slots = ceil_div(nseg, kEpiSpan);
   if (stft_fused_supported(dtype, seg, hop, nfft)) slots = std::max(slots, stft_fused_groups(dtype, nfft, nseg));
   StftOutLayout l;
-  l.panel = align_up((size_t)C * nseg * nfft * e) + align_up((size_t)C * nseg * nf * 2 * e);
+  l.panel = FftScratch(dtype, C, nseg, nfft).total;
   l.part_band = l.panel + (want_coef ? 0 : align_up((size_t)C * nf * nseg * 2 * e));
   l.part_stat = l.part_band + align_up((size_t)C * slots * nf * 8);
   l.total = l.part_stat + align_up((size_t)C * slots * 24);
   return l;
 }
 
+// qi_stft_out; `rq`: qi_stft's request (eps set)
 template <typename T>
-int stft_out_impl(int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop, int64_t nfft,
-                  double scale, const qi_tfr_out* out, char* scratch, hipStream_t st) {
-  const int dtype = sizeof(T) == 8 ? QI_F64 : QI_F32;
-  const int64_t nseg = qi_stft_segments(n, seg, hop), nf = nfft / 2 + 1;
-  const double eps = qi::host::eps_or_default(out->eps);
-  const StftOutLayout l = stft_out_layout(dtype, C, n, seg, hop, nfft, out->coef != nullptr);
+int stft_out_impl(int device, StftRequest rq, const T* sig, const T* window, const qi_tfr_out* out, char* scratch, hipStream_t st) {
+  const int64_t C = rq.C, nseg = rq.nseg, nf = rq.nfft / 2 + 1;
+  const StftOutLayout l = stft_out_layout(sizeof(T) == 8 ? QI_F64 : QI_F32, C, rq.n, rq.seg, rq.hop, rq.nfft, out->coef != nullptr);
   cplx<T>* Z = static_cast<cplx<T>*>(out->coef);
   T* bits = static_cast<T*>(out->bits);
   double* part_band = reinterpret_cast<double*>(scratch + l.part_band);
   double* part_stat = reinterpret_cast<double*>(scratch + l.part_stat);
-  const bool reduce = out->power_band != nullptr;
-  static const bool fused_off = tune_env("QI_STFT_FUSED") && atoi(tune_env("QI_STFT_FUSED")) == 0;
-  if (!fused_off && stft_fused_supported(dtype, seg, hop, nfft)) {
-    const StftReduce red{part_band, part_stat, out->power_time, static_cast<double*>(out->power_band),
-                         static_cast<double*>(out->stats), qi::host::power_scale_or_default(out->power_scale)};
-    const int rc = launch_stft_fused<T>(static_cast<const T*>(sig), static_cast<const T*>(window), Z, bits, C, n, seg, hop, nfft,
-                                        nseg, seg / 2, scale, eps, st, nullptr, nullptr, reduce ? &red : nullptr);
-    if (rc != QI_ERR_UNSUPPORTED) return rc;  // (a device with less LDS than the tile needs: the three-kernel path below)
-  }
-  // frames -> hipFFT -> transpose into the caller's panel or the scratch one, then the hipFFT engine's reduction kernels on it
-  T* frames = reinterpret_cast<T*>(scratch);
-  cplx<T>* F = reinterpret_cast<cplx<T>*>(scratch + align_up((size_t)C * nseg * nfft * sizeof(T)));
-  if (!Z) Z = reinterpret_cast<cplx<T>*>(scratch + l.panel);
-  QI_TRY(launch_stft_frames<T>(static_cast<const T*>(sig), static_cast<const T*>(window), frames, C, n, seg, hop, nfft, nseg,
-                               seg / 2, st));
-  {
-    std::lock_guard<std::mutex> lk(g_stft_mu);
-    QI_TRY(fft_r2c<T>(g_stft_fft[device], frames, F, nfft, C * nseg, st));
-  }
-  QI_TRY(launch_stft_transpose<T>(F, Z, bits, C, nseg, nf, (T)scale, (T)eps, st));
-  if (!reduce) return QI_OK;
-  const int64_t nblk = ceil_div(nseg, kEpiSpan);
-  EpiArgs<T> a{};
-  a.Y = Z;
-  a.L = a.n = nseg;
-  a.off = 0;
-  a.Ct = C;
-  a.Bt = a.B = nf;
-  a.j0 = 0;
-  a.power_time = static_cast<T*>(out->power_time);
-  a.part_band = part_band;
-  a.part_stat = part_stat;
-  a.tile_b = 0;
-  a.ntile_b = 1;
-  a.power_scale = (T)qi::host::power_scale_or_default(out->power_scale);
-  a.eps = (T)eps;
-  QI_TRY(launch_epilogue<T>(a, st));
-  return launch_finalize(part_band, part_stat, static_cast<double*>(out->power_band), static_cast<double*>(out->stats), C, nf,
-                         nblk, nblk, st);
+  double* power_band = static_cast<double*>(out->power_band);
+  double* stats = static_cast<double*>(out->stats);
+  const double power_scale = qi::host::power_scale_or_default(out->power_scale);
+  const bool reduce = power_band != nullptr;
+  return fused_or_hipfft(
+      stft_fused_supported(sizeof(T) == 8 ? QI_F64 : QI_F32, rq.seg, rq.hop, rq.nfft),
+      [&] {
+        StftRequest red = rq;
+        if (reduce) {
+          red.part_band = part_band;
+          red.part_stat = part_stat;
+          red.power_time = out->power_time;
+          red.power_band = power_band;
+          red.stats = stats;
+          red.power_scale = power_scale;
+        }
+        return launch_stft_fused<T>(red, sig, window, Z, bits, st);
+      },
+      [&]() -> int {
+        // into the caller's panel or the scratch one, then the hipFFT engine's reduction kernels on it
+        if (!Z) Z = reinterpret_cast<cplx<T>*>(scratch + l.panel);
+        QI_TRY(stft_hipfft<T>(device, rq, sig, window, Z, bits, scratch, st));
+        if (!reduce) return QI_OK;
+        const int64_t nblk = ceil_div(nseg, kEpiSpan);
+        EpiArgs<T> a{};
+        a.Y = Z;
+        a.L = a.n = nseg;
+        a.off = 0;
+        a.Ct = C;
+        a.Bt = a.B = nf;
+        a.j0 = 0;
+        a.power_time = static_cast<T*>(out->power_time);
+        a.part_band = part_band;
+        a.part_stat = part_stat;
+        a.tile_b = 0;
+        a.ntile_b = 1;
+        a.power_scale = (T)power_scale;
+        a.eps = (T)rq.eps;
+        QI_TRY(launch_epilogue<T>(a, st));
+        return launch_finalize(part_band, part_stat, power_band, stats, C, nf, nblk, nblk, st);
+      });
 }
 
-template <typename T>
-int welch_impl(int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop,
-               int64_t nfft, double scale, void* pxx, char* scratch, hipStream_t st) {
-  const int64_t nseg = (n - seg) / hop + 1;
-  const int64_t nf = nfft / 2 + 1;
-  static const bool fused_off = tune_env("QI_STFT_FUSED") && atoi(tune_env("QI_STFT_FUSED")) == 0;
-  if (!fused_off && stft_fused_supported(sizeof(T) == 8 ? QI_F64 : QI_F32, seg, hop, nfft)) {  // segments, transform, |X|^2 sums in one kernel
-    const int rc = launch_welch_fused<T>(static_cast<const T*>(sig), static_cast<const T*>(window), static_cast<T*>(pxx),
-                                         reinterpret_cast<double*>(scratch), C, n, seg, hop, nfft, nseg, scale * scale, st);
-    if (rc != QI_ERR_UNSUPPORTED) return rc;
-  }
-  T* frames = reinterpret_cast<T*>(scratch);
-  cplx<T>* F = reinterpret_cast<cplx<T>*>(scratch + align_up((size_t)C * nseg * nfft * sizeof(T)));
-  QI_TRY(launch_stft_frames<T>(static_cast<const T*>(sig), static_cast<const T*>(window), frames, C, n, seg, hop,
-                               nfft, nseg, 0, st));
-  {
-    std::lock_guard<std::mutex> lk(g_stft_mu);
-    QI_TRY(fft_r2c<T>(g_stft_fft[device], frames, F, nfft, C * nseg, st));
-  }
-  return launch_welch_mean<T>(F, static_cast<T*>(pxx), C, nseg, nf, nfft, (T)(scale * scale), st);
-}
-
-}  // namespace
-
-namespace {
-template <typename T>
-int sliding_stft_impl(int device, const T* sig, int64_t C, int64_t n, const T* window, int64_t seg, int64_t hop,
-                      int64_t nfft, int64_t first, int64_t nseg, int pad_mode, int detrend, int64_t roll, cplx<T>* Z, T* R,
-                      int kind, char* scratch, hipStream_t st) {
-  const int64_t nf = nfft / 2 + 1;
-  static const bool fused_off = tune_env("QI_STFT_FUSED") && atoi(tune_env("QI_STFT_FUSED")) == 0;
-  if (!fused_off && stft_fused_supported(sizeof(T) == 8 ? QI_F64 : QI_F32, seg, hop, nfft)) {
-    // one kernel: slices (padding mode, optional detrend), transform, phase roll, [frequency][slice] store
-    const StftSliding sl{pad_mode, detrend, R ? kind : 0, roll};
-    const int rc = launch_stft_fused<T>(sig, window, Z, R, C, n, seg, hop, nfft, nseg, -first, 1.0, 0.0, st, nullptr, &sl);
-    if (rc != QI_ERR_UNSUPPORTED) return rc;
-  }
-  T* frames = reinterpret_cast<T*>(scratch);
-  cplx<T>* F = reinterpret_cast<cplx<T>*>(scratch + align_up((size_t)C * nseg * nfft * sizeof(T)));
-  QI_TRY(launch_sliding_frames<T>(sig, window, frames, C, n, seg, hop, nfft, nseg, first, pad_mode, detrend, roll, st));
-  {
-    std::lock_guard<std::mutex> lk(g_stft_mu);
-    QI_TRY(fft_r2c<T>(g_stft_fft[device], frames, F, nfft, C * nseg, st));
-  }
-  return launch_sliding_transpose<T>(F, Z, R, kind, C, nseg, nf, st);
-}
-
-template <typename T>
-int sliding_istft_impl(int device, const cplx<T>* S, int64_t C, const T* dual, int64_t seg, int64_t hop, int64_t nfft,
-                       int64_t first, int64_t nseg, int64_t roll, int64_t k0, int64_t k1, T* out, char* scratch,
-                       hipStream_t st) {
-  const int64_t nf = nfft / 2 + 1;
-  static const bool fused_off = tune_env("QI_STFT_FUSED") && atoi(tune_env("QI_STFT_FUSED")) == 0;
-  if (!fused_off) {  // one kernel: fold, inverse transform in LDS, overlap-add in gather form
-    const int rc = launch_istft_fused<T>(S, dual, out, C, seg, hop, nfft, first, nseg, roll, k0, k1, st);
-    if (rc != QI_ERR_UNSUPPORTED) return rc;  // (other transform lengths, or a device without the LDS: the three-kernel path)
-  }
-  T* slices = reinterpret_cast<T*>(scratch);
-  cplx<T>* F = reinterpret_cast<cplx<T>*>(scratch + align_up((size_t)C * nseg * nfft * sizeof(T)));
-  QI_TRY(launch_sliding_untranspose<T>(S, F, C, nseg, nf, st));
-  {
-    std::lock_guard<std::mutex> lk(g_stft_mu);
-    QI_TRY(fft_c2r<T>(g_stft_fft[device], F, slices, nfft, C * nseg, st));
-  }
-  return launch_sliding_overlap_add<T>(slices, dual, out, C, k0, k1, seg, hop, nfft, nseg, first, roll, st);
-}
-}  // namespace
-
-namespace {
-template <typename T>
-int shannon_fft_impl(int device, const T* sig, int64_t C, int64_t n, cplx<T>* spectrum, T* angle, T* marginal,
-                     char* scratch, hipStream_t st) {
-  const int64_t nf = n / 2 + 1;
-  double* partial = reinterpret_cast<double*>(scratch);
-  int32_t* turns = reinterpret_cast<int32_t*>(scratch + align_up((size_t)C * shannon_spans(n) * 8));
-  T* copy = reinterpret_cast<T*>(scratch + align_up((size_t)C * shannon_spans(n) * 8) + align_up((size_t)C * nf * 4));
-  QI_HIP(hipMemcpyAsync(copy, sig, (size_t)C * n * sizeof(T), hipMemcpyDeviceToDevice, st));
-  {
-    std::lock_guard<std::mutex> lock(g_stft_mu);
-    QI_TRY(fft_r2c<T>(g_stft_fft[device], copy, spectrum, n, C, st));
-  }
-  return launch_fft_marginal<T>(spectrum, C, nf, angle, marginal, partial, turns, st);
-}
 }  // namespace
 
 extern "C" {
@@ -200,9 +149,7 @@ int64_t qi_stft_segments(int64_t n, int64_t seg, int64_t hop) {
 }
 
 int64_t qi_stft_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {
-  const int64_t nseg = qi_stft_segments(n, seg, hop);
-  const size_t e = dtype == QI_F64 ? 8 : 4;
-  return (int64_t)(align_up((size_t)C * nseg * nfft * e) + align_up((size_t)C * nseg * (nfft / 2 + 1) * 2 * e));
+  return (int64_t)FftScratch(dtype, C, qi_stft_segments(n, seg, hop), nfft).total;
 }
 
 int qi_stft(int dtype, int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg,
@@ -213,10 +160,18 @@ int qi_stft(int dtype, int device, const void* sig, int64_t C, int64_t n, const 
   QI_REQUIRE(C > 0 && n > 0 && seg > 0 && hop > 0 && hop <= seg && nfft >= seg, "bad STFT geometry");
   QI_REQUIRE(scratch_bytes >= qi_stft_scratch_bytes(dtype, C, n, seg, hop, nfft), "scratch too small");
   DeviceGuard g(device);
-  return dtype == QI_F64 ? stft_impl<double>(device, sig, C, n, window, seg, hop, nfft, scale, Z, bits, eps,
-                                             (char*)scratch, (hipStream_t)stream)
-                         : stft_impl<float>(device, sig, C, n, window, seg, hop, nfft, scale, Z, bits, eps,
-                                            (char*)scratch, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  StftRequest rq{C, n, seg, hop, nfft, qi_stft_segments(n, seg, hop), seg / 2};
+  rq.scale = scale;
+  rq.eps = qi::host::eps_or_default(eps);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const T *x = (const T*)sig, *w = (const T*)window;
+    return fused_or_hipfft(
+        stft_fused_supported(dtype, seg, hop, nfft),
+        [&] { return launch_stft_fused<T>(rq, x, w, (cplx<T>*)Z, (T*)bits, st); },  // one kernel: segments, transform, store from LDS
+        [&] { return stft_hipfft<T>(device, rq, x, w, (cplx<T>*)Z, (T*)bits, (char*)scratch, st); });
+  });
 }
 
 int64_t qi_stft_out_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft, int want_coef,
@@ -237,16 +192,22 @@ int qi_stft_out(int dtype, int device, const void* sig, int64_t C, int64_t n, co
   QI_REQUIRE(scratch_bytes >= qi_stft_out_scratch_bytes(dtype, C, n, seg, hop, nfft, out->coef != nullptr, out->bits != nullptr),
              "scratch too small");
   DeviceGuard g(device);
-  return dtype == QI_F64
-             ? stft_out_impl<double>(device, sig, C, n, window, seg, hop, nfft, scale, out, (char*)scratch, (hipStream_t)stream)
-             : stft_out_impl<float>(device, sig, C, n, window, seg, hop, nfft, scale, out, (char*)scratch, (hipStream_t)stream);
+  StftRequest rq{C, n, seg, hop, nfft, qi_stft_segments(n, seg, hop), seg / 2};
+  rq.scale = scale;
+  rq.eps = qi::host::eps_or_default(out->eps);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return stft_out_impl<T>(device, rq, (const T*)sig, (const T*)window, out, (char*)scratch, (hipStream_t)stream);
+  });
 }
 
+// The three-kernel sequence's scratch also holds the fused kernel's [C][groups][nfft / 2 + 1] double partials: groups <= nseg
+// and 8 <= 2 sizeof(T), so they are never the larger of the two.
 int64_t qi_welch_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {
   if (n < seg || seg <= 0 || hop <= 0) return 0;
   const int64_t nseg = (n - seg) / hop + 1;
-  const size_t e = dtype == QI_F64 ? 8 : 4;
-  return (int64_t)(align_up((size_t)C * nseg * nfft * e) + align_up((size_t)C * nseg * (nfft / 2 + 1) * 2 * e));
+  const size_t fused = align_up((size_t)C * stft_fused_groups(dtype, nfft, nseg) * (nfft / 2 + 1) * 8);
+  return (int64_t)std::max(FftScratch(dtype, C, nseg, nfft).total, fused);
 }
 
 int qi_welch(int dtype, int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg,
@@ -257,10 +218,22 @@ int qi_welch(int dtype, int device, const void* sig, int64_t C, int64_t n, const
   QI_REQUIRE(C > 0 && seg > 0 && n >= seg && hop > 0 && hop <= seg && nfft >= seg, "bad Welch geometry");
   QI_REQUIRE(scratch_bytes >= qi_welch_scratch_bytes(dtype, C, n, seg, hop, nfft), "scratch too small");
   DeviceGuard g(device);
-  return dtype == QI_F64 ? welch_impl<double>(device, sig, C, n, window, seg, hop, nfft, scale, pxx, (char*)scratch,
-                                              (hipStream_t)stream)
-                         : welch_impl<float>(device, sig, C, n, window, seg, hop, nfft, scale, pxx, (char*)scratch,
-                                             (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nseg = (n - seg) / hop + 1;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const T *x = (const T*)sig, *w = (const T*)window;
+    return fused_or_hipfft(
+        stft_fused_supported(dtype, seg, hop, nfft),
+        // segments, transform, |X|^2 sums in one kernel
+        [&] { return launch_welch_fused<T>(x, w, (T*)pxx, (double*)scratch, C, n, seg, hop, nfft, nseg, scale * scale, st); },
+        [&] {
+          return via_hipfft<T>(
+              device, (char*)scratch, C, nseg, nfft, st,
+              [&](T* frames) { return launch_stft_frames<T>(x, w, frames, C, n, seg, hop, nfft, nseg, 0, st); },
+              [&](cplx<T>* F) { return launch_welch_mean<T>(F, (T*)pxx, C, nseg, nfft / 2 + 1, nfft, (T)(scale * scale), st); });
+        });
+  });
 }
 
 // ---- tfr_info -------------------------------------------------------------------------------------
@@ -280,10 +253,10 @@ int qi_power_marginals(int dtype, int device, const void* power, int64_t C, int6
   const int64_t nblk = ceil_div(n, kEpiSpan);
   double* pb = reinterpret_cast<double*>(scratch);
   double* ps = reinterpret_cast<double*>((char*)scratch + align_up((size_t)C * B * nblk * 8));
-  if (dtype == QI_F64)
-    QI_TRY(launch_power_marginals<double>((const double*)power, C, B, n, (double*)power_time, pb, ps, st));
-  else
-    QI_TRY(launch_power_marginals<float>((const float*)power, C, B, n, (float*)power_time, pb, ps, st));
+  QI_TRY(by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_power_marginals<T>((const T*)power, C, B, n, (T*)power_time, pb, ps, st);
+  }));
   return launch_finalize(power_band ? pb : nullptr, stats ? ps : nullptr, (double*)power_band, (double*)stats, C, B,
                          nblk, nblk, st);
 }
@@ -294,10 +267,10 @@ int qi_log2_offset(int dtype, int device, const void* in, void* out, int64_t C, 
   QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
   QI_REQUIRE(C > 0 && count > 0, "bad shape");
   DeviceGuard g(device);
-  return dtype == QI_F64 ? launch_log2_offset<double>((const double*)in, (double*)out, C, count, eps,
-                                                      (const double*)ref, (hipStream_t)stream)
-                         : launch_log2_offset<float>((const float*)in, (float*)out, C, count, (float)eps,
-                                                     (const double*)ref, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_log2_offset<T>((const T*)in, (T*)out, C, count, (T)eps, (const double*)ref, (hipStream_t)stream);
+  });
 }
 
 int qi_widen(int device, const void* in, void* out, int64_t count, qi_stream stream) {
@@ -312,8 +285,10 @@ int qi_log2_abs(int dtype, int device, const void* in, int is_complex, void* out
   QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
   QI_REQUIRE(count > 0, "bad shape");
   DeviceGuard g(device);
-  return dtype == QI_F64 ? launch_log2_abs<double>((const double*)in, is_complex, (double*)out, count, eps, (hipStream_t)stream)
-                         : launch_log2_abs<float>((const float*)in, is_complex, (float*)out, count, (float)eps, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_log2_abs<T>((const T*)in, is_complex, (T*)out, count, (T)eps, (hipStream_t)stream);
+  });
 }
 
 int qi_shannon_panel(int dtype, int device, const void* power, const void* mult, int mode, int64_t C, int64_t B,
@@ -324,12 +299,11 @@ int qi_shannon_panel(int dtype, int device, const void* power, const void* mult,
   QI_REQUIRE(mode >= 0 && mode <= 2, "bad mode %d", mode);
   QI_REQUIRE(C > 0 && B > 0 && n > 0 && deg_free > 1.0, "bad shape");
   DeviceGuard g(device);
-  return dtype == QI_F64
-             ? launch_shannon<double>((const double*)power, (const double*)mult, mode, C, B, n, deg_free,
-                                      (double*)info, (double*)shannon_bits, (double*)isnr, (double*)esnr,
-                                      (hipStream_t)stream)
-             : launch_shannon<float>((const float*)power, (const float*)mult, mode, C, B, n, deg_free, (float*)info,
-                                     (float*)shannon_bits, (float*)isnr, (float*)esnr, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_shannon<T>((const T*)power, (const T*)mult, mode, C, B, n, deg_free, (T*)info, (T*)shannon_bits, (T*)isnr,
+                             (T*)esnr, (hipStream_t)stream);
+  });
 }
 
 // ---- 1-D Shannon family ---------------------------------------------------------------------------------------------
@@ -339,10 +313,10 @@ int qi_shannon_1d(int dtype, int device, const void* marginal, int64_t C, int64_
   QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
   QI_REQUIRE(C > 0 && n > 1, "bad shape");
   DeviceGuard g(device);
-  return dtype == QI_F64 ? launch_shannon_1d<double>((const double*)marginal, C, n, (double*)info, (double*)entropy,
-                                                     (double*)isnr, (double*)esnr, (hipStream_t)stream)
-                         : launch_shannon_1d<float>((const float*)marginal, C, n, (float*)info, (float*)entropy,
-                                                    (float*)isnr, (float*)esnr, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_shannon_1d<T>((const T*)marginal, C, n, (T*)info, (T*)entropy, (T*)isnr, (T*)esnr, (hipStream_t)stream);
+  });
 }
 
 int64_t qi_shannon_scratch_bytes(int dtype, int64_t C, int64_t n) {
@@ -359,11 +333,11 @@ int qi_shannon_tdr(int dtype, int device, const void* sig, int64_t C, int64_t n,
   QI_REQUIRE(C > 0 && n > 1, "bad shape");
   QI_REQUIRE(scratch_bytes >= qi_shannon_scratch_bytes(dtype, C, n), "scratch too small");
   DeviceGuard g(device);
-  double* partial = static_cast<double*>(scratch);
-  return dtype == QI_F64 ? launch_tdr_marginal<double>((const double*)sig, C, n, (double*)sig_norm, (double*)marginal,
-                                                       partial, (hipStream_t)stream)
-                         : launch_tdr_marginal<float>((const float*)sig, C, n, (float*)sig_norm, (float*)marginal,
-                                                      partial, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_tdr_marginal<T>((const T*)sig, C, n, (T*)sig_norm, (T*)marginal, static_cast<double*>(scratch),
+                                  (hipStream_t)stream);
+  });
 }
 
 int qi_shannon_fft(int dtype, int device, const void* sig, int64_t C, int64_t n, void* spectrum, void* angle,
@@ -373,17 +347,24 @@ int qi_shannon_fft(int dtype, int device, const void* sig, int64_t C, int64_t n,
   QI_REQUIRE(C > 0 && n > 1, "bad shape");
   QI_REQUIRE(scratch_bytes >= qi_shannon_scratch_bytes(dtype, C, n), "scratch too small");
   DeviceGuard g(device);
-  return dtype == QI_F64 ? shannon_fft_impl<double>(device, (const double*)sig, C, n, (double2*)spectrum, (double*)angle,
-                                                    (double*)marginal, (char*)scratch, (hipStream_t)stream)
-                         : shannon_fft_impl<float>(device, (const float*)sig, C, n, (float2*)spectrum, (float*)angle,
-                                                   (float*)marginal, (char*)scratch, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nf = n / 2 + 1;
+  char* s = static_cast<char*>(scratch);
+  double* partial = reinterpret_cast<double*>(s);
+  int32_t* turns = reinterpret_cast<int32_t*>(s + align_up((size_t)C * shannon_spans(n) * 8));
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    T* copy = reinterpret_cast<T*>(s + align_up((size_t)C * shannon_spans(n) * 8) + align_up((size_t)C * nf * 4));
+    QI_HIP(hipMemcpyAsync(copy, sig, (size_t)C * n * sizeof(T), hipMemcpyDeviceToDevice, st));
+    QI_TRY(locked_fft(device, [&](FftCache& fc) { return fft_r2c<T>(fc, copy, (cplx<T>*)spectrum, n, C, st); }));
+    return launch_fft_marginal<T>((cplx<T>*)spectrum, C, nf, (T*)angle, (T*)marginal, partial, turns, st);
+  });
 }
 
 // ---- sliding-window STFT in scipy.signal.ShortTimeFFT's convention ---------------------------------------------------
 int64_t qi_sliding_scratch_bytes(int dtype, int64_t C, int64_t nfft, int64_t n_slices) {
   if (C <= 0 || nfft <= 0 || n_slices <= 0) return 0;
-  const size_t esz = dtype == QI_F64 ? 8 : 4;
-  return (int64_t)(align_up((size_t)C * n_slices * nfft * esz) + align_up((size_t)C * n_slices * (nfft / 2 + 1) * 2 * esz));
+  return (int64_t)FftScratch(dtype, C, n_slices, nfft).total;
 }
 
 int qi_sliding_stft(int dtype, int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg,
@@ -397,13 +378,30 @@ int qi_sliding_stft(int dtype, int device, const void* sig, int64_t C, int64_t n
              "reflective padding reaches further than the record is long");
   QI_REQUIRE(scratch_bytes >= qi_sliding_scratch_bytes(dtype, C, nfft, n_slices), "scratch too small");
   DeviceGuard g(device);
-  return dtype == QI_F64
-             ? sliding_stft_impl<double>(device, (const double*)sig, C, n, (const double*)window, seg, hop, nfft, first,
-                                         n_slices, pad_mode, detrend, roll, (double2*)Z, (double*)real_out, real_kind,
-                                         (char*)scratch, (hipStream_t)stream)
-             : sliding_stft_impl<float>(device, (const float*)sig, C, n, (const float*)window, seg, hop, nfft, first,
-                                        n_slices, pad_mode, detrend, roll, (float2*)Z, (float*)real_out, real_kind,
-                                        (char*)scratch, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  StftRequest rq{C, n, seg, hop, nfft, n_slices, -first};
+  rq.pad_mode = pad_mode;
+  rq.detrend = detrend;
+  rq.real_kind = real_out ? real_kind : 0;
+  rq.roll = roll;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const T *x = (const T*)sig, *w = (const T*)window;
+    return fused_or_hipfft(
+        stft_fused_supported(dtype, seg, hop, nfft),
+        // one kernel: slices (padding mode, optional detrend), transform, phase roll, [frequency][slice] store
+        [&] { return launch_stft_fused<T>(rq, x, w, (cplx<T>*)Z, (T*)real_out, st); },
+        [&] {
+          return via_hipfft<T>(
+              device, (char*)scratch, C, n_slices, nfft, st,
+              [&](T* frames) {
+                return launch_sliding_frames<T>(x, w, frames, C, n, seg, hop, nfft, n_slices, first, pad_mode, detrend, roll, st);
+              },
+              [&](cplx<T>* F) {
+                return launch_sliding_transpose<T>(F, (cplx<T>*)Z, (T*)real_out, real_kind, C, n_slices, nfft / 2 + 1, st);
+              });
+        });
+  });
 }
 
 int qi_sliding_istft(int dtype, int device, const void* S, int64_t C, const void* dual_window, int64_t seg, int64_t hop,
@@ -414,11 +412,24 @@ int qi_sliding_istft(int dtype, int device, const void* S, int64_t C, const void
   QI_REQUIRE(C > 0 && seg > 0 && hop > 0 && nfft >= seg && n_slices > 0 && k1 > k0 && roll >= 0 && roll < nfft, "bad shape");
   QI_REQUIRE(scratch_bytes >= qi_sliding_scratch_bytes(dtype, C, nfft, n_slices), "scratch too small");
   DeviceGuard g(device);
-  return dtype == QI_F64
-             ? sliding_istft_impl<double>(device, (const double2*)S, C, (const double*)dual_window, seg, hop, nfft, first,
-                                          n_slices, roll, k0, k1, (double*)out, (char*)scratch, (hipStream_t)stream)
-             : sliding_istft_impl<float>(device, (const float2*)S, C, (const float*)dual_window, seg, hop, nfft, first,
-                                         n_slices, roll, k0, k1, (float*)out, (char*)scratch, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  const FftScratch l(dtype, C, n_slices, nfft);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const cplx<T>* spec = (const cplx<T>*)S;
+    const T* dual = (const T*)dual_window;
+    return fused_or_hipfft(
+        true,  // (the launcher knows the geometries it takes: not other transform lengths, nor a halo that fills the LDS)
+        // one kernel: fold, inverse transform in LDS, overlap-add in gather form
+        [&] { return launch_istft_fused<T>(spec, dual, (T*)out, C, seg, hop, nfft, first, n_slices, roll, k0, k1, st); },
+        [&]() -> int {  // un-transpose -> hipFFT -> overlap-add
+          T* slices = reinterpret_cast<T*>((char*)scratch + l.frames);
+          cplx<T>* F = reinterpret_cast<cplx<T>*>((char*)scratch + l.spectra);
+          QI_TRY(launch_sliding_untranspose<T>(spec, F, C, n_slices, nfft / 2 + 1, st));
+          QI_TRY(locked_fft(device, [&](FftCache& fc) { return fft_c2r<T>(fc, F, slices, nfft, C * n_slices, st); }));
+          return launch_sliding_overlap_add<T>(slices, dual, (T*)out, C, k0, k1, seg, hop, nfft, n_slices, first, roll, st);
+        });
+  });
 }
 
 }  // extern "C"

@@ -157,34 +157,37 @@ int launch_finalize(const double* part_band, const double* part_stat, double* po
 template <typename T>
 int launch_stft_frames(const T* sig, const T* win, T* frames, int64_t C, int64_t n, int64_t seg, int64_t hop,
                        int64_t nfft, int64_t nseg, int64_t lead, hipStream_t st);
-// options of scipy.signal.ShortTimeFFT's convention on the fused STFT kernel (qi_sliding_stft): record extension past its
-// ends (0 zeros, 1 edge, 2 / 3 even / odd reflection), mean removal, left rotation of the slice, real output (1 |X|, 2 |X|^2)
-struct StftSliding {
-  int32_t pad_mode, detrend, real_kind;
-  int64_t roll;
-};
 // fused STFT (qi_stft_fused.hip): frames, transform and [frequency][time] store in one kernel
 bool stft_fused_supported(int dtype, int64_t seg, int64_t hop, int64_t nfft);
-// reductions of the panel from the fused kernel's registers (qi_stft_out): part_band [C][groups][nfft / 2 + 1] and part_stat
-// [C][groups][3] doubles of scratch, groups = stft_fused_groups(); power_band [C][nfft / 2 + 1] and stats [C][4] float64,
-// power_time [C][nseg] in the record's precision or null.  Z and bits may then be null (no panel is stored).
-struct StftReduce {
-  double *part_band, *part_stat;
-  void* power_time;
-  double *power_band, *stats;
-  double power_scale;
-};
 // segment groups (workgroups) per record of a fused launch; 0: the transform length has no fused shape
 int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg);
+// One forward call of the fused kernel.  The mode fields default to qi_stft's own call (zeros past the record, segment mean
+// removed, coefficient and log2-bits panels); Welch, the ShortTimeFFT convention and the reductions set only what they mean.
+struct StftRequest {
+  int64_t C, n, seg, hop, nfft, nseg;
+  int64_t lead;  // samples of extension in front of the record (seg / 2 for the STFT, 0 Welch, -first sliding)
+  double scale = 1.0, eps = 0.0;
+  // Welch: [C][groups][nfft / 2 + 1] doubles of scratch for the groups' sums of |X|^2 (groups = stft_fused_groups()); no panel
+  double* welch_part = nullptr;
+  // scipy.signal.ShortTimeFFT's convention (qi_sliding_stft): record extension past its ends (0 zeros, 1 edge, 2 / 3 even / odd
+  // reflection), mean removal, left rotation of the slice, what the real output holds (0 log2 bits, 1 |X|, 2 |X|^2)
+  int32_t pad_mode = 0, detrend = 1, real_kind = 0;
+  int64_t roll = 0;
+  // reductions of the panel from the kernel's registers (qi_stft_out), asked for by power_band: part_band [C][groups][nfft / 2 + 1]
+  // and part_stat [C][groups][3] doubles of scratch; power_band [C][nfft / 2 + 1] and stats [C][4] float64, power_time [C][nseg]
+  // in the record's precision or null.  Z and bits may then be null (no panel is stored).
+  double *part_band = nullptr, *part_stat = nullptr;
+  void* power_time = nullptr;
+  double *power_band = nullptr, *stats = nullptr;
+  double power_scale = 1.0;
+};
 template <typename T>
-int launch_stft_fused(const T* sig, const T* win, cplx<T>* Z, T* bits, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                      int64_t nfft, int64_t nseg, int64_t lead, double scale, double eps, hipStream_t st,
-                      double* welch_part = nullptr, const StftSliding* sliding = nullptr, const StftReduce* red = nullptr);
+int launch_stft_fused(const StftRequest& rq, const T* sig, const T* win, cplx<T>* Z, T* bits, hipStream_t st);
 // fused inverse of the ShortTimeFFT-convention transform (QI_ERR_UNSUPPORTED, with no error text, where it does not apply)
 template <typename T>
 int launch_istft_fused(const cplx<T>* S, const T* dual, T* out, int64_t C, int64_t seg, int64_t hop, int64_t nfft, int64_t first,
                        int64_t nseg, int64_t roll, int64_t k0, int64_t k1, hipStream_t st);
-// Welch mean on the fused kernel (`part`: [C][<= nseg][nfft / 2 + 1] doubles of scratch)
+// Welch mean on the fused kernel (`part`: [C][stft_fused_groups()][nfft / 2 + 1] doubles of scratch)
 template <typename T>
 int launch_welch_fused(const T* sig, const T* win, T* pxx, double* part, int64_t C, int64_t n, int64_t seg, int64_t hop,
                        int64_t nfft, int64_t nseg, double scale2, hipStream_t st);

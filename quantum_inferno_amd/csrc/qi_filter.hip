@@ -379,7 +379,7 @@ int qi_decimate(int dtype, int device, const void* sig, int64_t n_channels, int6
     QI_REQUIRE(g.ok, "cannot select device %d", device);
     return launch_order<T, QI_IIR_SOS, true>(sections, a, tab, (hipStream_t)stream);
   };
-  return dtype == QI_F64 ? run(double{}) : run(float{});
+  return by_dtype(dtype, run);
 }
 
 }  // extern "C"

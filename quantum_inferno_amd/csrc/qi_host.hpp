@@ -31,6 +31,13 @@ struct DeviceGuard {
   }
 };
 
+// The element type of a C ABI call as a type: calls f(T{}) with T = double for QI_F64 and float otherwise (the entry points
+// check the dtype first) -- a generic lambda `[&](auto t) { using T = decltype(t); ... }` states its argument list once.
+template <typename F>
+inline auto by_dtype(int dtype, F&& f) {
+  return dtype == QI_F64 ? f(double{}) : f(float{});
+}
+
 // ---- hipFFT plan cache (one per qi_plan, plus a process-wide one for the plan-less STFT entry) ----
 struct FftCache {
   using Key = std::tuple<int, int64_t, int64_t, int64_t>;  // hipfftType, length, batch, distance between transforms

@@ -610,8 +610,9 @@ int qi_pool_panel(int dtype, int device, const void* in, int input_kind, int64_t
   if (cols == 0) return QI_OK;  // factor > n: nothing to write
   QI_REQUIRE(in && out, "null argument");
   DeviceGuard g(device);
-  return dtype == QI_F64 ? pool_dispatch<double>(in, input_kind, rows, n, factor, cols, method, power_scale, out, (hipStream_t)stream)
-                         : pool_dispatch<float>(in, input_kind, rows, n, factor, cols, method, power_scale, out, (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    return pool_dispatch<decltype(t)>(in, input_kind, rows, n, factor, cols, method, power_scale, out, (hipStream_t)stream);
+  });
 }
 
 int qi_pool_strip(int dtype, int device, const void* in, int64_t rows, int64_t row_stride, int64_t first, int64_t factor,
@@ -628,10 +629,10 @@ int qi_pool_strip(int dtype, int device, const void* in, int64_t rows, int64_t r
              (long long)out_stride, (long long)windows);
   if (windows == 0 || !(mean_out || max_out || sums_out)) return QI_OK;  // nothing to write
   DeviceGuard g(device);
-  return dtype == QI_F64 ? launch_strip<double>(device, in, rows, row_stride, first, factor, windows, power_scale, mean_out, max_out,
-                                                out_stride, static_cast<double*>(sums_out), (hipStream_t)stream)
-                         : launch_strip<float>(device, in, rows, row_stride, first, factor, windows, power_scale, mean_out, max_out,
-                                               out_stride, static_cast<double*>(sums_out), (hipStream_t)stream);
+  return by_dtype(dtype, [&](auto t) {
+    return launch_strip<decltype(t)>(device, in, rows, row_stride, first, factor, windows, power_scale, mean_out, max_out, out_stride,
+                                     static_cast<double*>(sums_out), (hipStream_t)stream);
+  });
 }
 
 int qi_pool_strip_stats(int device, const void* sums, int64_t records, int64_t bands, void* stats, qi_stream stream) {

@@ -11,6 +11,7 @@
 // coefficients (G = 16: 128 B).  HBM traffic = the record once (the 50 % overlap is served by the caches) + the
 // panel once (+ the bits panel when asked for): the algorithmic bytes of SURVEY s8(d).  No MFMA: an FFT has no dense
 // contraction.
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -717,28 +718,73 @@ __global__ void __launch_bounds__(256) k_stft_reduce(const double* __restrict__ 
 
 }  // namespace
 
-// M = R x C per transform length (R <= C <= 64: register transforms of at most 64 points; float64 keeps to 32)
-template <typename T>
-static bool stft_shape(int64_t M, int* lr, int* lc) {
-  int lm = 0;
-  while ((1ll << lm) < M) ++lm;
-  *lr = lm / 2;
-  *lc = lm - *lr;
-  return (1ll << lm) == M && *lc <= (sizeof(T) == 8 ? 5 : 6) && *lr >= 2;
-}
+// Everything the host knows about a transform length in one precision: M = nfft / 2 = R x C complex points per segment
+// (R = 2^lr <= C = 2^lc <= 64: register transforms of at most 64 points; float64 keeps to 32), for nfft a power of two
+// 64 .. 4096; the LDS a workgroup of G segments takes and the G a budget allows.
+struct StftShape {
+  int64_t M = 0;
+  int lr = 0, lc = 0;
+  size_t esz;       // bytes of a complex number
+  bool ok = false;  // the length has kernel instantiations in this precision
+  StftShape(int64_t nfft, bool f64) : esz(f64 ? sizeof(double2) : sizeof(float2)) {
+    if (nfft < 64 || nfft > 4096 || !is_pow2(nfft)) return;
+    M = nfft / 2;
+    int lm = 0;
+    while ((1ll << lm) < M) ++lm;
+    lr = lm / 2;
+    lc = lm - lr;
+    ok = lc <= (f64 ? 5 : 6);
+  }
+  // the geometry of a forward call the kernels take (the inverse adds its own conditions)
+  bool holds(int64_t seg, int64_t hop) const { return ok && seg >= 2 && seg <= 2 * M && hop >= 1; }
+  // complex elements of a segment's tile: R rows padded by one element, and one more
+  size_t tile() const { return ((size_t)1 << lr) * (((size_t)1 << lc) + 1) + 1; }
+  // dynamic LDS of a workgroup of G segments: the tiles | M + 1 twiddles; the reductions form lays its tail over them
+  size_t lds_bytes(int G) const { return ((size_t)G * tile() + (size_t)M + 1) * esz; }
+  size_t lds_bytes_reduced(int G) const { return std::max(lds_bytes(G), kStftRedLds); }
+  // the most segments (<= 16) a workgroup holds within `budget` bytes of LDS; 0: not even one
+  int largest_group(size_t budget) const {
+    int G = 16;
+    while (G > 0 && lds_bytes(G) > budget) --G;
+    return G;
+  }
+  // segments per workgroup of a forward launch: a power of two, two workgroups per CU
+  int launch_group() const {
+    size_t budget = 80 * 1024;
+    if (const char* e = tune_env("QI_STFT_LDS_KB")) budget = (size_t)atoi(e) * 1024;
+    int G = largest_group(budget);
+    while (G & (G - 1)) G &= G - 1;
+    return G;
+  }
+  // segment groups (workgroups) per record of a forward launch
+  int64_t groups(int64_t nseg) const {
+    const int G = ok ? launch_group() : 0;
+    return G < 1 ? 0 : ceil_div(nseg, G);
+  }
+};
 
-// segments per workgroup (a power of two <= 16) so that the tiles and the twiddles stay within `budget` bytes of LDS
-static int stft_fused_group(int64_t M, int lr, int lc, size_t esz, size_t budget) {
-  const size_t tile = ((size_t)1 << lr) * (((size_t)1 << lc) + 1) + 1;
-  for (int G = 16; G >= 1; G >>= 1)
-    if (((size_t)G * tile + M + 1) * esz <= budget) return G;
-  return 0;
-}
+bool stft_fused_supported(int dtype, int64_t seg, int64_t hop, int64_t nfft) { return StftShape(nfft, dtype == QI_F64).holds(seg, hop); }
+int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg) { return StftShape(nfft, dtype == QI_F64).groups(nseg); }
 
-bool stft_fused_supported(int dtype, int64_t seg, int64_t hop, int64_t nfft) {
-  int lr, lc;
-  if (!(nfft >= 64 && nfft <= 4096 && (nfft & (nfft - 1)) == 0 && seg <= nfft && seg >= 2 && hop >= 1)) return false;
-  return dtype == QI_F64 ? stft_shape<double>(nfft / 2, &lr, &lc) : stft_shape<float>(nfft / 2, &lr, &lc);
+// The kernels of a shape: calls f(std::integral_constant<int, lr>{}, std::integral_constant<int, lc>{}) -- a generic lambda
+// that names the instantiation -- for M = 32 ... 2048 (float64: ... 1024) and returns what it returns; QI_ERR_UNSUPPORTED,
+// with no error text, for a shape that has none.
+template <typename T, typename F>
+static int with_shape(const StftShape& s, F&& f) {
+  using std::integral_constant;
+  switch (s.lr * 8 + s.lc) {
+    case 2 * 8 + 3: return f(integral_constant<int, 2>{}, integral_constant<int, 3>{});
+    case 3 * 8 + 3: return f(integral_constant<int, 3>{}, integral_constant<int, 3>{});
+    case 3 * 8 + 4: return f(integral_constant<int, 3>{}, integral_constant<int, 4>{});
+    case 4 * 8 + 4: return f(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+    case 4 * 8 + 5: return f(integral_constant<int, 4>{}, integral_constant<int, 5>{});
+    case 5 * 8 + 5: return f(integral_constant<int, 5>{}, integral_constant<int, 5>{});
+    case 5 * 8 + 6:
+      if constexpr (sizeof(T) == 4) return f(integral_constant<int, 5>{}, integral_constant<int, 6>{});
+      break;
+    default: break;
+  }
+  return QI_ERR_UNSUPPORTED;
 }
 
 // exp(-i pi k / M), k = 0..M, per device and transform length (built on the host in long double, kept for the process)
@@ -767,145 +813,91 @@ static int stft_twiddles(int64_t M, const cplx<T>** out) {
   return QI_OK;
 }
 
-static thread_local int32_t g_last_ngroups = 0;  // segment groups per record of this thread's last launch (Welch partials)
-
-// segments per workgroup of a forward launch: two workgroups per CU
-static int stft_launch_group(int64_t M, int lr, int lc, size_t esz) {
-  size_t budget = 80 * 1024;
-  if (const char* e = tune_env("QI_STFT_LDS_KB")) budget = (size_t)atoi(e) * 1024;
-  return stft_fused_group(M, lr, lc, esz, budget);
-}
-
-int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg) {
-  int lr, lc;
-  const int64_t M = nfft / 2;
-  if (!(dtype == QI_F64 ? stft_shape<double>(M, &lr, &lc) : stft_shape<float>(M, &lr, &lc))) return 0;
-  const int G = stft_launch_group(M, lr, lc, dtype == QI_F64 ? sizeof(double2) : sizeof(float2));
-  return G < 1 ? 0 : ceil_div(nseg, G);
-}
-
-template <typename T, int LR, int LC, bool PLAIN, bool WZ, bool WB>
-static int launch_stft_red(const T* sig, const T* win, const cplx<T>* twg, cplx<T>* Z, T* bits, const StftFusedArgs& a, dim3 grid,
-                           size_t lds, hipStream_t st) {
-  QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(&k_stft_fused<T, LR, LC, PLAIN, true, WZ, WB>), lds));
-  k_stft_fused<T, LR, LC, PLAIN, true, WZ, WB><<<grid, kStftThreads, lds, st>>>(sig, win, twg, Z, bits, a);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
-}
-
-template <typename T, int LR, int LC>
-static int launch_stft_shape(const T* sig, const T* win, cplx<T>* Z, T* bits, int64_t C, int64_t nseg, StftFusedArgs a,
-                             hipStream_t st, const StftReduce* red) {
-  const int64_t M = 1ll << (LR + LC);
-  const int G = stft_launch_group(M, LR, LC, sizeof(cplx<T>));
-  if (G < 1) {
-    set_error("fused STFT: a transform of %lld points does not fit the LDS tile", (long long)(2 * M));
-    return QI_ERR_UNSUPPORTED;
-  }
-  a.G = G;
-  a.log2g = 0;
-  while ((1 << a.log2g) < G) ++a.log2g;
-  const size_t tile = ((size_t)1 << LR) * (((size_t)1 << LC) + 1) + 1;
-  size_t lds = ((size_t)G * tile + M + 1) * sizeof(cplx<T>);
-  const cplx<T>* twg = nullptr;
-  QI_TRY(stft_twiddles<T>(M, &twg));
-  a.ngroups = (int32_t)ceil_div(nseg, G);
-  g_last_ngroups = a.ngroups;
-  a.nitems = (int64_t)a.ngroups * C;
-  a.per_xcd = (int32_t)ceil_div(a.nitems, 8);
-  dim3 grid((unsigned)(8 * a.per_xcd));
-  if (red) {
-    // both panels or none: the PLAIN walk (its coefficients and bits are qi_stft's); one panel: the general walk
-    if (lds < kStftRedLds) lds = kStftRedLds;
-    a.red_band = red->part_band;
-    a.red_stat = red->part_stat;
-    a.power_time = red->power_time;
-    a.power_scale = red->power_scale;
-    if (Z && bits) QI_TRY((launch_stft_red<T, LR, LC, true, true, true>(sig, win, twg, Z, bits, a, grid, lds, st)));
-    else if (Z) QI_TRY((launch_stft_red<T, LR, LC, false, true, false>(sig, win, twg, Z, bits, a, grid, lds, st)));
-    else if (bits) QI_TRY((launch_stft_red<T, LR, LC, false, false, true>(sig, win, twg, Z, bits, a, grid, lds, st)));
-    else QI_TRY((launch_stft_red<T, LR, LC, true, false, false>(sig, win, twg, Z, bits, a, grid, lds, st)));
-    const int nf = (int)(M + 1);
-    dim3 gr((unsigned)(ceil_div(nf, 256) + 1), (unsigned)C);
-    k_stft_reduce<<<gr, 256, 0, st>>>(red->part_band, red->part_stat, red->power_band, red->stats, a.ngroups, nf);
-    QI_LAUNCH_CHECK();
-    return QI_OK;
-  }
-  // the product's own call (styx_fft: zeros beyond the record, both panels, log2 bits) runs the specialised loops
-  const bool plain = Z && bits && !a.welch_part && a.pad_mode == 0 && a.real_kind == 0 && a.roll == 0;
-  const void* fn = plain ? reinterpret_cast<const void*>(&k_stft_fused<T, LR, LC, true>)
-                         : reinterpret_cast<const void*>(&k_stft_fused<T, LR, LC, false>);
-  QI_TRY(allow_dynamic_lds(fn, lds));
-  if (plain)
-    k_stft_fused<T, LR, LC, true><<<grid, kStftThreads, lds, st>>>(sig, win, twg, Z, bits, a);
-  else
-    k_stft_fused<T, LR, LC, false><<<grid, kStftThreads, lds, st>>>(sig, win, twg, Z, bits, a);
+// allow `kernel` its dynamic LDS on this device, then launch it
+template <typename... P, typename... A>
+static int launch_with_lds(void (*kernel)(P...), dim3 grid, size_t lds, hipStream_t st, A... args) {
+  QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
+  kernel<<<grid, kStftThreads, lds, st>>>(args...);
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
 
 template <typename T>
-int launch_stft_fused(const T* sig, const T* win, cplx<T>* Z, T* bits, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                      int64_t nfft, int64_t nseg, int64_t lead, double scale, double eps, hipStream_t st,
-                      double* welch_part, const StftSliding* sl, const StftReduce* red) {
-  StftFusedArgs a;
-  a.red_band = a.red_stat = nullptr;
-  a.power_time = nullptr;
-  a.power_scale = 1.0;
-  a.welch_part = welch_part;
-  a.pad_mode = sl ? sl->pad_mode : 0;
-  a.detrend = sl ? sl->detrend : 1;
-  a.real_kind = sl ? sl->real_kind : 0;
-  a.roll = sl ? sl->roll : 0;
-  a.dbg = 0;
+int launch_stft_fused(const StftRequest& rq, const T* sig, const T* win, cplx<T>* Z, T* bits, hipStream_t st) {
+  const StftShape s(rq.nfft, sizeof(T) == 8);
+  if (!s.holds(rq.seg, rq.hop)) {
+    set_error("fused STFT: transform length %lld is not supported", (long long)rq.nfft);
+    return QI_ERR_UNSUPPORTED;
+  }
+  const int G = s.launch_group();
+  if (G < 1) {
+    set_error("fused STFT: a transform of %lld points does not fit the LDS tile", (long long)(2 * s.M));
+    return QI_ERR_UNSUPPORTED;
+  }
+  const bool red = rq.power_band != nullptr;
+  StftFusedArgs a{};
+  a.n = rq.n;
+  a.seg = rq.seg;
+  a.hop = rq.hop;
+  a.nseg = rq.nseg;
+  a.lead = rq.lead;
+  a.scale = rq.scale;
+  a.eps = rq.eps;
+  a.welch_part = rq.welch_part;
+  a.pad_mode = rq.pad_mode;
+  a.detrend = rq.detrend;
+  a.real_kind = rq.real_kind;
+  a.roll = rq.roll;
+  a.red_band = rq.part_band;
+  a.red_stat = rq.part_stat;
+  a.power_time = rq.power_time;
+  a.power_scale = rq.power_scale;
 #ifdef QI_STFT_DBG
   if (const char* e = tune_env("QI_STFT_DBG")) a.dbg = atoi(e);
 #endif
-  a.n = n;
-  a.seg = seg;
-  a.hop = hop;
-  a.nseg = nseg;
-  a.lead = lead;
-  a.scale = scale;
-  a.eps = eps;
-  a.G = a.log2g = 0;
-  int lr, lc;
-  if (!stft_shape<T>(nfft / 2, &lr, &lc)) {
-    set_error("fused STFT: transform length %lld is not supported", (long long)nfft);
-    return QI_ERR_UNSUPPORTED;
-  }
-  switch (lr * 8 + lc) {  // M = 32 ... 2048 (float64: ... 1024)
-    case 2 * 8 + 3: return launch_stft_shape<T, 2, 3>(sig, win, Z, bits, C, nseg, a, st, red);
-    case 3 * 8 + 3: return launch_stft_shape<T, 3, 3>(sig, win, Z, bits, C, nseg, a, st, red);
-    case 3 * 8 + 4: return launch_stft_shape<T, 3, 4>(sig, win, Z, bits, C, nseg, a, st, red);
-    case 4 * 8 + 4: return launch_stft_shape<T, 4, 4>(sig, win, Z, bits, C, nseg, a, st, red);
-    case 4 * 8 + 5: return launch_stft_shape<T, 4, 5>(sig, win, Z, bits, C, nseg, a, st, red);
-    case 5 * 8 + 5: return launch_stft_shape<T, 5, 5>(sig, win, Z, bits, C, nseg, a, st, red);
-    case 5 * 8 + 6:
-      if constexpr (sizeof(T) == 4) return launch_stft_shape<T, 5, 6>(sig, win, Z, bits, C, nseg, a, st, red);
-      break;
-    default: break;
-  }
-  set_error("fused STFT: transform length %lld is not supported", (long long)nfft);
-  return QI_ERR_UNSUPPORTED;
+  a.G = G;
+  while ((1 << a.log2g) < G) ++a.log2g;
+  a.ngroups = (int32_t)s.groups(rq.nseg);
+  a.nitems = (int64_t)a.ngroups * rq.C;
+  a.per_xcd = (int32_t)ceil_div(a.nitems, 8);
+  const dim3 grid((unsigned)(8 * a.per_xcd));
+  const size_t lds = red ? s.lds_bytes_reduced(G) : s.lds_bytes(G);
+  const cplx<T>* twg = nullptr;
+  QI_TRY(stft_twiddles<T>(s.M, &twg));
+  // the product's own call (styx_fft: zeros beyond the record, both panels, log2 bits) runs the specialised loops
+  const bool plain = Z && bits && !a.welch_part && a.pad_mode == 0 && a.real_kind == 0 && a.roll == 0;
+  QI_TRY(with_shape<T>(s, [&](auto lr, auto lc) {
+    constexpr int LR = decltype(lr)::value, LC = decltype(lc)::value;
+    // reductions with both panels or none: the PLAIN walk (its coefficients and bits are qi_stft's); one panel: the general walk
+    if (red)
+      return native::with_panels(Z != nullptr, bits != nullptr, [&](auto wz, auto wb) {
+        constexpr bool WZ = decltype(wz)::value, WB = decltype(wb)::value;
+        return launch_with_lds(&k_stft_fused<T, LR, LC, WZ == WB, true, WZ, WB>, grid, lds, st, sig, win, twg, Z, bits, a);
+      });
+    if (plain) return launch_with_lds(&k_stft_fused<T, LR, LC, true>, grid, lds, st, sig, win, twg, Z, bits, a);
+    return launch_with_lds(&k_stft_fused<T, LR, LC, false>, grid, lds, st, sig, win, twg, Z, bits, a);
+  }));
+  if (!red) return QI_OK;
+  const int nf = (int)(s.M + 1);
+  dim3 gr((unsigned)(ceil_div(nf, 256) + 1), (unsigned)rq.C);
+  k_stft_reduce<<<gr, 256, 0, st>>>(rq.part_band, rq.part_stat, rq.power_band, rq.stats, a.ngroups, nf);
+  QI_LAUNCH_CHECK();
+  return QI_OK;
 }
+template int launch_stft_fused<float>(const StftRequest&, const float*, const float*, float2*, float*, hipStream_t);
+template int launch_stft_fused<double>(const StftRequest&, const double*, const double*, double2*, double*, hipStream_t);
 
-template int launch_stft_fused<float>(const float*, const float*, float2*, float*, int64_t, int64_t, int64_t, int64_t,
-                                      int64_t, int64_t, int64_t, double, double, hipStream_t, double*, const StftSliding*,
-                                      const StftReduce*);
-template int launch_stft_fused<double>(const double*, const double*, double2*, double*, int64_t, int64_t, int64_t, int64_t,
-                                       int64_t, int64_t, int64_t, double, double, hipStream_t, double*, const StftSliding*,
-                                       const StftReduce*);
-
-// Welch power spectrum on the fused kernel: partial sums per segment group in `part` ([C][groups][nfft / 2 + 1] doubles,
-// groups <= nseg), then the mean over the segments with scipy's one-sided "spectrum" weights
+// Welch power spectrum on the fused kernel: partial sums per segment group in `part` ([C][groups][nfft / 2 + 1] doubles),
+// then the mean over the segments with scipy's one-sided "spectrum" weights
 template <typename T>
 int launch_welch_fused(const T* sig, const T* win, T* pxx, double* part, int64_t C, int64_t n, int64_t seg, int64_t hop,
                        int64_t nfft, int64_t nseg, double scale2, hipStream_t st) {
-  QI_TRY(launch_stft_fused<T>(sig, win, nullptr, nullptr, C, n, seg, hop, nfft, nseg, 0, 1.0, 0.0, st, part, nullptr, nullptr));
+  StftRequest rq{C, n, seg, hop, nfft, nseg, 0};
+  rq.welch_part = part;
+  QI_TRY(launch_stft_fused<T>(rq, sig, win, nullptr, nullptr, st));
   const int nf = (int)(nfft / 2 + 1);
   dim3 g((unsigned)ceil_div(nf, 256), (unsigned)C);
-  k_welch_reduce<T><<<g, 256, 0, st>>>(part, pxx, g_last_ngroups, nseg, nf, (T)scale2);
+  k_welch_reduce<T><<<g, 256, 0, st>>>(part, pxx, (int)StftShape(nfft, sizeof(T) == 8).groups(nseg), nseg, nf, (T)scale2);
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
@@ -914,64 +906,37 @@ template int launch_welch_fused<float>(const float*, const float*, float*, doubl
 template int launch_welch_fused<double>(const double*, const double*, double*, double*, int64_t, int64_t, int64_t, int64_t,
                                         int64_t, int64_t, double, hipStream_t);
 
-// the fused inverse: supported for the fused kernel's transform lengths when a workgroup's LDS holds at least one owned hop
-// beside the halo slices
-template <typename T, int LR, int LC>
-static int launch_istft_shape(const cplx<T>* S, const T* dual, T* out, int64_t C, IstftArgs a, hipStream_t st) {
-  const int64_t M = 1ll << (LR + LC);
-  const size_t tile = ((size_t)1 << LR) * (((size_t)1 << LC) + 1) + 1, budget = 80 * 1024;
-  int G = (int)((budget / sizeof(cplx<T>) - (size_t)(M + 1)) / tile);
-  if (G > 16) G = 16;
+// the fused inverse: supported for the forward kernel's geometries with hop <= seg when a workgroup's LDS holds at least one
+// owned hop beside the halo slices
+template <typename T>
+int launch_istft_fused(const cplx<T>* S, const T* dual, T* out, int64_t C, int64_t seg, int64_t hop, int64_t nfft, int64_t first,
+                       int64_t nseg, int64_t roll, int64_t k0, int64_t k1, hipStream_t st) {
+  const StftShape s(nfft, sizeof(T) == 8);
+  if (!s.holds(seg, hop) || hop > seg) return QI_ERR_UNSUPPORTED;
+  IstftArgs a{seg, hop, nseg, first, roll, k0, k1};  // (the counts that follow them start at zero)
+  a.halo = (int32_t)(ceil_div(seg, hop) - 1);
+  const int G = s.largest_group(80 * 1024);
   if (G - a.halo < 1) return QI_ERR_UNSUPPORTED;
   a.gown = G - a.halo;
   // owned hops: every sample up to the end of the last slice
   const int64_t hops = a.nseg + (a.seg - 1) / a.hop;
   if (hops < a.gown) a.gown = (int32_t)hops;
   a.ngroups = (int32_t)ceil_div(hops, a.gown);
-  a.log2gp = 0;
   while ((1 << a.log2gp) < a.gown + a.halo) ++a.log2gp;
-  const size_t lds = ((size_t)(a.gown + a.halo) * tile + M + 1) * sizeof(cplx<T>);
-  const cplx<T>* twg = nullptr;
-  QI_TRY(stft_twiddles<T>(M, &twg));
-  QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(&k_istft_fused<T, LR, LC>), lds));
-  if (a.k0 < a.first || a.k1 > a.first + hops * a.hop)  // (samples outside the hops the workgroups own)
-    QI_HIP(hipMemsetAsync(out, 0, (size_t)C * (size_t)(a.k1 - a.k0) * sizeof(T), st));
   a.nitems = (int64_t)a.ngroups * C;
   a.per_xcd = (int32_t)ceil_div(a.nitems, 8);
-  k_istft_fused<T, LR, LC><<<dim3((unsigned)(8 * a.per_xcd)), kStftThreads, lds, st>>>(S, dual, twg, out, a);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
-}
-
-template <typename T>
-int launch_istft_fused(const cplx<T>* S, const T* dual, T* out, int64_t C, int64_t seg, int64_t hop, int64_t nfft, int64_t first,
-                       int64_t nseg, int64_t roll, int64_t k0, int64_t k1, hipStream_t st) {
-  int lr, lc;
-  if (!(nfft >= 64 && nfft <= 4096 && (nfft & (nfft - 1)) == 0 && seg <= nfft && seg >= 2 && hop >= 1 && hop <= seg) ||
-      !stft_shape<T>(nfft / 2, &lr, &lc))
-    return QI_ERR_UNSUPPORTED;
-  IstftArgs a{};
-  a.seg = seg;
-  a.hop = hop;
-  a.nseg = nseg;
-  a.first = first;
-  a.roll = roll;
-  a.k0 = k0;
-  a.k1 = k1;
-  a.halo = (int32_t)(ceil_div(seg, hop) - 1);
-  switch (lr * 8 + lc) {
-    case 2 * 8 + 3: return launch_istft_shape<T, 2, 3>(S, dual, out, C, a, st);
-    case 3 * 8 + 3: return launch_istft_shape<T, 3, 3>(S, dual, out, C, a, st);
-    case 3 * 8 + 4: return launch_istft_shape<T, 3, 4>(S, dual, out, C, a, st);
-    case 4 * 8 + 4: return launch_istft_shape<T, 4, 4>(S, dual, out, C, a, st);
-    case 4 * 8 + 5: return launch_istft_shape<T, 4, 5>(S, dual, out, C, a, st);
-    case 5 * 8 + 5: return launch_istft_shape<T, 5, 5>(S, dual, out, C, a, st);
-    case 5 * 8 + 6:
-      if constexpr (sizeof(T) == 4) return launch_istft_shape<T, 5, 6>(S, dual, out, C, a, st);
-      break;
-    default: break;
-  }
-  return QI_ERR_UNSUPPORTED;
+  const size_t lds = s.lds_bytes(a.gown + a.halo);
+  const cplx<T>* twg = nullptr;
+  QI_TRY(stft_twiddles<T>(s.M, &twg));
+  return with_shape<T>(s, [&](auto lr, auto lc) -> int {
+    const auto kernel = &k_istft_fused<T, decltype(lr)::value, decltype(lc)::value>;
+    QI_TRY(allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
+    if (a.k0 < a.first || a.k1 > a.first + hops * a.hop)  // (samples outside the hops the workgroups own)
+      QI_HIP(hipMemsetAsync(out, 0, (size_t)C * (size_t)(a.k1 - a.k0) * sizeof(T), st));
+    kernel<<<dim3((unsigned)(8 * a.per_xcd)), kStftThreads, lds, st>>>(S, dual, twg, out, a);
+    QI_LAUNCH_CHECK();
+    return QI_OK;
+  });
 }
 template int launch_istft_fused<float>(const float2*, const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                                        int64_t, int64_t, int64_t, hipStream_t);

@@ -15,6 +15,8 @@
 //   * a synthetic table comes out as gen_tables.py says it must (every row on the native engines / the whole table on hipFFT);
 //   * degenerate band parameters (sigma or p_re of 0, negative, NaN, inf; NaN omega; a shift index outside [0, n)) are refused
 //     with QI_ERR_ARG and a message, and leave the plan's previous table in use;
+//   * the plan-less STFT family (qi_stft, qi_stft_out, qi_welch, qi_sliding_stft, qi_sliding_istft) on fused and hipFFT geometries in
+//     both precisions, each with scratch of exactly the advertised size (walk_stft);
 //   * launch geometry (fake hipLaunchKernel), signed overflow / shifts / misaligned access in the host arithmetic (UBSan).
 // Test infrastructure: built and run by tests/test_host_sanitize.py on the CPU container; never part of libqi_tfr.so.
 #include <algorithm>
@@ -28,6 +30,9 @@
 #include "qi_host.hpp"
 
 extern "C" size_t qi_fake_hip_launches();
+// the fused STFT's twiddle tables are kept per device for the life of the process, by design: not a leak to report
+extern "C" const char* __lsan_default_suppressions() { return "leak:stft_twiddles\n"; }
+extern "C" const char* __lsan_default_options() { return "print_suppressions=0"; }
 extern "C" size_t qi_layout_regions_checked();
 
 namespace {
@@ -254,6 +259,75 @@ void check_tables(const qi_plan* p, const Config& c) {
   }
 }
 
+// The plan-less STFT family (qi_api_ops.hip, the host half of qi_stft_fused.hip): every entry point once per precision on a
+// geometry the fused kernels take and on one that goes through frames -> hipFFT -> finish, with scratch of EXACTLY the
+// advertised size (AddressSanitizer's malloc: a pointer carved past it that anything touches is a report), so that UBSan and the
+// stand-in's launch-geometry check see the request, shape, scratch-layout and launch arithmetic.  Returns the calls made.
+size_t walk_stft() {
+  struct Geo {
+    int64_t seg, hop, nfft, n;
+  };
+  const Geo geos[] = {{256, 64, 256, 3 * 256 + 1} /* fused */, {200, 50, 300, 601} /* hipFFT */, {2048, 512, 2048, 3 * 2048 + 1} /* fused, fewer segments per workgroup */};
+  const int64_t C = 3;
+  size_t calls = 0;
+  auto need = [](int rc, const char* what, int dtype, const Geo& g) {
+    if (rc == QI_OK) return;
+    fprintf(stderr, "walk: %s (%s, seg %lld hop %lld nfft %lld): %s\n", what, dtype ? "f64" : "f32", (long long)g.seg, (long long)g.hop,
+            (long long)g.nfft, qi_last_error());
+    exit(1);
+  };
+  auto dev = [](size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) exit(2);
+    return p;
+  };
+  for (int dtype : {(int)QI_F32, (int)QI_F64})
+    for (const Geo& g : geos) {
+      const size_t e = dtype == QI_F64 ? 8 : 4;
+      const int64_t nf = g.nfft / 2 + 1, nseg = qi_stft_segments(g.n, g.seg, g.hop);
+      void *sig = dev(C * g.n * e), *win = dev(g.seg * e), *Z = dev(C * nf * nseg * 2 * e), *bits = dev(C * nf * nseg * e);
+      void *pt = dev(C * nseg * e), *pb = dev(C * nf * 8), *stats = dev(C * 4 * 8), *pxx = dev(C * nf * e);
+      int64_t sb = qi_stft_scratch_bytes(dtype, C, g.n, g.seg, g.hop, g.nfft);
+      void* scratch = dev(sb);
+      need(qi_stft(dtype, 0, sig, C, g.n, win, g.seg, g.hop, g.nfft, 0.5, Z, bits, 0.0, scratch, sb, nullptr), "qi_stft", dtype, g);
+      (void)hipFree(scratch);
+      qi_tfr_out panel{}, bits_only{}, reduced{};
+      panel.coef = Z;
+      panel.bits = bits;
+      panel.power_time = reduced.power_time = pt;
+      panel.power_band = reduced.power_band = pb;
+      panel.stats = reduced.stats = stats;
+      bits_only.bits = bits;
+      const struct {
+        const qi_tfr_out* out;
+        const char* what;
+      } forms[] = {{&panel, "qi_stft_out (panels and reductions)"}, {&bits_only, "qi_stft_out (bits only)"}, {&reduced, "qi_stft_out (reductions only)"}};
+      for (const auto& f : forms) {
+        sb = qi_stft_out_scratch_bytes(dtype, C, g.n, g.seg, g.hop, g.nfft, f.out->coef != nullptr, f.out->bits != nullptr);
+        scratch = dev(sb);
+        need(qi_stft_out(dtype, 0, sig, C, g.n, win, g.seg, g.hop, g.nfft, 0.5, f.out, scratch, sb, nullptr), f.what, dtype, g);
+        (void)hipFree(scratch);
+      }
+      sb = qi_welch_scratch_bytes(dtype, C, g.n, g.seg, g.hop, g.nfft);
+      scratch = dev(sb);
+      need(qi_welch(dtype, 0, sig, C, g.n, win, g.seg, g.hop, g.nfft, 0.5, pxx, scratch, sb, nullptr), "qi_welch", dtype, g);
+      (void)hipFree(scratch);
+      // ShortTimeFFT convention: slices from half a segment in front of the record to half a segment behind it
+      const int64_t first = -(g.seg / 2), slices = (g.n + g.seg) / g.hop + 1;
+      void *S = dev(C * nf * slices * 2 * e), *R = dev(C * nf * slices * e), *back = dev(C * g.n * e);
+      sb = qi_sliding_scratch_bytes(dtype, C, g.nfft, slices);
+      scratch = dev(sb);
+      need(qi_sliding_stft(dtype, 0, sig, C, g.n, win, g.seg, g.hop, g.nfft, first, slices, 1, 1, g.seg / 2, S, R, 2, scratch, sb, nullptr),
+           "qi_sliding_stft", dtype, g);
+      need(qi_sliding_istft(dtype, 0, S, C, win, g.seg, g.hop, g.nfft, first, slices, g.seg / 2, 0, g.n, back, scratch, sb, nullptr),
+           "qi_sliding_istft", dtype, g);
+      calls += 7;
+      for (void* q : {sig, win, Z, bits, pt, pb, stats, pxx, S, R, back, scratch}) (void)hipFree(q);
+    }
+  for (auto& kv : g_stft_fft) kv.second.clear();  // (the process-wide hipFFT plans: nothing frees them before the leak check)
+  return calls;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -348,8 +422,9 @@ int main(int argc, char** argv) {
     if (c.order == 0 && (c.flags & 15) == 5) refused += check_degenerate(c);  // (on the synthetic tables that are native on both sides)
   }
   if (dump) fclose(dump);
-  printf("{\"ok\": true, \"plans\": %zu, \"plans_on_native_engines\": %zu, \"calls\": %zu, \"kernel_launches\": %zu, \"scratch_regions_checked\": %zu, \"synthetic_plans\": %zu, "
+  const size_t stft_calls = walk_stft();
+  printf("{\"ok\": true, \"stft_calls\": %zu, \"plans\": %zu, \"plans_on_native_engines\": %zu, \"calls\": %zu, \"kernel_launches\": %zu, \"scratch_regions_checked\": %zu, \"synthetic_plans\": %zu, "
          "\"synthetic_on_native\": %zu, \"degenerate_tables_refused\": %zu}\n",
-         plans, native, calls, qi_fake_hip_launches(), qi_layout_regions_checked(), syn_plans, syn_native, refused);
+         stft_calls, plans, native, calls, qi_fake_hip_launches(), qi_layout_regions_checked(), syn_plans, syn_native, refused);
   return 0;
 }

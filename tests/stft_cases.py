@@ -201,7 +201,7 @@ BOTH_SCALINGS_AT = (200, 2048)  # "magnitude" and "psd" there, "magnitude" elsew
 # same ramp there) and a ramp with an imaginary part below it (200 in 256, 1000 in 1024; 3000 in 4096: fused in float32,
 # the rotation of k_sliding_frames before hipFFT in float64; 24 in 32: hipFFT in both)
 SLIDING_COMPLEX_SEGS = (24, 200, 512, 1000, 2048, 3000)
-# (seg, hop) of the inverse.  Halo ceil(seg / hop) - 1 = 1, 3, 7, 15; launch_istft_shape holds
+# (seg, hop) of the inverse.  Halo ceil(seg / hop) - 1 = 1, 3, 7, 15; launch_istft_fused holds
 # G = min(16, (80 KiB / sizeof(complex) - M - 1) / tile) slices per workgroup and needs G - halo >= 1:
 #   nfft   64,  512: G = 16 in both precisions                  -> every hop fused
 #   nfft 2048      : G = 8 float32 (fused to halo 7), 3 float64 (fused at halo 1 only)

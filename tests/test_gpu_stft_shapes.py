@@ -13,7 +13,7 @@ qi_stft_fused.hip / qi_stft_sliding.hip / qi_api_ops.hip each group is there for
       under the window's zero -- the column is the segment mean alone (divisor seg, not nfft, not the samples inside).
       n = seg: no segment inside the record, `nseg` 3 < G (tiles past the last segment zero-filled, never stored).
       n = 4 * 2048: every channel aligned, pairs on every interior pair.  seg 32 / 8192 (both precisions) and 4096
-      (float64): stft_impl's frames -> hipFFT R2C -> transpose path.
+      (float64): qi_stft's frames -> hipFFT R2C -> transpose path.
   test_stft_plan_matches_wrapper_and_keeps_no_state
       StftPlan's kept buffers (the same kernels through the plan's own scale / scratch).
   test_spectral_wrappers_general_kernel
@@ -25,7 +25,7 @@ qi_stft_fused.hip / qi_stft_sliding.hip / qi_api_ops.hip each group is there for
       PLAIN = true with seg < nfft and hop = seg: the all-zero last segment's coefficients and bits.
   test_welch_every_shape
       the `welch_part` branch at <2,3>, <3,3>, <4,5>, <5,5>, <5,6> (+ <3,4>, <4,4> below), one segment in one group,
-      k_welch_reduce over three partials with a last group of 9, seg < nfft with 3 / 4 overlap, welch_impl's hipFFT path
+      k_welch_reduce over three partials with a last group of 9, seg < nfft with 3 / 4 overlap, qi_welch's hipFFT path
       (8192; 4096 in float64).
   test_sliding_forward_vs_oracle / test_sliding_complex_vs_oracle
       PLAIN = false with pad_mode 0 .. 3 (stft_sample), detrend on / off, real_kind 1 / 2, the roll phase ramp

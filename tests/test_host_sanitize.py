@@ -35,6 +35,8 @@ def test_host_code_under_asan_ubsan_over_every_layout():
     total = 864 + syn["synthetic_plans"]
     assert rec["ok"] and rec["plans"] == total and rec["calls"] >= 8 * total and rec["scratch_regions_checked"] > 60000
     assert rec["synthetic_plans"] == syn["synthetic_plans"]
+    # the plan-less STFT family: seven calls on each of three geometries (two fused, one hipFFT) in both precisions
+    assert rec["stft_calls"] == 2 * 3 * 7
     # (every dyadic table of these shapes is one for the native engines, but float64 at 2^14 samples: hipFFT engine by choice;
     # the walker itself checks that each synthetic table comes out native / on the hipFFT engine as it was built to)
     assert rec["plans_on_native_engines"] - rec["synthetic_on_native"] == 864 - 12 * 4

@@ -178,7 +178,7 @@ def test_table_reaches_every_transform_shape():
 
 
 def test_istft_shapes_straddle_the_fused_limit():
-    """launch_istft_shape: G = min(16, (80 KiB / sizeof(complex) - (M + 1)) / tile) slices, tile = R (C + 1) + 1, fused
+    """launch_istft_fused: G = min(16, (80 KiB / sizeof(complex) - (M + 1)) / tile) slices, tile = R (C + 1) + 1, fused
     while G - halo >= 1.  Both sides of that point are in the table, per precision."""
     for dtype, esz in ((np.float32, 8), (np.float64, 16)):
         sides = set()
