@@ -388,6 +388,43 @@ int qi_decimate(int dtype, int device, const void* sig, int64_t n_channels, int6
                 const void* sos, const void* zi, int64_t edge, void* out, void* scratch, int64_t scratch_bytes,
                 qi_stream stream);
 
+/* ---- scaling and peak picking (utilities/picker.py:32-53 scale_signal_by_extraction_type; picker.py:79-151
+ * find_peaks_by_extraction_type, _with_bandpass, find_peaks_with_bits: scipy.signal.find_peaks with height / distance) ------
+ * Per record x [n], independently of every other record:
+ *  scaling   u = x for the SIG* kinds, u = log2(|x| + eps) in float64 for the LOG2* kinds (eps: 0 is read as 2^-52), and
+ *            s = u / nanmax(u) (SIGMAX, LOG2MAX), u / nanmin(u) (SIGMIN), u / nanmax(|u|) (SIGABS), u (LOG2).  The scaled type
+ *            is the record's for SIG* and float64 for LOG2*.  The division is IEEE division in that type, no reciprocal and no
+ *            special case: a divisor of 0 gives +-inf and NaN, a negative one reverses the order, a record of NaNs stays NaN.
+ *  maxima    sample i, 1 <= i <= n - 2, opens a peak when s[i-1] < s[i]; with j the first index behind i with s[j] != s[i]
+ *            (at most n - 1) it is a peak when s[j] < s[i], reported at (i + j - 1) / 2 rounded down: the middle of a
+ *            plateau of any length; one that starts at sample 0 or reaches sample n - 1 is none.  A NaN compares false.
+ *  height    the peak's value, widened to float64, is tested with >= against: nothing (NONE); `height` (ABS); max(s) - height
+ *            (BELOW_MAX); max(x) - height (BELOW_RAW_MAX: the maximum of the record itself, the peaks still those of s).  Both
+ *            maxima are np.max -- NaN when a sample is, and then there is no peak -- and the difference is formed in the
+ *            type of the maximum (the scaled type, the record's type), per record, on the device.
+ * Outputs (device; any but counts may be NULL): scaled [C][n] in the scaled type; positions int64 [C][capacity] ascending and
+ * values float64 [C][capacity], the scaled value at each peak; counts int64 [C], the peaks found even when more than
+ * capacity -- columns from min(count, capacity) on are not written.  positions with capacity 0 is QI_ERR_ARG; with
+ * positions and values NULL the call is the scaling (and the count).  Any n >= 1 (n < 3: no peak).
+ * Records are cut into tiles of QI_PEAKS_TILE samples.  Five or six kernel launches, four reads of the record (extrema;
+ * scaled values and tile summaries; count; store), no atomics and no waiting of one workgroup for another: a plateau that
+ * leaves its tile is followed through the summaries the previous launch left in scratch.  The same call gives the same bits.
+ * scratch: caller-owned device buffer of qi_peaks_scratch_bytes() bytes, aligned to 8 (host only; negative qi_status for an unknown
+ * dtype, n_channels < 1 or n < 1). */
+#define QI_PEAKS_TILE 256
+typedef enum { QI_PEAK_SIGMAX = 0, QI_PEAK_SIGMIN = 1, QI_PEAK_SIGABS = 2, QI_PEAK_LOG2 = 3, QI_PEAK_LOG2MAX = 4 } qi_peak_scale;
+typedef enum { QI_PEAK_HEIGHT_NONE = 0, QI_PEAK_HEIGHT_ABS = 1, QI_PEAK_HEIGHT_BELOW_MAX = 2,
+               QI_PEAK_HEIGHT_BELOW_RAW_MAX = 3 } qi_peak_height;
+int64_t qi_peaks_scratch_bytes(int dtype, int64_t n_channels, int64_t n);
+int qi_find_peaks(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, int scale, double eps, int height_kind,
+                  double height, void* scaled, int64_t* positions, double* values, int64_t capacity, int64_t* counts,
+                  void* scratch, int64_t scratch_bytes, qi_stream stream);
+/* scipy.signal.find_peaks(distance=) on HOST arrays of `count` candidates, positions ascending: from the highest value to
+ * the lowest, each candidate still kept removes every other one closer than `distance` samples; keep[i] = 1 for the kept.
+ * Among equal values the LATER candidate goes first (a stable ascending sort read from its end; SciPy's own order there is
+ * that of an unstable argsort and not defined).  distance < 1 is QI_ERR_ARG with SciPy's message.  Host only, plain C++. */
+int qi_peaks_select_distance(const int64_t* positions, const double* values, int64_t count, int64_t distance, uint8_t* keep);
+
 #ifdef __cplusplus
 }
 #endif

@@ -695,6 +695,59 @@ def zero_phase_decimate(sig, q, sos, zi, edge):
     return finish(out, was_numpy, was_1d)
 
 
+PEAK_SCALES = {"sigmax": _lib.QI_PEAK_SIGMAX, "sigmin": _lib.QI_PEAK_SIGMIN, "sigabs": _lib.QI_PEAK_SIGABS,
+               "log2": _lib.QI_PEAK_LOG2, "log2max": _lib.QI_PEAK_LOG2MAX}
+PEAK_HEIGHTS = {"none": _lib.QI_PEAK_HEIGHT_NONE, "abs": _lib.QI_PEAK_HEIGHT_ABS, "below_max": _lib.QI_PEAK_HEIGHT_BELOW_MAX,
+                "below_raw_max": _lib.QI_PEAK_HEIGHT_BELOW_RAW_MAX}
+
+
+def find_peaks(sig, scale, height_kind="none", height=0.0, want_scaled=False, capacity=None):
+    """Scale records [n] or [C, n] and pick their peaks on the device (qi_find_peaks): scipy.signal.find_peaks(s,
+    height=...)'s positions for s = the record scaled as utilities.picker.scale_signal_by_extraction_type scales it.
+    scale: "sigmax", "sigmin", "sigabs" (s in the record's type), "log2", "log2max" (s in float64).  height_kind: "none";
+    "abs" (s >= height); "below_max" (s >= max(s) - height); "below_raw_max" (s >= max(record) - height), the maxima taken
+    per record on the device.  float32 records stay float32, anything but float32 and float64 is read as float64.
+    -> (positions int64 [C, capacity], values float64 [C, capacity], counts int64 [C][, scaled [C, n]]), device tensors on
+    the current stream, nothing synchronised; C = 1 for a record [n].  Row r holds its counts[r] peaks in ascending order in
+    its first columns and leaves the others unwritten; counts[r] is the number found even when it exceeds `capacity`
+    (default (n - 1) // 2, the most a record can hold; 0 picks nothing and only counts)."""
+    if scale not in PEAK_SCALES:
+        raise ValueError(f"scale must be one of {sorted(PEAK_SCALES)}, got {scale!r}")
+    if height_kind not in PEAK_HEIGHTS:
+        raise ValueError(f"height_kind must be one of {sorted(PEAK_HEIGHTS)}, got {height_kind!r}")
+    height = float(height)
+    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"signal must be 1-D [n] or 2-D [channels, n], got shape {shape}")
+    n = shape[-1]
+    if n < 1:
+        raise ValueError("a record must hold at least one sample")
+    capacity = (n - 1) // 2 if capacity is None else operator.index(capacity)
+    if capacity < 0:
+        raise ValueError(f"capacity must not be negative, got {capacity}")
+    lib = _lib.require_gpu()
+    x, _, _ = as_signal(sig)
+    dev = x.device
+    n_ch = x.shape[0]
+    log = scale in ("log2", "log2max")
+    positions = torch.empty((n_ch, capacity), dtype=torch.int64, device=dev)
+    values = torch.empty((n_ch, capacity), dtype=torch.float64, device=dev)
+    counts = torch.zeros((n_ch,), dtype=torch.int64, device=dev)
+    scaled = torch.empty((n_ch, n), dtype=torch.float64 if log else x.dtype, device=dev) if want_scaled else None
+    if n_ch > 0:
+        code = _lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32
+        nbytes = int(lib.qi_peaks_scratch_bytes(code, n_ch, n))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.qi_find_peaks(code, dev.index, _lib.ptr(x), n_ch, n, PEAK_SCALES[scale], float(scales.EPSILON64),
+                                         PEAK_HEIGHTS[height_kind], height, _lib.ptr(scaled),
+                                         _lib.ptr(positions) if capacity else None, _lib.ptr(values) if capacity else None,
+                                         capacity, _lib.ptr(counts), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)))
+    return (positions, values, counts, scaled) if want_scaled else (positions, values, counts)
+
+
 # What the reference-signature wrappers hand back to NumPy callers for float32 records.  The reference returns
 # complex128 panels (float64 bits) whatever the record's dtype (styx_cwt.py:195-198, styx_stx.py:228,
 # cwt_atoms.py:408): "reference" computes in float32 and widens on the way out, so a drop-in caller sees the
