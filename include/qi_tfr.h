@@ -425,6 +425,41 @@ int qi_find_peaks(int dtype, int device, const void* sig, int64_t n_channels, in
  * that of an unstable argsort and not defined).  distance < 1 is QI_ERR_ARG with SciPy's message.  Host only, plain C++. */
 int qi_peaks_select_distance(const int64_t* positions, const double* values, int64_t count, int64_t distance, uint8_t* keep);
 
+/* ---- resampling (utilities/sampling.py:53-68 resample_uneven_timeseries: np.interp onto np.arange; sampling.py:71-83
+ * resample_with_sample_rate: scipy.signal.resample) ---------------------------------------------------------------------------
+ * Linear interpolation of records with uneven timestamps onto an even grid, np.interp's semantics.  Per record, with knots
+ * xp [n] (float64 timestamps, expected non-decreasing, duplicates allowed) and values fp [n] widened to double, output i is
+ *   x = start + (double)i * delta                      (the product rounded first, then the sum: np.arange's values)
+ *   x > xp[n-1]: fp[n-1];   x < xp[0]: fp[0];   otherwise with j the last index with xp[j] <= x
+ *   j == n-1 or xp[j] == x: fp[j]
+ *   else s = (fp[j+1] - fp[j]) / (xp[j+1] - xp[j]),  r = s * (x - xp[j]) + fp[j];  if r is NaN: r = s * (x - xp[j+1]) + fp[j+1];
+ *        if that is NaN too and fp[j] == fp[j+1]: r = fp[j]
+ * every operation an IEEE double operation rounded on its own (no fused multiply-add, a true division): NumPy's bits.
+ * values [C][n] in dtype (device); knots float64 (device): knot_stride 0 = [n], shared by all records, knot_stride n =
+ * [C][n], a row of timestamps per record (anything else: QI_ERR_ARG); out [C][m] float64 whatever the dtype (np.interp
+ * returns float64 for float32 data).  Any n >= 1, any m >= 0 (m = 0: a successful no-op), delta finite and > 0, start finite.
+ * A workgroup forms QI_INTERP_TILE consecutive outputs of one record: it brackets them in the knots with two bounded searches
+ * in global memory, then stages the bracketing knots and values in LDS when they are at most QI_INTERP_KNOTS (upsampling, unit
+ * rate, downsampling to about a quarter of the rate) and searches there; otherwise its lanes bisect in global memory.  One
+ * kernel launch (per 65535 records), no scratch, no atomics; the same call gives the same bits.  The order of the timestamps
+ * is not checked, as np.interp does not check it: with unsorted or NaN timestamps the values are undefined, but every search
+ * is bounded and every index it forms lies in [0, n-1]. */
+#define QI_INTERP_TILE 512   /* outputs of one workgroup */
+#define QI_INTERP_KNOTS 2560 /* knots a workgroup stages in LDS */
+int qi_interp_grid(int dtype, int device, const void* values, const void* knots, int64_t knot_stride, int64_t n_channels,
+                   int64_t n, double start, double delta, int64_t m, void* out, qi_stream stream);
+
+/* scipy.signal.resample(x, m) of real records along time, no window, domain="time": the m / 2 + 1 bins of the output spectrum
+ * are the input's bins 0 .. N / 2, N = min(n, m) -- for an even N the bin N / 2 times 2 when m < n, times 0.5 when n < m --
+ * and zeros above; the result is the inverse real transform of length m times m / n.  sig [C][n] -> out [C][m], both in
+ * dtype (SciPy keeps float32 for float32 records).  Any n >= 1, any m >= 1 (below 2^31).  A batched real-to-complex hipFFT
+ * of length n, one kernel for the spectrum (it also applies the 1 / n), a batched complex-to-real hipFFT of length m.
+ * scratch: caller-owned device buffer of qi_resample_fft_scratch_bytes() bytes (a copy of the records and the two spectra),
+ * aligned to 16 (host only; negative qi_status for an unknown dtype, n_channels < 1, n < 1, m < 1 or sizes out of range). */
+int64_t qi_resample_fft_scratch_bytes(int dtype, int64_t n_channels, int64_t n, int64_t m);
+int qi_resample_fft(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, int64_t m, void* out,
+                    void* scratch, int64_t scratch_bytes, qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

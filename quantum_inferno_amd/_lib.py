@@ -19,6 +19,7 @@ QI_IIR_BA, QI_IIR_SOS = 0, 1
 QI_PEAK_SIGMAX, QI_PEAK_SIGMIN, QI_PEAK_SIGABS, QI_PEAK_LOG2, QI_PEAK_LOG2MAX = 0, 1, 2, 3, 4
 QI_PEAK_HEIGHT_NONE, QI_PEAK_HEIGHT_ABS, QI_PEAK_HEIGHT_BELOW_MAX, QI_PEAK_HEIGHT_BELOW_RAW_MAX = 0, 1, 2, 3
 PEAKS_TILE = 256  # samples per tile of qi_find_peaks (QI_PEAKS_TILE of include/qi_tfr.h)
+INTERP_TILE, INTERP_KNOTS = 512, 2560  # outputs of a workgroup of qi_interp_grid, knots it stages in LDS (QI_INTERP_TILE, QI_INTERP_KNOTS)
 IIR_MAX = 16  # largest order of the (b, a) form, most second-order sections (qi_filtfilt)
 POOL_MEDIAN_MAX = 4096  # longest window the median sorts (qi_pool_panel)
 ROUTE_NOWRAP, ROUTE_SPLIT, ROUTE_BEHIND, ROUTE_F64_ZOOM = 16, 32, 256, 512
@@ -124,6 +125,9 @@ PROTOTYPES = {
     "qi_peaks_scratch_bytes": (_i64, [_int, _i64, _i64]),
     "qi_find_peaks": (_int, [_int, _int, _P, _i64, _i64, _int, _dbl, _int, _dbl, _P, _P, _P, _i64, _P, _P, _i64, _P]),
     "qi_peaks_select_distance": (_int, [_P, _P, _i64, _i64, _P]),
+    "qi_interp_grid": (_int, [_int, _int, _P, _P, _i64, _i64, _i64, _dbl, _dbl, _i64, _P, _P]),
+    "qi_resample_fft_scratch_bytes": (_i64, [_int, _i64, _i64, _i64]),
+    "qi_resample_fft": (_int, [_int, _int, _P, _i64, _i64, _i64, _P, _P, _i64, _P]),
 }
 
 _lib = None

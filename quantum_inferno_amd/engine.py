@@ -748,6 +748,76 @@ def find_peaks(sig, scale, height_kind="none", height=0.0, want_scaled=False, ca
     return (positions, values, counts, scaled) if want_scaled else (positions, values, counts)
 
 
+def interp_to_grid(values, timestamps, start, delta, m):
+    """Linear interpolation of records with uneven timestamps onto the even grid start + i * delta, i < m (qi_interp_grid):
+    np.interp(start + np.arange(m) * delta, timestamps, values) bit for bit, per record.  values [n] or [C, n]; timestamps
+    [n], shared by all records, or [C, n], a row per record -- records from sensors with different clocks come onto one
+    grid in one call.  Timestamps are read as float64 and expected non-decreasing (not checked, as np.interp).  float32
+    values are read as they are, anything but float32 and float64 as float64.  -> float64 [m] or [C, m]: NumPy in -> NumPy
+    out, CUDA tensor in -> CUDA tensor out on the current stream, nothing synchronised."""
+    start, delta = float(start), float(delta)
+    m = operator.index(m)
+    if m < 0:
+        raise ValueError(f"m must not be negative, got {m}")
+    if not np.isfinite(start):
+        raise ValueError(f"start must be finite, got {start}")
+    if not (np.isfinite(delta) and delta > 0.0):
+        raise ValueError(f"delta must be finite and positive, got {delta}")
+    shape = tuple(values.shape) if isinstance(values, torch.Tensor) else np.shape(values)
+    tshape = tuple(timestamps.shape) if isinstance(timestamps, torch.Tensor) else np.shape(timestamps)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"values must be 1-D [n] or 2-D [channels, n], got shape {shape}")
+    n = shape[-1]
+    if n < 1:
+        raise ValueError("a record must hold at least one sample")
+    if tshape != (n,) and not (len(shape) == 2 and tshape == shape):
+        raise ValueError(f"timestamps must be [n] or match values' shape {shape}, got shape {tshape}")
+    lib = _lib.require_gpu()
+    x, was_numpy, was_1d = as_signal(values)
+    dev = x.device
+    if not isinstance(timestamps, torch.Tensor):
+        timestamps = torch.from_numpy(np.ascontiguousarray(timestamps, dtype=np.float64))
+    t = timestamps.to(device=dev, dtype=torch.float64).contiguous()
+    n_ch = x.shape[0]
+    out = torch.empty((n_ch, m), dtype=torch.float64, device=dev)
+    if n_ch > 0 and m > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.qi_interp_grid(_lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32, dev.index, _lib.ptr(x), _lib.ptr(t),
+                                          n if t.dim() == 2 else 0, n_ch, n, start, delta, m, _lib.ptr(out), _lib.stream_ptr(dev)))
+    return finish(out, was_numpy, was_1d)
+
+
+def fft_resample(sig, m):
+    """Fourier resampling of records [n] or [C, n] to m samples (qi_resample_fft): scipy.signal.resample(sig, m, axis=-1)
+    for real records, no window.  float32 records stay float32, anything but float32 and float64 is read as float64.  The
+    call owns its scratch (a copy of the records and the two spectra).  NumPy in -> NumPy out, CUDA tensor in -> CUDA
+    tensor out on the current stream, nothing synchronised."""
+    m = operator.index(m)
+    if m < 1:
+        raise ValueError(f"the new length must be at least 1, got {m}")
+    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"signal must be 1-D [n] or 2-D [channels, n], got shape {shape}")
+    n = shape[-1]
+    if n < 1:
+        raise ValueError("a record must hold at least one sample")
+    lib = _lib.require_gpu()
+    x, was_numpy, was_1d = as_signal(sig)
+    dev = x.device
+    n_ch = x.shape[0]
+    out = torch.empty((n_ch, m), dtype=x.dtype, device=dev)
+    if n_ch > 0:
+        code = _lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32
+        nbytes = int(lib.qi_resample_fft_scratch_bytes(code, n_ch, n, m))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.qi_resample_fft(code, dev.index, _lib.ptr(x), n_ch, n, m, _lib.ptr(out), _lib.ptr(scratch), nbytes,
+                                           _lib.stream_ptr(dev)))
+    return finish(out, was_numpy, was_1d)
+
+
 # What the reference-signature wrappers hand back to NumPy callers for float32 records.  The reference returns
 # complex128 panels (float64 bits) whatever the record's dtype (styx_cwt.py:195-198, styx_stx.py:228,
 # cwt_atoms.py:408): "reference" computes in float32 and widens on the way out, so a drop-in caller sees the

@@ -11,8 +11,15 @@ type I, 0.05 dB ripple, cut-off 0.8 / q of Nyquist, as second-order sections -- 
 the record's own precision as in SciPy: float32 records are filtered and returned in float32, float64 in float64, anything
 else (integers, float16) as float64.  A record must be 28 samples or longer.
 
-There is no CPU fallback.  The reference's FFT resamplers (resample_with_sample_rate, resample_uneven_timeseries) are
-not part of this, nor are decimate's other parameters (the reference fixes ftype, n and zero_phase)."""
+Resampling (mirror of sampling.py:53-83).  resample_uneven_timeseries is linear interpolation, not a Fourier method: records
+[n] or [C, n] with shared uneven timestamps onto np.arange(t[0], t[-1], 1 / rate) by np.interp's rule, one kernel of the
+library (qi_interp_grid), float64 out whatever comes in and NumPy's bits.  resample_with_sample_rate is the Fourier
+resampler, scipy.signal.resample(x, int(n * new_rate / rate)): two hipFFT transforms and one kernel between them
+(qi_resample_fft), float32 records kept in float32.
+
+There is no CPU fallback.  Not part of this: decimate's other parameters (the reference fixes ftype, n and zero_phase),
+scipy.signal.resample's window, domain and complex input, np.interp's left / right / period."""
+import math
 import operator
 import warnings
 from typing import Tuple
@@ -126,3 +133,66 @@ def decimate_timeseries_collection(timeseries_collection, decimation_factor: int
     each must be 28 samples or longer.
     -> decimated signals [C, ceil(n / decimation_factor)]"""
     return _decimate(timeseries_collection, decimation_factor, 2, "timeseries_collection")
+
+
+def even_grid(first_s, last_s, sample_rate_hz):
+    """np.arange(first_s, last_s, 1 / sample_rate_hz) as (start, delta, m): its values are start + i * delta, i < m, with
+    m = max(ceil((last - first) / step), 0) and delta = (first + step) - first -- what NumPy's fill loop computes, which
+    differs from the step itself at epoch-sized timestamps."""
+    first_s, last_s = float(first_s), float(last_s)
+    rate = float(sample_rate_hz)
+    step = 1.0 / rate if rate != 0.0 else math.inf
+    if not (math.isfinite(first_s) and math.isfinite(last_s) and math.isfinite(step) and step > 0.0):
+        raise ValueError(f"no even grid from {first_s} to {last_s} at {sample_rate_hz} Hz: the ends and the rate must be finite, "
+                         "the rate positive")
+    m = max(math.ceil((last_s - first_s) / step), 0)
+    delta = (first_s + step) - first_s
+    if m > 0 and not delta > 0.0:
+        raise ValueError(f"a step of {step} s is lost in the rounding of timestamps near {first_s} s")
+    return first_s, delta, m
+
+
+def resample_uneven_timeseries(timeseries, timestamps_s, new_sample_rate_hz=None):
+    """Resample a time series [n] (or records [C, n] with the same timestamps) with uneven timestamps onto an even grid by
+    linear interpolation (sampling.py:53-68): np.interp(np.arange(t[0], t[-1], 1 / rate), timestamps_s, timeseries).  With
+    new_sample_rate_hz None the rate is the average one, 1 / mean(diff(timestamps_s)): NumPy's for NumPy timestamps; for
+    CUDA timestamps it is evaluated on the device and only the first and last timestamp and the rate come to the host.
+    float32 stays float32 on the way in, anything but float32 and float64 is read as float64; the result is float64.
+    -> (resampled series [m] or [C, m], new sample rate)"""
+    shape = tuple(timeseries.shape) if isinstance(timeseries, torch.Tensor) else np.shape(timeseries)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"timeseries must be [n] or [channels, n], got shape {shape}")
+    tshape = tuple(timestamps_s.shape) if isinstance(timestamps_s, torch.Tensor) else np.shape(timestamps_s)
+    if len(tshape) != 1 or tshape[0] != shape[-1] or tshape[0] < 1:
+        raise ValueError(f"timestamps_s must be 1-D with one timestamp per sample, got shape {tshape} for a timeseries of shape {shape}")
+    if isinstance(timestamps_s, torch.Tensor):
+        t = timestamps_s.to(torch.float64)
+        ends = [t[0], t[-1]]
+        if new_sample_rate_hz is None:
+            ends.append(1 / torch.mean(torch.diff(t)))
+        ends = torch.stack(ends).cpu().tolist()  # the only values that cross to the host
+        first, last = ends[0], ends[1]
+        if new_sample_rate_hz is None:
+            new_sample_rate_hz = ends[2]
+    else:
+        t = np.asarray(timestamps_s, dtype=np.float64)
+        first, last = t[0], t[-1]
+        if new_sample_rate_hz is None:
+            with np.errstate(all="ignore"), warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                new_sample_rate_hz = 1 / np.mean(np.diff(t))
+    start, delta, m = even_grid(first, last, new_sample_rate_hz)
+    return engine.interp_to_grid(timeseries, t, start, delta, m), new_sample_rate_hz
+
+
+def resample_with_sample_rate(timeseries, sample_rate_hz: float, new_sample_rate_hz: float):
+    """Resample a time series [n] (or records [C, n], along the last axis) to a new sample rate as scipy.signal.resample
+    does (sampling.py:71-83), to int(n * new_sample_rate_hz / sample_rate_hz) samples.
+    -> (resampled series, new sample rate)"""
+    shape = tuple(timeseries.shape) if isinstance(timeseries, torch.Tensor) else np.shape(timeseries)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"timeseries must be [n] or [channels, n], got shape {shape}")
+    new_length = int(shape[-1] * new_sample_rate_hz / sample_rate_hz)
+    if new_length < 1:
+        raise ValueError(f"the new length int({shape[-1]} * {new_sample_rate_hz} / {sample_rate_hz}) = {new_length} must be at least 1")
+    return engine.fft_resample(timeseries, new_length), new_sample_rate_hz
