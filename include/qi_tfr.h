@@ -460,6 +460,49 @@ int64_t qi_resample_fft_scratch_bytes(int dtype, int64_t n_channels, int64_t n, 
 int qi_resample_fft(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, int64_t m, void* out,
                     void* scratch, int64_t scratch_bytes, qi_stream stream);
 
+/* ---- integration and differentiation (utilities/calculations.py:16-63, 118-157: scipy.integrate.cumulative_trapezoid with
+ * initial=0, np.gradient with edge_order 1, np.diff) -----------------------------------------------------------------------
+ * Cumulative trapezoid of records y [C][n] (device, dtype).  x NULL: a constant spacing dx; otherwise float64 timestamps
+ * (device), x_stride 0 = [n], shared by all records, x_stride n = [C][n], a row per record (anything else: QI_ERR_ARG).
+ * Term i, 0 <= i < n - 1, in SciPy's order and types, every operation rounded on its own:
+ *   with x:  (x[i+1] - x[i]) * (double)(y[i+1] + y[i]) / 2.0     the sum in dtype first, the rest float64; out is float64
+ *   with dx: (T)dx * (y[i+1] + y[i]) / 2                          all in dtype T, dx rounded to it once; out is in dtype
+ * out [C][n] (device): out[0] = 0, out[i+1] = the sum of the terms 0 .. i.  The terms are SciPy's bits; the order in which
+ * they are added is not NumPy's left-to-right one but a fixed tree that depends on n alone (not on C, on the record's row,
+ * on the grid or on the run), R the result type:
+ *   the terms are cut into tiles of QI_SCAN_TILE; the last tile's missing terms are +0.0;
+ *   lane l (of 256) of a tile sums its terms 16 l .. 16 l + 15 left to right: r_0 = t_0, r_k = r_(k-1) + t_k;
+ *   the 64 lane totals r_15 of a wave go through an inclusive Hillis-Steele scan, steps 1, 2, 4, 8, 16, 32 (at step s
+ *     every lane l >= s takes v_(l-s) + v_l, all at once); e_l = the scanned value of lane l - 1, e_0 = 0; W_w = that of lane 63;
+ *   the four wave totals left to right: o_0 = 0, o_1 = W_0, o_2 = W_0 + W_1, o_3 = o_2 + W_2; the tile's total T = o_3 + W_3;
+ *   the tile totals of a record left to right: c_0 = 0, c_1 = T_0, c_t = c_(t-1) + T_(t-1);
+ *   out[QI_SCAN_TILE t + 16 l + k + 1] = (c_t + (o_w + e_l)) + r_k.
+ * Three kernel launches (tile totals; carries per record; the terms again, the scan and the stores), no atomics, no waiting
+ * of one workgroup for another; the same call gives the same bits.  Any n >= 1 (n = 1: out[0] = 0); n_channels = 0 is a
+ * successful no-op; a refused call writes nothing.
+ * scratch: caller-owned device buffer of qi_cumtrapz_scratch_bytes() bytes ([C][tiles] of float64), aligned to 8 (host only;
+ * negative qi_status for an unknown dtype, n_channels < 0, n < 1 or sizes out of range). */
+#define QI_SCAN_TILE 4096
+int64_t qi_cumtrapz_scratch_bytes(int dtype, int64_t n_channels, int64_t n);
+int qi_cumtrapz(int dtype, int device, const void* y, const void* x, int64_t x_stride, double dx, int64_t n_channels, int64_t n,
+                void* out, void* scratch, int64_t scratch_bytes, qi_stream stream);
+
+/* Derivative of records y [C][n] (device, dtype T); x and x_stride as above; one kernel launch, no scratch; NumPy's bits.
+ * QI_DERIV_GRADIENT (n >= 2, out_offset 0): out [C][n] in dtype.
+ *   x NULL: out[i] = (y[i+1] - y[i-1]) / (T)(2.0 * h) inside, (y[1] - y[0]) / (T)h and (y[n-1] - y[n-2]) / (T)h at the ends.
+ *   with x: dx1 = x[i] - x[i-1], dx2 = x[i+1] - x[i], a = -(dx2) / (dx1 * (dx1 + dx2)), b = (dx2 - dx1) / (dx1 * dx2),
+ *           c = dx1 / (dx2 * (dx1 + dx2)), out[i] = (T)((a * y[i-1] + b * y[i]) + c * y[i+1]) in float64 inside; at the ends
+ *           (T)((double)(y[1] - y[0]) / (x[1] - x[0])) and the same of the last two samples, the difference in dtype.
+ *           (np.gradient itself takes the first form when all x[i+1] - x[i] are equal: that choice is the caller's.)
+ * QI_DERIV_DIFFERENCE (n >= 1): n - 1 values, written to columns out_offset .. out_offset + n - 2 of out [C][n], out_offset 0
+ *   or 1; the column left over (n - 1 or 0: the fill slot) is not written.
+ *   x NULL: (y[i+1] - y[i]) * (T)h in dtype -- h is the FACTOR here (np.diff(y) * sample_rate); out is in dtype.
+ *   with x: (double)(y[i+1] - y[i]) / (x[i+1] - x[i]), the difference in dtype; out is float64.
+ * Equal timestamps divide by zero as in NumPy (inf, NaN).  n_channels = 0 is a successful no-op; a refused call writes nothing. */
+typedef enum { QI_DERIV_GRADIENT = 0, QI_DERIV_DIFFERENCE = 1 } qi_deriv_kind;
+int qi_derivative(int dtype, int device, int kind, const void* y, const void* x, int64_t x_stride, double h, int64_t n_channels,
+                  int64_t n, void* out, int64_t out_offset, qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@ QI_PEAK_SIGMAX, QI_PEAK_SIGMIN, QI_PEAK_SIGABS, QI_PEAK_LOG2, QI_PEAK_LOG2MAX = 
 QI_PEAK_HEIGHT_NONE, QI_PEAK_HEIGHT_ABS, QI_PEAK_HEIGHT_BELOW_MAX, QI_PEAK_HEIGHT_BELOW_RAW_MAX = 0, 1, 2, 3
 PEAKS_TILE = 256  # samples per tile of qi_find_peaks (QI_PEAKS_TILE of include/qi_tfr.h)
 INTERP_TILE, INTERP_KNOTS = 512, 2560  # outputs of a workgroup of qi_interp_grid, knots it stages in LDS (QI_INTERP_TILE, QI_INTERP_KNOTS)
+SCAN_TILE = 4096  # terms of one tile of qi_cumtrapz's summation tree (QI_SCAN_TILE)
+QI_DERIV_GRADIENT, QI_DERIV_DIFFERENCE = 0, 1
 IIR_MAX = 16  # largest order of the (b, a) form, most second-order sections (qi_filtfilt)
 POOL_MEDIAN_MAX = 4096  # longest window the median sorts (qi_pool_panel)
 ROUTE_NOWRAP, ROUTE_SPLIT, ROUTE_BEHIND, ROUTE_F64_ZOOM = 16, 32, 256, 512
@@ -128,6 +130,9 @@ PROTOTYPES = {
     "qi_interp_grid": (_int, [_int, _int, _P, _P, _i64, _i64, _i64, _dbl, _dbl, _i64, _P, _P]),
     "qi_resample_fft_scratch_bytes": (_i64, [_int, _i64, _i64, _i64]),
     "qi_resample_fft": (_int, [_int, _int, _P, _i64, _i64, _i64, _P, _P, _i64, _P]),
+    "qi_cumtrapz_scratch_bytes": (_i64, [_int, _i64, _i64]),
+    "qi_cumtrapz": (_int, [_int, _int, _P, _P, _i64, _dbl, _i64, _i64, _P, _P, _i64, _P]),
+    "qi_derivative": (_int, [_int, _int, _int, _P, _P, _i64, _dbl, _i64, _i64, _P, _i64, _P]),
 }
 
 _lib = None

@@ -818,6 +818,95 @@ def fft_resample(sig, m):
     return finish(out, was_numpy, was_1d)
 
 
+def _records_and_timestamps(sig, timestamps, what):
+    """Shape checks shared by cumulative_trapezoid and derivative -> (records [C, n] on the device, timestamps float64 on
+    the device or None, its stride for the C call, was_numpy, was_1d)."""
+    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"{what} must be 1-D [n] or 2-D [channels, n], got shape {shape}")
+    n = shape[-1]
+    if n < 1:
+        raise ValueError("a record must hold at least one sample")
+    if timestamps is not None:
+        tshape = tuple(timestamps.shape) if isinstance(timestamps, torch.Tensor) else np.shape(timestamps)
+        if tshape != (n,) and not (len(shape) == 2 and tshape == shape):
+            raise ValueError(f"timestamps must be [n] or match the records' shape {shape}, got shape {tshape}")
+    _lib.require_gpu()
+    x, was_numpy, was_1d = as_signal(sig)
+    t = None
+    if timestamps is not None:
+        if not isinstance(timestamps, torch.Tensor):
+            timestamps = torch.from_numpy(np.ascontiguousarray(timestamps, dtype=np.float64))
+        t = timestamps.to(device=x.device, dtype=torch.float64).contiguous()
+    return x, t, (n if t is not None and t.dim() == 2 else 0), was_numpy, was_1d
+
+
+def cumulative_trapezoid(sig, timestamps=None, dx=1.0):
+    """scipy.integrate.cumulative_trapezoid(sig, x=timestamps | dx=dx, initial=0) along the last axis of records [n] or
+    [C, n] (qi_cumtrapz).  timestamps [n], shared by all records, or [C, n], a row per record, read as float64: the result
+    is float64 whatever the records' type, as SciPy's.  Without them the spacing is the constant dx and float32 records
+    give a float32 result (dx rounded to float32 once: SciPy's result for a Python float).  Anything but float32 and
+    float64 is read as float64.  The terms are SciPy's bit for bit; they are added in the fixed tree of include/qi_tfr.h,
+    which depends on the record length alone -- a record gives the same bits alone and in any batch -- not in NumPy's
+    left-to-right order.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out on the current stream, nothing
+    synchronised; the call owns its scratch (one value per 4096 samples and record)."""
+    dx = float(dx)
+    x, t, stride, was_numpy, was_1d = _records_and_timestamps(sig, timestamps, "signal")
+    lib = _lib.load()
+    dev = x.device
+    n_ch, n = x.shape
+    out = torch.empty((n_ch, n), dtype=torch.float64 if t is not None else x.dtype, device=dev)
+    if n_ch > 0:
+        code = _lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32
+        nbytes = int(lib.qi_cumtrapz_scratch_bytes(code, n_ch, n))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.qi_cumtrapz(code, dev.index, _lib.ptr(x), _lib.ptr(t), stride, dx, n_ch, n, _lib.ptr(out), _lib.ptr(scratch),
+                                       nbytes, _lib.stream_ptr(dev)))
+    return finish(out, was_numpy, was_1d)
+
+
+DERIVATIVE_KINDS = {"gradient": _lib.QI_DERIV_GRADIENT, "difference": _lib.QI_DERIV_DIFFERENCE}
+
+
+def derivative(sig, timestamps=None, h=1.0, kind="gradient", fill_at="end"):
+    """Derivative of records [n] or [C, n] along the last axis (qi_derivative), NumPy's bits.  timestamps as in
+    cumulative_trapezoid.
+    kind "gradient": np.gradient(sig, h) or np.gradient(sig, timestamps) with edge_order 1, in the records' type (float32
+    records over float64 timestamps are computed in float64 and stored as float32, as NumPy does).  The timestamps take
+    NumPy's formula for uneven spacing; np.gradient itself switches to the even one when all their differences are equal
+    (utilities.calculations.derivative_with_gradient_timestamps_s looks and passes h then).  At least two samples.
+    kind "difference": np.diff(sig) * h -- h is the factor here, the sample rate, as the reference multiplies by it -- in the
+    records' type, or np.diff(sig) / np.diff(timestamps) in float64: n - 1 values in a result of n columns, the first of
+    them ("start") or the last ("end", fill_at) holding 0 for the caller's fill.
+    Anything but float32 and float64 is read as float64.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out on the
+    current stream, nothing synchronised."""
+    if kind not in DERIVATIVE_KINDS:
+        raise ValueError(f"kind must be one of {sorted(DERIVATIVE_KINDS)}, got {kind!r}")
+    if fill_at not in ("start", "end"):
+        raise ValueError(f"fill_at must be 'start' or 'end', got {fill_at!r}")
+    h = float(h)
+    difference = kind == "difference"
+    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
+    if not difference and len(shape) in (1, 2) and shape[-1] == 1:
+        raise ValueError("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are required.")
+    x, t, stride, was_numpy, was_1d = _records_and_timestamps(sig, timestamps, "signal")
+    lib = _lib.load()
+    dev = x.device
+    n_ch, n = x.shape
+    out =torch.empty((n_ch, n), dtype=torch.float64 if difference and t is not None else x.dtype, device=dev)
+    offset = 1 if difference and fill_at == "start" else 0
+    if n_ch > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.qi_derivative(_lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32, dev.index, DERIVATIVE_KINDS[kind],
+                                         _lib.ptr(x), _lib.ptr(t), stride, h, n_ch, n, _lib.ptr(out), offset, _lib.stream_ptr(dev)))
+        if difference:
+            out[:, 0 if offset else n - 1] = 0
+    return finish(out, was_numpy, was_1d)
+
+
 # What the reference-signature wrappers hand back to NumPy callers for float32 records.  The reference returns
 # complex128 panels (float64 bits) whatever the record's dtype (styx_cwt.py:195-198, styx_stx.py:228,
 # cwt_atoms.py:408): "reference" computes in float32 and widens on the way out, so a drop-in caller sees the
