@@ -200,3 +200,26 @@ def ptr(t):
 
 def stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def dtype_code(dtype):
+    """QI_F64 for torch.float64, QI_F32 otherwise (the callers hold float32 or float64 by then: engine.as_signal)."""
+    return QI_F64 if dtype == torch.float64 else QI_F32
+
+
+def scratch(query, device, *args):
+    """Scratch of one plan-less call -> (uint8 tensor on `device`, byte count for the call).  query: the library's
+    qi_*_scratch_bytes to ask with `args`; a request it refuses (a negative answer) raises QiError.  The tensor holds at
+    least one byte, so `ptr` of it is never null for a request the library accepts with no scratch at all."""
+    nbytes = int(query(*args))
+    if nbytes < 0:
+        check(nbytes)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device), nbytes
+
+
+def call(fn, device, *args):
+    """A plan-less entry point `fn` on the current stream of `device`: every one of them takes the stream last.  torch gets
+    the device as its index: an int is taken as it is, a torch.device is examined again by each of the two calls."""
+    index = device.index
+    with torch.cuda.device(index):
+        check(fn(*args, stream_ptr(index)))

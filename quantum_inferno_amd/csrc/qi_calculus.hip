@@ -225,8 +225,6 @@ __global__ void __launch_bounds__(kDvThreads) k_derivative(DerivArgs a) {
 
 int64_t scan_tiles(int64_t n) { return n > 1 ? ceil_div(n - 1, kScTile) : 1; }
 
-bool aligned(const void* p, uintptr_t size) { return (reinterpret_cast<uintptr_t>(p) & (size - 1)) == 0; }
-
 template <typename Y, bool X>
 int launch_scan(const ScanArgs& a, int64_t C, hipStream_t st) {
   using R = typename ScanTypes<Y, X>::R;
@@ -258,9 +256,7 @@ using namespace qi;
 extern "C" {
 
 int64_t qi_cumtrapz_scratch_bytes(int dtype, int64_t n_channels, int64_t n) {
-  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
-  QI_REQUIRE(n_channels >= 0, "bad record count %lld", (long long)n_channels);
-  QI_REQUIRE(n >= 1, "bad record length %lld", (long long)n);
+  QI_TRY(require_records(dtype, n_channels, n, 0));
   QI_REQUIRE(n < (1ll << 40) && n_channels < (1ll << 31) && n_channels * scan_tiles(n) < (1ll << 31), "request too large");
   // the tile totals, then carries, in the result type: float64 whenever timestamps are given
   return (int64_t)host::align_up((size_t)(n_channels > 0 ? n_channels : 1) * (size_t)scan_tiles(n) * 8);
@@ -270,12 +266,12 @@ int qi_cumtrapz(int dtype, int device, const void* y, const void* x, int64_t x_s
                 void* out, void* scratch, int64_t scratch_bytes, qi_stream stream) {
   const int64_t need = qi_cumtrapz_scratch_bytes(dtype, n_channels, n);
   if (need < 0) return (int)need;
-  QI_REQUIRE(x_stride == 0 || x_stride == n, "x_stride must be 0 (shared timestamps or none) or n, got %lld", (long long)x_stride);
+  QI_TRY(require_timestamp_stride("x_stride", x_stride, n));
   QI_REQUIRE(x || x_stride == 0, "x_stride must be 0 without timestamps");
   if (n_channels == 0) return QI_OK;
   QI_REQUIRE(y && out && scratch, "null argument");
-  QI_REQUIRE(scratch_bytes >= need, "scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
-  const uintptr_t esz = dtype == QI_F64 ? 8 : 4;
+  QI_TRY(require_scratch(scratch_bytes, need));
+  const size_t esz = elem_size(dtype);
   QI_REQUIRE(aligned(y, esz) && aligned(x, 8) && aligned(out, x ? 8 : esz) && aligned(scratch, 8),
              "y, x, out and scratch must be aligned to their element size");
   DeviceGuard g(device);
@@ -298,12 +294,10 @@ int qi_cumtrapz(int dtype, int device, const void* y, const void* x, int64_t x_s
 
 int qi_derivative(int dtype, int device, int kind, const void* y, const void* x, int64_t x_stride, double h, int64_t n_channels,
                   int64_t n, void* out, int64_t out_offset, qi_stream stream) {
-  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_TRY(require_records(dtype, n_channels, n, 0));
   QI_REQUIRE(kind == QI_DERIV_GRADIENT || kind == QI_DERIV_DIFFERENCE, "bad kind %d", kind);
-  QI_REQUIRE(n_channels >= 0, "bad record count %lld", (long long)n_channels);
-  QI_REQUIRE(n >= 1, "bad record length %lld", (long long)n);
   QI_REQUIRE(kind != QI_DERIV_GRADIENT || n >= 2, "bad record length %lld: a gradient needs two samples", (long long)n);
-  QI_REQUIRE(x_stride == 0 || x_stride == n, "x_stride must be 0 (shared timestamps or none) or n, got %lld", (long long)x_stride);
+  QI_TRY(require_timestamp_stride("x_stride", x_stride, n));
   QI_REQUIRE(x || x_stride == 0, "x_stride must be 0 without timestamps");
   QI_REQUIRE(out_offset == 0 || (kind == QI_DERIV_DIFFERENCE && out_offset == 1),
              "out_offset must be 0, or 1 for a difference, got %lld", (long long)out_offset);
@@ -312,7 +306,7 @@ int qi_derivative(int dtype, int device, int kind, const void* y, const void* x,
   QI_REQUIRE(n < (1ll << 40) && n_channels < (1ll << 31) && n_channels * chunks < (1ll << 31), "request too large");
   if (n_channels == 0) return QI_OK;
   QI_REQUIRE(y && out, "null argument");
-  const uintptr_t esz = dtype == QI_F64 ? 8 : 4;
+  const size_t esz = elem_size(dtype);
   QI_REQUIRE(aligned(y, esz) && aligned(x, 8) && aligned(out, x && kind == QI_DERIV_DIFFERENCE ? 8 : esz),
              "y, x and out must be aligned to their element size");
   if (count == 0) return QI_OK;

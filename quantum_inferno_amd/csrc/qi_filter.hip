@@ -294,9 +294,8 @@ int qi_filtfilt(int dtype, int device, const void* sig, int64_t n_channels, int6
   QI_REQUIRE(sig && out && scratch && coef && zi, "null argument");
   const int64_t need = qi_filtfilt_scratch_bytes(n_channels, n, edge);
   if (need < 0) return (int)need;
-  QI_REQUIRE(scratch_bytes >= need, "scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
-  QI_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
-             "scratch and out must be aligned to 8 bytes");
+  QI_TRY(require_scratch(scratch_bytes, need));
+  QI_REQUIRE(aligned(scratch, 8) && aligned(out, 8), "scratch and out must be aligned to 8 bytes");
   IirTables<double> tab{};
   int N;
   if (form == QI_IIR_BA) {
@@ -343,17 +342,15 @@ int64_t qi_decimate_scratch_bytes(int dtype, int64_t n_channels, int64_t n, int6
 int qi_decimate(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, int64_t q, int32_t sections,
                 const void* sos, const void* zi, int64_t edge, void* out, void* scratch, int64_t scratch_bytes,
                 qi_stream stream) {
-  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
   QI_REQUIRE(sig && out && scratch && sos && zi, "null argument");
   const int64_t need = qi_decimate_scratch_bytes(dtype, n_channels, n, edge);
   if (need < 0) return (int)need;
   const int64_t m = qi_decimate_columns(n, q);
   if (m < 0) return (int)m;
-  QI_REQUIRE(scratch_bytes >= need, "scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
-  const uintptr_t mask = dtype == QI_F64 ? 7 : 3;
-  QI_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & mask) == 0 && (reinterpret_cast<uintptr_t>(out) & mask) == 0 &&
-                 (reinterpret_cast<uintptr_t>(sig) & mask) == 0,
-             "sig, scratch and out must be aligned to %d bytes", (int)mask + 1);
+  QI_TRY(require_scratch(scratch_bytes, need));
+  const size_t esz = elem_size(dtype);
+  QI_REQUIRE(aligned(scratch, esz) && aligned(out, esz) && aligned(sig, esz), "sig, scratch and out must be aligned to %d bytes",
+             (int)esz);
   QI_REQUIRE(sections >= 1 && sections <= kIirMax, "%d sections: 1 .. %d", (int)sections, kIirMax);
   auto run = [&](auto zero) -> int {
     using T = decltype(zero);

@@ -37,6 +37,30 @@ template <typename F>
 inline auto by_dtype(int dtype, F&& f) {
   return dtype == QI_F64 ? f(double{}) : f(float{});
 }
+inline size_t elem_size(int dtype) { return dtype == QI_F64 ? 8 : 4; }
+// p lies on a multiple of `size` bytes (a power of two); a null pointer counts as aligned: optional arguments pass
+inline bool aligned(const void* p, size_t size) { return (reinterpret_cast<uintptr_t>(p) & (size - 1)) == 0; }
+
+// ---- the opening of a plan-less record call (records [n_channels][n]; qi_filter, qi_peaks, qi_resample, qi_calculus): each
+// sets the last-error text and returns QI_ERR_ARG as QI_REQUIRE does, for the caller's QI_TRY.  What depends on an op's own
+// grid arithmetic ("request too large") or tables stays in its file.
+// min_records 0: an op that takes an empty batch as a successful no-op
+inline int require_records(int dtype, int64_t n_channels, int64_t n, int64_t min_records = 1) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(n_channels >= min_records, "bad record count %lld", (long long)n_channels);
+  QI_REQUIRE(n >= 1, "bad record length %lld", (long long)n);
+  return QI_OK;
+}
+inline int require_scratch(int64_t scratch_bytes, int64_t need) {
+  QI_REQUIRE(scratch_bytes >= need, "scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
+  return QI_OK;
+}
+// timestamps: a row per record (stride n), or stride 0 -- one row shared by all records, or none where an op can do without;
+// `name`: the argument, for the message
+inline int require_timestamp_stride(const char* name, int64_t stride, int64_t n) {
+  QI_REQUIRE(stride == 0 || stride == n, "%s must be 0 (shared timestamps or none) or n, got %lld", name, (long long)stride);
+  return QI_OK;
+}
 
 // ---- hipFFT plan cache (one per qi_plan, plus a process-wide one for the plan-less STFT entry) ----
 struct FftCache {

@@ -422,9 +422,7 @@ using namespace qi;
 extern "C" {
 
 int64_t qi_peaks_scratch_bytes(int dtype, int64_t n_channels, int64_t n) {
-  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
-  QI_REQUIRE(n_channels >= 1, "bad record count %lld", (long long)n_channels);
-  QI_REQUIRE(n >= 1, "bad record length %lld", (long long)n);
+  QI_TRY(require_records(dtype, n_channels, n));
   QI_REQUIRE(n < (1ll << 40) && n_channels < (1ll << 31) / ceil_div(peak_tiles(n), kPkGroup), "request too large");
   return (n_channels * peak_tiles(n) * (kPkPart + kPkSumm + 1) + n_channels * kPkRec) * (int64_t)sizeof(double);
 }
@@ -432,7 +430,6 @@ int64_t qi_peaks_scratch_bytes(int dtype, int64_t n_channels, int64_t n) {
 int qi_find_peaks(int dtype, int device, const void* sig, int64_t n_channels, int64_t n, int scale, double eps, int height_kind,
                   double height, void* scaled, int64_t* positions, double* values, int64_t capacity, int64_t* counts,
                   void* scratch, int64_t scratch_bytes, qi_stream stream) {
-  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
   QI_REQUIRE(scale >= QI_PEAK_SIGMAX && scale <= QI_PEAK_LOG2MAX, "bad scaling %d", scale);
   QI_REQUIRE(height_kind >= QI_PEAK_HEIGHT_NONE && height_kind <= QI_PEAK_HEIGHT_BELOW_RAW_MAX, "bad height kind %d", height_kind);
   QI_REQUIRE(sig && counts && scratch, "null argument");
@@ -440,11 +437,9 @@ int qi_find_peaks(int dtype, int device, const void* sig, int64_t n_channels, in
   QI_REQUIRE(capacity > 0 || !positions, "positions given with a capacity of 0");
   const int64_t need = qi_peaks_scratch_bytes(dtype, n_channels, n);
   if (need < 0) return (int)need;
-  QI_REQUIRE(scratch_bytes >= need, "scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
+  QI_TRY(require_scratch(scratch_bytes, need));
   const bool log = scale == QI_PEAK_LOG2 || scale == QI_PEAK_LOG2MAX;
-  const uintptr_t mask = dtype == QI_F64 ? 7 : 3, smask = dtype == QI_F64 || log ? 7 : 3;
-  QI_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0 && (reinterpret_cast<uintptr_t>(sig) & mask) == 0 &&
-                 (reinterpret_cast<uintptr_t>(scaled) & smask) == 0,
+  QI_REQUIRE(aligned(scratch, 8) && aligned(sig, elem_size(dtype)) && aligned(scaled, log ? 8 : elem_size(dtype)),
              "scratch must be aligned to 8 bytes, sig and scaled to their element size");
   PeakArgs a{};
   a.sig = sig;

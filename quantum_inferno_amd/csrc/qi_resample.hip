@@ -237,7 +237,7 @@ int resample_locked_fft(int device, Transform&& transform) {
 struct ResampleScratch {
   size_t copy, spec_in, spec_out, total;
   ResampleScratch(int dtype, int64_t C, int64_t n, int64_t m) {
-    const size_t esz = dtype == QI_F64 ? 8 : 4;
+    const size_t esz = elem_size(dtype);
     copy = 0;  // the records (the real-to-complex transform may overwrite its input)
     spec_in = copy + host::align_up((size_t)C * n * esz);
     spec_out = spec_in + host::align_up((size_t)C * (n / 2 + 1) * 2 * esz);
@@ -255,23 +255,19 @@ extern "C" {
 
 int qi_interp_grid(int dtype, int device, const void* values, const void* knots, int64_t knot_stride, int64_t n_channels,
                    int64_t n, double start, double delta, int64_t m, void* out, qi_stream stream) {
-  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
-  QI_REQUIRE(n_channels >= 1, "bad record count %lld", (long long)n_channels);
-  QI_REQUIRE(n >= 1, "bad record length %lld", (long long)n);
+  QI_TRY(require_records(dtype, n_channels, n));
   QI_REQUIRE(m >= 0, "bad output length %lld", (long long)m);
-  QI_REQUIRE(knot_stride == 0 || knot_stride == n, "knot_stride must be 0 (shared timestamps) or n, got %lld", (long long)knot_stride);
+  QI_TRY(require_timestamp_stride("knot_stride", knot_stride, n));
   QI_REQUIRE(std::isfinite(start), "start must be finite");
   QI_REQUIRE(std::isfinite(delta) && delta > 0.0, "delta must be finite and positive");
   QI_REQUIRE(values && knots && out, "null argument");
   QI_REQUIRE(n < (1ll << 40) && m < (1ll << 40), "request too large");
-  const uintptr_t mask = dtype == QI_F64 ? 7 : 3;
-  QI_REQUIRE((reinterpret_cast<uintptr_t>(values) & mask) == 0 && (reinterpret_cast<uintptr_t>(knots) & 7) == 0 &&
-                 (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+  const size_t esz = elem_size(dtype);
+  QI_REQUIRE(aligned(values, esz) && aligned(knots, 8) && aligned(out, 8),
              "values, knots and out must be aligned to their element size");
   if (m == 0) return QI_OK;
   DeviceGuard g(device);
   QI_REQUIRE(g.ok, "cannot select device %d", device);
-  const size_t esz = dtype == QI_F64 ? 8 : 4;
   for (int64_t c0 = 0; c0 < n_channels; c0 += kItMaxRecords) {  // (one launch up to 65535 records: the grid's second extent)
     const int64_t cn = n_channels - c0 < kItMaxRecords ? n_channels - c0 : kItMaxRecords;
     InterpArgs a{};
@@ -292,9 +288,7 @@ int qi_interp_grid(int dtype, int device, const void* values, const void* knots,
 }
 
 int64_t qi_resample_fft_scratch_bytes(int dtype, int64_t n_channels, int64_t n, int64_t m) {
-  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
-  QI_REQUIRE(n_channels >= 1, "bad record count %lld", (long long)n_channels);
-  QI_REQUIRE(n >= 1, "bad record length %lld", (long long)n);
+  QI_TRY(require_records(dtype, n_channels, n));
   QI_REQUIRE(m >= 1, "bad output length %lld", (long long)m);
   QI_REQUIRE(n < (1ll << 31) && m < (1ll << 31) && n_channels < (1ll << 31) && n_channels * (n > m ? n : m) < (1ll << 40),
              "request too large");
@@ -306,8 +300,8 @@ int qi_resample_fft(int dtype, int device, const void* sig, int64_t n_channels, 
   const int64_t need = qi_resample_fft_scratch_bytes(dtype, n_channels, n, m);
   if (need < 0) return (int)need;
   QI_REQUIRE(sig && out && scratch, "null argument");
-  QI_REQUIRE(scratch_bytes >= need, "scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
-  QI_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "scratch must be aligned to 16 bytes");
+  QI_TRY(require_scratch(scratch_bytes, need));
+  QI_REQUIRE(aligned(scratch, 16), "scratch must be aligned to 16 bytes");
   DeviceGuard g(device);
   QI_REQUIRE(g.ok, "cannot select device %d", device);
   hipStream_t st = (hipStream_t)stream;

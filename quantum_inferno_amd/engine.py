@@ -76,10 +76,8 @@ def _log2_rows(x, eps=0.0):
     out = torch.empty_like(x)
     if x.numel() == 0:
         return out
-    with torch.cuda.device(x.device):
-        _lib.check(lib.qi_log2_offset(_lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32, x.device.index, _lib.ptr(x),
-                                      _lib.ptr(out), x.shape[0], x.numel() // x.shape[0], float(eps), None,
-                                      _lib.stream_ptr(x.device)))
+    _lib.call(lib.qi_log2_offset, x.device, _lib.dtype_code(x.dtype), x.device.index, _lib.ptr(x), _lib.ptr(out), x.shape[0],
+              x.numel() // x.shape[0], float(eps), None)
     return out
 
 
@@ -181,7 +179,7 @@ class TfrPlan:
             engine = _lib.QI_ENGINE_HIPFFT
         desc = _lib.PlanDesc(
             n=self.n,
-            dtype=_lib.QI_F64 if self.rdtype == torch.float64 else _lib.QI_F32,
+            dtype=_lib.dtype_code(self.rdtype),
             device=self.device.index,
             engine=engine,
             flags=0,
@@ -434,7 +432,7 @@ class TfrPlan:
         stats = torch.zeros((n_ch, 4), dtype=torch.float64, device=self.device)
         if windows == 0 or n_ch == 0:
             return strips, sums[:, :, 1].contiguous(), stats
-        code = _lib.QI_F64 if self.rdtype == torch.float64 else _lib.QI_F32
+        code = _lib.dtype_code(self.rdtype)
         mean, peak = strips.get("average"), strips.get("max")
         for c0, c1, panel in self._staged_panels(which, sig, True, power_scale, 0.0, tile_bytes):
             with torch.cuda.device(self.device):
@@ -584,6 +582,34 @@ def gabor_atoms(n, p_re, p_im, omega, amp, device=None, x=None):
     return out
 
 
+# ---- plan-less record calls: records [n] or [C, n] in, one library call on the current stream, `finish` out ----
+def _record_shape(a, what="signal", nonempty=True):
+    """Shape (n,) or (C, n) of records, NumPy or tensor, checked before anything needs the device; n is its last entry."""
+    shape = tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"{what} must be 1-D [n] or 2-D [channels, n], got shape {shape}")
+    if nonempty and shape[-1] < 1:
+        raise ValueError("a record must hold at least one sample")
+    return shape
+
+
+def _records_and_timestamps(sig, timestamps, what="signal", shape=None):
+    """Shape checks, the library and the uploads shared by interp_to_grid, cumulative_trapezoid and derivative -> (library,
+    records [C, n] on the device, timestamps float64 on the device or None, its stride for the C call, was_numpy, was_1d)."""
+    shape = shape or _record_shape(sig, what)  # (shape: of a caller that has checked the records already)
+    n = shape[-1]
+    if timestamps is not None and tuple(np.shape(timestamps)) not in ((n,), shape):
+        raise ValueError(f"timestamps must be [n] or match the records' shape {shape}, got shape {tuple(np.shape(timestamps))}")
+    lib = _lib.require_gpu()
+    x, was_numpy, was_1d = as_signal(sig)
+    t = None
+    if timestamps is not None:
+        if not isinstance(timestamps, torch.Tensor):
+            timestamps = torch.from_numpy(np.ascontiguousarray(timestamps, dtype=np.float64))
+        t = timestamps.to(device=x.device, dtype=torch.float64).contiguous()
+    return lib, x, t, (n if t is not None and t.dim() == 2 else 0), was_numpy, was_1d
+
+
 _IIR_FORMS = {"ba": _lib.QI_IIR_BA, "sos": _lib.QI_IIR_SOS, _lib.QI_IIR_BA: _lib.QI_IIR_BA, _lib.QI_IIR_SOS: _lib.QI_IIR_SOS}
 
 
@@ -617,10 +643,7 @@ def zero_phase_filter(sig, form, coef, zi, edge, taper=None):
         if not (coef[:, 3] == 1.0).all():
             raise ValueError("sos[:, 3] should be all ones")
     edge = int(edge)
-    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
-    if len(shape) not in (1, 2):
-        raise ValueError(f"signal must be 1-D [n] or 2-D [channels, n], got shape {shape}")
-    n = shape[-1]
+    n = _record_shape(sig, nonempty=False)[-1]
     if edge < 0 or n <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
     if taper is not None and tuple(taper.shape) != (n,):
@@ -636,14 +659,9 @@ def zero_phase_filter(sig, form, coef, zi, edge, taper=None):
         if not isinstance(taper, torch.Tensor):
             taper = torch.from_numpy(np.ascontiguousarray(taper, dtype=np.float64))
         taper = taper.to(device=dev, dtype=torch.float64).contiguous()
-    nbytes = int(lib.qi_filtfilt_scratch_bytes(n_ch, n, edge))
-    if nbytes < 0:
-        _lib.check(nbytes)
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.qi_filtfilt(_lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32, dev.index, _lib.ptr(x), n_ch, n,
-                                   _lib.ptr(taper), code, sections, order, coef.ctypes.data_as(_lib._D), zi.ctypes.data_as(_lib._D),
-                                   edge, _lib.ptr(out), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)))
+    scratch, nbytes = _lib.scratch(lib.qi_filtfilt_scratch_bytes, dev, n_ch, n, edge)
+    _lib.call(lib.qi_filtfilt, dev, _lib.dtype_code(x.dtype), dev.index, _lib.ptr(x), n_ch, n, _lib.ptr(taper), code, sections, order,
+              coef.ctypes.data_as(_lib._D), zi.ctypes.data_as(_lib._D), edge, _lib.ptr(out), _lib.ptr(scratch), nbytes)
     return finish(out, was_numpy, was_1d)
 
 
@@ -660,10 +678,7 @@ def zero_phase_decimate(sig, q, sos, zi, edge):
     if q < 1:
         raise ValueError(f"the decimation factor must be a positive integer, got {q}")
     edge = int(edge)
-    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
-    if len(shape) not in (1, 2):
-        raise ValueError(f"signal must be 1-D [n] or 2-D [channels, n], got shape {shape}")
-    n = shape[-1]
+    n = _record_shape(sig, nonempty=False)[-1]
     if edge < 0 or n <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
     sos = np.asarray(sos)
@@ -684,14 +699,10 @@ def zero_phase_decimate(sig, q, sos, zi, edge):
     out = torch.empty((n_ch, -(-n // q)), dtype=x.dtype, device=dev)
     if n_ch == 0:
         return finish(out, was_numpy, was_1d)
-    code = _lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32
-    nbytes = int(lib.qi_decimate_scratch_bytes(code, n_ch, n, edge))
-    if nbytes < 0:
-        _lib.check(nbytes)
-    scratch = torch.empty(nbytes // x.element_size(), dtype=x.dtype, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.qi_decimate(code, dev.index, _lib.ptr(x), n_ch, n, q, sos.shape[0], sos.ctypes.data, zi.ctypes.data, edge,
-                                   _lib.ptr(out), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)))
+    code = _lib.dtype_code(x.dtype)
+    scratch, nbytes = _lib.scratch(lib.qi_decimate_scratch_bytes, dev, code, n_ch, n, edge)
+    _lib.call(lib.qi_decimate, dev, code, dev.index, _lib.ptr(x), n_ch, n, q, sos.shape[0], sos.ctypes.data, zi.ctypes.data, edge,
+              _lib.ptr(out), _lib.ptr(scratch), nbytes)
     return finish(out, was_numpy, was_1d)
 
 
@@ -716,12 +727,7 @@ def find_peaks(sig, scale, height_kind="none", height=0.0, want_scaled=False, ca
     if height_kind not in PEAK_HEIGHTS:
         raise ValueError(f"height_kind must be one of {sorted(PEAK_HEIGHTS)}, got {height_kind!r}")
     height = float(height)
-    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
-    if len(shape) not in (1, 2):
-        raise ValueError(f"signal must be 1-D [n] or 2-D [channels, n], got shape {shape}")
-    n = shape[-1]
-    if n < 1:
-        raise ValueError("a record must hold at least one sample")
+    n = _record_shape(sig)[-1]
     capacity = (n - 1) // 2 if capacity is None else operator.index(capacity)
     if capacity < 0:
         raise ValueError(f"capacity must not be negative, got {capacity}")
@@ -735,16 +741,11 @@ def find_peaks(sig, scale, height_kind="none", height=0.0, want_scaled=False, ca
     counts = torch.zeros((n_ch,), dtype=torch.int64, device=dev)
     scaled = torch.empty((n_ch, n), dtype=torch.float64 if log else x.dtype, device=dev) if want_scaled else None
     if n_ch > 0:
-        code = _lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32
-        nbytes = int(lib.qi_peaks_scratch_bytes(code, n_ch, n))
-        if nbytes < 0:
-            _lib.check(nbytes)
-        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.qi_find_peaks(code, dev.index, _lib.ptr(x), n_ch, n, PEAK_SCALES[scale], float(scales.EPSILON64),
-                                         PEAK_HEIGHTS[height_kind], height, _lib.ptr(scaled),
-                                         _lib.ptr(positions) if capacity else None, _lib.ptr(values) if capacity else None,
-                                         capacity, _lib.ptr(counts), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev)))
+        code = _lib.dtype_code(x.dtype)
+        scratch, nbytes = _lib.scratch(lib.qi_peaks_scratch_bytes, dev, code, n_ch, n)
+        _lib.call(lib.qi_find_peaks, dev, code, dev.index, _lib.ptr(x), n_ch, n, PEAK_SCALES[scale], float(scales.EPSILON64),
+                  PEAK_HEIGHTS[height_kind], height, _lib.ptr(scaled), _lib.ptr(positions) if capacity else None,
+                  _lib.ptr(values) if capacity else None, capacity, _lib.ptr(counts), _lib.ptr(scratch), nbytes)
     return (positions, values, counts, scaled) if want_scaled else (positions, values, counts)
 
 
@@ -763,27 +764,15 @@ def interp_to_grid(values, timestamps, start, delta, m):
         raise ValueError(f"start must be finite, got {start}")
     if not (np.isfinite(delta) and delta > 0.0):
         raise ValueError(f"delta must be finite and positive, got {delta}")
-    shape = tuple(values.shape) if isinstance(values, torch.Tensor) else np.shape(values)
-    tshape = tuple(timestamps.shape) if isinstance(timestamps, torch.Tensor) else np.shape(timestamps)
-    if len(shape) not in (1, 2):
-        raise ValueError(f"values must be 1-D [n] or 2-D [channels, n], got shape {shape}")
-    n = shape[-1]
-    if n < 1:
-        raise ValueError("a record must hold at least one sample")
-    if tshape != (n,) and not (len(shape) == 2 and tshape == shape):
-        raise ValueError(f"timestamps must be [n] or match values' shape {shape}, got shape {tshape}")
-    lib = _lib.require_gpu()
-    x, was_numpy, was_1d = as_signal(values)
+    if timestamps is None:
+        raise ValueError("timestamps must be given: [n] or the records' shape")
+    lib, x, t, stride, was_numpy, was_1d = _records_and_timestamps(values, timestamps, "values")
     dev = x.device
-    if not isinstance(timestamps, torch.Tensor):
-        timestamps = torch.from_numpy(np.ascontiguousarray(timestamps, dtype=np.float64))
-    t = timestamps.to(device=dev, dtype=torch.float64).contiguous()
-    n_ch = x.shape[0]
+    n_ch, n = x.shape
     out = torch.empty((n_ch, m), dtype=torch.float64, device=dev)
     if n_ch > 0 and m > 0:
-        with torch.cuda.device(dev):
-            _lib.check(lib.qi_interp_grid(_lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32, dev.index, _lib.ptr(x), _lib.ptr(t),
-                                          n if t.dim() == 2 else 0, n_ch, n, start, delta, m, _lib.ptr(out), _lib.stream_ptr(dev)))
+        _lib.call(lib.qi_interp_grid, dev, _lib.dtype_code(x.dtype), dev.index, _lib.ptr(x), _lib.ptr(t), stride, n_ch, n, start,
+                  delta, m, _lib.ptr(out))
     return finish(out, was_numpy, was_1d)
 
 
@@ -795,50 +784,17 @@ def fft_resample(sig, m):
     m = operator.index(m)
     if m < 1:
         raise ValueError(f"the new length must be at least 1, got {m}")
-    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
-    if len(shape) not in (1, 2):
-        raise ValueError(f"signal must be 1-D [n] or 2-D [channels, n], got shape {shape}")
-    n = shape[-1]
-    if n < 1:
-        raise ValueError("a record must hold at least one sample")
+    n = _record_shape(sig)[-1]
     lib = _lib.require_gpu()
     x, was_numpy, was_1d = as_signal(sig)
     dev = x.device
     n_ch = x.shape[0]
     out = torch.empty((n_ch, m), dtype=x.dtype, device=dev)
     if n_ch > 0:
-        code = _lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32
-        nbytes = int(lib.qi_resample_fft_scratch_bytes(code, n_ch, n, m))
-        if nbytes < 0:
-            _lib.check(nbytes)
-        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.qi_resample_fft(code, dev.index, _lib.ptr(x), n_ch, n, m, _lib.ptr(out), _lib.ptr(scratch), nbytes,
-                                           _lib.stream_ptr(dev)))
+        code = _lib.dtype_code(x.dtype)
+        scratch, nbytes = _lib.scratch(lib.qi_resample_fft_scratch_bytes, dev, code, n_ch, n, m)
+        _lib.call(lib.qi_resample_fft, dev, code, dev.index, _lib.ptr(x), n_ch, n, m, _lib.ptr(out), _lib.ptr(scratch), nbytes)
     return finish(out, was_numpy, was_1d)
-
-
-def _records_and_timestamps(sig, timestamps, what):
-    """Shape checks shared by cumulative_trapezoid and derivative -> (records [C, n] on the device, timestamps float64 on
-    the device or None, its stride for the C call, was_numpy, was_1d)."""
-    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
-    if len(shape) not in (1, 2):
-        raise ValueError(f"{what} must be 1-D [n] or 2-D [channels, n], got shape {shape}")
-    n = shape[-1]
-    if n < 1:
-        raise ValueError("a record must hold at least one sample")
-    if timestamps is not None:
-        tshape = tuple(timestamps.shape) if isinstance(timestamps, torch.Tensor) else np.shape(timestamps)
-        if tshape != (n,) and not (len(shape) == 2 and tshape == shape):
-            raise ValueError(f"timestamps must be [n] or match the records' shape {shape}, got shape {tshape}")
-    _lib.require_gpu()
-    x, was_numpy, was_1d = as_signal(sig)
-    t = None
-    if timestamps is not None:
-        if not isinstance(timestamps, torch.Tensor):
-            timestamps = torch.from_numpy(np.ascontiguousarray(timestamps, dtype=np.float64))
-        t = timestamps.to(device=x.device, dtype=torch.float64).contiguous()
-    return x, t, (n if t is not None and t.dim() == 2 else 0), was_numpy, was_1d
 
 
 def cumulative_trapezoid(sig, timestamps=None, dx=1.0):
@@ -851,20 +807,15 @@ def cumulative_trapezoid(sig, timestamps=None, dx=1.0):
     left-to-right order.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out on the current stream, nothing
     synchronised; the call owns its scratch (one value per 4096 samples and record)."""
     dx = float(dx)
-    x, t, stride, was_numpy, was_1d = _records_and_timestamps(sig, timestamps, "signal")
-    lib = _lib.load()
+    lib, x, t, stride, was_numpy, was_1d = _records_and_timestamps(sig, timestamps)
     dev = x.device
     n_ch, n = x.shape
     out = torch.empty((n_ch, n), dtype=torch.float64 if t is not None else x.dtype, device=dev)
     if n_ch > 0:
-        code = _lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32
-        nbytes = int(lib.qi_cumtrapz_scratch_bytes(code, n_ch, n))
-        if nbytes < 0:
-            _lib.check(nbytes)
-        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.qi_cumtrapz(code, dev.index, _lib.ptr(x), _lib.ptr(t), stride, dx, n_ch, n, _lib.ptr(out), _lib.ptr(scratch),
-                                       nbytes, _lib.stream_ptr(dev)))
+        code = _lib.dtype_code(x.dtype)
+        scratch, nbytes = _lib.scratch(lib.qi_cumtrapz_scratch_bytes, dev, code, n_ch, n)
+        _lib.call(lib.qi_cumtrapz, dev, code, dev.index, _lib.ptr(x), _lib.ptr(t), stride, dx, n_ch, n, _lib.ptr(out),
+                  _lib.ptr(scratch), nbytes)
     return finish(out, was_numpy, was_1d)
 
 
@@ -889,19 +840,17 @@ def derivative(sig, timestamps=None, h=1.0, kind="gradient", fill_at="end"):
         raise ValueError(f"fill_at must be 'start' or 'end', got {fill_at!r}")
     h = float(h)
     difference = kind == "difference"
-    shape = tuple(sig.shape) if isinstance(sig, torch.Tensor) else np.shape(sig)
-    if not difference and len(shape) in (1, 2) and shape[-1] == 1:
+    shape = _record_shape(sig)
+    if not difference and shape[-1] == 1:
         raise ValueError("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are required.")
-    x, t, stride, was_numpy, was_1d = _records_and_timestamps(sig, timestamps, "signal")
-    lib = _lib.load()
+    lib, x, t, stride, was_numpy, was_1d = _records_and_timestamps(sig, timestamps, shape=shape)
     dev = x.device
     n_ch, n = x.shape
-    out =torch.empty((n_ch, n), dtype=torch.float64 if difference and t is not None else x.dtype, device=dev)
+    out = torch.empty((n_ch, n), dtype=torch.float64 if difference and t is not None else x.dtype, device=dev)
     offset = 1 if difference and fill_at == "start" else 0
     if n_ch > 0:
-        with torch.cuda.device(dev):
-            _lib.check(lib.qi_derivative(_lib.QI_F64 if x.dtype == torch.float64 else _lib.QI_F32, dev.index, DERIVATIVE_KINDS[kind],
-                                         _lib.ptr(x), _lib.ptr(t), stride, h, n_ch, n, _lib.ptr(out), offset, _lib.stream_ptr(dev)))
+        _lib.call(lib.qi_derivative, dev, _lib.dtype_code(x.dtype), dev.index, DERIVATIVE_KINDS[kind], _lib.ptr(x), _lib.ptr(t),
+                  stride, h, n_ch, n, _lib.ptr(out), offset)
         if difference:
             out[:, 0 if offset else n - 1] = 0
     return finish(out, was_numpy, was_1d)
@@ -928,8 +877,7 @@ def finish(result_tensor, was_numpy, was_1d, widen=False):
     if widen and NUMPY_RESULT_DTYPE == "reference" and t.dtype in (torch.complex64, torch.float32) and t.numel() > 0:
         wide = torch.empty(t.shape, dtype=torch.complex128 if t.dtype == torch.complex64 else torch.float64, device=t.device)
         src = torch.view_as_real(t) if t.is_complex() else t
-        with torch.cuda.device(t.device):
-            _lib.check(_lib.load().qi_widen(t.device.index, _lib.ptr(src), _lib.ptr(wide), src.numel(), _lib.stream_ptr(t.device)))
+        _lib.call(_lib.load().qi_widen, t.device, t.device.index, _lib.ptr(src), _lib.ptr(wide), src.numel())
         t = wide
     nbytes = t.numel() * t.element_size()
     if nbytes >= PINNED_RESULT_MAX_BYTES:

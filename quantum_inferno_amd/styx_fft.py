@@ -97,16 +97,15 @@ def _stft_out(lib, sig, window, seg, hop, nfft, scale, res, scratch=None):
     `scratch`: a kept buffer of qi_stft_out_scratch_bytes for this request, or None."""
     n_ch, n = sig.shape
     dev = sig.device
-    code = _lib.QI_F64 if sig.dtype == torch.float64 else _lib.QI_F32
-    nbytes = int(lib.qi_stft_out_scratch_bytes(code, n_ch, n, seg, hop, nfft, res.coef is not None, res.bits is not None))
+    code = _lib.dtype_code(sig.dtype)
     if scratch is None:
-        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        scratch, _ = _lib.scratch(lib.qi_stft_out_scratch_bytes, dev, code, n_ch, n, seg, hop, nfft, res.coef is not None,
+                                  res.bits is not None)
     desc = _lib.TfrOut(coef=_lib.ptr(res.coef), bits=_lib.ptr(res.bits), power_band=_lib.ptr(res.power_band),
                        power_time=_lib.ptr(res.power_time), stats=_lib.ptr(res.stats), power_scale=float(res.power_scale),
                        eps=float(get_epsilon()))
-    with torch.cuda.device(dev):
-        _lib.check(lib.qi_stft_out(code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(window), seg, hop, nfft, scale,
-                                   C.byref(desc), _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(dev)))
+    _lib.call(lib.qi_stft_out, dev, code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(window), seg, hop, nfft, scale, C.byref(desc),
+              _lib.ptr(scratch), scratch.numel())
     return res
 
 
@@ -155,14 +154,10 @@ def _stft_windowed(sig_wf, fs, window64, segment_points, overlap_points, nfft_po
     cdt = torch.complex128 if f64 else torch.complex64
     z = torch.empty((n_ch, n_f, n_seg), dtype=cdt, device=dev)
     bits = torch.empty((n_ch, n_f, n_seg), dtype=sig.dtype, device=dev) if want_bits else None
-    code = _lib.QI_F64 if f64 else _lib.QI_F32
-    scratch_bytes = int(lib.qi_stft_scratch_bytes(code, n_ch, n, seg, hop, nfft))
-    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(
-            lib.qi_stft(code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale, _lib.ptr(z),
-                        _lib.ptr(bits), float(get_epsilon()), _lib.ptr(scratch), scratch_bytes, _lib.stream_ptr(dev))
-        )
+    code = _lib.dtype_code(sig.dtype)
+    scratch, nbytes = _lib.scratch(lib.qi_stft_scratch_bytes, dev, code, n_ch, n, seg, hop, nfft)
+    _lib.call(lib.qi_stft, dev, code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale, _lib.ptr(z),
+              _lib.ptr(bits), float(get_epsilon()), _lib.ptr(scratch), nbytes)
     return freq_hz, time_s, engine.finish(z, was_numpy, was_1d), engine.finish(bits, was_numpy, was_1d)
 
 
@@ -201,7 +196,7 @@ class StftPlan:
         self.window = torch.from_numpy(np.ascontiguousarray(win)).to(self.device)
         self.n_seg = int(self._lib.qi_stft_segments(self.n, self.seg, self.hop))
         self.n_f = self.nfft // 2 + 1
-        self.code = _lib.QI_F64 if f64 else _lib.QI_F32
+        self.code = _lib.dtype_code(self.rdtype)
         self.z = torch.empty((self.channels, self.n_f, self.n_seg), dtype=engine._complex_of(self.rdtype), device=self.device)
         self.bits = torch.empty((self.channels, self.n_f, self.n_seg), dtype=self.rdtype, device=self.device)
         self.scratch_bytes = int(self._lib.qi_stft_scratch_bytes(self.code, self.channels, self.n, self.seg, self.hop, self.nfft))
@@ -220,13 +215,9 @@ class StftPlan:
     def run(self, sig):
         if sig.shape != (self.channels, self.n) or sig.dtype != self.rdtype or not sig.is_cuda:
             raise ValueError(f"signal must be a [{self.channels}, {self.n}] {self.rdtype} CUDA tensor")
-        with torch.cuda.device(self.device):
-            _lib.check(
-                self._lib.qi_stft(self.code, self.device.index, _lib.ptr(sig), self.channels, self.n, _lib.ptr(self.window),
-                                  self.seg, self.hop, self.nfft, self.scale, _lib.ptr(self.z), _lib.ptr(self.bits),
-                                  float(get_epsilon()), _lib.ptr(self.scratch), self.scratch_bytes,
-                                  _lib.stream_ptr(self.device))
-            )
+        _lib.call(self._lib.qi_stft, self.device, self.code, self.device.index, _lib.ptr(sig), self.channels, self.n,
+                  _lib.ptr(self.window), self.seg, self.hop, self.nfft, self.scale, _lib.ptr(self.z), _lib.ptr(self.bits),
+                  float(get_epsilon()), _lib.ptr(self.scratch), self.scratch_bytes)
         return self.z, self.bits
 
     def reduce(self, sig, coef=False, bits=False, reductions=True, power_scale=1.0, reduced_out=None):
@@ -371,11 +362,9 @@ def welch_power_pow2(
     win = win64 if f64 else win64.astype(np.float32)
     scale = float(1.0 / np.sum(win.astype(np.float64)))
     win_d = torch.from_numpy(np.ascontiguousarray(win)).to(sig.device)
-    code = _lib.QI_F64 if f64 else _lib.QI_F32
+    code = _lib.dtype_code(sig.dtype)
     pxx = torch.empty((n_ch, nfft // 2 + 1), dtype=sig.dtype, device=sig.device)
-    nbytes = int(lib.qi_welch_scratch_bytes(code, n_ch, n, seg, hop, nfft))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=sig.device)
-    with torch.cuda.device(sig.device):
-        _lib.check(lib.qi_welch(code, sig.device.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale,
-                                _lib.ptr(pxx), _lib.ptr(scratch), nbytes, _lib.stream_ptr(sig.device)))
+    scratch, nbytes = _lib.scratch(lib.qi_welch_scratch_bytes, sig.device, code, n_ch, n, seg, hop, nfft)
+    _lib.call(lib.qi_welch, sig.device, code, sig.device.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale,
+              _lib.ptr(pxx), _lib.ptr(scratch), nbytes)
     return np.fft.rfftfreq(nfft, 1 / frequency_sample_rate_hz), engine.finish(pxx, was_numpy, was_1d)

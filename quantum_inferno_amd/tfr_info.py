@@ -46,10 +46,6 @@ def _back(t, was_numpy, nd):
     return t.cpu().numpy() if was_numpy else t
 
 
-def _code(t):
-    return _lib.QI_F64 if t.dtype == torch.float64 else _lib.QI_F32
-
-
 def power_marginals(power):
     """One pass over P [C, B, n]: (sum over time [C, B] f64, sum over bands [C, n], stats [C, 4] f64 =
     max, total, sum P log2 P, 0).  The sums / max that tfr_info.py:82-94,231 take before the log2."""
@@ -59,13 +55,9 @@ def power_marginals(power):
     band = torch.empty((n_ch, n_b), dtype=torch.float64, device=dev)
     time = torch.empty((n_ch, n), dtype=power.dtype, device=dev)
     stats = torch.empty((n_ch, 4), dtype=torch.float64, device=dev)
-    nbytes = int(lib.qi_power_marginals_scratch_bytes(n_ch, n_b, n))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(
-            lib.qi_power_marginals(_code(power), dev.index, _lib.ptr(power), n_ch, n_b, n, _lib.ptr(band),
-                                   _lib.ptr(time), _lib.ptr(stats), _lib.ptr(scratch), nbytes, _lib.stream_ptr(dev))
-        )
+    scratch, nbytes = _lib.scratch(lib.qi_power_marginals_scratch_bytes, dev, n_ch, n_b, n)
+    _lib.call(lib.qi_power_marginals, dev, _lib.dtype_code(power.dtype), dev.index, _lib.ptr(power), n_ch, n_b, n, _lib.ptr(band),
+              _lib.ptr(time), _lib.ptr(stats), _lib.ptr(scratch), nbytes)
     return band, time, stats
 
 
@@ -75,11 +67,8 @@ def _log2_offset(x, ref=None, eps=_EPS):
     out = torch.empty_like(x)
     n_ch = x.shape[0]
     count = x.numel() // n_ch
-    with torch.cuda.device(x.device):
-        _lib.check(
-            lib.qi_log2_offset(_code(x), x.device.index, _lib.ptr(x), _lib.ptr(out), n_ch, count, eps, _lib.ptr(ref),
-                               _lib.stream_ptr(x.device))
-        )
+    _lib.call(lib.qi_log2_offset, x.device, _lib.dtype_code(x.dtype), x.device.index, _lib.ptr(x), _lib.ptr(out), n_ch, count, eps,
+              _lib.ptr(ref))
     return out
 
 
@@ -96,9 +85,8 @@ def log2_abs(x, eps=_EPS):
     if x.numel() == 0:
         return out
     src = torch.view_as_real(x) if cplx else x
-    with torch.cuda.device(x.device):
-        _lib.check(lib.qi_log2_abs(_lib.QI_F64 if rdt == torch.float64 else _lib.QI_F32, x.device.index, _lib.ptr(src),
-                                   1 if cplx else 0, _lib.ptr(out), x.numel(), float(eps), _lib.stream_ptr(x.device)))
+    _lib.call(lib.qi_log2_abs, x.device, _lib.dtype_code(rdt), x.device.index, _lib.ptr(src), 1 if cplx else 0, _lib.ptr(out),
+              x.numel(), float(eps))
     return out
 
 
@@ -145,11 +133,8 @@ class ShannonStft:
             _mult = torch.ones(n_ch, dtype=p.dtype, device=p.device)
         mult = _mult.to(p.dtype).contiguous()
         outs = [torch.empty_like(p) for _ in range(4)]
-        with torch.cuda.device(p.device):
-            _lib.check(
-                lib.qi_shannon_panel(_code(p), p.device.index, _lib.ptr(p), _lib.ptr(mult), _mode, n_ch, n_b, n,
-                                     float(deg_free), *[_lib.ptr(o) for o in outs], _lib.stream_ptr(p.device))
-            )
+        _lib.call(lib.qi_shannon_panel, p.device, _lib.dtype_code(p.dtype), p.device.index, _lib.ptr(p), _lib.ptr(mult), _mode, n_ch,
+                  n_b, n, float(deg_free), *[_lib.ptr(o) for o in outs])
         self.info, self.shannon_bits, self.isnr, self.esnr = (_back(o, was_numpy, nd) for o in outs)
         self.ref_bits: float = np.log2(deg_free) / deg_free
 
@@ -207,9 +192,8 @@ def _shannon_1d(marginal):
     lib = _lib.require_gpu()
     n_ch, n = marginal.shape
     outs = [torch.empty_like(marginal) for _ in range(4)]
-    with torch.cuda.device(marginal.device):
-        _lib.check(lib.qi_shannon_1d(_code(marginal), marginal.device.index, _lib.ptr(marginal), n_ch, n,
-                                     *[_lib.ptr(o) for o in outs], _lib.stream_ptr(marginal.device)))
+    _lib.call(lib.qi_shannon_1d, marginal.device, _lib.dtype_code(marginal.dtype), marginal.device.index, _lib.ptr(marginal), n_ch, n,
+              *[_lib.ptr(o) for o in outs])
     return outs
 
 
@@ -238,8 +222,7 @@ class Shannon:
 
 
 def _scratch(lib, t):
-    nbytes = int(lib.qi_shannon_scratch_bytes(_code(t), t.shape[0], t.shape[1]))
-    return torch.empty(nbytes, dtype=torch.uint8, device=t.device), nbytes
+    return _lib.scratch(lib.qi_shannon_scratch_bytes, t.device, _lib.dtype_code(t.dtype), t.shape[0], t.shape[1])
 
 
 class ShannonTDR(Shannon):
@@ -251,9 +234,8 @@ class ShannonTDR(Shannon):
         sig = torch.empty_like(x)
         marginal = torch.empty_like(x)
         scratch, nbytes = _scratch(lib, x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.qi_shannon_tdr(_code(x), x.device.index, _lib.ptr(x), x.shape[0], x.shape[1], _lib.ptr(sig),
-                                          _lib.ptr(marginal), _lib.ptr(scratch), nbytes, _lib.stream_ptr(x.device)))
+        _lib.call(lib.qi_shannon_tdr, x.device, _lib.dtype_code(x.dtype), x.device.index, _lib.ptr(x), x.shape[0], x.shape[1],
+                  _lib.ptr(sig), _lib.ptr(marginal), _lib.ptr(scratch), nbytes)
         self.sig = _rows_back(sig, was_numpy, one)
         super().__init__(None, _rows=(marginal, was_numpy, one))
 
@@ -280,9 +262,8 @@ class ShannonFFT(Shannon):
         angle = torch.empty((n_ch, nf), dtype=x.dtype, device=x.device)
         marginal = torch.empty((n_ch, nf), dtype=x.dtype, device=x.device)
         scratch, nbytes = _scratch(lib, x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.qi_shannon_fft(_code(x), x.device.index, _lib.ptr(x), n_ch, n, _lib.ptr(spec), _lib.ptr(angle),
-                                          _lib.ptr(marginal), _lib.ptr(scratch), nbytes, _lib.stream_ptr(x.device)))
+        _lib.call(lib.qi_shannon_fft, x.device, _lib.dtype_code(x.dtype), x.device.index, _lib.ptr(x), n_ch, n, _lib.ptr(spec),
+                  _lib.ptr(angle), _lib.ptr(marginal), _lib.ptr(scratch), nbytes)
         self.sig = _rows_back(spec, was_numpy, one)
         self.angle_rads = _rows_back(angle, was_numpy, one)
         self.frequency = np.arange(nf) / nf / 2.0

@@ -59,9 +59,8 @@ def pool_rows(x, factor, method, kind=_lib.QI_POOL_REAL, power_scale=1.0, out=No
     rows = x.numel() // n if n else 0
     if rows == 0:
         return out
-    with torch.cuda.device(x.device):
-        _lib.check(lib.qi_pool_panel(_lib.QI_F64 if rdtype == torch.float64 else _lib.QI_F32, x.device.index, _lib.ptr(x), kind,
-                                     rows, n, int(factor), code, float(power_scale), _lib.ptr(out), _lib.stream_ptr(x.device)))
+    _lib.call(lib.qi_pool_panel, x.device, _lib.dtype_code(rdtype), x.device.index, _lib.ptr(x), kind, rows, n, int(factor), code,
+              float(power_scale), _lib.ptr(out))
     return out
 
 

@@ -143,10 +143,6 @@ def _as_rows(x, complex_ok=False):
     return t.contiguous(), was_numpy
 
 
-def _code(real_dtype):
-    return _lib.QI_F64 if real_dtype == torch.float64 else _lib.QI_F32
-
-
 def _forward(obj: TukeyStft, timeseries, padding, detrend, real_kind):
     """|STFT| (real_kind 1) or |STFT|^2 (2) of the record(s): [.., f_pts, p_num]."""
     lib = _lib.require_gpu()
@@ -160,13 +156,11 @@ def _forward(obj: TukeyStft, timeseries, padding, detrend, real_kind):
     first = p0 * obj.hop - obj.m_num_mid
     win = torch.from_numpy(obj.win).to(device=x.device, dtype=x.dtype)
     out = torch.empty((n_ch, obj.f_pts, n_slices), dtype=x.dtype, device=x.device)
-    nbytes = int(lib.qi_sliding_scratch_bytes(_code(x.dtype), n_ch, obj.mfft, n_slices))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.qi_sliding_stft(_code(x.dtype), x.device.index, _lib.ptr(x), n_ch, n, _lib.ptr(win), obj.m_num,
-                                       obj.hop, obj.mfft, first, n_slices, _PAD_CODE[padding], 1 if detrend else 0,
-                                       obj.m_num_mid, None, _lib.ptr(out), real_kind, _lib.ptr(scratch), nbytes,
-                                       _lib.stream_ptr(x.device)))
+    code = _lib.dtype_code(x.dtype)
+    scratch, nbytes = _lib.scratch(lib.qi_sliding_scratch_bytes, x.device, code, n_ch, obj.mfft, n_slices)
+    _lib.call(lib.qi_sliding_stft, x.device, code, x.device.index, _lib.ptr(x), n_ch, n, _lib.ptr(win), obj.m_num, obj.hop, obj.mfft,
+              first, n_slices, _PAD_CODE[padding], 1 if detrend else 0, obj.m_num_mid, None, _lib.ptr(out), real_kind,
+              _lib.ptr(scratch), nbytes)
     if one:
         out = out[0]
     return out.cpu().numpy() if was_numpy else out
@@ -221,12 +215,10 @@ def istft_tukey(stft_to_invert, sample_rate_hz, tukey_alpha, segment_length, ove
     dual = torch.from_numpy(obj.dual_win).to(device=s.device, dtype=rdtype)
     out = torch.empty((n_ch, k1 - k0), dtype=rdtype, device=s.device)
     first = obj.p_min * obj.hop - obj.m_num_mid
-    nbytes = int(lib.qi_sliding_scratch_bytes(_code(rdtype), n_ch, obj.mfft, n_slices))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
-    with torch.cuda.device(s.device):
-        _lib.check(lib.qi_sliding_istft(_code(rdtype), s.device.index, _lib.ptr(s), n_ch, _lib.ptr(dual), obj.m_num, obj.hop,
-                                        obj.mfft, first, n_slices, obj.m_num_mid, k0, k1, _lib.ptr(out), _lib.ptr(scratch),
-                                        nbytes, _lib.stream_ptr(s.device)))
+    code = _lib.dtype_code(rdtype)
+    scratch, nbytes = _lib.scratch(lib.qi_sliding_scratch_bytes, s.device, code, n_ch, obj.mfft, n_slices)
+    _lib.call(lib.qi_sliding_istft, s.device, code, s.device.index, _lib.ptr(s), n_ch, _lib.ptr(dual), obj.m_num, obj.hop, obj.mfft,
+              first, n_slices, obj.m_num_mid, k0, k1, _lib.ptr(out), _lib.ptr(scratch), nbytes)
     if one:
         out = out[0]
     timestamps = np.arange(start=0, stop=k1 / sample_rate_hz, step=1 / sample_rate_hz)

@@ -17,6 +17,9 @@
 //     with QI_ERR_ARG and a message, and leave the plan's previous table in use;
 //   * the plan-less STFT family (qi_stft, qi_stft_out, qi_welch, qi_sliding_stft, qi_sliding_istft) on fused and hipFFT geometries in
 //     both precisions, each with scratch of exactly the advertised size (walk_stft);
+//   * the plan-less record calls (qi_filtfilt, qi_decimate, qi_find_peaks, qi_interp_grid, qi_resample_fft, qi_cumtrapz,
+//     qi_derivative): the host code of an accepted call on buffers of exactly the stated sizes in both precisions, and every
+//     single-fault refusal (walk_records);
 //   * launch geometry (fake hipLaunchKernel), signed overflow / shifts / misaligned access in the host arithmetic (UBSan).
 // Test infrastructure: built and run by tests/test_host_sanitize.py on the CPU container; never part of libqi_tfr.so.
 #include <algorithm>
@@ -328,6 +331,202 @@ size_t walk_stft() {
   return calls;
 }
 
+// The plan-less record calls (qi_filter.hip, qi_peaks.hip, qi_resample.hip, qi_calculus.hip): each entry point accepted once per
+// precision (the calls with timestamps also with a row per record) on caller buffers and scratch of EXACTLY the sizes the
+// ABI states, then every single-fault refusal of tests/test_*_cpu.py through the call itself: QI_ERR_ARG and the word the
+// message must hold.  Kernels do not run here, so the exact sizes are seen by the host code only: the size and pointer
+// arithmetic under UBSan, the copies and memsets the host issues (qi_resample_fft's copy of the records) under
+// AddressSanitizer.  Returns the calls made.
+struct Rec {  // the arguments of one record call; an entry point reads the ones it takes
+  int dtype = QI_F64, kind = QI_DERIV_GRADIENT;
+  int64_t C = 3, n = 300, m = 77, stride = 0, edge = 27, q = 4, offset = 0, capacity = 16, scratch_short = 0;
+  double start = 0.25, delta = 0.5;
+  bool with_x = false;        // qi_cumtrapz, qi_derivative: timestamps given
+  const char* null_arg = "";  // the pointer argument passed as null
+  template <typename T, typename V>
+  Rec with(T Rec::*field, V v) const {
+    Rec r = *this;
+    r.*field = (T)v;
+    return r;
+  }
+  // sizes of the caller's buffers: the stated ones, for the shapes a call accepts (a refused call touches none of them)
+  int64_t e() const { return dtype == QI_F32 ? 4 : 8; }
+  int64_t rows(int64_t per_row) const {
+    return std::min<int64_t>(std::max<int64_t>(C, 0), 64) * std::min<int64_t>(std::max<int64_t>(per_row, 0), 4096);
+  }
+};
+struct Dev {  // a "device" buffer of exactly `bytes`: AddressSanitizer's malloc behind the stand-in's hipMalloc
+  void* p = nullptr;
+  explicit Dev(int64_t bytes) {
+    if (hipMalloc(&p, (size_t)std::max<int64_t>(bytes, 1)) != hipSuccess) exit(2);
+  }
+  Dev(const Dev&) = delete;
+  ~Dev() { (void)hipFree(p); }
+  void* unless(const Rec& r, const char* name) const { return strcmp(r.null_arg, name) ? p : nullptr; }
+};
+const double kUnitSos64[6] = {1, 0, 0, 1, 0, 0}, kZi64[2] = {0, 0};
+const float kUnitSos32[6] = {1, 0, 0, 1, 0, 0}, kZi32[2] = {0, 0};
+
+int rec_filtfilt(const Rec& r) {
+  const int64_t need = qi_filtfilt_scratch_bytes(r.C, r.n, r.edge);
+  Dev sig(r.rows(r.n) * r.e()), out(r.rows(r.n) * 8), scratch(need - r.scratch_short);
+  return qi_filtfilt(r.dtype, 0, sig.unless(r, "sig"), r.C, r.n, nullptr, QI_IIR_SOS, 1, 2, kUnitSos64, kZi64, r.edge, out.unless(r, "out"),
+                     scratch.unless(r, "scratch"), need - r.scratch_short, nullptr);
+}
+int rec_decimate(const Rec& r) {
+  const int64_t need = qi_decimate_scratch_bytes(r.dtype, r.C, r.n, r.edge);
+  Dev sig(r.rows(r.n) * r.e()), out(r.rows(qi_decimate_columns(r.n, r.q)) * r.e()), scratch(need - r.scratch_short);
+  const bool f32 = r.dtype == QI_F32;
+  return qi_decimate(r.dtype, 0, sig.unless(r, "sig"), r.C, r.n, r.q, 1, f32 ? (const void*)kUnitSos32 : kUnitSos64,
+                     f32 ? (const void*)kZi32 : kZi64, r.edge, out.unless(r, "out"), scratch.unless(r, "scratch"), need - r.scratch_short, nullptr);
+}
+int rec_find_peaks(const Rec& r) {
+  const int64_t need = qi_peaks_scratch_bytes(r.dtype, r.C, r.n);
+  Dev sig(r.rows(r.n) * r.e()), scaled(r.rows(r.n) * r.e()), pos(r.rows(r.capacity) * 8), val(r.rows(r.capacity) * 8), counts(r.rows(1) * 8),
+      scratch(need - r.scratch_short);
+  return qi_find_peaks(r.dtype, 0, sig.unless(r, "sig"), r.C, r.n, QI_PEAK_SIGMAX, 0.0, QI_PEAK_HEIGHT_NONE, 0.0, scaled.p,
+                       static_cast<int64_t*>(pos.p), static_cast<double*>(val.p), r.capacity, static_cast<int64_t*>(counts.unless(r, "counts")),
+                       scratch.unless(r, "scratch"), need - r.scratch_short, nullptr);
+}
+int rec_interp_grid(const Rec& r) {
+  Dev values(r.rows(r.n) * r.e()), knots((r.stride ? r.rows(r.n) : std::max<int64_t>(r.n, 0)) * 8), out(r.rows(r.m) * 8);
+  return qi_interp_grid(r.dtype, 0, values.unless(r, "values"), knots.unless(r, "knots"), r.stride, r.C, r.n, r.start, r.delta, r.m,
+                        out.unless(r, "out"), nullptr);
+}
+int rec_resample_fft(const Rec& r) {
+  const int64_t need = qi_resample_fft_scratch_bytes(r.dtype, r.C, r.n, r.m);
+  Dev sig(r.rows(r.n) * r.e()), out(r.rows(r.m) * r.e()), scratch(need - r.scratch_short);
+  return qi_resample_fft(r.dtype, 0, sig.unless(r, "sig"), r.C, r.n, r.m, out.unless(r, "out"), scratch.unless(r, "scratch"),
+                         need - r.scratch_short, nullptr);
+}
+int rec_cumtrapz(const Rec& r) {
+  const int64_t need = qi_cumtrapz_scratch_bytes(r.dtype, r.C, r.n);
+  Dev y(r.rows(r.n) * r.e()), x((r.stride ? r.rows(r.n) : std::max<int64_t>(r.n, 0)) * 8), out(r.rows(r.n) * (r.with_x ? 8 : r.e())),
+      scratch(need - r.scratch_short);
+  return qi_cumtrapz(r.dtype, 0, y.unless(r, "y"), r.with_x ? x.p : nullptr, r.stride, 1.0, r.C, r.n, out.unless(r, "out"),
+                     scratch.unless(r, "scratch"), need - r.scratch_short, nullptr);
+}
+int rec_derivative(const Rec& r) {
+  Dev y(r.rows(r.n) * r.e()), x((r.stride ? r.rows(r.n) : std::max<int64_t>(r.n, 0)) * 8),
+      out(r.rows(r.n) * (r.with_x && r.kind == QI_DERIV_DIFFERENCE ? 8 : r.e()));
+  return qi_derivative(r.dtype, 0, r.kind, y.unless(r, "y"), r.with_x ? x.p : nullptr, r.stride, 1.0, r.C, r.n, out.unless(r, "out"), r.offset,
+                       nullptr);
+}
+
+size_t walk_records() {
+  struct Case {
+    const char* name;
+    int (*call)(const Rec&);
+    Rec r;
+    const char* word;  // of the refusal's message; null: the call is accepted
+  };
+  std::vector<Case> cases;
+  const Rec base;
+  for (int dtype : {(int)QI_F32, (int)QI_F64}) {
+    const Rec d = base.with(&Rec::dtype, dtype), rows = d.with(&Rec::stride, d.n), timed = rows.with(&Rec::with_x, true);
+    cases.insert(cases.end(), {{"qi_filtfilt", rec_filtfilt, d, nullptr},
+                               {"qi_decimate", rec_decimate, d, nullptr},
+                               {"qi_find_peaks", rec_find_peaks, d, nullptr},
+                               {"qi_interp_grid (shared timestamps)", rec_interp_grid, d, nullptr},
+                               {"qi_interp_grid (timestamps per record)", rec_interp_grid, rows, nullptr},
+                               {"qi_resample_fft", rec_resample_fft, d, nullptr},
+                               {"qi_cumtrapz (dx)", rec_cumtrapz, d, nullptr},
+                               {"qi_cumtrapz (timestamps per record)", rec_cumtrapz, timed, nullptr},
+                               {"qi_derivative (gradient, h)", rec_derivative, d, nullptr},
+                               {"qi_derivative (difference, timestamps per record, filled at the start)", rec_derivative,
+                                timed.with(&Rec::kind, QI_DERIV_DIFFERENCE).with(&Rec::offset, 1), nullptr}});
+  }
+  // no records, or one sample and no difference: successful no-ops
+  cases.push_back({"qi_cumtrapz (no records)", rec_cumtrapz, base.with(&Rec::C, 0), nullptr});
+  cases.push_back({"qi_derivative (no records)", rec_derivative, base.with(&Rec::C, 0), nullptr});
+  cases.push_back({"qi_derivative (difference of one sample)", rec_derivative, base.with(&Rec::kind, QI_DERIV_DIFFERENCE).with(&Rec::n, 1), nullptr});
+  const double nan = std::nan(""), inf = HUGE_VAL;
+  const Rec bad_dtype = base.with(&Rec::dtype, 2), none = base.with(&Rec::C, 0), empty = base.with(&Rec::n, 0),
+            short_scratch = base.with(&Rec::scratch_short, 8), x = base.with(&Rec::with_x, true), diff = base.with(&Rec::kind, QI_DERIV_DIFFERENCE);
+  auto null = [&](const char* arg) { return base.with(&Rec::null_arg, arg); };
+  cases.insert(cases.end(), {
+      {"qi_filtfilt", rec_filtfilt, bad_dtype, "dtype"},
+      {"qi_filtfilt", rec_filtfilt, none, "record count"},
+      {"qi_filtfilt", rec_filtfilt, base.with(&Rec::n, base.edge), "longer"},
+      {"qi_filtfilt", rec_filtfilt, base.with(&Rec::edge, -1), "longer"},
+      {"qi_filtfilt", rec_filtfilt, null("sig"), "null"},
+      {"qi_filtfilt", rec_filtfilt, null("out"), "null"},
+      {"qi_filtfilt", rec_filtfilt, null("scratch"), "null"},
+      {"qi_filtfilt", rec_filtfilt, short_scratch, "needed"},
+      {"qi_decimate", rec_decimate, bad_dtype, "dtype"},
+      {"qi_decimate", rec_decimate, none, "record count"},
+      {"qi_decimate", rec_decimate, base.with(&Rec::n, base.edge), "longer"},
+      {"qi_decimate", rec_decimate, base.with(&Rec::edge, -1), "longer"},
+      {"qi_decimate", rec_decimate, base.with(&Rec::q, 0), "positive"},
+      {"qi_decimate", rec_decimate, null("sig"), "null"},
+      {"qi_decimate", rec_decimate, null("out"), "null"},
+      {"qi_decimate", rec_decimate, null("scratch"), "null"},
+      {"qi_decimate", rec_decimate, short_scratch, "needed"},
+      {"qi_find_peaks", rec_find_peaks, bad_dtype, "dtype"},
+      {"qi_find_peaks", rec_find_peaks, none, "record count"},
+      {"qi_find_peaks", rec_find_peaks, empty, "record length"},
+      {"qi_find_peaks", rec_find_peaks, base.with(&Rec::C, 1ll << 30).with(&Rec::n, 1ll << 20), "too large"},
+      {"qi_find_peaks", rec_find_peaks, base.with(&Rec::capacity, -1), "capacity"},
+      {"qi_find_peaks", rec_find_peaks, null("sig"), "null"},
+      {"qi_find_peaks", rec_find_peaks, null("counts"), "null"},
+      {"qi_find_peaks", rec_find_peaks, null("scratch"), "null"},
+      {"qi_find_peaks", rec_find_peaks, short_scratch, "needed"},
+      {"qi_interp_grid", rec_interp_grid, bad_dtype, "dtype"},
+      {"qi_interp_grid", rec_interp_grid, empty, "record length"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::m, -1), "output length"},
+      {"qi_interp_grid", rec_interp_grid, none, "record count"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::delta, 0.0), "delta"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::delta, -1.0), "delta"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::delta, nan), "delta"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::delta, inf), "delta"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::start, nan), "start"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::start, -inf), "start"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::stride, 4), "knot_stride"},
+      {"qi_interp_grid", rec_interp_grid, base.with(&Rec::stride, -8), "knot_stride"},
+      {"qi_interp_grid", rec_interp_grid, null("values"), "null"},
+      {"qi_interp_grid", rec_interp_grid, null("knots"), "null"},
+      {"qi_interp_grid", rec_interp_grid, null("out"), "null"},
+      {"qi_resample_fft", rec_resample_fft, bad_dtype, "dtype"},
+      {"qi_resample_fft", rec_resample_fft, none, "record count"},
+      {"qi_resample_fft", rec_resample_fft, empty, "record length"},
+      {"qi_resample_fft", rec_resample_fft, base.with(&Rec::m, 0), "output length"},
+      {"qi_resample_fft", rec_resample_fft, base.with(&Rec::n, 1ll << 31), "too large"},
+      {"qi_resample_fft", rec_resample_fft, null("scratch"), "null"},
+      {"qi_resample_fft", rec_resample_fft, short_scratch, "needed"},
+      {"qi_cumtrapz", rec_cumtrapz, bad_dtype, "dtype"},
+      {"qi_cumtrapz", rec_cumtrapz, empty, "record length"},
+      {"qi_cumtrapz", rec_cumtrapz, base.with(&Rec::C, -1), "record count"},
+      {"qi_cumtrapz", rec_cumtrapz, x.with(&Rec::stride, 4), "x_stride"},
+      {"qi_cumtrapz", rec_cumtrapz, x.with(&Rec::stride, -8), "x_stride"},
+      {"qi_cumtrapz", rec_cumtrapz, base.with(&Rec::stride, base.n), "x_stride"},
+      {"qi_cumtrapz", rec_cumtrapz, null("y"), "null"},
+      {"qi_cumtrapz", rec_cumtrapz, null("out"), "null"},
+      {"qi_cumtrapz", rec_cumtrapz, null("scratch"), "null"},
+      {"qi_cumtrapz", rec_cumtrapz, short_scratch, "needed"},
+      {"qi_derivative", rec_derivative, bad_dtype, "dtype"},
+      {"qi_derivative", rec_derivative, base.with(&Rec::kind, 2), "kind"},
+      {"qi_derivative", rec_derivative, empty, "record length"},
+      {"qi_derivative", rec_derivative, base.with(&Rec::n, 1), "gradient"},
+      {"qi_derivative", rec_derivative, diff.with(&Rec::n, 0), "record length"},
+      {"qi_derivative", rec_derivative, base.with(&Rec::C, -1), "record count"},
+      {"qi_derivative", rec_derivative, x.with(&Rec::stride, 4), "x_stride"},
+      {"qi_derivative", rec_derivative, base.with(&Rec::stride, base.n), "x_stride"},
+      {"qi_derivative", rec_derivative, base.with(&Rec::offset, 1), "out_offset"},
+      {"qi_derivative", rec_derivative, diff.with(&Rec::offset, 2), "out_offset"},
+      {"qi_derivative", rec_derivative, diff.with(&Rec::offset, -1), "out_offset"},
+      {"qi_derivative", rec_derivative, null("y"), "null"},
+      {"qi_derivative", rec_derivative, null("out"), "null"}});
+  for (const Case& c : cases) {
+    const int rc = c.call(c.r);
+    if (c.word ? rc == QI_ERR_ARG && strstr(qi_last_error(), c.word) : rc == QI_OK) continue;
+    fprintf(stderr, "walk: %s (dtype %d, %lld records of %lld samples): status %d where %s%s was expected: %s\n", c.name, c.r.dtype,
+            (long long)c.r.C, (long long)c.r.n, rc, c.word ? "a refusal naming " : "success", c.word ? c.word : "", qi_last_error());
+    exit(1);
+  }
+  for (auto& kv : g_stft_fft) kv.second.clear();  // (qi_resample_fft's hipFFT plans live in the process-wide cache)
+  return cases.size();
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -422,9 +621,9 @@ int main(int argc, char** argv) {
     if (c.order == 0 && (c.flags & 15) == 5) refused += check_degenerate(c);  // (on the synthetic tables that are native on both sides)
   }
   if (dump) fclose(dump);
-  const size_t stft_calls = walk_stft();
-  printf("{\"ok\": true, \"stft_calls\": %zu, \"plans\": %zu, \"plans_on_native_engines\": %zu, \"calls\": %zu, \"kernel_launches\": %zu, \"scratch_regions_checked\": %zu, \"synthetic_plans\": %zu, "
+  const size_t stft_calls = walk_stft(), record_calls = walk_records();
+  printf("{\"ok\": true, \"stft_calls\": %zu, \"record_calls\": %zu, \"plans\": %zu, \"plans_on_native_engines\": %zu, \"calls\": %zu, \"kernel_launches\": %zu, \"scratch_regions_checked\": %zu, \"synthetic_plans\": %zu, "
          "\"synthetic_on_native\": %zu, \"degenerate_tables_refused\": %zu}\n",
-         stft_calls, plans, native, calls, qi_fake_hip_launches(), qi_layout_regions_checked(), syn_plans, syn_native, refused);
+         stft_calls, record_calls, plans, native, calls, qi_fake_hip_launches(), qi_layout_regions_checked(), syn_plans, syn_native, refused);
   return 0;
 }

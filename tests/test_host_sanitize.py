@@ -37,6 +37,9 @@ def test_host_code_under_asan_ubsan_over_every_layout():
     assert rec["synthetic_plans"] == syn["synthetic_plans"]
     # the plan-less STFT family: seven calls on each of three geometries (two fused, one hipFFT) in both precisions
     assert rec["stft_calls"] == 2 * 3 * 7
+    # the plan-less record calls: ten accepted calls in both precisions and three no-ops, then the single-fault refusals of
+    # qi_filtfilt, qi_decimate, qi_find_peaks, qi_interp_grid, qi_resample_fft, qi_cumtrapz and qi_derivative
+    assert rec["record_calls"] == 2 * 10 + 3 + (8 + 9 + 9 + 15 + 7 + 10 + 13)
     # (every dyadic table of these shapes is one for the native engines, but float64 at 2^14 samples: hipFFT engine by choice;
     # the walker itself checks that each synthetic table comes out native / on the hipFFT engine as it was built to)
     assert rec["plans_on_native_engines"] - rec["synthetic_on_native"] == 864 - 12 * 4
