@@ -503,6 +503,66 @@ typedef enum { QI_DERIV_GRADIENT = 0, QI_DERIV_DIFFERENCE = 1 } qi_deriv_kind;
 int qi_derivative(int dtype, int device, int kind, const void* y, const void* x, int64_t x_stride, double h, int64_t n_channels,
                   int64_t n, void* out, int64_t out_offset, qi_stream stream);
 
+/* ---- synthetic records (synth/benchmark_signals.py, synth/synthetic_signals.py, synth/blast_gt_pulse.py, synth/doppler.py) ----
+ * qi_synth writes records out [C][n] (complex_out 0) or [C][n][2] interleaved (complex_out 1; the imaginary part is 0 for every
+ * kind but QI_SYNTH_QCHIRP) in dtype (device) from a closed formula.  Sample k of record c is evaluated in float64 and rounded
+ * once to dtype.  Every operation below is an IEEE double operation rounded on its own (no fused multiply-add, true divisions),
+ * so the argument of every sin, cos, exp and log is NumPy's bit for bit; kinds without one are NumPy's result bit for bit.
+ * Parameters: params (device, float64), QI_SYNTH_PARAMS values per row; param_stride 0 = one row for all records,
+ *   QI_SYNTH_PARAMS = a row per record (anything else: QI_ERR_ARG).  p0 .. p11 below are the row's values.
+ * Time: t = (base(k) - s0) - s1, each subtraction rounded on its own, with base(k) by `axis`:
+ *   QI_AXIS_RATE        (double)k / axis_value       np.arange(n) / rate          x NULL, x_stride 0
+ *   QI_AXIS_STEP        (double)k * axis_value       np.arange(n) * step          x NULL, x_stride 0
+ *   QI_AXIS_TIMESTAMPS  x[k]                         x float64 (device): x_stride 0 = [n] shared, x_stride n = [C][n]
+ *   s0 and s1 are the caller's (time[-1] / 2.0, sensor_epoch_s[0], ...; 0.0 subtracts nothing).
+ * Kinds, v = the sample (sq(u) = u * u):
+ *   QI_SYNTH_TONE          cos(p0 * t)                                                      p0 = 2 pi f_c
+ *   QI_SYNTH_SINES3        (g0 + g1) + g2, g_i = sin(p_i * t) where p(3+2i) <= t <= p(4+2i), +0.0 elsewhere (rectangular gates)
+ *   QI_SYNTH_01            cos(p0 * t - (p1 * t) * t) + cos(p3 * sin(p2 * t) + p4 * t)
+ *   QI_SYNTH_02            ((u0 + u1) + u2) + u3, u_q = exp(p(3q) * sq(t - p(3q+1))) * cos(p(3q+2) * t)
+ *   QI_SYNTH_03            cos(p0 * log(p1 * t + 1.0)) + cos(p2 * t + p3 * sq(t))
+ *   QI_SYNTH_QCHIRP        q = t / p2, phase = p0 * t + p1 * sq(q), amp = p3 != 0 ? exp(-0.5 * sq(q)) : 1;
+ *                          v = (amp * cos(phase), amp * sin(phase))     p0 omega, p1 gamma / 2, p2 the chirp scale, p3 gauss
+ *   QI_SYNTH_CHIRP_LINEAR  cos(2 pi * (p0 * t + (p1 * t) * t) + 0.0)     p0 = f0, p1 = beta / 2 (scipy.signal.chirp, linear, phi 0)
+ *   QI_SYNTH_SAWTOOTH      r = fmod(p0 * t, 2 pi); r < 0: r += 2 pi; r == 0: r = +0.0; v = (pi - r) / pi   (sawtooth, width 0;
+ *                          with the timestamp axis, s0 = s1 = 0 and p0 = 1 the "timestamps" are a phase record)
+ *   QI_SYNTH_GT, _GT_HILBERT, _GT_DERIVATIVE, _GT_INTEGRAL: tau = t / p0 + 1.0 (p0 a quarter of the pseudo period), a = 1 + sqrt(6);
+ *     on 0 <= tau <= 1 and on 1 < tau <= a the expressions of blast_gt_pulse.py:23-71, 140-196 in their written order, +0.0
+ *     elsewhere; tau^3 of the integral correctly rounded; p1 = the integral's integration_constant, added on 1 < tau <= a.
+ * Envelope, applied to v:
+ *   QI_ENVELOPE_NONE
+ *   QI_ENVELOPE_TUKEY  v * tukey(n, alpha)[k]: scipy.signal.windows.tukey, symmetric (alpha <= 0 or n == 1: ones; alpha >= 1: Hann)
+ *   QI_ENVELOPE_GATE   benchmark_signals.signal_gate: +0.0 where t < tmin or t > tmax; v * tukey(m, alpha)[k - k0] where
+ *                      tmin <= t <= tmax.  k0 = the first included sample and m = their count are the caller's, found with the
+ *                      same rounded t(k); 0 <= k0, 0 <= m, k0 + m <= n (anything else: QI_ERR_ARG).
+ * A workgroup forms QI_SYNTH_TILE consecutive samples of one record.  One kernel launch (per 65535 records), no scratch, no
+ * atomics; the same call gives the same bits.  Any n >= 1; n_channels = 0 is a successful no-op; a refused call writes nothing. */
+#define QI_SYNTH_TILE 1024  /* samples of one workgroup */
+#define QI_SYNTH_PARAMS 12  /* float64 values of a parameter row of qi_synth */
+#define QI_DOPPLER_PARAMS 12 /* float64 values of a parameter row of qi_doppler */
+typedef enum { QI_SYNTH_TONE = 0, QI_SYNTH_SINES3 = 1, QI_SYNTH_01 = 2, QI_SYNTH_02 = 3, QI_SYNTH_03 = 4, QI_SYNTH_QCHIRP = 5,
+               QI_SYNTH_CHIRP_LINEAR = 6, QI_SYNTH_SAWTOOTH = 7, QI_SYNTH_GT = 8, QI_SYNTH_GT_HILBERT = 9,
+               QI_SYNTH_GT_DERIVATIVE = 10, QI_SYNTH_GT_INTEGRAL = 11, QI_SYNTH_KINDS = 12 } qi_synth_kind;
+typedef enum { QI_AXIS_RATE = 0, QI_AXIS_STEP = 1, QI_AXIS_TIMESTAMPS = 2 } qi_synth_axis;
+typedef enum { QI_ENVELOPE_NONE = 0, QI_ENVELOPE_TUKEY = 1, QI_ENVELOPE_GATE = 2 } qi_synth_envelope;
+int qi_synth(int dtype, int device, int kind, int complex_out, const double* params, int64_t param_stride, int axis,
+             double axis_value, const double* x, int64_t x_stride, double s0, double s1, int envelope, double alpha, double tmin,
+             double tmax, int64_t k0, int64_t m, int64_t n_channels, int64_t n, void* out, qi_stream stream);
+
+/* doppler._get_final_vals (doppler.py:149-207) for a row of times per record; the axis, x, s0 and s1 as for qi_synth.  A
+ * parameter row (param_stride 0 or QI_DOPPLER_PARAMS) is c, c2, denom, the source velocity s[3], the receiver velocity v[3]
+ * and the initial range r[3] = receiver - source: c2 = c**2 and denom = 1. / (c**2 - speed**2) (the receiver's speed forward,
+ * the source's inverse) are the caller's, by the reference's own expressions.  dot(a, b) = (a0 b0 + a1 b1) + a2 b2.  Per sample:
+ *   forward:  q = r - s * t;  term1 = (c2 * t + dot(v, q)) * denom        inverse:  q = r + v * t;  term1 = (c2 * t - dot(s, q)) * denom
+ *   rm = sqrt(dot(q, q));  term2 = (rm * rm - (t * c) * (t * c)) * denom;  root = sqrt(term1 * term1 + term2)
+ *   forward:  time = term1 + root;  g = q + v * time                     inverse:  time = term1 - root;  g = q - s * time
+ *   range = sqrt(dot(g, g));  omega = (c - dot(g, v) / range) / (c - dot(g, s) / range)
+ * every operation an IEEE double operation rounded on its own.  time_out, range_out, omega_out: [C][n] float64 (device).  One
+ * kernel launch (per 65535 records), no scratch, no atomics; n_channels = 0 is a successful no-op; a refused call writes nothing. */
+int qi_doppler(int device, int inverse, const double* params, int64_t param_stride, int axis, double axis_value, const double* x,
+               int64_t x_stride, double s0, double s1, int64_t n_channels, int64_t n, double* time_out, double* range_out,
+               double* omega_out, qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,11 @@ PEAKS_TILE = 256  # samples per tile of qi_find_peaks (QI_PEAKS_TILE of include/
 INTERP_TILE, INTERP_KNOTS = 512, 2560  # outputs of a workgroup of qi_interp_grid, knots it stages in LDS (QI_INTERP_TILE, QI_INTERP_KNOTS)
 SCAN_TILE = 4096  # terms of one tile of qi_cumtrapz's summation tree (QI_SCAN_TILE)
 QI_DERIV_GRADIENT, QI_DERIV_DIFFERENCE = 0, 1
+SYNTH_TILE, SYNTH_PARAMS, DOPPLER_PARAMS = 1024, 12, 12  # samples of a workgroup of qi_synth, values of a parameter row (QI_SYNTH_TILE, QI_SYNTH_PARAMS, QI_DOPPLER_PARAMS)
+SYNTH_KINDS = ("tone", "sines3", "synth_01", "synth_02", "synth_03", "quantum_chirp", "chirp_linear", "sawtooth", "gt", "gt_hilbert",
+               "gt_derivative", "gt_integral")  # qi_synth_kind, in its order
+QI_AXIS_RATE, QI_AXIS_STEP, QI_AXIS_TIMESTAMPS = 0, 1, 2
+QI_ENVELOPE_NONE, QI_ENVELOPE_TUKEY, QI_ENVELOPE_GATE = 0, 1, 2
 IIR_MAX = 16  # largest order of the (b, a) form, most second-order sections (qi_filtfilt)
 POOL_MEDIAN_MAX = 4096  # longest window the median sorts (qi_pool_panel)
 ROUTE_NOWRAP, ROUTE_SPLIT, ROUTE_BEHIND, ROUTE_F64_ZOOM = 16, 32, 256, 512
@@ -133,6 +138,8 @@ PROTOTYPES = {
     "qi_cumtrapz_scratch_bytes": (_i64, [_int, _i64, _i64]),
     "qi_cumtrapz": (_int, [_int, _int, _P, _P, _i64, _dbl, _i64, _i64, _P, _P, _i64, _P]),
     "qi_derivative": (_int, [_int, _int, _int, _P, _P, _i64, _dbl, _i64, _i64, _P, _i64, _P]),
+    "qi_synth": (_int, [_int, _int, _int, _int, _P, _i64, _int, _dbl, _P, _i64, _dbl, _dbl, _int, _dbl, _dbl, _dbl, _i64, _i64, _i64, _i64, _P, _P]),
+    "qi_doppler": (_int, [_int, _int, _P, _i64, _int, _dbl, _P, _i64, _dbl, _dbl, _i64, _i64, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -856,6 +856,164 @@ def derivative(sig, timestamps=None, h=1.0, kind="gradient", fill_at="end"):
     return finish(out, was_numpy, was_1d)
 
 
+SYNTH_KINDS = {name: code for code, name in enumerate(_lib.SYNTH_KINDS)}
+SYNTH_AXES = {"rate": _lib.QI_AXIS_RATE, "step": _lib.QI_AXIS_STEP, "timestamps": _lib.QI_AXIS_TIMESTAMPS}
+SYNTH_ENVELOPES = {"none": _lib.QI_ENVELOPE_NONE, "tukey": _lib.QI_ENVELOPE_TUKEY, "gate": _lib.QI_ENVELOPE_GATE}
+
+
+def _synth_axis(axis, n):
+    """("rate", rate[, s0[, s1]]), ("step", step[, s0[, s1]]) or ("timestamps", x[, s0[, s1]]) -> (code, value, x, s0, s1), host
+    checks only: x stays what the caller gave ([n] or [C, n], NumPy or tensor)."""
+    if not isinstance(axis, (tuple, list)) or not 2 <= len(axis) <= 4 or axis[0] not in SYNTH_AXES:
+        raise ValueError(f"axis must be (form, value[, s0[, s1]]) with form one of {sorted(SYNTH_AXES)}, got {axis!r}")
+    s0 = float(axis[2]) if len(axis) > 2 else 0.0
+    s1 = float(axis[3]) if len(axis) > 3 else 0.0
+    if axis[0] == "timestamps":
+        shape = tuple(np.shape(axis[1]))
+        if len(shape) not in (1, 2) or shape[-1] != n:
+            raise ValueError(f"timestamps must be [n] or [records, n] with n = {n}, got shape {shape}")
+        return SYNTH_AXES["timestamps"], 0.0, axis[1], s0, s1
+    value = float(axis[1])
+    if axis[0] == "rate" and value == 0.0:
+        raise ValueError("the rate must not be 0")
+    return SYNTH_AXES[axis[0]], value, None, s0, s1
+
+
+def synth_time(k, axis):
+    """The time of sample k as the kernels round it, in Python floats: t = (base(k) - s0) - s1 for an index form of `axis`."""
+    form, value = axis[0], float(axis[1])
+    s0 = float(axis[2]) if len(axis) > 2 else 0.0
+    s1 = float(axis[3]) if len(axis) > 3 else 0.0
+    return ((float(k) / value if form == "rate" else float(k) * value) - s0) - s1
+
+
+def gate_span(n, axis, tmin, tmax):
+    """(k0, m) of benchmark_signals.signal_gate on n samples of `axis`: the first sample with tmin <= t <= tmax and how many
+    there are.  Index forms (non-decreasing in k for a positive rate or step): two bisections with the kernel's own t(k);
+    shared timestamps [n]: counted."""
+    if axis[0] == "timestamps":
+        s0 = float(axis[2]) if len(axis) > 2 else 0.0
+        s1 = float(axis[3]) if len(axis) > 3 else 0.0
+        x = axis[1].detach().cpu().numpy() if isinstance(axis[1], torch.Tensor) else np.asarray(axis[1], dtype=np.float64)
+        if x.ndim != 1:
+            raise ValueError("a gate needs one time axis for all records: shared timestamps [n] or an index form")
+        t = (x - s0) - s1
+        include = np.logical_and(t >= tmin, t <= tmax)
+        m = int(include.sum())
+        k0 = int(np.argmax(include)) if m else 0
+        if m and not include[k0:k0 + m].all():
+            raise ValueError("the gate's samples must be consecutive: timestamps in ascending order")
+        return k0, m
+    if not float(axis[1]) > 0.0:
+        raise ValueError("a gate needs a positive rate or step")
+
+    def first(pred):  # the first k in [0, n] where pred(t(k)) holds; pred is monotone in k
+        lo, hi = 0, n
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if pred(synth_time(mid, axis)):
+                hi = mid
+            else:
+                lo = mid + 1
+        return lo
+
+    k0 = first(lambda t: t >= tmin)
+    k1 = first(lambda t: t > tmax)
+    return (k0, k1 - k0) if k1 > k0 else (0, 0)
+
+
+def _param_rows(params, width, what):
+    rows = np.ascontiguousarray(params.detach().cpu().numpy() if isinstance(params, torch.Tensor) else params, dtype=np.float64)
+    if rows.ndim not in (1, 2) or rows.shape[-1] > width or rows.shape[-1] < 1:
+        raise ValueError(f"{what} must be [p] or [records, p] with 1 <= p <= {width}, got shape {rows.shape}")
+    padded = np.zeros(rows.shape[:-1] + (width,))
+    padded[..., :rows.shape[-1]] = rows
+    return padded
+
+
+def _rows_and_axis(params, width, n, axis, records, device):
+    """Host checks of synthesize and doppler, then the library and the uploads -> (lib, device, parameter rows on the
+    device, their stride, C, 1-D result?, axis code, value, timestamps on the device or None, their stride, s0, s1)."""
+    n = operator.index(n)
+    if n < 1:
+        raise ValueError("a record must hold at least one sample")
+    rows = _param_rows(params, width, "params")
+    code, value, x, s0, s1 = _synth_axis(axis, n)
+    counts = {c for c in (rows.shape[0] if rows.ndim == 2 else None, np.shape(x)[0] if x is not None and np.ndim(x) == 2 else None,
+                          None if records is None else operator.index(records)) if c is not None}
+    if len(counts) > 1:
+        raise ValueError(f"the parameter rows, the timestamp rows and `records` disagree on the record count: {sorted(counts)}")
+    one = not counts
+    n_ch = counts.pop() if counts else 1
+    if n_ch < 0:
+        raise ValueError(f"records must not be negative, got {n_ch}")
+    lib = _lib.require_gpu()
+    if device is None:
+        device = x.device if isinstance(x, torch.Tensor) and x.is_cuda else default_device()
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    p = torch.from_numpy(rows).to(device)
+    t = None
+    if x is not None:
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+        t = x.to(device=device, dtype=torch.float64).contiguous()
+    return (lib, device, p, width if rows.ndim == 2 else 0, n_ch, one, code, value, t, n if t is not None and t.dim() == 2 else 0,
+            s0, s1)
+
+
+def synthesize(kind, params, n, axis=("step", 1.0), envelope=None, dtype=torch.float64, device=None, complex_out=False, records=None):
+    """Records from a closed formula, made on the device (qi_synth; the formulas are spelled out in include/qi_tfr.h): the
+    batch path of the synth package.  kind: one of SYNTH_KINDS.  params: the kind's float64 parameter row [p] -- one for
+    all records -- or a row per record [C, p], p <= 12 (missing values are 0).  axis: ("rate", rate), ("step", step) or
+    ("timestamps", x) with x [n] or [C, n], optionally followed by s0 and s1: t = (base(k) - s0) - s1.  envelope: None,
+    ("tukey", alpha) -- a Tukey window over the whole record -- or ("gate", tmin, tmax, alpha) -- benchmark_signals.signal_gate,
+    which needs one time axis for all records.  dtype: the stored type, float32 or float64; every sample is evaluated in
+    float64 and rounded once.  complex_out: a complex tensor ("quantum_chirp"; the other kinds have no imaginary part).
+    records: the record count when neither params nor timestamps have rows (every record the same).
+    -> a tensor [C, n] on `device` ([n] when nothing gave a record count), on the current stream, nothing synchronised."""
+    if kind not in SYNTH_KINDS:
+        raise ValueError(f"kind must be one of {sorted(SYNTH_KINDS)}, got {kind!r}")
+    rdtype = _real_dtype(dtype)
+    n = operator.index(n)
+    env, alpha, tmin, tmax, k0, m = SYNTH_ENVELOPES["none"], 0.0, 0.0, 0.0, 0, 0
+    if envelope is not None:
+        if not isinstance(envelope, (tuple, list)) or not envelope or envelope[0] not in ("tukey", "gate") or \
+                len(envelope) != (2 if envelope[0] == "tukey" else 4):
+            raise ValueError(f'envelope must be None, ("tukey", alpha) or ("gate", tmin, tmax, alpha), got {envelope!r}')
+        env = SYNTH_ENVELOPES[envelope[0]]
+        alpha = float(envelope[-1])
+        if envelope[0] == "gate":
+            tmin, tmax = float(envelope[1]), float(envelope[2])
+            if n >= 1:
+                _synth_axis(axis, n)
+                k0, m = gate_span(n, axis, tmin, tmax)
+    lib, dev, p, p_stride, n_ch, one, code, value, t, t_stride, s0, s1 = _rows_and_axis(params, _lib.SYNTH_PARAMS, n, axis, records, device)
+    out = torch.empty((n_ch, n), dtype=_complex_of(rdtype) if complex_out else rdtype, device=dev)
+    if n_ch > 0:
+        _lib.call(lib.qi_synth, dev, _lib.dtype_code(rdtype), dev.index, SYNTH_KINDS[kind], int(bool(complex_out)), _lib.ptr(p), p_stride,
+                  code, value, _lib.ptr(t), t_stride, s0, s1, env, alpha, tmin, tmax, k0, m, n_ch, n, _lib.ptr(out))
+    return out[0] if one else out
+
+
+def doppler(params, n, axis, inverse=False, device=None, records=None):
+    """Source / receiver geometry of synth.doppler on the device (qi_doppler): doppler._get_final_vals for a row of times per
+    record.  params: [12] or [C, 12] float64 -- c, c**2, 1. / (c**2 - speed**2), the source velocity, the receiver velocity,
+    the initial range receiver - source (synth.doppler.geometry_row builds one) -- a row per receiver computes an array of
+    receivers in one call.  axis, records: as for synthesize.  -> (time, range, omega over omega_c), float64 tensors [C, n]
+    ([n] when nothing gave a record count) on the current stream, nothing synchronised."""
+    if np.shape(params)[-1:] != (_lib.DOPPLER_PARAMS,):
+        raise ValueError(f"params must be [{_lib.DOPPLER_PARAMS}] or [records, {_lib.DOPPLER_PARAMS}], got shape {tuple(np.shape(params))}")
+    lib, dev, p, p_stride, n_ch, one, code, value, t, t_stride, s0, s1 = _rows_and_axis(params, _lib.DOPPLER_PARAMS, n, axis, records, device)
+    n = operator.index(n)
+    outs = [torch.empty((n_ch, n), dtype=torch.float64, device=dev) for _ in range(3)]
+    if n_ch > 0:
+        _lib.call(lib.qi_doppler, dev, dev.index, int(bool(inverse)), _lib.ptr(p), p_stride, code, value, _lib.ptr(t), t_stride, s0, s1,
+                  n_ch, n, *(_lib.ptr(o) for o in outs))
+    return tuple(o[0] for o in outs) if one else tuple(outs)
+
+
 # What the reference-signature wrappers hand back to NumPy callers for float32 records.  The reference returns
 # complex128 panels (float64 bits) whatever the record's dtype (styx_cwt.py:195-198, styx_stx.py:228,
 # cwt_atoms.py:408): "reference" computes in float32 and widens on the way out, so a drop-in caller sees the

@@ -1,6 +1,9 @@
 """Seeded synthetic records for benchmarks and demos: per channel a logarithmic
 chirp from fs * 2^-14 to 0.4 fs under a 5 % Tukey taper, plus white noise 8 bits below the signal's
-standard deviation, numpy.random.default_rng(20250213 + channel).  This build's own generator."""
+standard deviation, numpy.random.default_rng(20250213 + channel).  This build's own generator.
+
+The reference's synth modules live beside it -- benchmark_signals, synthetic_signals, blast_gt_pulse, doppler -- and are imported
+by name, as the reference's are (they need the device; this module does not)."""
 import numpy as np
 
 SEED = 20250213
