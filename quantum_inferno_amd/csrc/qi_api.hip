@@ -43,8 +43,6 @@ int qi_plan_create(qi_plan** plan, const qi_plan_desc* desc) {
   // scipy.signal.fftconvolve pads to next_fast_len(2n-1) (= 2n when n = 2^k); any L >= 2n-1 gives the
   // same linear correlation, so other n use the next power of two.
   p->L = is_pow2(desc->n) ? 2 * desc->n : next_pow2(2 * desc->n - 1);
-  if (p->native_kmax > (int64_t)native::kMaxPrunedTerms * native::kN2)
-    p->native_kmax = (int64_t)native::kMaxPrunedTerms * native::kN2;
   if (const char* e = tune_env("QI_NATIVE_DEBUG")) p->native_debug = atoi(e);
   if (const char* e = tune_env("QI_NATIVE_FWD")) p->native_fwd = atoi(e);
   if (const char* e = tune_env("QI_NATIVE_FWD_LOW")) p->native_fwd_low = atoi(e);
@@ -370,7 +368,7 @@ int qi_plan_band_route(const qi_plan* p, int which, int32_t band, int64_t record
   const bool split = which == 0 && std::find(p->h_split_bands.begin(), p->h_split_bands.end(), band) != p->h_split_bands.end();
   for (const auto& z : t.h_zoom)
     if (z.first == band) {
-      const int run = records < p->native_zoom_short_from && z.second >= native::kZoomLevels ? 0 : z.second;
+      const int run = records < native::kZoomShortFrom && z.second >= native::kZoomLevels ? 0 : z.second;
       *route = qi_band_route{QI_STAGE_ZOOM, z.second, run, split ? QI_ROUTE_SPLIT : 0};
       ++found;
     }
@@ -512,7 +510,6 @@ int qi_cwt_stx(qi_plan* p, int bank, const void* sig, int64_t C, const qi_tfr_ou
     // size is settled by iteration; it only ever shrinks).
     DeviceGuard g0(p->d.device);
     int64_t tile = C;
-    if (p->native_tile > 0 && tile > p->native_tile) tile = p->native_tile;
     // (the settled size is kept per request shape: the probes are pure host work, but a step of one record is a quarter
     // of a millisecond)
     auto want = [](const qi_tfr_out* o) {

@@ -1238,25 +1238,9 @@ __global__ void __launch_bounds__(kBlkThreads, QI_BLK_WAVES) k_block_dual(BlockA
 #endif
 }
 
-// Coarse stage of the zoom engine (qi_zoom.hip): workgroup (tau1, band, record) transforms the 4096 folded and
-// twiddled baseband bins that k_zoom_gather left in plane tau1 of the band, in place: afterwards
-// plane tau1 of the band holds the envelope samples tau = P tau2 + tau1 of its coarse grid at [tau2].
-template <typename T>
-__device__ __forceinline__ void zoom_coarse_plane(cplx<T>* __restrict__ plane0) {
-  __shared__ cplx<T> buf[kBlkBuf];
-  __shared__ cplx<T> tw256[256];
-  const int tid = threadIdx.x, col = fft4096_col(tid);
-  cplx<T>* __restrict__ plane = plane0 + col;
-  cplx<T> v[16];
-#pragma unroll
-  for (int b = 0; b < 16; ++b) v[b] = plane[256 * b];
-  const cplx<T> w = fft4096_setup<T>(tw256, tid, col);
-  fft4096<T, 1>(v, buf, tw256, w, tid, col);
-#pragma unroll
-  for (int c = 0; c < 16; ++c) plane[256 * c] = v[brev(c, 4)];
-}
-// The same with the gather step inside: the plane's 4096 inputs are formed in registers (zoom_gather_value) instead of
-// being written by a gather launch and read back -- one launch and two passes over the coarse storage fewer.
+// Coarse stage of the zoom engine (qi_zoom.hip): workgroup (tau1, band, record) forms the 4096 folded and twiddled
+// baseband bins of plane tau1 of the band in registers (zoom_gather16) and transforms them: afterwards plane tau1 of the
+// band holds the envelope samples tau = P tau2 + tau1 of its coarse grid at [tau2].
 template <typename T, bool STX, int NF>
 __device__ __forceinline__ void zoom_coarse_plane_gather(const ZoomArgs<T>& a, const uint32_t plane_i,
                                                          cplx<T>* __restrict__ buf, cplx<T>* __restrict__ tw256) {
@@ -1292,11 +1276,7 @@ __global__ void __launch_bounds__(kBlkThreads) k_zoom_coarse2g(ZoomArgs<T> a0, Z
   // Consecutive workgroups go to consecutive XCDs; the planes of a band (>= 4 or 8 consecutive plane indices) all gather the
   // same bins of the spectrum and the same filter row: runs of eight consecutive planes stay behind one L2, the runs take
   // turns over the XCDs (the grid is rounded up to a multiple of 64).
-#ifdef QI_COARSE_PLAIN_ORDER
-  const uint32_t pi = blockIdx.x;
-#else
   const uint32_t q = blockIdx.x >> 3, pi = (q >> 3) * 64u + (blockIdx.x & 7u) * 8u + (q & 7u);
-#endif
   if (pi >= (uint32_t)(a0.planes + a2.planes)) return;
   if (pi < (uint32_t)a0.planes) zoom_coarse_plane_gather<T, false, NF>(a0, pi, buf, tw256);
   else zoom_coarse_plane_gather<T, true, NF>(a2, pi - (uint32_t)a0.planes, buf, tw256);
@@ -1306,19 +1286,6 @@ __global__ void __launch_bounds__(kBlkThreads) k_zoom_coarse_g(ZoomArgs<T> a) {
   __shared__ cplx<T> buf[kBlkBuf];
   __shared__ cplx<T> tw256[256];
   zoom_coarse_plane_gather<T, STX, 8>(a, blockIdx.x, buf, tw256);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(kBlkThreads) k_zoom_coarse(ZoomArgs<T> a) {
-  zoom_coarse_plane<T>(a.coarse + ((int64_t)blockIdx.z * a.planes + blockIdx.x) * kBlk);
-}
-// qi_cwt_stx: the planes of both tables in one launch
-template <typename T>
-__global__ void __launch_bounds__(kBlkThreads) k_zoom_coarse2(ZoomArgs<T> a0, ZoomArgs<T> a2) {
-  const bool first = blockIdx.x < (uint32_t)a0.planes;
-  const ZoomArgs<T>& a = first ? a0 : a2;
-  const int64_t plane = first ? blockIdx.x : blockIdx.x - (uint32_t)a0.planes;
-  zoom_coarse_plane<T>(a.coarse + ((int64_t)blockIdx.z * a.planes + plane) * kBlk);
 }
 
 // taps of a Gabor atom as a 4096-point circular-convolution kernel: g[(-u) mod 4096] = conj(psi(u + 1/2)), |u| <= W
@@ -1596,18 +1563,9 @@ int launch_block_dual<float>(const BlockArgs<float>& a0, const BlockArgs<float>&
 }
 
 template <>
-int launch_zoom_coarse<float>(const ZoomArgs<float>& a, int64_t n_channels, hipStream_t st) {
-  if (a.nbands <= 0) return QI_OK;
-  dim3 grid((unsigned)a.planes, 1, (unsigned)n_channels);  // every plane of every band is one 4096-point transform
-  k_zoom_coarse<float><<<grid, kBlkThreads, 0, st>>>(a);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
-}
-
-template <>
 int launch_zoom_coarse_gather<float>(const ZoomArgs<float>& a, int64_t n_channels, hipStream_t st) {
   if (a.nbands <= 0) return QI_OK;
-  dim3 grid((unsigned)a.planes, 1, (unsigned)n_channels);
+  dim3 grid((unsigned)a.planes, 1, (unsigned)n_channels);  // every plane of every band is one 4096-point transform
   if (a.stx) k_zoom_coarse_g<float, true><<<grid, kBlkThreads, 0, st>>>(a);
   else k_zoom_coarse_g<float, false><<<grid, kBlkThreads, 0, st>>>(a);
   QI_LAUNCH_CHECK();
@@ -1626,14 +1584,6 @@ int launch_zoom_coarse_gather2<float>(const ZoomArgs<float>& a0, const ZoomArgs<
   static const int nf_env = tune_env("QI_NATIVE_COARSE_NF") ? atoi(tune_env("QI_NATIVE_COARSE_NF")) : 0;
   if (nf_env == 8 || (nf_env == 0 && n_channels > 2)) k_zoom_coarse2g<float, 8><<<grid, kBlkThreads, 0, st>>>(a0, a2);
   else k_zoom_coarse2g<float, 16><<<grid, kBlkThreads, 0, st>>>(a0, a2);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
-}
-
-template <>
-int launch_zoom_coarse2<float>(const ZoomArgs<float>& a0, const ZoomArgs<float>& a2, int64_t n_channels, hipStream_t st) {
-  dim3 grid((unsigned)(a0.planes + a2.planes), 1, (unsigned)n_channels);
-  k_zoom_coarse2<float><<<grid, kBlkThreads, 0, st>>>(a0, a2);
   QI_LAUNCH_CHECK();
   return QI_OK;
 }

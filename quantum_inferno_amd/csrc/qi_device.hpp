@@ -31,27 +31,10 @@ __device__ __forceinline__ double lane_get(double v, int lane) {
   const int hi = __builtin_amdgcn_readlane((int)(u >> 32), lane);
   return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
-#ifdef QI_WAVE_SHFL  // (A/B: the shuffle trees of rounds 1-2)
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_max(T v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    T w = __shfl_down(v, o, kWave);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-#else
 // PRECONDITION of wave_sum / wave_max below: the WHOLE wave is active (call them after the loops have reconverged, never
 // inside a divergent branch).  The row reductions run under EXEC, but the last step reads lanes 0, 16, 32 and 48 with
-// v_readlane, which ignores EXEC: an inactive one of those lanes would hand back stale register contents.  -DQI_WAVE_SHFL
-// selects the shuffle trees above, which only need lane 0; -DQI_NATIVE_DEBUG builds trap on a partial wave.
+// v_readlane, which ignores EXEC: an inactive one of those lanes would hand back stale register contents.
+// -DQI_NATIVE_DEBUG builds trap on a partial wave.
 __device__ __forceinline__ void wave_full_check() {
 #ifdef QI_NATIVE_DEBUG
   if (__builtin_amdgcn_read_exec() != ~0ull) __builtin_trap();
@@ -81,7 +64,6 @@ __device__ __forceinline__ T wave_max(T v) {
   const T ab = b > a ? b : a, cd = d > c ? d : c;
   return cd > ab ? cd : ab;
 }
-#endif
 
 // Read-only global data through the constant address space: a load whose address is the same for the whole wave becomes a
 // scalar load (s_load_dword*): its result lives in scalar registers and is an operand of the lanes' arithmetic.  For small
@@ -95,12 +77,8 @@ __device__ __forceinline__ qi_cptr<V> as_const(const V* p) {
 
 // A struct at a wave-uniform address (a work item, a band descriptor) by scalar loads: its fields live in scalar registers,
 // not in vector registers of every lane (a band descriptor fetched a band ahead was 24 vector registers of the block kernels).
-// QI_NO_UNIFORM_LOADS: the plain (vector) loads, for A/B.
 template <typename S>
 __device__ __forceinline__ S load_uniform(const S* p) {
-#ifdef QI_NO_UNIFORM_LOADS
-  return *p;
-#else
   static_assert(sizeof(S) % 4 == 0, "whole dwords");
   S out;
   const auto src = as_const(reinterpret_cast<const uint32_t*>(p));
@@ -108,7 +86,6 @@ __device__ __forceinline__ S load_uniform(const S* p) {
 #pragma unroll
   for (size_t i = 0; i < sizeof(S) / 4; ++i) dst[i] = src[i];
   return out;
-#endif
 }
 
 // streaming stores of panel data that is never read back by this launch (nontemporal: no allocation in the caches)
@@ -116,25 +93,13 @@ typedef float qi_f2 __attribute__((ext_vector_type(2)));
 typedef float qi_f4 __attribute__((ext_vector_type(4)));
 typedef double qi_d2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void stream_store(float2* p, float2 v) {
-#ifdef QI_NO_STREAM_STORES
-  *p = v;
-#else
   __builtin_nontemporal_store((qi_f2){v.x, v.y}, reinterpret_cast<qi_f2*>(p));
-#endif
 }
 __device__ __forceinline__ void stream_store(double2* p, double2 v) {
-#ifdef QI_NO_STREAM_STORES
-  *p = v;
-#else
   __builtin_nontemporal_store((qi_d2){v.x, v.y}, reinterpret_cast<qi_d2*>(p));
-#endif
 }
 __device__ __forceinline__ void stream_store(float4* p, float4 v) {
-#ifdef QI_NO_STREAM_STORES
-  *p = v;
-#else
   __builtin_nontemporal_store((qi_f4){v.x, v.y, v.z, v.w}, reinterpret_cast<qi_f4*>(p));
-#endif
 }
 
 // |z|^2 and scaled power in one fixed instruction form, so that every kernel variant (with or without the

@@ -373,15 +373,9 @@ struct qi_plan {
   bool shared_valid = false;
   int32_t* d_band_slots[3][2] = {};  // per table kind and item cut: partial slots each band's engine writes
   int native_zoom = 1;         // use the zoom engine for narrow-spectrum bands (0: one-pass loader of pass 2)
-  int native_zoom_short = 1;      // bands oversampled >= 8 / >= 32 times on the coarsest grid use 6- / 4-tap interpolators
-  int native_zoom_short_from = 4; // ... in calls (tiles) of at least this many records; below, they run with the 10-tap class
   int native_zoom_max_level = 3;  // finest coarse grid the zoom engine may use (level 4 costs more in the coarse stage than two-pass saves)
-  int native_zoom_waves = 2048; // native_zoom_wgs = 0: waves each level of a zoom launch should have at least
-  int native_zoom_wgs_joint = 768;   // the same budget per table in the joint launch of qi_cwt_stx (512 .. 1024 measured within 1.5 %)
-  int native_zoom_wgs = 0;      // > 0: workgroups of a zoom launch, dealt to the levels by work (measured: 1.5 % slower than the per-level rule)
   float* d_zoom_w[native::kZoomClasses] = {};  // interpolation weights per class
   int native_z64 = 1;      // float64: narrow-spectrum bands at the decimated rate (coarse inverse FFT + 16-tap interpolation)
-  int native_z64_levels = native::kZ64Levels;  // ... on coarse grids of Lf / 64 ... Lf / (64 >> (levels - 1)) samples
   double* d_z64_w[native::kZ64Levels] = {};  // interpolation weights per coarse-grid level
   double* d_z64f_w[native::kZ64FineClasses] = {};  // lane weights per class of the fine kernel
   double2* d_demod_t1 = nullptr;  // float64 block engine, Stockwell demodulation: exp(-2 pi i 1024 j / n), j < n / 1024
@@ -404,11 +398,7 @@ struct qi_plan {
   int native_blk64_wtab = 1;  // float64 block engine: Gaussian filter weights from a plan-time table instead of sixteen exp2 per band and thread
   int native_z64_block_from = 4;  // a band that needs coarse-grid level >= this (0-based) goes to the block engine when its atom is short enough
   int native_z64_coarse = 3;  // coarse-grid levels whose coarse stage is one launch of in-LDS plane transforms (the finer ones: hipFFT)
-  int native_z64_rows = 0;  // rows (band chunks = per-time planes) of the fine launches of a call together, at least
   int native_f64 = 1;      // float64 plans run on the native engines in double arithmetic (2^20 / 2^21-point transforms)
-  int native_gather_fused = 1;  // zoom engine: from this many records per tile the coarse stage forms its inputs in registers
-                                // (no gather launch, two passes over the coarse storage fewer, the loads of a thread's sixteen
-                                // inputs batched: -35 % of that stage at 16 records, -20 % at one); 0: never
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // split bands of the styx bank (atoms longer than the record): zoom engine + edge pieces, see split_taper
@@ -418,7 +408,6 @@ struct qi_plan {
   int32_t* d_split_bands = nullptr;  // [nsplit] panel rows of the split bands
   std::vector<int32_t> h_split_bands;
   int32_t nsplit = 0;
-  int native_blk_analytic = 1; // evaluate Gaussian filter spectra in registers instead of reading their table rows
   FusedCarry carry;
   native::DualItem* d_dual[2] = {nullptr, nullptr};  // joint block launch of qi_cwt_stx (styx + Stockwell tables) per item cut, built on first use
   int32_t n_dual[2] = {0, 0};
@@ -426,26 +415,13 @@ struct qi_plan {
   bool dual_valid[2] = {false, false};
   int native_fuse = 4;         // qi_cwt_stx: 1 the block launches and the tails of the two transforms go out back to back, 2 as one
                                // launch each, 3 also the gather and the coarse stage of the zoom engine, 4 and its interpolation
-  int native_blk_narrow = 1;   // block bands whose filter spectrum spans <= 256 bins skip the first radix-16 pass of the inverse transform
-  int native_blk_fastw = 1;    // Gaussian weights without wrap-around logic where no alias of the filter spectrum matters
-  int native_edge_merge = 1;   // tables for many records (cut 1): the split bands of a block share one edge item and its forward transforms
-  int native_blk_long = 1;     // narrow Gaussian bands of the 1024-sample reach group in 8192-sample blocks (75 % of the outputs kept instead of 50 %)
-  int native_blk_half = 1;     // block bands whose filter spectrum lies in the lower half of the block spectrum: eight weights, pruned first pass
-  int native_tail = 1;         // time reduction and finalisation of the reductions in one launch
-  int64_t native_tile = 0;     // qi_cwt_stx: at most this many records per joint tile (0: as many as the scratch holds)
-  int native_blk_maxwq = 4;    // reach groups above this one (1, 2, 4) prefer the zoom engine when their spectrum fits it
-  int native_blk_bands = 6;    // bands one block workgroup walks at most (each workgroup pays one forward transform)
-  int native_blk_bands_batch = 12;  // the same for batches of native_blk_batch_from records or more (item cut 1)
-  int native_blk_batch_from = 0;    // 0: 4 records, 8 for tables with few block bands (batch_from())
   native::EdgeBand* d_edge = nullptr;  // short-atom bands of table 3
   int32_t nedge = 0;
   int64_t edge_wmax = 0;
   int native_short = 1;  // evaluate short-atom styx bands circularly at length n (0: everything at 2n)
-  int64_t native_kmax = 12288;  // widest spectrum support handled by the one-pass (pruned) loader
   int native_debug = 0;
   int native_fwd = 1;          // forward transform of the records on the native kernels (0: hipFFT)
   int native_fwd_low = 1;      // ... only the bins near DC when nothing reads the others (forward_low); 0: always every bin
-  int native_wgs = 256;        // workgroups a pass-2 launch should have at least (band chunks are sized for it)
   unsigned long long* stamps = nullptr;  // diagnostic builds: phase cycle counters of the last pass-2 launch
   unsigned long long* blk_stamps = nullptr;  // idem, last block launch
   int native_group = 0;        // wide bands per launch group (0: all in one group)

@@ -7,6 +7,8 @@ namespace native {
 
 constexpr int kN2 = 1024;  // points of the in-LDS row transform of pass 2
 constexpr int kMaxPrunedTerms = 16;  // widest pruned support = kMaxPrunedTerms * kN2 spectrum bins
+constexpr int64_t kOnePassMax = 12288;  // widest spectrum support the plan hands to the one-pass (pruned) loader
+static_assert(kOnePassMax <= (int64_t)kMaxPrunedTerms * kN2, "the one-pass loader holds kMaxPrunedTerms rows of kN2 bins");
 
 struct BandDesc {
   int32_t mode;      // 0: pruned (spectrum support short enough for the one-pass loader), 1: general
@@ -225,6 +227,8 @@ constexpr int zoom_taps(int cls) { return zoom_ntap(cls) + zoom_span(cls) - 1; }
 constexpr int zoom_steps(int cls) { return zoom_grid(cls) <= 2 ? 16 : (64 >> zoom_grid(cls)); }  // wave-steps per wave and band
                                                                                    // (window of <= 128 coarse samples)
 constexpr int kZoomOversample = 4;
+// classes 5 and 6 run on their own in calls (tiles) of at least this many records; below, as part of the 10-tap class 0
+constexpr int kZoomShortFrom = 4;
 template <typename T>
 struct ZoomArgs {
   int64_t n, Lf;
@@ -261,24 +265,16 @@ struct ZoomArgs {
   T power_scale, eps;
 };
 int64_t zoom_groups(int64_t n, int level);  // workgroups along time (partial slots per band, stat slots per chunk)
-template <typename T>
-int launch_zoom_gather(const ZoomArgs<T>& a, int64_t n_channels, hipStream_t st);  // folded baseband bins, then
-template <typename T>
-int launch_zoom_coarse(const ZoomArgs<T>& a, int64_t n_channels, hipStream_t st);  // their 4096-point transforms, in place (qi_block.hip)
-template <typename T>
-int launch_zoom(const ZoomArgs<T>& a, int64_t n_channels, hipStream_t st);
-// qi_cwt_stx: gather / coarse stage of the styx table (a0) and the Stockwell table (a2) in one launch each
-template <typename T>
-int launch_zoom_gather2(const ZoomArgs<T>& a0, const ZoomArgs<T>& a2, int64_t n_channels, hipStream_t st);
-template <typename T>
-int launch_zoom2(const ZoomArgs<T>& a0, const ZoomArgs<T>& a2, int64_t n_channels, hipStream_t st);  // and the interpolation
-template <typename T>
-int launch_zoom_coarse2(const ZoomArgs<T>& a0, const ZoomArgs<T>& a2, int64_t n_channels, hipStream_t st);
-// gather and plane transforms in one launch (the inputs of a plane are formed in registers)
+// coarse stage: the folded baseband bins of a plane formed in registers and its 4096-point transform, one launch (qi_block.hip)
 template <typename T>
 int launch_zoom_coarse_gather(const ZoomArgs<T>& a, int64_t n_channels, hipStream_t st);
 template <typename T>
+int launch_zoom(const ZoomArgs<T>& a, int64_t n_channels, hipStream_t st);  // the interpolation
+// qi_cwt_stx: coarse stage / interpolation of the styx table (a0) and the Stockwell table (a2) in one launch each
+template <typename T>
 int launch_zoom_coarse_gather2(const ZoomArgs<T>& a0, const ZoomArgs<T>& a2, int64_t n_channels, hipStream_t st);
+template <typename T>
+int launch_zoom2(const ZoomArgs<T>& a0, const ZoomArgs<T>& a2, int64_t n_channels, hipStream_t st);
 // ---- float64 zoom (qi_zoom64.hip) ------------------------------------------------------------------------------------
 constexpr int kZ64Taps = 16;       // interpolator taps (oversampling >= 4: 2.8e-12 of a unit tone)
 #ifndef QI_Z64_TILE

@@ -77,7 +77,7 @@ int build_small_twiddles(qi_plan* p) {
 // oversamples four times.
 bool z64_table(const qi_plan* p, int table) { return p->d.dtype == QI_F64 && p->native_z64 && table != 3; }
 int64_t narrow_limit(const qi_plan* p, int table, int64_t Lf) {
-  return z64_table(p, table) ? std::max<int64_t>(p->native_kmax, Lf >> (9 - p->native_z64_levels)) : p->native_kmax;
+  return z64_table(p, table) ? std::max<int64_t>(native::kOnePassMax, Lf >> (9 - native::kZ64Levels)) : native::kOnePassMax;
 }
 
 // Records per call from which the block launches use their batch geometry (12 bands per workgroup, long blocks): fewer
@@ -85,7 +85,6 @@ int64_t narrow_limit(const qi_plan* p, int table, int64_t Lf) {
 // of an order-3 table the batch geometry pays from 8 records (+2 % at 4 and 6 records without it), with the 35 / 46 of
 // orders 6 / 12 from 4 (+2-3 % with it).  The same answer for both tables of a joint call.
 int batch_from(const qi_plan* p) {
-  if (p->native_blk_batch_from > 0) return p->native_blk_batch_from;
   const int32_t rows = std::max(p->blk[0].ready ? p->blk[0].rows : 0, p->blk[2].ready ? p->blk[2].rows : 0);
   return rows <= 24 ? 8 : 4;
 }
@@ -118,7 +117,7 @@ int zoom_class(const qi_plan* p, int table, int64_t Lf, int64_t len) {
       // lengths it keeps the table off the hipFFT engine)
       if (g > p->native_zoom_max_level && native_len_ok(Lf)) return -1;
       // on the coarsest grid the band may be oversampled far more than 4 times: shorter interpolators (classes 5, 6)
-      if (g == 0 && p->native_zoom_short) {
+      if (g == 0) {
         if ((int64_t)native::zoom_design_oversampling(6) * len <= M0) return 6;
         if ((int64_t)native::zoom_design_oversampling(5) * len <= M0) return 5;
       }
@@ -129,11 +128,11 @@ int zoom_class(const qi_plan* p, int table, int64_t Lf, int64_t len) {
 }
 
 // Float64 zoom level of a band with `len` occupied bins out of Lf (-1: the band is not for that engine): the coarsest grid
-// (Lf / 64) << g of the plan's native_z64_levels that oversamples it four times.  (The finest grid, Lf / 4 samples, is what
+// (Lf / 64) << g, g < kZ64Levels, that oversamples it four times.  (The finest grid, Lf / 4 samples, is what
 // narrow_limit allows at most: at transform lengths below 2^19 the one-pass loader's limit is wider than that.)
 int z64_level(const qi_plan* p, int table, int64_t Lf, int64_t len) {
   if (!z64_table(p, table) || len <= 0 || len > narrow_limit(p, table, Lf)) return -1;
-  for (int g = 0; g < p->native_z64_levels; ++g)
+  for (int g = 0; g < native::kZ64Levels; ++g)
     if (4 * len <= ((Lf / 64) << g)) return g;
   return -1;
 }
@@ -213,7 +212,7 @@ int upload_zoom_list(qi_plan* p, qi_plan::NativeTable& t, int64_t Lf, std::vecto
   t.x_lo = 0;
   t.x_hi = -1;
   for (const auto& lvl : by_level)
-    for (const auto& d : lvl) {  // bins zoom_gather_value reads: k (+ shift), k in [k_lo, k_lo + k_len)
+    for (const auto& d : lvl) {  // bins zoom_gather16 reads: k (+ shift), k in [k_lo, k_lo + k_len)
       const int64_t lo = d.k_lo + (stx ? d.shift : 0), hi = lo + d.k_len - 1;
       if (t.x_lo > t.x_hi) {
         t.x_lo = lo;
@@ -522,6 +521,8 @@ int fill_native_bank(qi_plan* p, int table, int circular, int64_t L, int32_t B, 
 // narrow Gaussian bands of the 1024-sample group whose spectrum lies in the lower half of the 8192-bin grid
 constexpr int kBlockGroups = 4;
 constexpr int kBlockGroupWq[kBlockGroups] = {1, 2, 4, native::kBlkLongWq};
+constexpr int kBlockMaxWq = 4;  // reach groups above this one (1, 2, 4) prefer the zoom engine when their spectrum fits it
+constexpr int kBlockBandsPerWg = 6, kBlockBandsPerWgBatch = 12;  // bands one block workgroup walks at most (each pays one forward transform): item cut 0 / 1
 
 // first bin of the 256-bin window of a long band: centred on the band, kept inside the lower half of the 8192-bin grid
 // (the half a long block holds)
@@ -531,7 +532,7 @@ int64_t long_window(const BlockPick& pk) {
 // does item cut `cut` run this band in long blocks?  (float32 tables only)
 bool long_ok(const qi_plan* p, const BlockPick& pk, int cut) {
   if (cut == 0) return false;  // few records: the long blocks' own launch would cost more than the blocks save
-  if (!p->native_blk_long || !p->native_blk_analytic || !p->native_blk_narrow || pk.wq != 4 || !pk.analytic) return false;
+  if (pk.wq != 4 || !pk.analytic) return false;
   if (p->n < 4 * native::kBlkLong) return false;
   const double half8 = std::ceil(std::sqrt(drop_bits(false)) / (0.5 * pk.cw));  // weights >= 2^-30 of the peak on the 8192-bin grid
   const int64_t klo8 = long_window(pk);
@@ -548,7 +549,7 @@ int block_band_desc(const qi_plan* p, const BlockPick& pk, int32_t row, bool is_
   b.out_band = pk.band;
   b.bank_row = row;
   b.shift = (int32_t)pk.shift;
-  b.analytic = p->native_blk_analytic ? pk.analytic : 0;
+  b.analytic = pk.analytic;
   const double grid = is_long ? 2.0 : 1.0;  // the band on the 8192-bin grid of a long block: twice the bins
   const double kappa = grid * pk.kappa, cw = pk.cw / grid;
   b.kappa_int = (int32_t)std::floor(kappa);
@@ -563,8 +564,7 @@ int block_band_desc(const qi_plan* p, const BlockPick& pk, int32_t row, bool is_
   }
   // (float64 since round 5: `half` is then the 2^-52 half-width, the weight comes from the table -- bands of the 512- and
   // 1024-sample reach groups; analytic = 2, an aliased spectrum, is not narrow)
-  if ((!F64 || (b.analytic == 1 && p->native_blk64_wtab && p->native_blk64_narrow)) && b.analytic && p->native_blk_narrow &&
-      2.0 * half + 2.0 <= 256.0) {
+  if ((!F64 || (b.analytic == 1 && p->native_blk64_wtab && p->native_blk64_narrow)) && b.analytic && 2.0 * half + 2.0 <= 256.0) {
     b.narrow = 1;
     b.klo = is_long ? (int32_t)long_window(pk)
                     : (int32_t)((((int64_t)std::llround(kappa) - 128) % native::kBlk + native::kBlk) % native::kBlk);
@@ -577,10 +577,10 @@ int block_band_desc(const qi_plan* p, const BlockPick& pk, int32_t row, bool is_
     b.rot8_a[1] = (T)std::sin(M_PI * ba / 16.0);
     b.rot8_b[0] = (T)std::cos(M_PI * (ba + 1) / 16.0);
     b.rot8_b[1] = (T)std::sin(M_PI * (ba + 1) / 16.0);
-  } else if (!F64 && b.analytic && p->native_blk_half && kappa - half - 1.0 >= 0.0 && kappa + half + 1.0 < (double)(native::kBlk / 2)) {
+  } else if (!F64 && b.analytic && kappa - half - 1.0 >= 0.0 && kappa + half + 1.0 < (double)(native::kBlk / 2)) {
     b.narrow = 2;  // every weight above 2^-30 of the peak lies in the lower half of the block spectrum
   }
-  if (b.analytic && p->native_blk_fastw && b.amp > (T)0 && kappa - half - 1.0 >= 0.0 && kappa + half + 1.0 < (double)native::kBlk) {
+  if (b.analytic && b.amp > (T)0 && kappa - half - 1.0 >= 0.0 && kappa + half + 1.0 < (double)native::kBlk) {
     b.nowrap = 1;
     b.la = (T)std::log2(pk.amp / grid);
   }
@@ -607,7 +607,7 @@ std::vector<native::BlockItem> block_cut_items(const qi_plan* p, int kind, int c
   for (int g = 0; g < kBlockGroups; ++g) {
     if (count[g] == 0) continue;
     // the group's bands are dealt to `nchunk` workgroups per block (each pays one forward transform of the block)
-    const int per_wg = cut == 0 ? p->native_blk_bands : p->native_blk_bands_batch;
+    const int per_wg = cut == 0 ? kBlockBandsPerWg : kBlockBandsPerWgBatch;
     const int32_t nchunk = (int32_t)ceil_div(count[g], per_wg);
     const int64_t nblocks = ceil_div(p->n, native::block_valid(kBlockGroupWq[g]));
     if (tune_env("QI_NATIVE_VERBOSE")) {
@@ -637,7 +637,7 @@ std::vector<native::BlockItem> block_cut_items(const qi_plan* p, int kind, int c
     // band has a per-time plane and one partial slot per block like the other bands of the launch
     // -- in the table for many records one item per block covers all of them (one plane, one launch of its own)
     const int wq = (int)(p->native_split_e / 512);
-    il.edge_merged = (cut == 1 && p->native_edge_merge != 0) || sizeof(T) == 8;  // (float64: always, k_block64_edge)
+    il.edge_merged = cut == 1 || sizeof(T) == 8;  // (float64: always, k_block64_edge)
     if (il.edge_merged) {
       for (int64_t b = 0; b < split_blocks; ++b)
         items.push_back({-wq, (int32_t)b, 0, p->nsplit, il.nplanes, (int32_t)items.size()});
@@ -877,7 +877,7 @@ GaborRoutes classify_gabor_bands(const qi_plan* p, int bank, int64_t L, int32_t 
     // (float64: a band the float64 zoom takes stays there, unless it needs one of the finest grids)
     const int z64 = z64_level(p, bank, L, len);
     const bool zoom_first = (z64 >= 0 && !z64_level_for_block(p, z64)) ||
-                            (group > p->native_blk_maxwq && zoom_class(p, bank, L, len) >= 0);
+                            (group > kBlockMaxWq && zoom_class(p, bank, L, len) >= 0);
     bool to_block = group > 0 && !zoom_first, wide = band_mode(p, bank, L, len) == 1;
     BlockPick pk{j, group, 0};
     if (to_block) {
@@ -1072,7 +1072,7 @@ StxRoutes classify_stx_bands(const qi_plan* p, int32_t B, const int64_t* shift_i
     // (a band of the float64 zoom's finest grids goes to the block engine when that can take it: native_z64_block_from)
     const int z64 = z64_level(p, 2, p->n, len);
     const bool zoom_first = (z64 >= 0 && !z64_level_for_block(p, z64)) ||
-                            (group > p->native_blk_maxwq && zoom_class(p, 2, p->n, len) >= 0);
+                            (group > kBlockMaxWq && zoom_class(p, 2, p->n, len) >= 0);
     if (group > 0 && !zoom_first) {
       BlockPick pk{j, group, shift_index[j]};
       pk.analytic = 1;

@@ -331,12 +331,7 @@ int build_dual_items(qi_plan* p, int cut) {
 
 int launch_zoom_all(qi_plan* p, const native::ZoomArgs<float>& z, int64_t ct, hipStream_t st) {
   p->prof.begin(st, QI_STAGE_ZOOM_COARSE);
-  if (p->native_gather_fused > 0 && ct >= p->native_gather_fused) {
-    QI_TRY(native::launch_zoom_coarse_gather<float>(z, ct, st));
-  } else {
-    QI_TRY(native::launch_zoom_gather<float>(z, ct, st));
-    QI_TRY(native::launch_zoom_coarse<float>(z, ct, st));
-  }
+  QI_TRY(native::launch_zoom_coarse_gather<float>(z, ct, st));
   p->prof.end(QI_STAGE_ZOOM_COARSE, st);
   p->prof.begin(st, QI_STAGE_ZOOM);
   QI_TRY(native::launch_zoom<float>(z, ct, st));
@@ -379,6 +374,8 @@ struct TwoPass {
   int64_t nblk_max = 0, imd_elems = 0;  // most row groups of a sub-table; elements of the largest intermediate
 };
 
+constexpr int kPass2Wgs = 256;  // workgroups a pass-2 or float64 interpolation launch should have at least (band chunks are sized for it)
+
 // G: consecutive time residues (rows) per pass-2 workgroup
 TwoPass plan_two_pass(const qi_plan* p, int kind, int64_t C, int G) {
   TwoPass tp;
@@ -392,7 +389,7 @@ TwoPass plan_two_pass(const qi_plan* p, int kind, int64_t C, int G) {
     if ((int64_t)sb.t->imd_slots * sb.t->Lf > tp.imd_elems) tp.imd_elems = (int64_t)sb.t->imd_slots * sb.t->Lf;
     for (const auto& grp : sb.t->groups) {
       // chunks (workgroups along the band list): enough workgroups to fill the chip
-      int nc = (int)ceil_div(p->native_wgs, sb.nblk * C);
+      int nc = (int)ceil_div(kPass2Wgs, sb.nblk * C);
       if (nc < 1) nc = 1;
       if (nc > grp.count) nc = grp.count;
       sb.nchunk.push_back(nc);
@@ -618,11 +615,11 @@ native::TailCall<T> tail_call(const TileOut<T>& v, int64_t ct, const int32_t* ba
 }
 
 // epilogue: the per-time planes summed into the output row (when there are planes) and the partial sums finalised, in
-// fixed order -- one launch when both are wanted (one_launch = 0: always two)
+// fixed order -- one launch when both are wanted
 template <typename T>
-int launch_reductions(const native::TailCall<T>& t, bool time_via_part, bool one_launch, hipStream_t st) {
+int launch_reductions(const native::TailCall<T>& t, bool time_via_part, hipStream_t st) {
   const bool sums = t.part_band || t.part_stat;
-  if (time_via_part && sums && one_launch) return native::launch_tail<T>(t, st);
+  if (time_via_part && sums) return native::launch_tail<T>(t, st);
   if (time_via_part)
     QI_TRY(native::launch_time_reduce<T>(t.time_part, t.out_time, t.ct, t.n, t.chunk_total, t.edge_time, t.wmax, st));
   if (sums)
@@ -640,6 +637,9 @@ struct ZoomRows {
   int64_t stats = 0, slots = 0;  // stat slots of the launch; most partial slots a band fills
 };
 
+constexpr int kZoomWaves = 2048;    // waves each level of a zoom launch of one table should have at least
+constexpr int kZoomWgsJoint = 768;  // workgroups per table in the joint launch of qi_cwt_stx (512 .. 1024 measured within 1.5 %)
+
 // joint: the launch is one half of a joint launch of qi_cwt_stx
 ZoomRows plan_zoom_rows(const qi_plan* p, int kind, int64_t C, bool joint) {
   constexpr int NL = native::kZoomClasses;
@@ -650,13 +650,13 @@ ZoomRows plan_zoom_rows(const qi_plan* p, int kind, int64_t C, bool joint) {
   // budget is dealt over the rows), so the short-interpolator classes run as part of the 10-tap class of their grid
   // (their bands are oversampled enough for any of the three interpolators)
   for (int g = 0; g < NL; ++g) r.count[g] = zt.zoom_count[g];
-  if (C < p->native_zoom_short_from) {
+  if (C < native::kZoomShortFrom) {
     r.count[0] += r.count[5] + r.count[6];
     r.count[5] = r.count[6] = 0;
   }
   if (zt.nzoom <= 0) return r;
   // one launch for every level: each (level, chunk) pair is a row of the grid and owns a per-time plane
-  // All workgroups of the launch should be resident at once (native_zoom_wgs of them) and finish together: every
+  // All workgroups of the launch should be resident at once (zoom_wgs of them) and finish together: every
   // level starts with one row, then the level whose rows carry the most work per workgroup gets the next one
   // (per band: a little more at the higher levels, half at level 3 and up where a workgroup covers half the samples).
   const double level_cost[NL] = {1.0, 1.08, 1.25, 0.75, 1.0, 0.85, 0.75};
@@ -669,7 +669,7 @@ ZoomRows plan_zoom_rows(const qi_plan* p, int kind, int64_t C, bool joint) {
   }
   // (in the joint launch of qi_cwt_stx the rows of both tables queue behind each other: there the split by work wins,
   // measured 3 %; in a launch of one table the per-level rule does, 1.5 %)
-  const int64_t zoom_wgs = p->native_zoom_wgs > 0 ? p->native_zoom_wgs : (joint && p->native_fuse > 3 ? p->native_zoom_wgs_joint : 0);
+  const int64_t zoom_wgs = joint && p->native_fuse > 3 ? kZoomWgsJoint : 0;
   if (zoom_wgs > 0) {
     for (;;) {
       int best = -1;
@@ -695,7 +695,7 @@ ZoomRows plan_zoom_rows(const qi_plan* p, int kind, int64_t C, bool joint) {
   } else {
     for (int g = 0; g < NL; ++g) {
       if (r.count[g] <= 0) continue;
-      int nc = (int)ceil_div(p->native_zoom_waves, 4 * r.groups[g] * C);
+      int nc = (int)ceil_div(kZoomWaves, 4 * r.groups[g] * C);
       if (nc < 1) nc = 1;
       if (nc > r.count[g]) nc = r.count[g];
       r.nchunk[g] = nc;
@@ -792,17 +792,10 @@ int launch_zoom_stage(qi_plan* p, const native::ZoomArgs<float>& z, FusedCarry* 
   }
   const bool joint = finish && finish->has_zoom && finish->ct == ct;
   p->prof.begin(st, QI_STAGE_ZOOM_COARSE);
-  const bool gfused = p->native_gather_fused > 0 && ct >= p->native_gather_fused;
-  if (joint && gfused) {
+  if (joint) {
     QI_TRY(native::launch_zoom_coarse_gather2<T>(finish->zoom, z, ct, st));
-  } else if (joint) {
-    QI_TRY(native::launch_zoom_gather2<T>(finish->zoom, z, ct, st));
-    QI_TRY(native::launch_zoom_coarse2<T>(finish->zoom, z, ct, st));
-  } else if (gfused) {
-    QI_TRY(native::launch_zoom_coarse_gather<T>(z, ct, st));
   } else {
-    QI_TRY(native::launch_zoom_gather<T>(z, ct, st));
-    QI_TRY(native::launch_zoom_coarse<T>(z, ct, st));
+    QI_TRY(native::launch_zoom_coarse_gather<T>(z, ct, st));
   }
   p->prof.end(QI_STAGE_ZOOM_COARSE, st);
   p->prof.begin(st, QI_STAGE_ZOOM);
@@ -939,7 +932,7 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
     return QI_ERR_STATE;
   }
   // ---- qi_cwt_stx: which half of a joint tile this run is ----
-  const bool tail_one = time_via_part && sums && p->native_tail;
+  const bool tail_one = time_via_part && sums;
   // a CWT run whose records fit one tile leaves its block launch and tail to the Stockwell run ...
   const bool deferring = defer && kind == 0 && Ct == C && blocks && !shorts && tail_one;
   // ... which keeps the CWT run's scratch intact (its own follows it; only the spectra are shared) and finishes both
@@ -1001,7 +994,7 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
     } else {
       tc.edge_time = shorts ? s.edge_time : nullptr;
       tc.wmax = p->edge_wmax;
-      QI_TRY(launch_reductions<T>(tc, time_via_part, p->native_tail != 0, st));
+      QI_TRY(launch_reductions<T>(tc, time_via_part, st));
     }
     p->prof.end(QI_STAGE_EPILOGUE, st);
   }
@@ -1033,7 +1026,7 @@ Z64Rows plan_z64_rows(const qi_plan* p, const qi_plan::NativeTable& t, int64_t C
     r.z_off[g] = r.bytes / sizeof(cplx<T>);
     r.bytes += (size_t)t.z64_count[g] * (size_t)(((Lf / 64) << g) + 2 * native::kZ64Pad) * sizeof(cplx<T>);
     if (r.fine && g < native::kZ64FineLevels) continue;
-    int nc = (int)ceil_div(p->native_wgs, (n / native::kZ64Tile) * C);
+    int nc = (int)ceil_div(kPass2Wgs, (n / native::kZ64Tile) * C);
     r.zchunk[g] = nc < 1 ? 1 : (nc > t.z64_count[g] ? t.z64_count[g] : nc);
     r.chunks += r.zchunk[g];
   }
@@ -1043,8 +1036,7 @@ Z64Rows plan_z64_rows(const qi_plan* p, const qi_plan::NativeTable& t, int64_t C
     // epilogue), at least one row
     double work = 0.0, mine = (double)t.zf_count[c] * (2.0 * native::z64f_win(c) + 40.0);
     for (int q = 0; q < native::kZ64FineClasses; ++q) work += (double)t.zf_count[q] * (2.0 * native::z64f_win(q) + 40.0);
-    // (native_z64_rows: rows of all classes together a call should have at least)
-    const double want_rows = std::max<double>((double)p->native_z64_rows, (double)p->native_wgs / (double)(tiles_f * C));
+    const double want_rows = (double)kPass2Wgs / (double)(tiles_f * C);
     int nr = (int)std::ceil(want_rows * (mine / work));
     r.frow[c] = nr < 1 ? 1 : (nr > t.zf_count[c] ? t.zf_count[c] : nr);
     r.chunks += r.frow[c];
@@ -1227,7 +1219,7 @@ int run_native64(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tf
     native::TailCall<T> tc = tail_call<T>(v, ct, nullptr);
     tc.edge_time = shorts ? s.edge_time : nullptr;
     tc.wmax = p->edge_wmax;
-    QI_TRY(launch_reductions<T>(tc, time_via_part, true, st));
+    QI_TRY(launch_reductions<T>(tc, time_via_part, st));
     p->prof.end(QI_STAGE_EPILOGUE, st);
     p->prof.unchain();
   }
@@ -1339,7 +1331,7 @@ int run_small(qi_plan* p, int njobs, const int* kinds, const qi_tfr_out* const* 
       QI_TRY(native::launch_tail2<T>(tc[0], tc[1], st));
     } else {
       for (int q = 0; q < njobs; ++q)
-        if (job[q].planes || sums(tc[q])) QI_TRY(launch_reductions<T>(tc[q], job[q].planes, true, st));
+        if (job[q].planes || sums(tc[q])) QI_TRY(launch_reductions<T>(tc[q], job[q].planes, st));
     }
     p->prof.end(QI_STAGE_EPILOGUE, st);
     p->prof.unchain();

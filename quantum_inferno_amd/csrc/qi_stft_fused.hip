@@ -28,11 +28,6 @@ namespace {
 #define QI_STFT_THREADS 256
 #endif
 constexpr int kStftThreads = QI_STFT_THREADS;
-#ifdef QI_STFT_WAVES  // experiments: waves per SIMD the register budget must allow
-#define QI_STFT_BOUNDS __launch_bounds__(kStftThreads, QI_STFT_WAVES)
-#else
-#define QI_STFT_BOUNDS __launch_bounds__(kStftThreads)
-#endif
 
 template <typename T>
 __device__ __forceinline__ void sincospi_t(T x, T* s, T* c);
@@ -169,9 +164,9 @@ __device__ __forceinline__ void stft_red_tail(unsigned char* lds_raw, const Stft
 // of one bin, so the sum over a group's segments is group_sum over G adjacent lanes; no thread leaves before the tail (a
 // segment past the last one is a tile of zeros: P = 0, nothing stored).  No atomics: every partial has one writer.
 template <typename T, int LOG2R, int LOG2C, bool PLAIN, bool RED = false, bool WZ = true, bool WB = true>
-__global__ void QI_STFT_BOUNDS k_stft_fused(const T* __restrict__ sig, const T* __restrict__ win,
-                                                            const cplx<T>* __restrict__ twg, cplx<T>* __restrict__ Z,
-                                                            T* __restrict__ bits, StftFusedArgs a) {
+__global__ void __launch_bounds__(kStftThreads) k_stft_fused(const T* __restrict__ sig, const T* __restrict__ win,
+                                                             const cplx<T>* __restrict__ twg, cplx<T>* __restrict__ Z,
+                                                             T* __restrict__ bits, StftFusedArgs a) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   constexpr int R = 1 << LOG2R, C = 1 << LOG2C, M = R * C, RS = C + 1, TILE = R * RS + 1;
   const int G = a.G;
@@ -259,11 +254,7 @@ __global__ void QI_STFT_BOUNDS k_stft_fused(const T* __restrict__ sig, const T* 
   };
   // Two consecutive segments at half overlap (the product's geometry) share their middle half: a wave loads the three
   // halves once, all in flight together, and windows them twice.
-#ifdef QI_STFT_NO_PAIRS
-  constexpr bool kPairs = false;
-#else
   constexpr bool kPairs = PLAIN && NP >= 2 && NP * kWave == M && kFast;
-#endif
   bool pairs = false;
   if constexpr (kPairs)
     pairs = a.hop == M && a.seg == 2 * M && (G & 1) == 0 && (reinterpret_cast<uintptr_t>(win) & (2 * sizeof(T) - 1)) == 0;

@@ -1,7 +1,8 @@
 // Zoom engine: the narrow-spectrum bands of a panel (long atoms: a few hundred to a few ten thousand occupied bins
 // out of a million) are slowly varying envelopes on a carrier.  Their occupied bins, moved to baseband, are
 // transformed on a COARSE time grid on which the band is oversampled at least 4 times (one small inverse FFT per
-// band: k_zoom_gather + k_zoom_coarse), and the panel is produced from that by band-limited interpolation -- N-tap
+// band: k_zoom_coarse_g / k_zoom_coarse2g of qi_block.hip), and the panel is produced from that by band-limited interpolation
+// -- N-tap
 // interpolators that are exact at the Chebyshev nodes of the band (10 taps at 4 x oversampling: 9e-8 of a unit tone
 // anywhere in the band; 6 and 4 taps for bands oversampled 8 and 32 times: see zoom_weights) -- times the carrier
 // phasor.  About 35-60 instructions per output instead of a
@@ -18,7 +19,6 @@
 #include "qi_device.hpp"
 #include "qi_native.hpp"
 #include "qi_fft_reg.hpp"
-#include "qi_zoom_gather.hpp"
 
 namespace qi {
 namespace native {
@@ -29,30 +29,6 @@ constexpr int kZoomThreads = 256;
 
 __device__ __forceinline__ float lane_value(float v, int lane) {
   return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), lane));
-}
-
-// One thread per (kappa0, tau1) of the coarse stage's input (zoom_gather_value), written to the band's planes
-// [tau1][kappa0], transformed in place by the coarse stage -- the stand-alone form; qi_cwt_stx's joint launch gathers
-// inside the plane transforms (k_zoom_coarse2g, qi_block.hip).
-template <typename T, bool STX>
-__device__ __forceinline__ void zoom_gather_plane(const ZoomArgs<T>& a, const uint32_t plane) {
-  const BandDesc bd = load_uniform(a.bands + *as_const(a.plane_band + plane));  // plane of the record's coarse storage
-  const int32_t kappa0 = (int32_t)(blockIdx.x * 256 + threadIdx.x);
-  const uint32_t tau1 = plane - (uint32_t)bd.edge;
-  const int64_t ch = blockIdx.z;
-  const cplx<T>* __restrict__ X = a.X + ch * ((int64_t)a.x_mask + 1);
-  a.coarse[((int64_t)ch * a.planes + bd.edge) * kBlk + (int32_t)tau1 * kBlk + kappa0] =
-      zoom_gather_value<T, STX>(a, bd, tau1, kappa0, X);
-}
-template <typename T, bool STX>
-__global__ void __launch_bounds__(256) k_zoom_gather(ZoomArgs<T> a) {
-  zoom_gather_plane<T, STX>(a, blockIdx.y);
-}
-// qi_cwt_stx: the planes of the styx table (a0) and of the Stockwell table (a2) in one launch
-template <typename T>
-__global__ void __launch_bounds__(256) k_zoom_gather2(ZoomArgs<T> a0, ZoomArgs<T> a2) {
-  if (blockIdx.y < (uint32_t)a0.planes) zoom_gather_plane<T, false>(a0, blockIdx.y);
-  else zoom_gather_plane<T, true>(a2, blockIdx.y - (uint32_t)a0.planes);
 }
 
 // Fine stage of one level.  PHASOR: multiply by the carrier exp(2 pi i k_c f / Lf) (Gabor banks; the Stockwell bands
@@ -270,28 +246,6 @@ int launch_zoom_v(const ZoomArgs<T>& a, dim3 grid, hipStream_t st) {
 
 int64_t zoom_groups(int64_t n, int level) {
   return n / ((int64_t)kZoomD * zoom_steps(level) * (kZoomThreads / kWave));
-}
-
-template <>
-int launch_zoom_gather<float>(const ZoomArgs<float>& a, int64_t n_channels, hipStream_t st) {
-  if (a.nbands <= 0) return QI_OK;
-  dim3 grid((unsigned)(kBlk / 256), (unsigned)a.planes, (unsigned)n_channels);
-  if (a.stx) k_zoom_gather<float, true><<<grid, 256, 0, st>>>(a);
-  else k_zoom_gather<float, false><<<grid, 256, 0, st>>>(a);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
-}
-
-template <>
-int launch_zoom_gather2<float>(const ZoomArgs<float>& a0, const ZoomArgs<float>& a2, int64_t n_channels, hipStream_t st) {
-  if (a0.stx || !a2.stx || a0.nbands <= 0 || a2.nbands <= 0) {
-    set_error("zoom engine: the joint gather takes a styx table and a Stockwell table");
-    return QI_ERR_STATE;
-  }
-  dim3 grid((unsigned)(kBlk / 256), (unsigned)(a0.planes + a2.planes), (unsigned)n_channels);
-  k_zoom_gather2<float><<<grid, 256, 0, st>>>(a0, a2);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
 }
 
 // grid of a table's fine launch: workgroups along time (the level with the most) x rows

@@ -613,9 +613,10 @@ void launch_fine_cls(const Z64FineArgs& a, dim3 grid, hipStream_t st) {
 
 template <int KIND>
 int launch_interp_v(const Z64Args& a, dim3 grid, hipStream_t st) {
-  // the grids of Lf / 16 and Lf / 8 samples: interpolation on the matrix pipe (QI_NATIVE_Z64_MFMA=0: the LDS-window kernel)
-  static const bool use_mfma = !(tune_env("QI_NATIVE_Z64_MFMA") && atoi(tune_env("QI_NATIVE_Z64_MFMA")) == 0);
-  if (use_mfma && (a.log2d == 4 || a.log2d == 3) && kZ64Tile % (4 * 256) == 0 && (a.n / 2) % 256 == 0) {
+  // the grids of Lf / 16 and Lf / 8 samples: interpolation on the matrix pipe.  Every wave of k_z64_mfma starts on a
+  // multiple of 256 samples, (n / 2) % 256 == 0: launch_z64_interp has checked that n is a multiple of kZ64Tile, so of 1024
+  static_assert(kZ64Tile % (4 * 256) == 0, "k_z64_mfma: each of the four waves takes whole 256-sample groups of the tile");
+  if (a.log2d == 4 || a.log2d == 3) {
     const bool coef = a.coef != nullptr;
     if (a.log2d == 4) {
       if (coef) k_z64_mfma<KIND, 4, true><<<grid, kZ64Threads, 0, st>>>(a);
@@ -630,8 +631,6 @@ int launch_interp_v(const Z64Args& a, dim3 grid, hipStream_t st) {
   switch (a.log2d) {
     case 6: k_z64_interp<KIND, 6><<<grid, kZ64Threads, 0, st>>>(a); break;
     case 5: k_z64_interp<KIND, 5><<<grid, kZ64Threads, 0, st>>>(a); break;
-    case 4: k_z64_interp<KIND, 4><<<grid, kZ64Threads, 0, st>>>(a); break;
-    case 3: k_z64_interp<KIND, 3><<<grid, kZ64Threads, 0, st>>>(a); break;
     default: k_z64_interp<KIND, 2><<<grid, kZ64Threads, 0, st>>>(a); break;
   }
   QI_LAUNCH_CHECK();

@@ -544,7 +544,7 @@ REQUIRED = [
 ]
 # A category no table can reach, with the reason from the plan code (qi_plan_build.hip): dead code as the library is configured.
 UNREACHABLE = {
-    "pass2/one-pass": "make_native_table marks a band for the one-pass loader when its support is <= native_kmax = 12288 bins and "
+    "pass2/one-pass": "make_native_table marks a band for the one-pass loader when its support is <= kOnePassMax = 12288 bins and "
                       "zoom_class refuses it; at the lengths where pass 2 runs (Lf = 2^20, 2^21) the zoom grids of levels 0..3 take "
                       "any support up to Lf / 32 >= 32768 bins, and in float64 upload_native_table gives every such band to the "
                       "float64 zoom (support <= Lf / 16).  Only the short-atom table (zoom_class returns -1 for it) still uses the "

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of development switches on one bench leg, settings interleaved twice in ONE job (boxes differ by a few percent):
-#   tools/ab_leg.sh "<bench.py args>" "ENV=a ENV2=b" "ENV=c" ...     e.g.  tools/ab_leg.sh "--legs f64" "QI_NATIVE_Z64_SLOTS=0" "QI_NATIVE_Z64_SLOTS=1"
+#   tools/ab_leg.sh "<bench.py args>" "ENV=a ENV2=b" "ENV=c" ...     e.g.  tools/ab_leg.sh "--legs f64" "QI_NATIVE_Z64_FINE=0" "QI_NATIVE_Z64_FINE=1"
 args=$1; shift
 for rep in 1 2; do
   for cfg in "$@"; do

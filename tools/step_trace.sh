@@ -1,11 +1,11 @@
 #!/bin/bash
 # per-kernel average durations of the one-record step (BASELINE configs[1]): rocprofv3 --kernel-trace --stats of tools/pair_probe.py
 # usage (GPU box): bash tools/step_trace.sh [tag] [channels]   -> gpurun_out/<tag>/{probe.txt,kernel_stats.csv,stats.txt}
-tag=${1:-step}; ch=${2:-1}
+tag=${1:-step}; ch=${2:-1}; here=$(cd "$(dirname "$0")" && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-QI_TUNE=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $GRAFT_REPO_ROOT/tools/pair_probe.py $ch 0:0:0 > $out/probe.txt 2>&1
+QI_TUNE=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $here/pair_probe.py $ch > $out/probe.txt 2>&1
 rc=$?
 cd $GRAFT_REPO_ROOT
 cat $out/probe.txt | grep -v amdgpu.ids
