@@ -277,36 +277,20 @@ __device__ __forceinline__ void fft4096_tail(cplx<T> (&v)[16], cplx<T>* __restri
 template <typename T>
 __device__ __forceinline__ void flush_band_sum(const BlockArgs<T>& a, int64_t ch, int64_t blk, int pending, const double* sums,
                                                int tid) {
-  if (pending >= 0 && tid == 0) {
-    double r = 0.0;
-    for (int q = 0; q < kBlkThreads / kWave; ++q) r += sums[q];
-    a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + blk] = r;
-  }
+  if (pending >= 0 && tid == 0)
+    a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + blk] = fold_band_sum<kBlkThreads / kWave>(sums);
 }
 
-// Workgroup maximum / sum / sum of the waves' r0 / r1 / r2 through buf (free: a barrier has passed since its last reader);
-// thread 0 writes them to statistics slot `stat_slot` -- `follows`: the slot already holds earlier bands and is added to --
-// and the sum r1 to a.part_band[band_slot] (band_slot >= 0: edge_item, whose one band has no wave sums to flush).
+// Workgroup maximum / sum / sum of the waves' r0 / r1 / r2 (fold_wave_stats) through buf (free: a barrier has passed since
+// its last reader); thread 0 writes them to statistics slot `stat_slot` -- `follows`: the slot already holds earlier bands and
+// is added to -- and the sum to a.part_band[band_slot] (band_slot >= 0: edge_item, whose one band has no wave sums to flush).
 template <typename T>
 __device__ __forceinline__ void reduce_stats(const BlockArgs<T>& a, cplx<T>* __restrict__ buf, double r0, double r1, double r2,
                                              int64_t ch, int32_t stat_slot, int tid, bool follows = false, int64_t band_slot = -1) {
-  constexpr int NW = kBlkThreads / kWave;
   if (!a.part_stat && band_slot < 0) return;  // (the same for the whole workgroup)
-  const int lane = tid & (kWave - 1), wv = tid / kWave;
-  double* fin = reinterpret_cast<double*>(buf);
-  if (lane == 0) {
-    fin[wv] = r0;
-    fin[NW + wv] = r1;
-    fin[2 * NW + wv] = r2;
-  }
-  __syncthreads();
+  const PanelStats ps = fold_wave_stats<kBlkThreads / kWave>(r0, r1, r2, reinterpret_cast<double*>(buf), tid);
   if (tid == 0) {
-    double m = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int q = 0; q < NW; ++q) {
-      m = fin[q] > m ? fin[q] : m;
-      s1 += fin[NW + q];
-      s2 += fin[2 * NW + q];
-    }
+    const double m = ps.mx, s1 = ps.sum, s2 = ps.plogp;
     if (band_slot >= 0 && a.part_band) a.part_band[band_slot] = s1;
     if (a.part_stat) {
       double* o = a.part_stat + ((int64_t)ch * a.stat_stride + a.stat_base + stat_slot) * 3;

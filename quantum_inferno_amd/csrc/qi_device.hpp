@@ -65,6 +65,63 @@ __device__ __forceinline__ T wave_max(T v) {
   return cd > ab ? cd : ab;
 }
 
+// ---- the two workgroup folds behind every panel engine's epilogue (NW waves) ---------------------------------------------
+// Their order -- wave_max / wave_sum, one LDS slot per wave, a barrier, thread 0 over the slots in wave order from 0.0 -- is
+// what makes the partials, and with them power_band and stats, the same bits whatever the batch or engine mix.
+
+// Band-sum fold: the sum of the NW wave sums in `sums` (an LDS row that lane 0 of every wave has written and a barrier has
+// made visible: slot and barrier are the caller's).  For thread 0.
+template <int NW>
+__device__ __forceinline__ double fold_band_sum(const double* sums) {
+  double s = 0.0;
+  for (int q = 0; q < NW; ++q) s += sums[q];
+  return s;
+}
+
+// Statistics fold (fold_stats, below): the workgroup's {max P, sum P, sum P log2 P} from every lane's mx / tot / plogp, through
+// the 3 NW doubles of LDS at `fin`, slot [k * NW + wave]; one barrier inside -- a barrier the area needs BEFORE it may be
+// overwritten is the caller's.  The result is for thread 0 ONLY; every other thread gets zeros.
+// PRECONDITION: every thread of the workgroup calls it, outside any divergent branch: the WHOLE wave is active (see wave_sum /
+// wave_max above) and the barrier is met by all.
+struct PanelStats {
+  double mx, sum, plogp;
+};
+// Two things in its form were decided by the kernels that sit on their register budget (HISTORY s8l).  The area is handed
+// over as the kernel's `double s_fin[3][NW]` or, by the block kernels, as a plain pointer into their transform buffer: the same
+// slot, but the compiler forms its address differently, and the other form is an occupancy step of one k_pass2 or 4 bytes of
+// scratch in three k_block64 -- so each keeps the form it had.  And the fold from the wave results r0 / r1 / r2 on can be called
+// alone (fold_wave_stats): the block kernels reduce over the wave BEFORE the barrier that frees `fin`, and reducing behind it
+// is again 4 bytes of scratch in two k_block64.  The lanes' values are widened to double just before each reduction.
+template <int NW>
+__device__ __forceinline__ double& stat_slot(double (*fin)[NW], int k, int wave) { return fin[k][wave]; }
+template <int NW>
+__device__ __forceinline__ double& stat_slot(double* fin, int k, int wave) { return fin[k * NW + wave]; }
+template <int NW, class Area>
+__device__ __forceinline__ PanelStats fold_wave_stats(double r0, double r1, double r2, Area fin, int tid) {
+  if ((tid & (kWave - 1)) == 0) {
+    const int wv = tid / kWave;
+    stat_slot<NW>(fin, 0, wv) = r0;
+    stat_slot<NW>(fin, 1, wv) = r1;
+    stat_slot<NW>(fin, 2, wv) = r2;
+  }
+  __syncthreads();
+  PanelStats s = {0.0, 0.0, 0.0};
+  if (tid == 0) {
+    for (int q = 0; q < NW; ++q) {
+      const double m = stat_slot<NW>(fin, 0, q);
+      s.mx = m > s.mx ? m : s.mx;
+      s.sum += stat_slot<NW>(fin, 1, q);
+      s.plogp += stat_slot<NW>(fin, 2, q);
+    }
+  }
+  return s;
+}
+template <int NW, typename T, typename P, class Area>
+__device__ __forceinline__ PanelStats fold_stats(T mx, T tot, P plogp, Area fin, int tid) {
+  const double r0 = wave_max((double)mx), r1 = wave_sum((double)tot), r2 = wave_sum((double)plogp);
+  return fold_wave_stats<NW>(r0, r1, r2, fin, tid);
+}
+
 // Read-only global data through the constant address space: a load whose address is the same for the whole wave becomes a
 // scalar load (s_load_dword*): its result lives in scalar registers and is an operand of the lanes' arithmetic.  For small
 // wave-uniform tables only -- the scalar cache is no streaming path.

@@ -87,8 +87,9 @@ __global__ void k_stx_window(const cplx<T>* __restrict__ X, cplx<T>* __restrict_
 // of one channel and walks the tile's bands, so the per-time sums stay in registers.
 template <typename T, bool REAL_IN>
 __global__ void __launch_bounds__(kEpiThreads) k_epilogue(EpiArgs<T> a) {
-  __shared__ double s_red[2][kEpiThreads / kWave];
-  __shared__ double s_fin[3][kEpiThreads / kWave];
+  constexpr int NW = kEpiThreads / kWave;
+  __shared__ double s_red[2][NW];
+  __shared__ double s_fin[3][NW];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
   const int64_t blk = blockIdx.x, c = blockIdx.y, nblk = gridDim.x;
   const int64_t t0 = blk * kEpiSpan + (int64_t)tid * kEpiVec;
@@ -128,12 +129,7 @@ __global__ void __launch_bounds__(kEpiThreads) k_epilogue(EpiArgs<T> a) {
       double r = wave_sum((double)rowacc);
       if (lane == 0) s_red[j & 1][wv] = r;
       __syncthreads();
-      if (tid == 0) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < kEpiThreads / kWave; ++w) s += s_red[j & 1][w];
-        a.part_band[(c * a.B + a.j0 + j) * nblk + blk] = s;
-      }
+      if (tid == 0) a.part_band[(c * a.B + a.j0 + j) * nblk + blk] = fold_band_sum<NW>(s_red[j & 1]);
     }
   }
   T tot = T(0);
@@ -149,25 +145,12 @@ __global__ void __launch_bounds__(kEpiThreads) k_epilogue(EpiArgs<T> a) {
     }
   }
   if (a.part_stat) {
-    double r0 = wave_max((double)mx), r1 = wave_sum((double)tot), r2 = wave_sum(plogp);
-    if (lane == 0) {
-      s_fin[0][wv] = r0;
-      s_fin[1][wv] = r1;
-      s_fin[2][wv] = r2;
-    }
-    __syncthreads();
+    const PanelStats st = fold_stats<NW>(mx, tot, plogp, s_fin, tid);
     if (tid == 0) {
-      double m = 0.0, s1 = 0.0, s2 = 0.0;
-#pragma unroll
-      for (int w = 0; w < kEpiThreads / kWave; ++w) {
-        m = s_fin[0][w] > m ? s_fin[0][w] : m;
-        s1 += s_fin[1][w];
-        s2 += s_fin[2][w];
-      }
       double* o = a.part_stat + ((c * a.ntile_b + a.tile_b) * nblk + blk) * 3;
-      o[0] = m;
-      o[1] = s1;
-      o[2] = s2;
+      o[0] = st.mx;
+      o[1] = st.sum;
+      o[2] = st.plogp;
     }
   }
 }

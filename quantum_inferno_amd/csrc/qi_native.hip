@@ -46,17 +46,24 @@ struct Cfg {
 
 // In-kernel phase stamps (diagnostic build only, -DQI_NATIVE_STAMPS): wave 0 of every workgroup sums the cycles it
 // spends in each phase of the band loop; never enabled in the shipped library.
+// A kernel's `Stamps st` travels by reference to the functions that stamp (QI_STAMP finds it by that name); it is empty in
+// the shipped library.
 #ifdef QI_NATIVE_STAMPS
+struct Stamps {
+  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long last = __builtin_amdgcn_s_memtime();
+};
 #define QI_STAMP(k)                                                        \
   do {                                                                     \
     __builtin_amdgcn_sched_barrier(0);                                     \
     const unsigned long long now_ = __builtin_amdgcn_s_memtime();          \
     __builtin_amdgcn_s_waitcnt(0xC07F);                                    \
-    st_acc[k] += now_ - st_last;                                           \
-    st_last = now_;                                                        \
+    st.acc[k] += now_ - st.last;                                           \
+    st.last = now_;                                                        \
     __builtin_amdgcn_sched_barrier(0);                                     \
   } while (0)
 #else
+struct Stamps {};
 #define QI_STAMP(k)
 #endif
 
@@ -247,11 +254,7 @@ __device__ __forceinline__ void fill_step_twiddles(cplx<T>* tw) {
 // thread right after the first barrier (flush of a pending reduction), `before_step2` after the last one.
 template <typename T, class C, class F, class F2>
 __device__ __forceinline__ void rows_fft1024_regs(cplx<T> (&v)[16], cplx<T>* buf, const cplx<T>* tw, cplx<T> (&u)[16],
-                                                  bool skip, F between, F2 before_step2
-#ifdef QI_NATIVE_STAMPS
-                                                  , unsigned long long (&st_acc)[8], unsigned long long& st_last
-#endif
-) {
+                                                  bool skip, F between, F2 before_step2, Stamps& st) {
   const int tid = threadIdx.x;
   const int g1 = tid / 64, a1 = tid % 64;
   const int d2 = tid / (4 * C::G), c2 = (tid % (4 * C::G)) / C::G, g2 = tid % C::G;
@@ -295,20 +298,12 @@ __device__ __forceinline__ void rows_fft1024_regs(cplx<T> (&v)[16], cplx<T>* buf
 
 // same, starting from the natural-order LDS image A[g][k] (row stride SR) the caller filled and synchronised
 template <typename T, class C>
-__device__ __forceinline__ void rows_fft1024(cplx<T>* buf, const cplx<T>* tw, cplx<T> (&u)[16], bool skip
-#ifdef QI_NATIVE_STAMPS
-                                             , unsigned long long (&st_acc)[8], unsigned long long& st_last
-#endif
-) {
+__device__ __forceinline__ void rows_fft1024(cplx<T>* buf, const cplx<T>* tw, cplx<T> (&u)[16], bool skip, Stamps& st) {
   const int g1 = threadIdx.x / 64, a1 = threadIdx.x % 64;
   cplx<T> v[16];
 #pragma unroll
   for (int b = 0; b < 16; ++b) v[b] = buf[g1 * C::SR + a1 + 64 * b];
-#ifdef QI_NATIVE_STAMPS
-  rows_fft1024_regs<T, C>(v, buf, tw, u, skip, [] {}, [] {}, st_acc, st_last);
-#else
-  rows_fft1024_regs<T, C>(v, buf, tw, u, skip, [] {}, [] {});
-#endif
+  rows_fft1024_regs<T, C>(v, buf, tw, u, skip, [] {}, [] {}, st);
 }
 
 // ---- pass 1 (wide bands, and the forward transform of the records) -------------------------------------------------
@@ -356,21 +351,14 @@ __global__ void __launch_bounds__(C::TH) k_pass1(RowArgs<T> a) {
   cplx<T>* __restrict__ dst = LOW ? a.imd + (int64_t)ch * fwd_low_rows(a.N1) * kN2 + k2
                                   : a.imd + ((int64_t)ch * a.imd_slots + bd.gen_slot) * a.Lf + k2;
   const uint32_t roll = a.neg_last_row ? 1u : 0u, cmask = (uint32_t)a.N1 - 1u;
-#ifdef QI_NATIVE_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = __builtin_amdgcn_s_memtime();
-#endif
+  Stamps st;
 #pragma unroll 1
   for (int ph = ph_first; ph < ph_last; ++ph) {
     if (!QI_DBG(2)) load_full<T, C, SRC, NPH>(buf, a, bd, Xc, sigc, row0, ph);
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
     cplx<T> u[16];
-#ifdef QI_NATIVE_STAMPS
-    rows_fft1024<T, C>(buf, tw, u, QI_DBG(4), st_acc, st_last);
-#else
-    rows_fft1024<T, C>(buf, tw, u, QI_DBG(4));
-#endif
+    rows_fft1024<T, C>(buf, tw, u, QI_DBG(4), st);
     // pass twiddle W_Lf^(k2 t1) along t1 = NPH (d2 + 16 c2 + 64 c1) + ph by a float64 recurrence over c1
     double wr, wi, sr, si;
     unit_root_t<T>((k2 * (uint32_t)(NPH * (d2 + 16 * c2) + ph)) & mask, a.two_over_len, &wr, &wi);
@@ -408,13 +396,8 @@ __global__ void __launch_bounds__(C::TH) k_fwd2(RowArgs<T> a, cplx<T>* __restric
   cplx<T> v[16], u[16];
   load_imd_direct<T>(v, a.imd + (int64_t)ch * a.imd_slots * a.Lf, row0 + tid / 64, tid % 64);
   __syncthreads();  // step twiddles ready
-#ifdef QI_NATIVE_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = 0;
-  rows_fft1024_regs<T, C>(v, buf, tw, u, false, [] {}, [] {}, st_acc, st_last);
-#else
-  rows_fft1024_regs<T, C>(v, buf, tw, u, false, [] {}, [] {});
-#endif
+  Stamps st;  // (nobody reads this kernel's)
+  rows_fft1024_regs<T, C>(v, buf, tw, u, false, [] {}, [] {}, st);
   cplx<T>* __restrict__ dst = Xout + ch * a.Lf + row0 + g2 + (uint32_t)a.N1 * (d2 + 16 * c2);
   const uint32_t tstep = 64u * (uint32_t)a.N1;
 #pragma unroll
@@ -497,8 +480,9 @@ __global__ void __launch_bounds__(C::TH) k_pass2(RowArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cplx<T>* buf = reinterpret_cast<cplx<T>*>(smem);
   cplx<T>* tw = buf + C::BUF;
-  __shared__ double s_red[2][C::TH / kWave];
-  __shared__ double s_fin[3][C::TH / kWave];
+  constexpr int NW = C::TH / kWave;
+  __shared__ double s_red[2][NW];
+  __shared__ double s_fin[3][NW];
   __shared__ double ltab[sizeof(T) == 8 ? 128 : 1][2];  // float64: the log2 table of the entropy sums in LDS (log2_pos)
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
   if (sizeof(T) == 8 && tid < 128) {
@@ -526,24 +510,18 @@ __global__ void __launch_bounds__(C::TH) k_pass2(RowArgs<T> a) {
   const cplx<T>* Xc = a.X + ch * a.Lf;
   int64_t pending = -1;  // band whose row sum sits in s_red waiting for a barrier
   int par = 0;
+  auto flush = [&] {  // the pending band's wave sums (complete once a barrier has passed) into its part_band slot
+    if (pending >= 0 && tid == 0)
+      a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + grp] = fold_band_sum<NW>(s_red[par ^ 1]);
+  };
 
-#ifdef QI_NATIVE_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = __builtin_amdgcn_s_memtime();
-#endif
+  Stamps st;
   // list entries blockIdx.y, blockIdx.y + nchunk, ...: every chunk gets the same mix of narrow and wide bands
   for (int64_t jj = blockIdx.y; jj < a.nbands; jj += gridDim.y) {
     const BandDesc bd = a.bands[jj];
     const int64_t j = bd.out_band;  // row of the panel this band writes
     QI_STAMP(7);
     cplx<T> v[16], u[16];
-    auto flush = [&] {
-      if (pending >= 0 && tid == 0) {
-        double s = 0.0;
-        for (int w = 0; w < C::TH / kWave; ++w) s += s_red[par ^ 1][w];
-        a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + grp] = s;
-      }
-    };
     if (bd.mode == 0) {
       if (!QI_DBG(2)) load_pruned<T, C, STX>(buf, tw + C::NR + C::TW2, a, bd, Xc, t1_first);
       __builtin_amdgcn_sched_barrier(0);
@@ -557,11 +535,7 @@ __global__ void __launch_bounds__(C::TH) k_pass2(RowArgs<T> a) {
         load_imd_direct<T>(v, a.imd + ((int64_t)ch * a.imd_slots + bd.gen_slot) * a.Lf, row0 + tid / 64, tid % 64);
       QI_STAMP(0);
     }
-#ifdef QI_NATIVE_STAMPS
-    rows_fft1024_regs<T, C>(v, buf, tw, u, QI_DBG(4), flush, [] {}, st_acc, st_last);
-#else
-    rows_fft1024_regs<T, C>(v, buf, tw, u, QI_DBG(4), flush, [] {});
-#endif
+    rows_fft1024_regs<T, C>(v, buf, tw, u, QI_DBG(4), flush, [] {}, st);
 
     const int64_t orow = ((int64_t)ch * a.panel_bands + j) * a.n;
     char* __restrict__ coef_row = reinterpret_cast<char*>(a.coef ? a.coef + orow : nullptr);
@@ -613,16 +587,12 @@ __global__ void __launch_bounds__(C::TH) k_pass2(RowArgs<T> a) {
 #ifdef QI_NATIVE_STAMPS
   if (a.stamps && tid == 0) {
     unsigned long long* o = a.stamps + ((((int64_t)ch * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8);
-    for (int k = 0; k < 8; ++k) o[k] = st_acc[k];
+    for (int k = 0; k < 8; ++k) o[k] = st.acc[k];
   }
 #endif
 
   __syncthreads();
-  if (pending >= 0 && tid == 0) {
-    double s = 0.0;
-    for (int w = 0; w < C::TH / kWave; ++w) s += s_red[par ^ 1][w];
-    a.part_band[((int64_t)ch * a.panel_bands + pending) * a.nblk + grp] = s;
-  }
+  flush();
   T tot = T(0);
   char* __restrict__ time_row =
       reinterpret_cast<char*>(a.time_part ? a.time_part + ((int64_t)ch * a.chunk_total + a.chunk_base + blockIdx.y) * a.n
@@ -634,24 +604,12 @@ __global__ void __launch_bounds__(C::TH) k_pass2(RowArgs<T> a) {
     if (time_row) *reinterpret_cast<T*>(time_row + (size_t)(tt * (uint32_t)sizeof(T))) = col[i];
   }
   if (a.part_stat) {
-    const double r0 = wave_max((double)mx), r1 = wave_sum((double)tot), r2 = wave_sum(plogp);
-    if (lane == 0) {
-      s_fin[0][wv] = r0;
-      s_fin[1][wv] = r1;
-      s_fin[2][wv] = r2;
-    }
-    __syncthreads();
+    const PanelStats ps = fold_stats<NW>(mx, tot, plogp, s_fin, tid);
     if (tid == 0) {
-      double m = 0.0, s1 = 0.0, s2 = 0.0;
-      for (int w = 0; w < C::TH / kWave; ++w) {
-        m = s_fin[0][w] > m ? s_fin[0][w] : m;
-        s1 += s_fin[1][w];
-        s2 += s_fin[2][w];
-      }
       double* o = a.part_stat + ((int64_t)ch * a.stat_stride + (int64_t)(a.chunk_base + blockIdx.y) * a.stat_nblk + grp) * 3;
-      o[0] = m;
-      o[1] = s1;
-      o[2] = s2;
+      o[0] = ps.mx;
+      o[1] = ps.sum;
+      o[2] = ps.plogp;
     }
   }
 }

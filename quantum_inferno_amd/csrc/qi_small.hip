@@ -223,12 +223,7 @@ __global__ void __launch_bounds__((1 << LOG2L) / 16) k_small_band(SmallArgs<T> a
       const double rs = wave_sum((double)rowacc);
       if (lane == 0) s_red[0][wv] = rs;
       __syncthreads();  // (the next write of s_red[0] lies behind the barriers of the next band's transform)
-      if (tid == 0) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) s += s_red[0][w];
-        a.part_band[c * a.B + j] = s;
-      }
+      if (tid == 0) a.part_band[c * a.B + j] = fold_band_sum<NW>(s_red[0]);
     }
   }
 
@@ -245,26 +240,13 @@ __global__ void __launch_bounds__((1 << LOG2L) / 16) k_small_band(SmallArgs<T> a
     }
   }
   if (a.part_stat) {
-    const double r0 = wave_max((double)mx), r1 = wave_sum((double)tot), r2 = wave_sum(plogp);
     __syncthreads();  // thread 0 is done with the last band's s_red[0]
-    if (lane == 0) {
-      s_red[0][wv] = r0;
-      s_red[1][wv] = r1;
-      s_red[2][wv] = r2;
-    }
-    __syncthreads();
+    const PanelStats ps = fold_stats<NW>(mx, tot, plogp, s_red, tid);
     if (tid == 0) {
-      double m = 0.0, s1 = 0.0, s2 = 0.0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        m = s_red[0][w] > m ? s_red[0][w] : m;
-        s1 += s_red[1][w];
-        s2 += s_red[2][w];
-      }
       double* o = a.part_stat + (c * a.nchunk + chunk) * 3;
-      o[0] = m;
-      o[1] = s1;
-      o[2] = s2;
+      o[0] = ps.mx;
+      o[1] = ps.sum;
+      o[2] = ps.plogp;
     }
   }
 }

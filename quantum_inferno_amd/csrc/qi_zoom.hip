@@ -161,11 +161,8 @@ __device__ __forceinline__ void zoom_level(const ZoomArgs<T>& a, int chunk, int 
       const double r = wave_sum((double)rowacc);
       if (lane == 0) s_red[par][wv] = r;
       __syncthreads();
-      if (tid == 0 && !part) {
-        double t = 0.0;
-        for (int q = 0; q < NW; ++q) t += s_red[par][q];
-        a.part_band[((int64_t)ch * a.panel_bands + bd.out_band) * a.nblk + blockIdx.x] = t;
-      }
+      if (tid == 0 && !part)
+        a.part_band[((int64_t)ch * a.panel_bands + bd.out_band) * a.nblk + blockIdx.x] = fold_band_sum<NW>(s_red[par]);
       par ^= 1;
     }
   }
@@ -180,25 +177,13 @@ __device__ __forceinline__ void zoom_level(const ZoomArgs<T>& a, int chunk, int 
     if (time_row) *reinterpret_cast<T*>(time_row + (size_t)(tt * (uint32_t)sizeof(T))) = colp[s];
   }
   if (a.part_stat) {
-    const double r0 = wave_max((double)mx), r1 = wave_sum((double)tot), r2 = wave_sum(plogp);
-    if (lane == 0) {
-      s_fin[0][wv] = r0;
-      s_fin[1][wv] = r1;
-      s_fin[2][wv] = r2;
-    }
-    __syncthreads();
+    const PanelStats ps = fold_stats<NW>(mx, tot, plogp, s_fin, tid);
     if (tid == 0) {
-      double m = 0.0, s1 = 0.0, s2 = 0.0;
-      for (int q = 0; q < NW; ++q) {
-        m = s_fin[0][q] > m ? s_fin[0][q] : m;
-        s1 += s_fin[1][q];
-        s2 += s_fin[2][q];
-      }
       const int64_t groups = a.n / ((int64_t)kZoomD * STEPS * NW);
       double* o = a.part_stat + ((int64_t)ch * a.stat_stride + a.lvl_stat_base[LEVEL] + (int64_t)chunk * groups + blockIdx.x) * 3;
-      o[0] = m;
-      o[1] = s1;
-      o[2] = s2;
+      o[0] = ps.mx;
+      o[1] = ps.sum;
+      o[2] = ps.plogp;
     }
   }
 }

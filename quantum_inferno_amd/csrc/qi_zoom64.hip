@@ -54,6 +54,111 @@ __global__ void __launch_bounds__(256) k_z64_gather(Z64Args a) {
   a.Z[((int64_t)ch * a.nbands + blockIdx.y) * (a.M + 2 * kZ64Pad) + kZ64Pad + q] = y;
 }
 
+// ---- what k_z64_interp and k_z64_mfma share: everything around the tap sum ------------------------------------------------
+
+// the log2 table of the entropy sums into LDS (see log2_pos); a barrier of the caller's makes it visible
+__device__ __forceinline__ void z64_fill_ltab(double (*ltab)[2], int tid) {
+  if (tid < 128) {
+    ltab[tid][0] = kLog2Tab[tid][0];
+    ltab[tid][1] = kLog2Tab[tid][1];
+  }
+}
+
+// Where a band's outputs go and what they count for, and the lane's running sums over the band.
+struct Z64Band {
+  bool part;  // split band (bd.add_row): this is only the tapered part of its atom -- the samples go to row add_row - 1 of
+              // split_part and count for nothing here; the edge items of the block launch add their part and finish the band
+  cd* __restrict__ coef_row;
+  bool carrier;  // (false: no sample leaves the kernel, and the carrier, of modulus 1, changes no power -- the envelope will do)
+  cd ph, st;     // exp(2 pi i k_c tau / Lf) at the lane's next output and its step; the phases are exact integers modulo Lf
+  double* __restrict__ bits_row;
+  double pscale;
+  double rowacc, pl;
+};
+// coef: the panel is stored; tau_lane: full-length sample of the lane's first output; step: samples between its outputs
+template <int KIND>
+__device__ __forceinline__ Z64Band z64_band_setup(const Z64Args& a, const BandDesc& bd, int64_t ch, bool coef, uint32_t tau_lane,
+                                                  uint32_t step) {
+  const int64_t n = a.n;
+  const uint32_t lmask = (uint32_t)a.Lf - 1u;
+  Z64Band b;
+  const int64_t orow = ((int64_t)ch * a.panel_bands + bd.out_band) * n;
+  b.part = bd.add_row != 0;
+  b.coef_row = b.part ? a.split_part + ((int64_t)ch * a.split_rows + (bd.add_row - 1)) * n : (coef ? a.coef + orow : nullptr);
+  b.carrier = KIND != 2 && b.coef_row != nullptr;
+  b.ph = mk<double>(1.0, 0.0);
+  b.st = b.ph;
+  if (b.carrier) {
+    const uint32_t kc = (uint32_t)(bd.k_lo + bd.k_len / 2);
+    double c, s;
+    unit_root_t<double>((kc * (tau_lane - (KIND == 0 ? 1u : 0u))) & lmask, a.two_over_len, &c, &s);
+    b.ph = mk<double>(c, s);
+    unit_root_t<double>((kc * step) & lmask, a.two_over_len, &c, &s);
+    b.st = mk<double>(c, s);
+  }
+  b.bits_row = a.bits && !b.part ? a.bits + orow : nullptr;
+  b.pscale = b.part ? 0.0 : a.power_scale;
+  b.rowacc = 0.0;
+  b.pl = 0.0;
+  return b;
+}
+
+// one output: the interpolated envelope z is panel sample tt of the band (stores, power, the lane's sums; col: its per-time sum)
+__device__ __forceinline__ void z64_output(const Z64Args& a, Z64Band& b, cd z, uint32_t tt, double* col, bool want_time,
+                                           double& mx, const double (*ltab)[2]) {
+  if (b.carrier) {
+    z = cmul_rn(z, b.ph);
+    b.ph = cmul_rn(b.ph, b.st);
+  }
+  if (b.coef_row) stream_store(b.coef_row + tt, z);
+  const double m2 = norm2(z.x, z.y);
+  if (b.bits_row) b.bits_row[tt] = log2_t(sqrt_t(m2) + a.eps);
+  const double p = mul_rn(b.pscale, m2);
+  if (want_time) *col += p;
+  b.rowacc += p;
+  mx = max_t(mx, p);
+  b.pl += plog2p_flat(p, ltab);
+}
+
+// behind a band's outputs: the lane's sums into the kernel's, the band's power into its part_band slot of this tile
+template <int NW>
+__device__ __forceinline__ void z64_band_done(const Z64Args& a, const Z64Band& b, const BandDesc& bd, int64_t ch, int64_t tile,
+                                              double& plogp, double& ptot, double* s_red, int tid, int lane, int wv) {
+  plogp += b.pl;
+  ptot += b.rowacc;
+  if (a.part_band && !b.part) {  // (the same for every thread)
+    const double rs = wave_sum(b.rowacc);
+    if (lane == 0) s_red[wv] = rs;
+    __syncthreads();
+    if (tid == 0) a.part_band[((int64_t)ch * a.panel_bands + bd.out_band) * a.pb_stride + tile] = fold_band_sum<NW>(s_red);
+  }
+}
+
+// behind the band loop: the lane's STEPS per-time sums (col0[s * STRIDE] is panel sample tt0 + s * STRIDE) to time_part, and
+// the workgroup's statistics slot (ptot: the total power when no per-time sums are kept)
+template <int NW, int STEPS, int STRIDE>
+__device__ __forceinline__ void z64_tail(const Z64Args& a, int64_t ch, int64_t tile, const double* col0, uint32_t tt0,
+                                         bool want_time, double ptot, double mx, double plogp, double (*s_fin)[NW], int tid) {
+  double tot = 0.0;
+  double* __restrict__ time_row = a.time_part ? a.time_part + ((int64_t)ch * a.chunk_total + a.chunk_base + blockIdx.y) * a.n : nullptr;
+#pragma unroll
+  for (int s = 0; s < STEPS; ++s) {
+    const double v = col0[s * STRIDE];
+    tot += v;
+    if (time_row) time_row[tt0 + (uint32_t)(STRIDE * s)] = v;
+  }
+  if (!want_time) tot = ptot;
+  if (a.part_stat) {
+    const PanelStats ps = fold_stats<NW>(mx, tot, plogp, s_fin, tid);
+    if (tid == 0) {
+      double* o = a.part_stat + ((int64_t)ch * a.stat_stride + (int64_t)(a.chunk_base + blockIdx.y) * a.stat_nblk + tile) * 3;
+      o[0] = ps.mx;
+      o[1] = ps.sum;
+      o[2] = ps.plogp;
+    }
+  }
+}
+
 // KIND: 0 zero-padded linear correlation (Lf = 2 n, panel sample t = full-length sample t + n / 2 - 1), 1 circular
 // correlation rolled by n / 2, 2 Stockwell (no carrier: its bands are centred on bin 0 after the shift).
 // One workgroup = one tile of kZ64Tile consecutive panel samples (one partial slot per band and tile) of the bands
@@ -78,10 +183,7 @@ __global__ void __launch_bounds__(kZ64Threads, QI_Z64_INTERP_WAVES) k_z64_interp
   __shared__ double s_fin[3][NW];
   __shared__ double ltab[128][2];  // log2 table of the entropy sums (see log2_pos)
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  if (tid < 128) {
-    ltab[tid][0] = kLog2Tab[tid][0];
-    ltab[tid][1] = kLog2Tab[tid][1];
-  }
+  z64_fill_ltab(ltab, tid);
   const int64_t ch = blockIdx.z, tile = blockIdx.x;
   const int64_t n = a.n;
   constexpr uint32_t TT = (uint32_t)R * kZ64Threads;
@@ -115,28 +217,8 @@ __global__ void __launch_bounds__(kZ64Threads, QI_Z64_INTERP_WAVES) k_z64_interp
     const cd* __restrict__ C = a.Z + ((int64_t)ch * a.nbands + jj) * (a.M + 2 * kZ64Pad) + kZ64Pad;
     __syncthreads();  // the previous band's readers are done with the window (and with s_red)
     for (int i = tid; i < nwin; i += kZ64Threads) win[i] = C[(m_first + (uint32_t)i) & mmask];
-    // carrier: exp(2 pi i k_c tau / Lf) at this thread's first sample, advanced by exp(2 pi i k_c 256 / Lf); the
-    // phases are exact integers modulo Lf
-    const int64_t orow = ((int64_t)ch * a.panel_bands + bd.out_band) * n;
-    // split band (bd.add_row): this is only the tapered part of its atom -- the samples go to row add_row - 1 of
-    // split_part and count for nothing here; the edge items of the block launch add their part and finish the band
-    const bool part = bd.add_row != 0;
-    cd* __restrict__ coef_row =
-        part ? a.split_part + ((int64_t)ch * a.split_rows + (bd.add_row - 1)) * n : (a.coef ? a.coef + orow : nullptr);
-    // (no sample leaves the kernel -- reductions only --: the carrier, of modulus 1, changes no power; the envelope will do)
-    const bool carrier = KIND != 2 && coef_row != nullptr;
-    cd ph = mk<double>(1.0, 0.0), st = ph;
-    if (carrier) {
-      const uint32_t kc = (uint32_t)(bd.k_lo + bd.k_len / 2);
-      double c, s;
-      unit_root_t<double>((kc * (tau_first - (KIND == 0 ? 1u : 0u))) & lmask, a.two_over_len, &c, &s);
-      ph = mk<double>(c, s);
-      unit_root_t<double>((kc * (uint32_t)kZ64Threads) & lmask, a.two_over_len, &c, &s);
-      st = mk<double>(c, s);
-    }
-    double* __restrict__ bits_row = a.bits && !part ? a.bits + orow : nullptr;
-    const double pscale = part ? 0.0 : a.power_scale;
-    double rowacc = 0.0, pl = 0.0;
+    // carrier: at this thread's first sample, advanced by exp(2 pi i k_c 256 / Lf)
+    Z64Band b = z64_band_setup<KIND>(a, bd, ch, a.coef != nullptr, tau_first, kZ64Threads);
     __syncthreads();
 #pragma unroll QI_Z64_INTERP_UNROLL
     for (int r = 0; r < R; ++r) {
@@ -148,64 +230,12 @@ __global__ void __launch_bounds__(kZ64Threads, QI_Z64_INTERP_WAVES) k_z64_interp
         zr[j & 1] = fma(w[j], x.x, zr[j & 1]);
         zi[j & 1] = fma(w[j], x.y, zi[j & 1]);
       }
-      cd z = mk<double>(zr[0] + zr[1], zi[0] + zi[1]);
-      if (carrier) {
-        z = cmul_rn(z, ph);
-        ph = cmul_rn(ph, st);
-      }
-      const uint32_t tt = t_first + (uint32_t)r * kZ64Threads;
-      if (coef_row) stream_store(coef_row + tt, z);
-      const double m2 = norm2(z.x, z.y);
-      if (bits_row) bits_row[tt] = log2_t(sqrt_t(m2) + a.eps);
-      const double p = mul_rn(pscale, m2);
-      if (want_time) col0[r * kZ64Threads] += p;
-      rowacc += p;
-      mx = max_t(mx, p);
-      pl += plog2p_flat(p, ltab);
+      z64_output(a, b, mk<double>(zr[0] + zr[1], zi[0] + zi[1]), t_first + (uint32_t)r * kZ64Threads, col0 + r * kZ64Threads,
+                 want_time, mx, ltab);
     }
-    plogp += pl;
-    ptot += rowacc;
-    if (a.part_band && !part) {  // (the same for every thread)
-      const double rs = wave_sum(rowacc);
-      if (lane == 0) s_red[wv] = rs;
-      __syncthreads();
-      if (tid == 0) {
-        double t = 0.0;
-        for (int q = 0; q < NW; ++q) t += s_red[q];
-        a.part_band[((int64_t)ch * a.panel_bands + bd.out_band) * a.pb_stride + tile] = t;
-      }
-    }
+    z64_band_done<NW>(a, b, bd, ch, tile, plogp, ptot, s_red, tid, lane, wv);
   }
-  double tot = 0.0;
-  double* __restrict__ time_row = a.time_part ? a.time_part + ((int64_t)ch * a.chunk_total + a.chunk_base + blockIdx.y) * n : nullptr;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const double v = col0[r * kZ64Threads];
-    tot += v;
-    if (time_row) time_row[t_first + (uint32_t)r * kZ64Threads] = v;
-  }
-  if (!want_time) tot = ptot;
-  if (a.part_stat) {
-    const double r0 = wave_max(mx), r1 = wave_sum(tot), r2 = wave_sum(plogp);
-    if (lane == 0) {
-      s_fin[0][wv] = r0;
-      s_fin[1][wv] = r1;
-      s_fin[2][wv] = r2;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double m = 0.0, s1 = 0.0, s2 = 0.0;
-      for (int q = 0; q < NW; ++q) {
-        m = s_fin[0][q] > m ? s_fin[0][q] : m;
-        s1 += s_fin[1][q];
-        s2 += s_fin[2][q];
-      }
-      double* o = a.part_stat + ((int64_t)ch * a.stat_stride + (int64_t)(a.chunk_base + blockIdx.y) * a.stat_nblk + tile) * 3;
-      o[0] = m;
-      o[1] = s1;
-      o[2] = s2;
-    }
-  }
+  z64_tail<NW, R, kZ64Threads>(a, ch, tile, col0, t_first, want_time, ptot, mx, plogp, s_fin, tid);
 }
 
 // ---- interpolation on the matrix pipe (round 5): the grids of Lf / 16 and Lf / 8 samples ---------------------------------
@@ -246,10 +276,7 @@ __global__ void __launch_bounds__(kZ64Threads, QI_Z64_MX_WAVES) k_z64_mfma(Z64Ar
   __shared__ double colv[kZ64Tile];
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
   const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
-  if (tid < 128) {
-    ltab[tid][0] = kLog2Tab[tid][0];
-    ltab[tid][1] = kLog2Tab[tid][1];
-  }
+  z64_fill_ltab(ltab, tid);
   const int64_t ch = blockIdx.z, tile = blockIdx.x, n = a.n;
   const uint32_t off = KIND == 2 ? 0u : (uint32_t)(n / 2);
   const uint32_t lmask = (uint32_t)a.Lf - 1u, mmask = (uint32_t)a.M - 1u;
@@ -304,23 +331,7 @@ __global__ void __launch_bounds__(kZ64Threads, QI_Z64_MX_WAVES) k_z64_mfma(Z64Ar
       }
     }
     if (jj + (int)gridDim.y < a.nbands) request(jj + gridDim.y);
-    const int64_t orow = ((int64_t)ch * a.panel_bands + bd.out_band) * n;
-    const bool part = bd.add_row != 0;  // split band: the tapered part only, to split_part, counts for nothing here
-    cd* __restrict__ coef_row =
-        part ? a.split_part + ((int64_t)ch * a.split_rows + (bd.add_row - 1)) * n : (COEF ? a.coef + orow : nullptr);
-    const bool carrier = KIND != 2 && coef_row != nullptr;
-    cd ph = mk<double>(1.0, 0.0), st = ph;
-    if (carrier) {
-      const uint32_t kc = (uint32_t)(bd.k_lo + bd.k_len / 2);
-      double c, s;
-      unit_root_t<double>((kc * (tau_wave + (uint32_t)lane - (KIND == 0 ? 1u : 0u))) & lmask, a.two_over_len, &c, &s);
-      ph = mk<double>(c, s);
-      unit_root_t<double>((kc * (uint32_t)kWave) & lmask, a.two_over_len, &c, &s);
-      st = mk<double>(c, s);
-    }
-    double* __restrict__ bits_row = a.bits && !part ? a.bits + orow : nullptr;
-    const double pscale = part ? 0.0 : a.power_scale;
-    double rowacc = 0.0, pl = 0.0;
+    Z64Band b = z64_band_setup<KIND>(a, bd, ch, COEF, tau_wave + (uint32_t)lane, kWave);
     __syncthreads();
 #pragma unroll 1  // (unrolled, the compiler hoists every group's window reads to the top: 256 registers)
     for (int g = 0; g < GROUPS; ++g) {
@@ -334,65 +345,13 @@ __global__ void __launch_bounds__(kZ64Threads, QI_Z64_MX_WAVES) k_z64_mfma(Z64Ar
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {  // register r = wave-step 4 g + r: sample tt0 + 64 (4 g + r)
-        cd z = mk<double>(zr[r], zi[r]);
-        if (carrier) {
-          z = cmul_rn(z, ph);
-          ph = cmul_rn(ph, st);
-        }
-        const uint32_t tt = tt0 + (uint32_t)(kWave * (4 * g + r));
-        if (coef_row) stream_store(coef_row + tt, z);
-        const double m2 = norm2(z.x, z.y);
-        if (bits_row) bits_row[tt] = log2_t(sqrt_t(m2) + a.eps);
-        const double p = mul_rn(pscale, m2);
-        if (want_time) col0[(4 * g + r) * kWave] += p;
-        rowacc += p;
-        mx = max_t(mx, p);
-        pl += plog2p_flat(p, ltab);
+        z64_output(a, b, mk<double>(zr[r], zi[r]), tt0 + (uint32_t)(kWave * (4 * g + r)), col0 + (4 * g + r) * kWave, want_time, mx,
+                   ltab);
       }
     }
-    plogp += pl;
-    ptot += rowacc;
-    if (a.part_band && !part) {  // (the same for every thread)
-      const double rs = wave_sum(rowacc);
-      if (lane == 0) s_red[wv] = rs;
-      __syncthreads();
-      if (tid == 0) {
-        double t = 0.0;
-        for (int q = 0; q < NW; ++q) t += s_red[q];
-        a.part_band[((int64_t)ch * a.panel_bands + bd.out_band) * a.pb_stride + tile] = t;
-      }
-    }
+    z64_band_done<NW>(a, b, bd, ch, tile, plogp, ptot, s_red, tid, lane, wv);
   }
-  double tot = 0.0;
-  double* __restrict__ time_row = a.time_part ? a.time_part + ((int64_t)ch * a.chunk_total + a.chunk_base + blockIdx.y) * n : nullptr;
-#pragma unroll
-  for (int s = 0; s < STEPS; ++s) {
-    const double v = col0[s * kWave];
-    tot += v;
-    if (time_row) time_row[tt0 + (uint32_t)(kWave * s)] = v;
-  }
-  if (!want_time) tot = ptot;
-  if (a.part_stat) {
-    const double r0 = wave_max(mx), r1 = wave_sum(tot), r2 = wave_sum(plogp);
-    if (lane == 0) {
-      s_fin[0][wv] = r0;
-      s_fin[1][wv] = r1;
-      s_fin[2][wv] = r2;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double m = 0.0, s1 = 0.0, s2 = 0.0;
-      for (int q = 0; q < NW; ++q) {
-        m = s_fin[0][q] > m ? s_fin[0][q] : m;
-        s1 += s_fin[1][q];
-        s2 += s_fin[2][q];
-      }
-      double* o = a.part_stat + ((int64_t)ch * a.stat_stride + (int64_t)(a.chunk_base + blockIdx.y) * a.stat_nblk + tile) * 3;
-      o[0] = m;
-      o[1] = s1;
-      o[2] = s2;
-    }
-  }
+  z64_tail<NW, STEPS, kWave>(a, ch, tile, col0, tt0, want_time, ptot, mx, plogp, s_fin, tid);
 }
 
 // ---- fine stage with wave-uniform windows (see Z64FineArgs in qi_native.hpp) -----------------------------------------
@@ -587,10 +546,7 @@ __global__ void __launch_bounds__(kZ64Threads, z64f_ntap(CLS) >= 16 ? 3 : 4) k_z
   __shared__ double ltab[128][2];  // log2 table of the entropy sums (see log2_pos)
   __shared__ double colv[(kZ64Threads / kWave) * kZ64FineWave];
   const int tid = threadIdx.x;
-  if (tid < 128) {
-    ltab[tid][0] = kLog2Tab[tid][0];
-    ltab[tid][1] = kLog2Tab[tid][1];
-  }
+  z64_fill_ltab(ltab, tid);
   __syncthreads();
   z64_fine_class<KIND, CLS, COEF>(a, blockIdx.y, ltab, colv);
 }
