@@ -563,6 +563,48 @@ int qi_doppler(int device, int inverse, const double* params, int64_t param_stri
                int64_t x_stride, double s0, double s1, int64_t n_channels, int64_t n, double* time_out, double* range_out,
                double* omega_out, qi_stream stream);
 
+/* ---- the STFT of a segment range: a record that is streamed through the device piece by piece --------------------------------
+ * The record has n_total samples and qi_stft_segments(n_total, seg, hop) segments; segment m covers the record samples
+ * [m hop - seg / 2, m hop - seg / 2 + seg), and samples outside [0, n_total) are zeros that count in the segment mean (the
+ * boundary extension and padded=True of qi_stft).  A segment depends on its own samples only, so the ranges of a record
+ * give the coefficients of the one-call transform, and their sums add up to its reductions.
+ *   first_segment, segments     the range; the outputs are those of the qi_stft_out form with n_seg = segments: coef / bits
+ *                               [C][nfft/2+1][segments], power_band [C][nfft/2+1] and stats over these segments only,
+ *                               power_time [C][segments]
+ *   sample0, n_avail, row_stride  row c of sig holds the record samples sample0 .. sample0 + n_avail - 1 at
+ *                               sig[c * row_stride + i]; nothing outside [0, n_avail) of a row is read.  Every record sample
+ *                               that a segment of the range covers must lie in that interval (qi_stft_range_samples gives the
+ *                               smallest one); n_avail = 0 is valid for a range inside the zero extension (sig may then be NULL)
+ *   pool_factor F               0: no pooling (pool_mean and pool_max NULL); F >= 2: pool_mean / pool_max, real
+ *                               [C][nfft/2+1][segments / F] in the record's precision, either may be NULL -- the average
+ *                               (accumulated in float64 in a fixed order, rounded once) and the maximum (one of the values)
+ *                               of P = power_scale |Z|^2 over the windows of F consecutive segments.  first_segment % F == 0
+ *                               and segments % F == 0, except that a range ending at the record's last segment may be ragged:
+ *                               its incomplete window is dropped (utilities/sampling.py:106-120).  They come with power_band.
+ * Anything else is QI_ERR_ARG, found on the host before any device call.  At the fused transform lengths the pooled values
+ * leave the kernel as the per-workgroup sums (and maxima) of every bin -- a workgroup holds min(its usual count, the largest
+ * power of two dividing F) consecutive segments -- and one small kernel folds F / that many groups in index order: no panel
+ * is stored, no atomics.  Other lengths pool the hipFFT panel (in coef, or in scratch) with the strip kernel.  With
+ * first_segment = 0, every segment, sample0 = 0, n_avail = row_stride = n_total and F = 0 the call is the qi_stft_out form:
+ * the same launches, the same bits.  The ShortTimeFFT-convention pad modes are not offered for ranges. */
+typedef struct qi_stft_range {
+  int64_t n_total;
+  int64_t first_segment, segments;
+  int64_t sample0, n_avail, row_stride;
+  int64_t pool_factor;
+  void* pool_mean;
+  void* pool_max;
+} qi_stft_range;
+/* the smallest sample interval of a range: *sample0 its first record sample, *n_avail their count (0: none).  Host only. */
+int qi_stft_range_samples(int64_t n_total, int64_t seg, int64_t hop, int64_t first_segment, int64_t segments, int64_t* sample0,
+                          int64_t* n_avail);
+/* scratch of qi_stft_out_range for this range and want_coef = (coef != NULL); a negative qi_status for a range it refuses */
+int64_t qi_stft_range_scratch_bytes(int dtype, int64_t n_channels, int64_t seg, int64_t hop, int64_t nfft,
+                                    const qi_stft_range* range, int want_coef);
+int qi_stft_out_range(int dtype, int device, const void* sig, int64_t n_channels, const void* window, int64_t seg, int64_t hop,
+                      int64_t nfft, double scale, const qi_stft_range* range, const qi_tfr_out* out, void* scratch,
+                      int64_t scratch_bytes, qi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

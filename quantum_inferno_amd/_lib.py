@@ -75,6 +75,20 @@ class TfrOut(C.Structure):
     ]
 
 
+class StftRange(C.Structure):
+    _fields_ = [
+        ("n_total", C.c_int64),
+        ("first_segment", C.c_int64),
+        ("segments", C.c_int64),
+        ("sample0", C.c_int64),
+        ("n_avail", C.c_int64),
+        ("row_stride", C.c_int64),
+        ("pool_factor", C.c_int64),
+        ("pool_mean", C.c_void_p),
+        ("pool_max", C.c_void_p),
+    ]
+
+
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _I64 = C.POINTER(C.c_int64)
@@ -140,6 +154,9 @@ PROTOTYPES = {
     "qi_derivative": (_int, [_int, _int, _int, _P, _P, _i64, _dbl, _i64, _i64, _P, _i64, _P]),
     "qi_synth": (_int, [_int, _int, _int, _int, _P, _i64, _int, _dbl, _P, _i64, _dbl, _dbl, _int, _dbl, _dbl, _dbl, _i64, _i64, _i64, _i64, _P, _P]),
     "qi_doppler": (_int, [_int, _int, _P, _i64, _int, _dbl, _P, _i64, _dbl, _dbl, _i64, _i64, _P, _P, _P, _P]),
+    "qi_stft_range_samples": (_int, [_i64, _i64, _i64, _i64, _i64, _I64, _I64]),
+    "qi_stft_range_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, C.POINTER(StftRange), _int]),
+    "qi_stft_out_range": (_int, [_int, _int, _P, _i64, _P, _i64, _i64, _i64, _dbl, C.POINTER(StftRange), C.POINTER(TfrOut), _P, _i64, _P]),
 }
 
 _lib = None

@@ -61,34 +61,48 @@ template <typename T>
 int stft_hipfft(int device, const StftRequest& rq, const T* sig, const T* window, cplx<T>* Z, T* bits, char* scratch, hipStream_t st) {
   return via_hipfft<T>(
       device, scratch, rq.C, rq.nseg, rq.nfft, st,
-      [&](T* frames) { return launch_stft_frames<T>(sig, window, frames, rq.C, rq.n, rq.seg, rq.hop, rq.nfft, rq.nseg, rq.lead, st); },
+      [&](T* frames) {
+        return launch_stft_frames<T>(sig, window, frames, rq.C, rq.n, rq.seg, rq.hop, rq.nfft, rq.nseg, rq.lead, st, rq.row_stride);
+      },
       [&](cplx<T>* F) { return launch_stft_transpose<T>(F, Z, bits, rq.C, rq.nseg, rq.nfft / 2 + 1, (T)rq.scale, (T)rq.eps, st); });
 }
 
 // Scratch of qi_stft_out: [0] the three-kernel path's frames and spectra (qi_stft_scratch_bytes) | [1] the panel when the
 // caller keeps none | [2] band partials | [3] statistics partials -- [2] and [3] hold either engine's: per segment group of
-// the fused kernel, or per kEpiSpan columns of k_epilogue.
+// the fused kernel, or per kEpiSpan columns of k_epilogue.  A pooling range call (qi_stft_out_range) has smaller groups --
+// more slots -- and, for a pooled maximum from the fused kernel, [4] the groups' maxima of every bin in the record's type.
 struct StftOutLayout {
-  size_t panel, part_band, part_stat, total;
+  size_t panel, part_band, part_stat, part_max, total;
 };
-StftOutLayout stft_out_layout(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft, bool want_coef) {
-  const int64_t nseg = qi_stft_segments(n, seg, hop), nf = nfft / 2 + 1;
+StftOutLayout stft_out_layout(int dtype, int64_t C, int64_t nseg, int64_t seg, int64_t hop, int64_t nfft, bool want_coef,
+                              int64_t pool_factor = 0, bool pool_max = false) {
+  const int64_t nf = nfft / 2 + 1;
   const size_t e = dtype == QI_F64 ? 8 : 4;
   int64_t slots = ceil_div(nseg, kEpiSpan);
-  if (stft_fused_supported(dtype, seg, hop, nfft)) slots = std::max(slots, stft_fused_groups(dtype, nfft, nseg));
+  const bool fused = stft_fused_supported(dtype, seg, hop, nfft);
+  if (fused) slots = std::max(slots, stft_fused_groups(dtype, nfft, nseg, pool_factor));
   StftOutLayout l;
   l.panel = FftScratch(dtype, C, nseg, nfft).total;
   l.part_band = l.panel + (want_coef ? 0 : align_up((size_t)C * nf * nseg * 2 * e));
   l.part_stat = l.part_band + align_up((size_t)C * slots * nf * 8);
-  l.total = l.part_stat + align_up((size_t)C * slots * 24);
+  l.part_max = l.part_stat + align_up((size_t)C * slots * 24);
+  l.total = l.part_max + (fused && pool_factor > 0 && pool_max ? align_up((size_t)C * slots * nf * e) : 0);
   return l;
 }
 
-// qi_stft_out; `rq`: qi_stft's request (eps set)
+// The record samples [*lo, *hi) inside [0, n_total) that the segments first .. first + count - 1 cover (segment m: the samples
+// [m hop - seg / 2, m hop - seg / 2 + seg)); *hi <= *lo: none, the range lies in the zero extension
+void stft_range_interval(int64_t n_total, int64_t seg, int64_t hop, int64_t first, int64_t count, int64_t* lo, int64_t* hi) {
+  *lo = std::min(n_total, std::max<int64_t>(0, first * hop - seg / 2));
+  *hi = std::min(n_total, (first + count - 1) * hop - seg / 2 + seg);
+}
+
+// qi_stft_out and qi_stft_out_range; `rq`: qi_stft's request (eps set), of a range with its own origin, row stride and pooling
 template <typename T>
 int stft_out_impl(int device, StftRequest rq, const T* sig, const T* window, const qi_tfr_out* out, char* scratch, hipStream_t st) {
   const int64_t C = rq.C, nseg = rq.nseg, nf = rq.nfft / 2 + 1;
-  const StftOutLayout l = stft_out_layout(sizeof(T) == 8 ? QI_F64 : QI_F32, C, rq.n, rq.seg, rq.hop, rq.nfft, out->coef != nullptr);
+  const StftOutLayout l = stft_out_layout(sizeof(T) == 8 ? QI_F64 : QI_F32, C, nseg, rq.seg, rq.hop, rq.nfft, out->coef != nullptr,
+                                          rq.pool_factor, rq.pool_max != nullptr);
   cplx<T>* Z = static_cast<cplx<T>*>(out->coef);
   T* bits = static_cast<T*>(out->bits);
   double* part_band = reinterpret_cast<double*>(scratch + l.part_band);
@@ -108,6 +122,7 @@ int stft_out_impl(int device, StftRequest rq, const T* sig, const T* window, con
           red.power_band = power_band;
           red.stats = stats;
           red.power_scale = power_scale;
+          red.part_max = scratch + l.part_max;
         }
         return launch_stft_fused<T>(red, sig, window, Z, bits, st);
       },
@@ -132,7 +147,12 @@ int stft_out_impl(int device, StftRequest rq, const T* sig, const T* window, con
         a.power_scale = (T)power_scale;
         a.eps = (T)rq.eps;
         QI_TRY(launch_epilogue<T>(a, st));
-        return launch_finalize(part_band, part_stat, power_band, stats, C, nf, nblk, nblk, st);
+        QI_TRY(launch_finalize(part_band, part_stat, power_band, stats, C, nf, nblk, nblk, st));
+        // a range's pooled spectrogram: the strip kernel on the panel's rows (no sums: the epilogue has them)
+        if (rq.pool_factor > 0 && (rq.pool_mean || rq.pool_max))
+          return qi_pool_strip(sizeof(T) == 8 ? QI_F64 : QI_F32, device, Z, C * nf, nseg, 0, rq.pool_factor, nseg / rq.pool_factor,
+                               power_scale, rq.pool_mean, rq.pool_max, nseg / rq.pool_factor, nullptr, (qi_stream)st);
+        return QI_OK;
       });
 }
 
@@ -178,7 +198,7 @@ int64_t qi_stft_out_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, 
                                   int want_bits) {
   (void)want_bits;  // (the bits panel is never formed in scratch)
   if (C <= 0 || nfft < seg || qi_stft_segments(n, seg, hop) <= 0) return 0;
-  return (int64_t)stft_out_layout(dtype, C, n, seg, hop, nfft, want_coef != 0).total;
+  return (int64_t)stft_out_layout(dtype, C, qi_stft_segments(n, seg, hop), seg, hop, nfft, want_coef != 0).total;
 }
 
 int qi_stft_out(int dtype, int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop,
@@ -195,6 +215,91 @@ int qi_stft_out(int dtype, int device, const void* sig, int64_t C, int64_t n, co
   StftRequest rq{C, n, seg, hop, nfft, qi_stft_segments(n, seg, hop), seg / 2};
   rq.scale = scale;
   rq.eps = qi::host::eps_or_default(out->eps);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return stft_out_impl<T>(device, rq, (const T*)sig, (const T*)window, out, (char*)scratch, (hipStream_t)stream);
+  });
+}
+
+// ---- the STFT of a segment range (a streamed record: stream.StftStream) ---------------------------------------------------
+int qi_stft_range_samples(int64_t n_total, int64_t seg, int64_t hop, int64_t first_segment, int64_t segments, int64_t* sample0,
+                          int64_t* n_avail) {
+  QI_REQUIRE(sample0 && n_avail, "null argument");
+  const int64_t total = qi_stft_segments(n_total, seg, hop);
+  QI_REQUIRE(total > 0, "bad STFT geometry");
+  QI_REQUIRE(first_segment >= 0 && segments >= 1 && segments <= total - first_segment,
+             "segments %lld .. %lld of a record of %lld", (long long)first_segment, (long long)(first_segment + segments - 1),
+             (long long)total);
+  int64_t lo, hi;
+  stft_range_interval(n_total, seg, hop, first_segment, segments, &lo, &hi);
+  *sample0 = lo;
+  *n_avail = std::max<int64_t>(0, hi - lo);
+  return QI_OK;
+}
+
+// every refusal of a range; host arithmetic only
+static int stft_range_check(int64_t seg, int64_t hop, int64_t nfft, const qi_stft_range* r) {
+  QI_REQUIRE(r, "null argument");
+  QI_REQUIRE(seg > 0 && hop > 0 && hop <= seg && nfft >= seg && r->n_total > 0, "bad STFT geometry");
+  const int64_t total = qi_stft_segments(r->n_total, seg, hop);
+  QI_REQUIRE(r->first_segment >= 0 && r->segments >= 1 && r->segments <= total - r->first_segment,
+             "segments %lld .. %lld of a record of %lld", (long long)r->first_segment,
+             (long long)(r->first_segment + r->segments - 1), (long long)total);
+  QI_REQUIRE(r->sample0 >= 0 && r->n_avail >= 0 && r->n_avail <= r->n_total - r->sample0,
+             "samples %lld .. +%lld are not inside a record of %lld", (long long)r->sample0, (long long)r->n_avail,
+             (long long)r->n_total);
+  QI_REQUIRE(r->row_stride >= r->n_avail, "rows of %lld samples cannot hold %lld", (long long)r->row_stride, (long long)r->n_avail);
+  int64_t lo, hi;
+  stft_range_interval(r->n_total, seg, hop, r->first_segment, r->segments, &lo, &hi);
+  QI_REQUIRE(hi <= lo || (r->sample0 <= lo && hi <= r->sample0 + r->n_avail),
+             "the range needs the record samples %lld .. %lld, the rows hold %lld .. %lld", (long long)lo, (long long)hi - 1,
+             (long long)r->sample0, (long long)(r->sample0 + r->n_avail) - 1);
+  const int64_t F = r->pool_factor;
+  QI_REQUIRE(F == 0 || F >= 2, "pooling factor %lld: 0 (none), or 2 or more", (long long)F);
+  QI_REQUIRE(F > 0 || !(r->pool_mean || r->pool_max), "pooled outputs without a pooling factor");
+  if (F > 0) {
+    QI_REQUIRE(r->first_segment % F == 0, "first segment %lld is no multiple of the pooling factor %lld",
+               (long long)r->first_segment, (long long)F);
+    QI_REQUIRE(r->segments % F == 0 || r->first_segment + r->segments == total,
+               "%lld segments are no multiple of the pooling factor %lld and do not end the record", (long long)r->segments,
+               (long long)F);
+  }
+  return QI_OK;
+}
+
+int64_t qi_stft_range_scratch_bytes(int dtype, int64_t C, int64_t seg, int64_t hop, int64_t nfft, const qi_stft_range* range,
+                                    int want_coef) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(C > 0, "bad channel count");
+  QI_TRY(stft_range_check(seg, hop, nfft, range));
+  return (int64_t)stft_out_layout(dtype, C, range->segments, seg, hop, nfft, want_coef != 0, range->pool_factor,
+                                  range->pool_max != nullptr).total;
+}
+
+int qi_stft_out_range(int dtype, int device, const void* sig, int64_t C, const void* window, int64_t seg, int64_t hop, int64_t nfft,
+                      double scale, const qi_stft_range* range, const qi_tfr_out* out, void* scratch, int64_t scratch_bytes,
+                      qi_stream stream) {
+  QI_REQUIRE(window && out && scratch && range, "null argument");
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(C > 0, "bad channel count");
+  QI_TRY(stft_range_check(seg, hop, nfft, range));
+  QI_REQUIRE(sig || range->n_avail == 0, "null argument");
+  const bool pooled = range->pool_mean || range->pool_max;
+  QI_REQUIRE(out->coef || out->bits || out->power_band || out->power_time || out->stats || pooled, "nothing to produce");
+  QI_REQUIRE((out->power_band != nullptr) == (out->stats != nullptr), "power_band and stats come together");
+  QI_REQUIRE(!out->power_time || out->power_band, "power_time needs power_band and stats");
+  QI_REQUIRE(!pooled || out->power_band, "the pooled outputs come with power_band and stats");
+  QI_REQUIRE(scratch_bytes >= qi_stft_range_scratch_bytes(dtype, C, seg, hop, nfft, range, out->coef != nullptr), "scratch too small");
+  DeviceGuard g(device);
+  StftRequest rq{C, range->n_avail, seg, hop, nfft, range->segments, seg / 2 + range->sample0 - range->first_segment * hop};
+  rq.scale = scale;
+  rq.eps = qi::host::eps_or_default(out->eps);
+  rq.row_stride = range->row_stride;
+  if (pooled) {
+    rq.pool_factor = range->pool_factor;
+    rq.pool_mean = range->pool_mean;
+    rq.pool_max = range->pool_max;
+  }
   return by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     return stft_out_impl<T>(device, rq, (const T*)sig, (const T*)window, out, (char*)scratch, (hipStream_t)stream);

@@ -156,16 +156,19 @@ int launch_finalize(const double* part_band, const double* part_stat, double* po
 
 template <typename T>
 int launch_stft_frames(const T* sig, const T* win, T* frames, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                       int64_t nfft, int64_t nseg, int64_t lead, hipStream_t st);
+                       int64_t nfft, int64_t nseg, int64_t lead, hipStream_t st, int64_t stride = -1);  // stride < 0: rows of n
 // fused STFT (qi_stft_fused.hip): frames, transform and [frequency][time] store in one kernel
 bool stft_fused_supported(int dtype, int64_t seg, int64_t hop, int64_t nfft);
 // segment groups (workgroups) per record of a fused launch; 0: the transform length has no fused shape
-int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg);
+// (pool_factor > 0: of a launch that pools windows of that many segments)
+int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg, int64_t pool_factor = 0);
 // One forward call of the fused kernel.  The mode fields default to qi_stft's own call (zeros past the record, segment mean
 // removed, coefficient and log2-bits panels); Welch, the ShortTimeFFT convention and the reductions set only what they mean.
 struct StftRequest {
   int64_t C, n, seg, hop, nfft, nseg;
-  int64_t lead;  // samples of extension in front of the record (seg / 2 for the STFT, 0 Welch, -first sliding)
+  // samples of extension in front of the record (seg / 2 for the STFT, 0 Welch, -first sliding; a segment range: the signed
+  // origin seg / 2 + sample0 - first_segment hop, `n` the samples a row holds and `nseg` the range's segments)
+  int64_t lead;
   double scale = 1.0, eps = 0.0;
   // Welch: [C][groups][nfft / 2 + 1] doubles of scratch for the groups' sums of |X|^2 (groups = stft_fused_groups()); no panel
   double* welch_part = nullptr;
@@ -180,6 +183,13 @@ struct StftRequest {
   void* power_time = nullptr;
   double *power_band = nullptr, *stats = nullptr;
   double power_scale = 1.0;
+  int64_t row_stride = -1;  // samples between the rows of `sig`; < 0: n
+  // time pooling of P from the reductions form's registers (qi_stft_out_range): windows of pool_factor consecutive segments,
+  // pool_mean / pool_max [C][nfft / 2 + 1][nseg / pool_factor] in the record's precision (either may be null); part_max
+  // [C][groups][nfft / 2 + 1] of the record's type beside part_band.  The workgroups then hold min(launch group, largest
+  // power of two dividing pool_factor) segments, so that each lies inside one window (stft_fused_groups with the factor).
+  int64_t pool_factor = 0;
+  void *pool_mean = nullptr, *pool_max = nullptr, *part_max = nullptr;
 };
 template <typename T>
 int launch_stft_fused(const StftRequest& rq, const T* sig, const T* win, cplx<T>* Z, T* bits, hipStream_t st);

@@ -170,14 +170,14 @@ __global__ void __launch_bounds__(256) k_finalize(const double* __restrict__ par
 // boundary='zeros', padded=True, detrend='constant').  One workgroup per (segment, channel).
 template <typename T>
 __global__ void __launch_bounds__(256) k_stft_frames(const T* __restrict__ sig, const T* __restrict__ win,
-                                                     T* __restrict__ frames, int64_t n, int64_t seg, int64_t hop,
-                                                     int64_t nfft, int64_t nseg, int64_t lead) {
+                                                     T* __restrict__ frames, int64_t n, int64_t stride, int64_t seg,
+                                                     int64_t hop, int64_t nfft, int64_t nseg, int64_t lead) {
   __shared__ double s[256 / kWave];
   __shared__ double s_mean;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
   const int64_t m = blockIdx.x, c = blockIdx.y;
-  const int64_t base = m * hop - lead;  // lead = seg/2 zero-extended samples (stft) or 0 (welch)
-  const T* x = sig + c * n;
+  const int64_t base = m * hop - lead;  // lead = seg/2 zero-extended samples (stft), 0 (welch), a range's signed origin
+  const T* x = sig + c * stride;  // rows of `stride` samples, the first n of them the record's
   double acc = 0.0;
   for (int64_t i = tid; i < seg; i += 256) {
     int64_t k = base + i;
@@ -362,9 +362,9 @@ int launch_finalize(const double* part_band, const double* part_stat, double* po
 
 template <typename T>
 int launch_stft_frames(const T* sig, const T* win, T* frames, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                       int64_t nfft, int64_t nseg, int64_t lead, hipStream_t st) {
+                       int64_t nfft, int64_t nseg, int64_t lead, hipStream_t st, int64_t stride) {
   dim3 g((unsigned)nseg, (unsigned)C);
-  k_stft_frames<T><<<g, 256, 0, st>>>(sig, win, frames, n, seg, hop, nfft, nseg, lead);
+  k_stft_frames<T><<<g, 256, 0, st>>>(sig, win, frames, n, stride < 0 ? n : stride, seg, hop, nfft, nseg, lead);
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
@@ -494,7 +494,7 @@ int launch_shannon(const T* P, const T* mult, int mode, int64_t C, int64_t B, in
                                     const double*, hipStream_t);                                                   \
   template int launch_epilogue<T>(const EpiArgs<T>&, hipStream_t);                                                 \
   template int launch_stft_frames<T>(const T*, const T*, T*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, \
-                                     int64_t, hipStream_t);                                                        \
+                                     int64_t, hipStream_t, int64_t);                                               \
   template int launch_welch_mean<T>(const cplx<T>*, T*, int64_t, int64_t, int64_t, int64_t, T, hipStream_t);       \
   template int launch_stft_transpose<T>(const cplx<T>*, cplx<T>*, T*, int64_t, int64_t, int64_t, T, T,             \
                                         hipStream_t);                                                              \

@@ -61,7 +61,9 @@ __device__ __forceinline__ T stft_sample(const T* __restrict__ x, int64_t n, int
 }
 
 struct StftFusedArgs {
-  int64_t n, seg, hop, nseg, lead;  // lead: zero-extended samples in front of the record (seg / 2 for the STFT, 0 Welch)
+  // lead: zero-extended samples in front of the record (seg / 2 for the STFT, 0 Welch); signed -- a segment range's rows start
+  // at record sample sample0 and its first segment is first_segment: lead = seg / 2 + sample0 - first_segment hop
+  int64_t n, seg, hop, nseg, lead;
   int32_t log2g, G;                 // G = 1 << log2g segments per workgroup
   int32_t ngroups, per_xcd;         // segment groups per record; work items (record, group) per XCD
   int64_t nitems;                   // records x groups
@@ -81,6 +83,8 @@ struct StftFusedArgs {
   double* red_stat;
   void* power_time;
   double power_scale;
+  int64_t stride;  // samples between the rows of `sig` (the first n of a row are the record's)
+  void* red_max;   // MX instantiations: [C][ngroups][nfft / 2 + 1] maxima of P over a group's segments, in the record's type
 };
 
 // The untangling's complex product (z - conj z') w of the reductions form's PLAIN walk in one fixed instruction form per
@@ -106,6 +110,17 @@ __device__ __forceinline__ double group_sum(double v, int lg) {
   if (lg > 1) v += dpp_mov<0x4E>(v);   // quad_perm [2, 3, 0, 1]
   if (lg > 2) v += dpp_mov<0x141>(v);  // row_half_mirror
   if (lg > 3) v += dpp_mov<0x140>(v);  // row_mirror
+  return v;
+}
+
+// Maximum over the same lanes, in the same steps
+template <typename T>
+__device__ __forceinline__ T group_max(T v, int lg) {
+  T w;
+  if (lg > 0) w = dpp_mov<0xB1>(v), v = w > v ? w : v;
+  if (lg > 1) w = dpp_mov<0x4E>(v), v = w > v ? w : v;
+  if (lg > 2) w = dpp_mov<0x141>(v), v = w > v ? w : v;
+  if (lg > 3) w = dpp_mov<0x140>(v), v = w > v ? w : v;
   return v;
 }
 
@@ -163,7 +178,9 @@ __device__ __forceinline__ void stft_red_tail(unsigned char* lds_raw, const Stft
 // the coefficients in registers, the panel stores compile-time optional (WZ, WB).  Consecutive lanes hold consecutive segments
 // of one bin, so the sum over a group's segments is group_sum over G adjacent lanes; no thread leaves before the tail (a
 // segment past the last one is a tile of zeros: P = 0, nothing stored).  No atomics: every partial has one writer.
-template <typename T, int LOG2R, int LOG2C, bool PLAIN, bool RED = false, bool WZ = true, bool WB = true>
+// MX (RED only; the pooled maximum of qi_stft_out_range): the group's maximum of every bin beside its sum, group_max over the
+// same lanes -- a compile-time option, so that the instantiations without it are the ones they were.
+template <typename T, int LOG2R, int LOG2C, bool PLAIN, bool RED = false, bool WZ = true, bool WB = true, bool MX = false>
 __global__ void __launch_bounds__(kStftThreads) k_stft_fused(const T* __restrict__ sig, const T* __restrict__ win,
                                                              const cplx<T>* __restrict__ twg, cplx<T>* __restrict__ Z,
                                                              T* __restrict__ bits, StftFusedArgs a) {
@@ -180,7 +197,7 @@ __global__ void __launch_bounds__(kStftThreads) k_stft_fused(const T* __restrict
   const int64_t item = (int64_t)(blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= a.per_xcd || item >= a.nitems) return;
   const int64_t c = item / a.ngroups, m0 = (item % a.ngroups) * G;
-  const T* __restrict__ x = sig + c * a.n;
+  const T* __restrict__ x = sig + c * a.stride;
 
   // exp(-i pi k / M), k = 0..M: requested first, left in LDS after the segments (one round trip, not one per sweep)
   constexpr int NT = (M + kStftThreads) / kStftThreads;
@@ -397,6 +414,14 @@ __global__ void __launch_bounds__(kStftThreads) k_stft_fused(const T* __restrict
         pband[k] = sa;
         if (2 * k != M) pband[M - k] = sb;
       }
+      if constexpr (MX) {
+        const T ma = group_max<T>(pa, lg), mb = group_max<T>(pb, lg);
+        if (on && g == 0) {
+          T* __restrict__ pmax = static_cast<T*>(a.red_max) + ((size_t)c * a.ngroups + (size_t)grp) * nf;
+          pmax[k] = ma;
+          if (2 * k != M) pmax[M - k] = mb;
+        }
+      }
       pt += pa + pb;
       mx = native::max_t(mx, native::max_t(pa, pb));
       pl += (double)native::plog2p(pa) + (double)native::plog2p(pb);
@@ -481,6 +506,10 @@ __global__ void __launch_bounds__(kStftThreads) k_stft_fused(const T* __restrict
       }
       const double sp = group_sum((double)p, lg);
       if (on && g == 0) pband[k] = sp;
+      if constexpr (MX) {
+        const T mp = group_max<T>(p, lg);
+        if (on && g == 0) (static_cast<T*>(a.red_max) + ((size_t)c * a.ngroups + (size_t)grp) * nf)[k] = mp;
+      }
       pt += p;
       mx = native::max_t(mx, p);
       pl += (double)native::plog2p(p);
@@ -707,6 +736,45 @@ __global__ void __launch_bounds__(256) k_stft_reduce(const double* __restrict__ 
   power_band[c * nf + f] = acc;
 }
 
+// Pooled spectrogram of the reductions form (qi_stft_out_range): window w of a record is the `per` consecutive segment groups
+// w per .. w per + per - 1 (the launch holds a power of two of segments per group that divides the factor), folded in index
+// order: mean[c][f][w] = (the groups' float64 sums added) / factor, rounded once; mx[c][f][w] = the largest of their maxima.
+// A workgroup takes 16 bins x 16 windows: the partials are read along the bins, turned in LDS and written along the windows.
+template <typename T>
+__global__ void __launch_bounds__(256) k_stft_pool_fold(const double* __restrict__ part_band, const T* __restrict__ part_max,
+                                                        T* __restrict__ mean, T* __restrict__ mx, int64_t ngroups, int nf,
+                                                        int64_t per, int64_t windows, double factor) {
+  __shared__ double ssum[16][17];
+  __shared__ T smax[16][17];
+  const int64_t c = blockIdx.z, w0 = (int64_t)blockIdx.x * 16;
+  const int f0 = blockIdx.y * 16, lo = threadIdx.x & 15, hi = threadIdx.x >> 4;
+  {
+    const int f = f0 + lo;
+    const int64_t w = w0 + hi;
+    double acc = 0.0;
+    T m = T(0);
+    if (f < nf && w < windows) {
+      const size_t at = ((size_t)c * ngroups + (size_t)(w * per)) * nf + f;
+      for (int64_t i = 0; i < per; ++i) {
+        acc += part_band[at + (size_t)i * nf];
+        if (part_max) {
+          const T v = part_max[at + (size_t)i * nf];
+          m = v > m ? v : m;
+        }
+      }
+    }
+    ssum[hi][lo] = acc;
+    smax[hi][lo] = m;
+  }
+  __syncthreads();
+  const int f = f0 + hi;
+  const int64_t w = w0 + lo;
+  if (f >= nf || w >= windows) return;
+  const size_t at = ((size_t)c * nf + f) * windows + w;
+  if (mean) mean[at] = (T)(ssum[lo][hi] / factor);
+  if (mx) mx[at] = smax[lo][hi];
+}
+
 }  // namespace
 
 // Everything the host knows about a transform length in one precision: M = nfft / 2 = R x C complex points per segment
@@ -747,15 +815,23 @@ struct StftShape {
     while (G & (G - 1)) G &= G - 1;
     return G;
   }
+  // ... of a launch that pools windows of `factor` segments (0: none): the largest power of two that divides the factor,
+  // the launch group at most -- every workgroup then lies inside one window
+  int pool_group(int64_t factor) const {
+    const int G = launch_group();
+    return factor > 0 ? (int)std::min<int64_t>(G, factor & -factor) : G;
+  }
   // segment groups (workgroups) per record of a forward launch
-  int64_t groups(int64_t nseg) const {
-    const int G = ok ? launch_group() : 0;
+  int64_t groups(int64_t nseg, int64_t factor = 0) const {
+    const int G = ok ? pool_group(factor) : 0;
     return G < 1 ? 0 : ceil_div(nseg, G);
   }
 };
 
 bool stft_fused_supported(int dtype, int64_t seg, int64_t hop, int64_t nfft) { return StftShape(nfft, dtype == QI_F64).holds(seg, hop); }
-int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg) { return StftShape(nfft, dtype == QI_F64).groups(nseg); }
+int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg, int64_t pool_factor) {
+  return StftShape(nfft, dtype == QI_F64).groups(nseg, pool_factor);
+}
 
 // The kernels of a shape: calls f(std::integral_constant<int, lr>{}, std::integral_constant<int, lc>{}) -- a generic lambda
 // that names the instantiation -- for M = 32 ... 2048 (float64: ... 1024) and returns what it returns; QI_ERR_UNSUPPORTED,
@@ -820,12 +896,13 @@ int launch_stft_fused(const StftRequest& rq, const T* sig, const T* win, cplx<T>
     set_error("fused STFT: transform length %lld is not supported", (long long)rq.nfft);
     return QI_ERR_UNSUPPORTED;
   }
-  const int G = s.launch_group();
+  const bool red = rq.power_band != nullptr;
+  const bool pool = red && rq.pool_factor > 0 && (rq.pool_mean || rq.pool_max);
+  const int G = s.pool_group(pool ? rq.pool_factor : 0);
   if (G < 1) {
     set_error("fused STFT: a transform of %lld points does not fit the LDS tile", (long long)(2 * s.M));
     return QI_ERR_UNSUPPORTED;
   }
-  const bool red = rq.power_band != nullptr;
   StftFusedArgs a{};
   a.n = rq.n;
   a.seg = rq.seg;
@@ -843,12 +920,14 @@ int launch_stft_fused(const StftRequest& rq, const T* sig, const T* win, cplx<T>
   a.red_stat = rq.part_stat;
   a.power_time = rq.power_time;
   a.power_scale = rq.power_scale;
+  a.stride = rq.row_stride < 0 ? rq.n : rq.row_stride;
+  a.red_max = pool && rq.pool_max ? rq.part_max : nullptr;
 #ifdef QI_STFT_DBG
   if (const char* e = tune_env("QI_STFT_DBG")) a.dbg = atoi(e);
 #endif
   a.G = G;
   while ((1 << a.log2g) < G) ++a.log2g;
-  a.ngroups = (int32_t)s.groups(rq.nseg);
+  a.ngroups = (int32_t)ceil_div(rq.nseg, G);
   a.nitems = (int64_t)a.ngroups * rq.C;
   a.per_xcd = (int32_t)ceil_div(a.nitems, 8);
   const dim3 grid((unsigned)(8 * a.per_xcd));
@@ -863,6 +942,8 @@ int launch_stft_fused(const StftRequest& rq, const T* sig, const T* win, cplx<T>
     if (red)
       return native::with_panels(Z != nullptr, bits != nullptr, [&](auto wz, auto wb) {
         constexpr bool WZ = decltype(wz)::value, WB = decltype(wb)::value;
+        if (a.red_max)  // (the pooled maximum: the groups' maxima beside their sums)
+          return launch_with_lds(&k_stft_fused<T, LR, LC, WZ == WB, true, WZ, WB, true>, grid, lds, st, sig, win, twg, Z, bits, a);
         return launch_with_lds(&k_stft_fused<T, LR, LC, WZ == WB, true, WZ, WB>, grid, lds, st, sig, win, twg, Z, bits, a);
       });
     if (plain) return launch_with_lds(&k_stft_fused<T, LR, LC, true>, grid, lds, st, sig, win, twg, Z, bits, a);
@@ -873,6 +954,14 @@ int launch_stft_fused(const StftRequest& rq, const T* sig, const T* win, cplx<T>
   dim3 gr((unsigned)(ceil_div(nf, 256) + 1), (unsigned)rq.C);
   k_stft_reduce<<<gr, 256, 0, st>>>(rq.part_band, rq.part_stat, rq.power_band, rq.stats, a.ngroups, nf);
   QI_LAUNCH_CHECK();
+  const int64_t windows = pool ? rq.nseg / rq.pool_factor : 0;
+  if (windows > 0) {
+    const dim3 gp((unsigned)ceil_div(windows, 16), (unsigned)ceil_div(nf, 16), (unsigned)rq.C);
+    k_stft_pool_fold<T><<<gp, 256, 0, st>>>(rq.part_band, static_cast<const T*>(a.red_max), static_cast<T*>(rq.pool_mean),
+                                           static_cast<T*>(rq.pool_max), a.ngroups, nf, rq.pool_factor / G, windows,
+                                           (double)rq.pool_factor);
+    QI_LAUNCH_CHECK();
+  }
   return QI_OK;
 }
 template int launch_stft_fused<float>(const StftRequest&, const float*, const float*, float2*, float*, hipStream_t);

@@ -15,7 +15,11 @@ picture of the record.  `StreamPipeline(pooled=factor)` closes both: every pooli
 RECORD is owned by exactly one chunk (`owned_windows`), an item keeps the pooled power strips and the sums of the range
 its chunk owns (`TfrPlan.pooled_strip`: the chunk's panel goes through a staging tensor on the device, tile by tile), and
 `PooledRecord` puts the strips side by side and adds the sums up: a display-resolution panel, band powers and entropy of
-the whole record."""
+the whole record.
+
+The STFT streams by SEGMENT ranges instead (`segment_items`, `StftStream`, `StftRecord`; styx_fft.StftRangePlan): a segment
+depends on its own samples only, so an item's coefficients are those of the one-call transform of the whole record, every
+segment belongs to exactly one item, and the items' sums add up to the record's reductions with nothing counted twice."""
 from dataclasses import dataclass
 from typing import Iterator, List, Optional, Tuple
 
@@ -134,6 +138,69 @@ class StreamItem:
     windows: Optional[int] = None  # ... and how many (owned_windows)
 
 
+class _Staging:
+    """The double buffering of a streamed record set: two pinned host buffers and two device buffers [block, width], a copy
+    stream and three events -- `stage(j, rows)` gathers one item's host rows into pinned buffer j and queues its copy to
+    device buffer j on the copy stream; the consumer's stream waits for `copied[j]` before it reads device buffer j and
+    records `consumed[j]` behind the last launch that does.  (StreamPipeline and StftStream.)"""
+
+    def __init__(self, block, width, rdtype, device):
+        np_dtype = np.float64 if rdtype == torch.float64 else np.float32
+        self.gpu = torch.device(device).type == "cuda"
+        self.pinned = [torch.empty((block, width), dtype=rdtype) for _ in range(2)]
+        if self.gpu:
+            self.pinned = [p.pin_memory() for p in self.pinned]
+        self.pinned_np = [p.numpy() for p in self.pinned]
+        assert self.pinned_np[0].dtype == np_dtype
+        self.dev = [torch.empty((block, width), dtype=rdtype, device=device) for _ in range(2)]
+        self.copy_stream = torch.cuda.Stream(device=device) if self.gpu else None
+        # the device buffers come from the caching allocator of the current stream, which hands out a freed block at once:
+        # work queued there before may still read or write that memory, so the copy stream's first writes wait for it
+        self.allocated = torch.cuda.Event() if self.gpu else None
+        if self.gpu:
+            self.allocated.record(torch.cuda.current_stream(device))
+        self.copied = [torch.cuda.Event() for _ in range(2)] if self.gpu else None    # H2D of buffer j done
+        self.consumed = [torch.cuda.Event() for _ in range(2)] if self.gpu else None  # launches that read buffer j done
+        self.used = [False, False]
+
+    def stage(self, j, rows):
+        """Host rows [cb, w] (w <= width: the first w samples of the buffers' rows) into pinned buffer j, then to device buffer j."""
+        cb, w = rows.shape
+        full = w == self.pinned[j].shape[1]
+        pin_np = self.pinned_np[j][:cb] if full else self.pinned_np[j][:cb, :w]
+        pin, dev = (self.pinned[j][:cb], self.dev[j][:cb]) if full else (self.pinned[j][:cb, :w], self.dev[j][:cb, :w])
+        if not self.gpu:
+            np.copyto(pin_np, rows, casting="same_kind")
+            dev.copy_(pin)
+            return
+        if self.used[j]:
+            self.copied[j].synchronize()  # the previous copy out of this pinned buffer has finished
+        np.copyto(pin_np, rows, casting="same_kind")
+        with torch.cuda.stream(self.copy_stream):
+            if self.used[j]:
+                self.copy_stream.wait_event(self.consumed[j])  # the launches that read device buffer j are done
+            else:
+                self.copy_stream.wait_event(self.allocated)  # what was queued where device buffer j was allocated is done
+            if w > 0:
+                dev.copy_(pin, non_blocking=True)
+            self.copied[j].record(self.copy_stream)
+        self.used[j] = True
+
+
+def _merge_sums(mine, other):
+    """power_band and stats of two assemblers: sums added, maxima compared"""
+    mine.power_band += other.power_band
+    mine.stats[:, 1:3] += other.stats[:, 1:3]
+    mine.stats[:, 0] = torch.maximum(mine.stats[:, 0], other.stats[:, 0])
+
+
+def _merge_panels(mine, other):
+    """What `other` filled where `mine` holds NaN (nobody added there), in place"""
+    for m in mine:
+        gap = torch.isnan(mine[m])
+        mine[m][gap] = other[m].to(mine[m].device)[gap]
+
+
 class PooledRecord:
     """Assembles the items of a `StreamPipeline(pooled=factor)` run into the pooled panel and the reductions of the whole
     record set: `add(item, "cwt")` puts the item's strips at [first_channel : first_channel + channels, :, window0 :
@@ -142,8 +209,10 @@ class PooledRecord:
     (power_band, stats -> total_power, entropy_bits, power_per_band_bits()).  One assembler per transform.
 
     Strips carry their own position, so a rank that owns only some of the items fills only its part: the columns nobody
-    added stay NaN and the sums hold what was added.  Combining the assemblers of several ranks (the panel parts side by
-    side, the sums added, the maxima compared) is not built here."""
+    added stay NaN and the sums hold what was added.  `merge(other)` combines the assemblers of several ranks: the columns
+    that are NaN here are taken from the other, the sums added, the maxima compared (a record whose items were split between
+    two ranks has its sums added in another order than one assembler would: equal up to rounding, and bit for bit where
+    every record's items came from one rank)."""
 
     def __init__(self, n_channels, n_bands, n_windows, methods=("average",), dtype=torch.float32, device=None):
         self.methods = tuple(methods)
@@ -164,6 +233,15 @@ class PooledRecord:
         self.stats[ch, 1:3] += res.stats[:, 1:3]
         self.stats[ch, 0] = torch.maximum(self.stats[ch, 0], res.stats[:, 0])
         self.frequency_hz, self.power_scale = res.frequency_hz, res.power_scale
+
+    def merge(self, other: "PooledRecord"):
+        if self.methods != other.methods or any(self.panel[m].shape != other.panel[m].shape for m in self.methods):
+            raise ValueError("the assemblers are not of one record set: methods or panel shapes differ")
+        _merge_panels(self.panel, other.panel)
+        _merge_sums(self, other)
+        if self.frequency_hz is None:
+            self.frequency_hz, self.power_scale = other.frequency_hz, other.power_scale
+        return self
 
     def result(self) -> engine.TfrResult:
         return engine.TfrResult(frequency_hz=self.frequency_hz, power_band=self.power_band, stats=self.stats,
@@ -209,44 +287,16 @@ class StreamPipeline:
             if not self.pooled_methods or any(m not in ("average", "max") for m in self.pooled_methods):
                 raise ValueError(f'pooled_methods must be a subset of ("average", "max"), got {self.pooled_methods!r}')
             self._starts, self._edges = owned_windows(self.sig.shape[1], plan.n, self.hop, self.pooled)
-        np_dtype = np.float64 if plan.rdtype == torch.float64 else np.float32
         # (a plan on the CPU exists only as the stand-in of bench.py --stub: the item walk without streams or pinning)
-        self._gpu = torch.device(plan.device).type == "cuda"
-        self._pinned = [torch.empty((self.block, plan.n), dtype=plan.rdtype) for _ in range(2)]
-        if self._gpu:
-            self._pinned = [p.pin_memory() for p in self._pinned]
-        self._pinned_np = [p.numpy() for p in self._pinned]
-        assert self._pinned_np[0].dtype == np_dtype
-        self._dev = [torch.empty((self.block, plan.n), dtype=plan.rdtype, device=plan.device) for _ in range(2)]
-        self._copy_stream = torch.cuda.Stream(device=plan.device) if self._gpu else None
-        # the device buffers come from the caching allocator of the current stream, which hands out a freed block at once:
-        # work queued there before may still read or write that memory, so the copy stream's first writes wait for it
-        self._allocated = torch.cuda.Event() if self._gpu else None
-        if self._gpu:
-            self._allocated.record(torch.cuda.current_stream(plan.device))
-        self._copied = [torch.cuda.Event() for _ in range(2)] if self._gpu else None    # H2D of buffer j done
-        self._consumed = [torch.cuda.Event() for _ in range(2)] if self._gpu else None  # transforms that read buffer j done
-        self._used = [False, False]
+        self._staging = _Staging(self.block, plan.n, plan.rdtype, plan.device)
+        self._gpu, self._dev = self._staging.gpu, self._staging.dev
+        self._copied, self._consumed = self._staging.copied, self._staging.consumed
         self._out = {}  # (transform, channels) -> result buffers reused item after item
 
     def _stage(self, j, item):
         """Host gather of one item into pinned buffer j and its asynchronous copy to device buffer j."""
         c0, cb, _, s = item
-        if not self._gpu:
-            np.copyto(self._pinned_np[j][:cb], self.sig[c0 : c0 + cb, s : s + self.plan.n], casting="same_kind")
-            self._dev[j][:cb].copy_(self._pinned[j][:cb])
-            return
-        if self._used[j]:
-            self._copied[j].synchronize()  # the previous copy out of this pinned buffer has finished
-        np.copyto(self._pinned_np[j][:cb], self.sig[c0 : c0 + cb, s : s + self.plan.n], casting="same_kind")
-        with torch.cuda.stream(self._copy_stream):
-            if self._used[j]:
-                self._copy_stream.wait_event(self._consumed[j])  # the transforms that read device buffer j are done
-            else:
-                self._copy_stream.wait_event(self._allocated)  # what was queued where device buffer j was allocated is done
-            self._dev[j][:cb].copy_(self._pinned[j][:cb], non_blocking=True)
-            self._copied[j].record(self._copy_stream)
-        self._used[j] = True
+        self._staging.stage(j, self.sig[c0 : c0 + cb, s : s + self.plan.n])
 
     def run(self, rank: int = 0, world: int = 1, first_item: int = 0) -> Iterator[StreamItem]:
         mine = rank_items(self.items, rank, world)[first_item:]
@@ -299,3 +349,167 @@ class StreamPipeline:
         small = engine.TfrResult(frequency_hz=res.frequency_hz, power_scale=res.power_scale)
         small.power_band, small.stats = res.power_band.clone(), res.stats.clone()
         return small
+
+
+# ---- the streamed STFT: items own SEGMENT ranges ------------------------------------------------------------------------------
+def segment_items(n_total: int, seg: int, hop: int, segments_per_item: int) -> List[Tuple[int, int, int, int]]:
+    """The segments of a record's STFT (scipy.signal.stft, boundary="zeros", padded=True: styx_fft) as consecutive runs of
+    `segments_per_item`: -> [(first_segment, segments, sample0, n_avail)].  Every segment lies in exactly one item; an item
+    carries the smallest interval of record samples its segments need (styx_fft.range_samples: neighbouring items overlap by
+    seg - hop samples; n_avail = 0 where a last padded segment lies in the zero extension).  Host arithmetic only."""
+    from .styx_fft import _frame_count, range_samples
+
+    per = int(segments_per_item)
+    if per < 1:
+        raise ValueError(f"segments_per_item {segments_per_item}: 1 or more")
+    n_seg = _frame_count(int(n_total), int(seg), int(hop))
+    if n_seg < 1:
+        raise ValueError(f"no STFT segments for n = {n_total}, segment {seg}, hop {hop}")
+    items = []
+    for first in range(0, n_seg, per):
+        count = min(per, n_seg - first)
+        items.append((first, count) + range_samples(int(n_total), int(seg), int(hop), first, count))
+    return items
+
+
+@dataclass
+class StftItem:
+    index: int          # position in the item list (the restart cursor: pass index + 1 as `first_item`)
+    first_channel: int
+    channels: int
+    first_segment: int
+    segments: int
+    sample0: int        # first record sample the item carried ...
+    n_avail: int        # ... and how many
+    stft: engine.TfrResult  # of the range: power_band / stats over its segments, power_time [channels, segments], pooled strips
+    window0: Optional[int] = None  # pooled=factor: first pooling window of the record in `stft.pooled` ...
+    windows: Optional[int] = None  # ... and how many
+
+
+class StftStream:
+    """Double-buffered host -> device streaming of (channel block, segment range) items through a styx_fft.StftRangePlan.
+
+        plan = styx_fft.StftRangePlan(n_total, 800.0, 12)
+        pipe = StftStream(plan, host_records, segments_per_item=4096, block=16, pooled=64, pooled_methods=("average", "max"))
+        record = StftRecord(channels, plan.n_f, plan.n_seg, pooled=64, methods=("average", "max"), dtype=plan.rdtype, device="cuda")
+        for item in pipe.run(rank=r, world=w):
+            record.add(item)
+
+    `host_records` as StreamPipeline takes them.  An STFT segment depends on its own samples only, so -- unlike a chunk of the
+    CWT -- the items' coefficients are those of the one-call transform of the whole record, and their sums add up to its
+    reductions in another order of summation.  Every yielded item owns its products; no panel is stored.  keep_time=False:
+    no per-time power.  pooled=factor: `item.stft.pooled[method]` [channels, n_f, item.windows], the record's pooled
+    spectrogram from window item.window0 on; segments_per_item must be a multiple of the factor."""
+
+    def __init__(self, stft_plan, host_records, segments_per_item: int, block: int = 16, pooled: Optional[int] = None,
+                 pooled_methods=("average",), keep_time: bool = True, power_scale: float = 1.0, device=None):
+        self.plan, self.block, self.per = stft_plan, int(block), int(segments_per_item)
+        self.pooled, self.pooled_methods = (None if pooled is None else int(pooled)), tuple(pooled_methods)
+        self.keep_time, self.power_scale = keep_time, power_scale
+        self.sig = host_records if hasattr(host_records, "shape") and hasattr(host_records, "__getitem__") else np.asarray(host_records)
+        if len(self.sig.shape) == 1:
+            self.sig = self.sig[None, :]
+        if self.sig.shape[1] != stft_plan.n_total:
+            raise ValueError(f"records of {self.sig.shape[1]} samples, the plan is for {stft_plan.n_total}")
+        if self.block < 1:
+            raise ValueError(f"block {block}: 1 or more")
+        self.ranges = segment_items(stft_plan.n_total, stft_plan.seg, stft_plan.hop, self.per)
+        if self.pooled is not None:
+            if not self.pooled_methods or any(m not in ("average", "max") for m in self.pooled_methods):
+                raise ValueError(f'pooled_methods must be a subset of ("average", "max"), got {self.pooled_methods!r}')
+            if self.pooled < 2:
+                raise ValueError(f"pooling factor {self.pooled}: 2 or more")
+            if self.per % self.pooled:
+                raise ValueError(f"segments_per_item {self.per} is no multiple of the pooling factor {self.pooled}")
+        n_ch = self.sig.shape[0]
+        # block-major, as work_items: a rank's contiguous share walks whole blocks through their ranges
+        self.items = [(c0, min(self.block, n_ch - c0)) + r for c0 in range(0, n_ch, self.block) for r in self.ranges]
+        self.device = torch.device(device) if device is not None else engine.default_device()
+        self._width = max(1, max(r[3] for r in self.ranges))
+        self._staging = None  # (the pinned and device buffers are made by the first run)
+
+    def _stage(self, j, item):
+        c0, cb, _, _, s0, n_avail = item
+        self._staging.stage(j, self.sig[c0 : c0 + cb, s0 : s0 + n_avail])
+
+    def run(self, rank: int = 0, world: int = 1, first_item: int = 0) -> Iterator[StftItem]:
+        mine = rank_items(self.items, rank, world)[first_item:]
+        if not mine:
+            return
+        if self._staging is None:
+            self._staging = _Staging(self.block, self._width, self.plan.rdtype, self.device)
+        st = self._staging
+        compute = torch.cuda.current_stream(self.device) if st.gpu else None
+        self._stage(0, mine[0])
+        for k, item in enumerate(mine):
+            j = k & 1
+            c0, cb, first, count, s0, n_avail = item
+            if st.gpu:
+                compute.wait_event(st.copied[j])
+            res = self.plan.segment_range(st.dev[j][:cb], first, count, s0, reductions=True if self.keep_time else "band",
+                                          pooled=self.pooled, pooled_methods=self.pooled_methods, power_scale=self.power_scale,
+                                          n_avail=n_avail)
+            if st.gpu:
+                st.consumed[j].record(compute)
+            # (the next item's host gather and copy run after this item's launches are queued, as in StreamPipeline)
+            if k + 1 < len(mine):
+                self._stage(j ^ 1, mine[k + 1])
+            w0, nw = (None, None) if self.pooled is None else (first // self.pooled, count // self.pooled)
+            yield StftItem(first_item + k, c0, cb, first, count, s0, n_avail, res, w0, nw)  # (segment_range's outputs are new tensors)
+
+
+class StftRecord:
+    """Assembles the items of an `StftStream` run into the products of the whole record set: `add(item)` puts the item's
+    pooled strips at [channels, :, window0 : window0 + windows] and its per-time power at [channels, first_segment :
+    first_segment + segments], adds its band powers, sum P and sum P log2 P, and keeps the larger maximum (PooledRecord's
+    rules).  `panel[method]` is [n_channels, n_f, n_segments // pooled], `power_time` [n_channels, n_segments] (keep_time),
+    both NaN where nothing was added; `result()` a TfrResult of the whole record (total_power, entropy_bits,
+    power_per_band_bits()).  `merge(other)` combines the assemblers of several ranks as PooledRecord.merge does."""
+
+    def __init__(self, n_channels, n_f, n_segments, pooled=None, methods=("average",), keep_time=True, dtype=torch.float32,
+                 device=None):
+        self.pooled, self.methods = (None if pooled is None else int(pooled)), (tuple(methods) if pooled is not None else ())
+        n_windows = 0 if pooled is None else n_segments // self.pooled
+        self.panel = {m: torch.full((n_channels, n_f, n_windows), float("nan"), dtype=dtype, device=device) for m in self.methods}
+        self.power_time = torch.full((n_channels, n_segments), float("nan"), dtype=dtype, device=device) if keep_time else None
+        self.power_band = torch.zeros((n_channels, n_f), dtype=torch.float64, device=device)
+        self.stats = torch.zeros((n_channels, 4), dtype=torch.float64, device=device)
+        self.frequency_hz = None
+        self.power_scale = 1.0
+
+    def add(self, item: "StftItem"):
+        res = item.stft
+        if res is None or res.power_band is None:
+            raise ValueError(f"item {item.index} carries no reductions")
+        ch = slice(item.first_channel, item.first_channel + item.channels)
+        if self.methods:
+            if res.pooled is None or item.windows is None:
+                raise ValueError(f"item {item.index} carries no pooled strips (StftStream(pooled=factor))")
+            for m in self.methods:
+                self.panel[m][ch, :, item.window0 : item.window0 + item.windows] = res.pooled[m]
+        if self.power_time is not None:
+            if res.power_time is None:
+                raise ValueError(f"item {item.index} carries no per-time power (StftStream(keep_time=True))")
+            self.power_time[ch, item.first_segment : item.first_segment + item.segments] = res.power_time
+        self.power_band[ch] += res.power_band
+        self.stats[ch, 1:3] += res.stats[:, 1:3]
+        self.stats[ch, 0] = torch.maximum(self.stats[ch, 0], res.stats[:, 0])
+        self.frequency_hz, self.power_scale = res.frequency_hz, res.power_scale
+
+    def merge(self, other: "StftRecord"):
+        if (self.methods != other.methods or self.power_band.shape != other.power_band.shape
+                or any(self.panel[m].shape != other.panel[m].shape for m in self.methods)
+                or (self.power_time is None) != (other.power_time is None)
+                or (self.power_time is not None and self.power_time.shape != other.power_time.shape)):
+            raise ValueError("the assemblers are not of one record set: methods or shapes differ")
+        _merge_panels(self.panel, other.panel)
+        if self.power_time is not None:
+            _merge_panels({"t": self.power_time}, {"t": other.power_time})
+        _merge_sums(self, other)
+        if self.frequency_hz is None:
+            self.frequency_hz, self.power_scale = other.frequency_hz, other.power_scale
+        return self
+
+    def result(self) -> engine.TfrResult:
+        return engine.TfrResult(frequency_hz=self.frequency_hz, power_band=self.power_band, power_time=self.power_time,
+                                stats=self.stats, power_scale=self.power_scale, pooled=self.panel if self.methods else None)

@@ -246,6 +246,150 @@ class StftPlan:
         return _stft_out(self._lib, sig, self.window, self.seg, self.hop, self.nfft, self.scale, res, self._out_scratch)
 
 
+def _frame_count(n, seg, hop):
+    """qi_stft_segments restated (scipy.signal.stft, boundary="zeros", padded=True): host arithmetic, no library."""
+    if n <= 0 or seg <= 0 or not 0 < hop <= seg:
+        return 0
+    length = n + 2 * (seg // 2)
+    length += (-(length - seg) % hop) % seg
+    return (length - seg) // hop + 1
+
+
+def range_samples(n_total, seg, hop, first_segment, segments):
+    """(sample0, n_avail): the smallest interval of record samples that the segments first_segment .. first_segment +
+    segments - 1 need -- segment m covers [m hop - seg // 2, m hop - seg // 2 + seg), cut to [0, n_total); n_avail = 0 for a
+    range that lies in the zero extension (qi_stft_range_samples restated: host arithmetic)."""
+    lo = min(n_total, max(0, first_segment * hop - seg // 2))
+    hi = min(n_total, (first_segment + segments - 1) * hop - seg // 2 + seg)
+    return lo, max(0, hi - lo)
+
+
+class StftRangePlan:
+    """The STFT of a record that is too long for the device, one range of segments at a time (qi_stft_out_range): a segment
+    depends on its own samples only, so the ranges of a record give the coefficients of the one-call transform and their
+    sums add up to its reductions (stream.StftStream feeds the ranges, stream.StftRecord adds them up).
+
+    Geometry: stft_from_sig's from `band_order_nth` (periodic Hann, half overlap, scale 2 sqrt(pi) / segment), or an explicit
+    `window` [seg] (float64 NumPy) with `overlap_points` / `nfft_points` as stft_complex_pow2 takes them (`extra_scale`
+    multiplies 1 / sum(window)).  Building a plan is host work; the device is asked for at the first `segment_range`."""
+
+    def __init__(self, n_total, frequency_sample_rate_hz, band_order_nth=None, window=None, overlap_points=None, nfft_points=None,
+                 extra_scale=1.0, dtype=torch.float32, device=None):
+        self.n_total, self.fs = int(n_total), float(frequency_sample_rate_hz)
+        if (band_order_nth is None) == (window is None):
+            raise ValueError("give band_order_nth (stft_from_sig's geometry) or a window, not both")
+        if window is None:
+            self.seg = stft_segment_points(self.fs, band_order_nth)
+            if self.n_total < self.seg:
+                raise ValueError(f"Signal length: {self.n_total} is less than time_fft_nd: {self.seg}")
+            win64 = tukey_window_periodic(self.seg, 1.0)
+            self.hop, self.nfft = self.seg // 2, self.seg
+            extra_scale = 2 * np.sqrt(np.pi) / self.seg
+        else:
+            win64 = np.asarray(window, dtype=np.float64)
+            if win64.ndim != 1 or len(win64) < 1:
+                raise ValueError("window must be 1-D")
+            self.seg = len(win64)
+            if self.n_total < self.seg:
+                raise ValueError(f"record of {self.n_total} samples is shorter than the segment of {self.seg}")
+            self.hop = self.seg - (int(self.seg / 2) if overlap_points is None else int(overlap_points))
+            self.nfft = int(2 ** np.ceil(np.log2(self.seg))) if nfft_points is None else int(nfft_points)
+            if not 0 < self.hop <= self.seg:
+                raise ValueError("noverlap must be less than nperseg.")
+            if self.nfft < self.seg:
+                raise ValueError("nfft must be greater than or equal to nperseg.")
+        self.rdtype = engine._real_dtype(dtype)
+        self._device = device
+        win = win64 if self.rdtype == torch.float64 else win64.astype(np.float32)
+        self._win_host = np.ascontiguousarray(win)
+        self.scale = float(np.sqrt(1.0 / np.sum(win.astype(np.float64)) ** 2)) * extra_scale
+        self.n_seg = _frame_count(self.n_total, self.seg, self.hop)
+        self.n_f = self.nfft // 2 + 1
+        self.code = _lib.dtype_code(self.rdtype)
+        padded = self.n_total + 2 * (self.seg // 2)
+        padded += (-(padded - self.seg) % self.hop) % self.seg
+        self.time_s = np.arange(self.seg / 2, padded - self.seg / 2 + 1, self.hop) / self.fs - (self.seg / 2) / self.fs
+        self.frequency_hz = np.fft.rfftfreq(self.nfft, 1 / self.fs)
+        self._lib, self.device, self.window, self._scratch = None, None, None, None
+
+    def check_range(self, first_segment, segments, sample0, n_avail, pooled=None, pooled_methods=("average",)):
+        """The refusals of a range that need no device: ValueError.  -> the pooled windows of the range (0 without pooling)."""
+        first_segment, segments, sample0, n_avail = int(first_segment), int(segments), int(sample0), int(n_avail)
+        if first_segment < 0 or segments < 1 or first_segment + segments > self.n_seg:
+            raise ValueError(f"segments {first_segment} .. {first_segment + segments - 1} of a record of {self.n_seg}")
+        if sample0 < 0 or n_avail < 0 or sample0 + n_avail > self.n_total:
+            raise ValueError(f"samples {sample0} .. +{n_avail} are not inside a record of {self.n_total}")
+        lo, need = range_samples(self.n_total, self.seg, self.hop, first_segment, segments)
+        if need > 0 and not (sample0 <= lo and lo + need <= sample0 + n_avail):
+            raise ValueError(f"the range needs the record samples {lo} .. {lo + need - 1}, the rows hold {sample0} .. {sample0 + n_avail - 1}")
+        if pooled is None:
+            return 0
+        pooled, methods = int(pooled), tuple(pooled_methods)
+        if not methods or any(m not in ("average", "max") for m in methods) or len(set(methods)) != len(methods):
+            raise ValueError(f'pooled_methods must be a subset of ("average", "max"), got {methods!r}')
+        if pooled < 2:
+            raise ValueError(f"pooling factor {pooled}: 2 or more")
+        if first_segment % pooled:
+            raise ValueError(f"first segment {first_segment} is no multiple of the pooling factor {pooled}")
+        if segments % pooled and first_segment + segments != self.n_seg:
+            raise ValueError(f"{segments} segments are no multiple of the pooling factor {pooled} and do not end the record")
+        return segments // pooled
+
+    def segment_range(self, rows, first_segment, segments, sample0, n_total=None, coef=False, bits=False, reductions=True,
+                      pooled=None, pooled_methods=("average",), power_scale=1.0, n_avail=None):
+        """The segments first_segment .. first_segment + segments - 1 of the record from `rows` [C, width], a device tensor
+        whose row c holds the record samples sample0 .. sample0 + n_avail - 1 (n_avail: default what a row can hold of the
+        record; nothing past it is read; rows may be a view with a longer row stride).  -> TfrResult of the range: coef /
+        bits [C, n_f, segments] when asked for, power_band / stats over these segments, power_time [C, segments]
+        (reductions="band": without it), and with pooled=F `pooled` {method: [C, n_f, segments // F]}, the average / maximum
+        of P = power_scale |Z|^2 over the windows of F consecutive segments (first_segment and segments multiples of F; the
+        range that ends the record may be ragged, its incomplete window is dropped).  Host-side refusals are ValueErrors
+        raised before the device is touched."""
+        if n_total is not None and int(n_total) != self.n_total:
+            raise ValueError(f"the plan is for records of {self.n_total} samples, not {n_total}")
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype != self.rdtype:
+            raise ValueError(f"rows must be a 2-D {self.rdtype} tensor [channels, samples]")
+        if rows.shape[1] > 1 and rows.stride(1) != 1:
+            raise ValueError("the samples of a row must be contiguous")
+        first_segment, segments, sample0 = int(first_segment), int(segments), int(sample0)
+        if n_avail is None:
+            n_avail = max(0, min(rows.shape[1], self.n_total - sample0))
+        n_avail = int(n_avail)
+        n_ch, stride = rows.shape[0], (rows.stride(0) if rows.shape[0] > 1 else max(rows.shape[1], rows.stride(0)))
+        if n_avail > rows.shape[1] or stride < n_avail:
+            raise ValueError(f"rows of {rows.shape[1]} samples (stride {stride}) cannot hold {n_avail}")
+        windows = self.check_range(first_segment, segments, sample0, n_avail, pooled, pooled_methods)
+        if pooled is not None and not reductions:
+            raise ValueError("the pooled outputs come with the reductions")
+        if not (coef or bits or reductions):
+            raise ValueError("nothing to produce")
+        self._lib = _lib.require_gpu()
+        if not rows.is_cuda:
+            raise ValueError("rows must be a CUDA tensor")
+        if self.window is None or self.device != rows.device:
+            self.device = rows.device
+            self.window = torch.from_numpy(self._win_host).to(self.device)
+        dev = self.device
+        res = _stft_result(self.frequency_hz, n_ch, self.n_f, segments, self.rdtype, dev, coef, bits, reductions, power_scale)
+        rng = _lib.StftRange(n_total=self.n_total, first_segment=first_segment, segments=segments, sample0=sample0, n_avail=n_avail,
+                             row_stride=stride, pool_factor=0)
+        if pooled is not None:
+            res.pooled = {m: torch.empty((n_ch, self.n_f, windows), dtype=self.rdtype, device=dev) for m in pooled_methods}
+            rng.pool_factor = int(pooled)
+            rng.pool_mean, rng.pool_max = _lib.ptr(res.pooled.get("average")), _lib.ptr(res.pooled.get("max"))
+        nbytes = int(self._lib.qi_stft_range_scratch_bytes(self.code, n_ch, self.seg, self.hop, self.nfft, C.byref(rng), int(bool(coef))))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        if self._scratch is None or self._scratch.numel() < nbytes or self._scratch.device != dev:
+            self._scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        desc = _lib.TfrOut(coef=_lib.ptr(res.coef), bits=_lib.ptr(res.bits), power_band=_lib.ptr(res.power_band),
+                           power_time=_lib.ptr(res.power_time), stats=_lib.ptr(res.stats), power_scale=float(power_scale),
+                           eps=float(get_epsilon()))
+        _lib.call(self._lib.qi_stft_out_range, dev, self.code, dev.index, _lib.ptr(rows), n_ch, _lib.ptr(self.window), self.seg,
+                  self.hop, self.nfft, self.scale, C.byref(rng), C.byref(desc), _lib.ptr(self._scratch), self._scratch.numel())
+        return res
+
+
 def stft_complex_pow2(
     sig_wf,
     frequency_sample_rate_hz: float,
