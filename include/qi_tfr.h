@@ -16,7 +16,9 @@
  *  - every call returns 0 on success or a negative qi_status; qi_last_error() gives the
  *    message for the calling thread.  Nothing throws, nothing aborts.
  *  - transforms are asynchronous on the given stream and do no host synchronisation;
- *    a plan is thread-compatible (one plan per host thread / stream).
+ *    a plan is thread-compatible (one plan per host thread / stream).  The calls that upload
+ *    host tables -- qi_plan_set_gabor_bank, qi_gabor_atoms, qi_gabor_atoms_at -- wait for the
+ *    stream before they return (their uploads live in temporaries).
  *  - panels are [channel][band][time], C-contiguous, band frequency ascending, as the
  *    reference returns them for one channel (styx_cwt.py:198, styx_stx.py:236).
  *  - dtype selects the arithmetic: QI_F32 (float / float2) or QI_F64 (double / double2).

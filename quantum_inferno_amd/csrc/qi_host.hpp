@@ -66,7 +66,9 @@ inline int require_timestamp_stride(const char* name, int64_t stride, int64_t n)
 struct FftCache {
   using Key = std::tuple<int, int64_t, int64_t, int64_t>;  // hipfftType, length, batch, distance between transforms
   std::map<Key, hipfftHandle> plans;
-  void* work = nullptr;
+  // One work area of work_bytes per stream: the handles are shared, and transforms queued on two streams run side by side --
+  // with one area for all of them the later one overwrote the intermediate rows of the earlier one.
+  std::map<hipStream_t, void*> work;
   size_t work_bytes = 0;
   std::vector<void*> retired;  // outgrown work areas, freed with the cache
 
@@ -88,27 +90,34 @@ struct FftCache {
     if (dist == len) QI_FFT(hipfftMakePlanMany(h, 1, nn, nullptr, 1, (int)len, nullptr, 1, (int)len, type, (int)batch, &ws));
     else QI_FFT(hipfftMakePlanMany(h, 1, nn, nn, 1, (int)dist, nn, 1, (int)dist, type, (int)batch, &ws));  // (in place, padded rows)
     if (ws > work_bytes) {
-      // growing the shared work area happens while a plan warms up, never in steady state.  No synchronisation: the old
-      // area stays allocated (transforms already queued keep using it) until the cache is cleared
-      if (work) retired.push_back(work);
-      work = nullptr;
-      work_bytes = 0;
-      QI_HIP(hipMalloc(&work, ws));
+      // growing the work areas happens while a plan warms up, never in steady state.  No synchronisation: the old areas
+      // stay allocated (transforms already queued keep using them) until the cache is cleared; `bind` makes the new ones
+      for (auto& kv : work) retired.push_back(kv.second);
+      work.clear();
       work_bytes = ws;
-      for (auto& kv : plans) QI_FFT(hipfftSetWorkArea(kv.second, work));
     }
-    if (work) QI_FFT(hipfftSetWorkArea(h, work));
     plans[k] = h;
     *out = h;
+    return QI_OK;
+  }
+  // Point handle `h` at stream `st` and at that stream's work area (made at the stream's first transform), for the
+  // execution the caller queues next.  The caller holds whatever lock guards the cache until that execution is queued.
+  int bind(hipfftHandle h, hipStream_t st) {
+    if (work_bytes > 0) {
+      void*& w = work[st];
+      if (!w) QI_HIP(hipMalloc(&w, work_bytes));
+      QI_FFT(hipfftSetWorkArea(h, w));
+    }
+    QI_FFT(hipfftSetStream(h, st));
     return QI_OK;
   }
   void clear() {
     for (auto& kv : plans) hipfftDestroy(kv.second);
     plans.clear();
-    if (work) (void)hipFree(work);
+    for (auto& kv : work) (void)hipFree(kv.second);
     for (void* w : retired) (void)hipFree(w);
     retired.clear();
-    work = nullptr;
+    work.clear();
     work_bytes = 0;
   }
 };

@@ -25,7 +25,7 @@ template <>
 int fft_c2c<float>(FftCache& fc, float2* data, int64_t len, int64_t batch, int dir, hipStream_t st) {
   hipfftHandle h;
   QI_TRY(fc.get(HIPFFT_C2C, len, batch, &h));
-  QI_FFT(hipfftSetStream(h, st));
+  QI_TRY(fc.bind(h, st));
   QI_FFT(hipfftExecC2C(h, (hipfftComplex*)data, (hipfftComplex*)data, dir));
   return QI_OK;
 }
@@ -33,14 +33,14 @@ template <>
 int fft_c2c<double>(FftCache& fc, double2* data, int64_t len, int64_t batch, int dir, hipStream_t st) {
   hipfftHandle h;
   QI_TRY(fc.get(HIPFFT_Z2Z, len, batch, &h));
-  QI_FFT(hipfftSetStream(h, st));
+  QI_TRY(fc.bind(h, st));
   QI_FFT(hipfftExecZ2Z(h, (hipfftDoubleComplex*)data, (hipfftDoubleComplex*)data, dir));
   return QI_OK;
 }
 int fft_z2z_rows(FftCache& fc, double2* data, int64_t len, int64_t dist, int64_t batch, int dir, hipStream_t st) {
   hipfftHandle h;
   QI_TRY(fc.get(HIPFFT_Z2Z, len, batch, &h, dist));
-  QI_FFT(hipfftSetStream(h, st));
+  QI_TRY(fc.bind(h, st));
   QI_FFT(hipfftExecZ2Z(h, (hipfftDoubleComplex*)data, (hipfftDoubleComplex*)data, dir));
   return QI_OK;
 }
@@ -50,7 +50,7 @@ template <>
 int fft_r2c<float>(FftCache& fc, float* in, float2* out, int64_t len, int64_t batch, hipStream_t st) {
   hipfftHandle h;
   QI_TRY(fc.get(HIPFFT_R2C, len, batch, &h));
-  QI_FFT(hipfftSetStream(h, st));
+  QI_TRY(fc.bind(h, st));
   QI_FFT(hipfftExecR2C(h, in, (hipfftComplex*)out));
   return QI_OK;
 }
@@ -58,7 +58,7 @@ template <>
 int fft_r2c<double>(FftCache& fc, double* in, double2* out, int64_t len, int64_t batch, hipStream_t st) {
   hipfftHandle h;
   QI_TRY(fc.get(HIPFFT_D2Z, len, batch, &h));
-  QI_FFT(hipfftSetStream(h, st));
+  QI_TRY(fc.bind(h, st));
   QI_FFT(hipfftExecD2Z(h, in, (hipfftDoubleComplex*)out));
   return QI_OK;
 }
@@ -69,7 +69,7 @@ template <>
 int fft_c2r<float>(FftCache& fc, float2* in, float* out, int64_t len, int64_t batch, hipStream_t st) {
   hipfftHandle h;
   QI_TRY(fc.get(HIPFFT_C2R, len, batch, &h));
-  QI_FFT(hipfftSetStream(h, st));
+  QI_TRY(fc.bind(h, st));
   QI_FFT(hipfftExecC2R(h, (hipfftComplex*)in, out));
   return QI_OK;
 }
@@ -77,7 +77,7 @@ template <>
 int fft_c2r<double>(FftCache& fc, double2* in, double* out, int64_t len, int64_t batch, hipStream_t st) {
   hipfftHandle h;
   QI_TRY(fc.get(HIPFFT_Z2D, len, batch, &h));
-  QI_FFT(hipfftSetStream(h, st));
+  QI_TRY(fc.bind(h, st));
   QI_FFT(hipfftExecZ2D(h, (hipfftDoubleComplex*)in, out));
   return QI_OK;
 }

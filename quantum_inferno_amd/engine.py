@@ -953,7 +953,9 @@ def _rows_and_axis(params, width, n, axis, records, device):
     device = torch.device(device)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    p = torch.from_numpy(rows).to(device)
+    # through page-locked memory: a copy from pageable memory holds the host until the current stream has run it, and these
+    # calls promise to synchronise nothing (the pinned block is PyTorch's to reuse once the copy has run)
+    p = torch.from_numpy(rows).pin_memory().to(device, non_blocking=True)
     t = None
     if x is not None:
         if not isinstance(x, torch.Tensor):
