@@ -9,7 +9,7 @@ extern "C" int64_t qi_stft_segments(int64_t n, int64_t seg, int64_t hop);
 
 namespace {
 
-// ---- the STFT family's two engines: the fused kernels (qi_stft_fused.hip), or frames -> hipFFT -> finish ----------------
+// ---- the STFT family's two engines: the fused kernels (qi_stft_fused.hip), or frames -> hipFFT -> finish (qi_stft_hipfft.hip) ----
 // the fused kernels switched off (development switch, read once per process)
 bool stft_fused_off() {
   static const bool off = tune_env("QI_STFT_FUSED") && atoi(tune_env("QI_STFT_FUSED")) == 0;
@@ -45,26 +45,22 @@ int locked_fft(int device, Transform&& transform) {
   return transform(g_stft_fft[device]);
 }
 
-// `frames` fills the real rows, hipFFT transforms them, `finish` consumes the spectra
-template <typename T, typename Frames, typename Finish>
-int via_hipfft(int device, char* scratch, int64_t C, int64_t rows, int64_t nfft, hipStream_t st, Frames&& frames, Finish&& finish) {
-  const FftScratch l(sizeof(T) == 8 ? QI_F64 : QI_F32, C, rows, nfft);
-  T* re = reinterpret_cast<T*>(scratch + l.frames);
+// the hipFFT engine on a request: its frames -> hipFFT -> `finish` on the spectra [C][nseg][nfft / 2 + 1]
+template <typename T, typename Finish>
+int via_hipfft(int device, const StftRequest& rq, const T* sig, const T* window, char* scratch, hipStream_t st, Finish&& finish) {
+  const FftScratch l(sizeof(T) == 8 ? QI_F64 : QI_F32, rq.C, rq.nseg, rq.nfft);
+  T* frames = reinterpret_cast<T*>(scratch + l.frames);
   cplx<T>* F = reinterpret_cast<cplx<T>*>(scratch + l.spectra);
-  QI_TRY(frames(re));
-  QI_TRY(locked_fft(device, [&](FftCache& fc) { return fft_r2c<T>(fc, re, F, nfft, C * rows, st); }));
+  QI_TRY(launch_hipfft_frames<T>(rq, sig, window, frames, st));
+  QI_TRY(locked_fft(device, [&](FftCache& fc) { return fft_r2c<T>(fc, frames, F, rq.nfft, rq.C * rq.nseg, st); }));
   return finish(F);
 }
 
-// qi_stft / qi_stft_out on the three-kernel sequence: frames -> hipFFT -> transpose into the panels
+// ... finished by the transpose into the panels: Z and / or the real panel R of rq.real_kind
 template <typename T>
-int stft_hipfft(int device, const StftRequest& rq, const T* sig, const T* window, cplx<T>* Z, T* bits, char* scratch, hipStream_t st) {
-  return via_hipfft<T>(
-      device, scratch, rq.C, rq.nseg, rq.nfft, st,
-      [&](T* frames) {
-        return launch_stft_frames<T>(sig, window, frames, rq.C, rq.n, rq.seg, rq.hop, rq.nfft, rq.nseg, rq.lead, st, rq.row_stride);
-      },
-      [&](cplx<T>* F) { return launch_stft_transpose<T>(F, Z, bits, rq.C, rq.nseg, rq.nfft / 2 + 1, (T)rq.scale, (T)rq.eps, st); });
+int stft_hipfft(int device, const StftRequest& rq, const T* sig, const T* window, cplx<T>* Z, T* R, char* scratch, hipStream_t st) {
+  return via_hipfft<T>(device, rq, sig, window, scratch, st,
+                       [&](const cplx<T>* F) { return launch_hipfft_transpose<T>(rq, F, Z, R, st); });
 }
 
 // Scratch of qi_stft_out: [0] the three-kernel path's frames and spectra (qi_stft_scratch_bytes) | [1] the panel when the
@@ -324,19 +320,18 @@ int qi_welch(int dtype, int device, const void* sig, int64_t C, int64_t n, const
   QI_REQUIRE(scratch_bytes >= qi_welch_scratch_bytes(dtype, C, n, seg, hop, nfft), "scratch too small");
   DeviceGuard g(device);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t nseg = (n - seg) / hop + 1;
+  StftRequest rq{C, n, seg, hop, nfft, (n - seg) / hop + 1, 0};
+  rq.scale = scale;
   return by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     const T *x = (const T*)sig, *w = (const T*)window;
     return fused_or_hipfft(
         stft_fused_supported(dtype, seg, hop, nfft),
         // segments, transform, |X|^2 sums in one kernel
-        [&] { return launch_welch_fused<T>(x, w, (T*)pxx, (double*)scratch, C, n, seg, hop, nfft, nseg, scale * scale, st); },
+        [&] { return launch_welch_fused<T>(rq, x, w, (T*)pxx, (double*)scratch, st); },
         [&] {
-          return via_hipfft<T>(
-              device, (char*)scratch, C, nseg, nfft, st,
-              [&](T* frames) { return launch_stft_frames<T>(x, w, frames, C, n, seg, hop, nfft, nseg, 0, st); },
-              [&](cplx<T>* F) { return launch_welch_mean<T>(F, (T*)pxx, C, nseg, nfft / 2 + 1, nfft, (T)(scale * scale), st); });
+          return via_hipfft<T>(device, rq, x, w, (char*)scratch, st,
+                               [&](const cplx<T>* F) { return launch_welch_mean<T>(rq, F, (T*)pxx, st); });
         });
   });
 }
@@ -496,16 +491,7 @@ int qi_sliding_stft(int dtype, int device, const void* sig, int64_t C, int64_t n
         stft_fused_supported(dtype, seg, hop, nfft),
         // one kernel: slices (padding mode, optional detrend), transform, phase roll, [frequency][slice] store
         [&] { return launch_stft_fused<T>(rq, x, w, (cplx<T>*)Z, (T*)real_out, st); },
-        [&] {
-          return via_hipfft<T>(
-              device, (char*)scratch, C, n_slices, nfft, st,
-              [&](T* frames) {
-                return launch_sliding_frames<T>(x, w, frames, C, n, seg, hop, nfft, n_slices, first, pad_mode, detrend, roll, st);
-              },
-              [&](cplx<T>* F) {
-                return launch_sliding_transpose<T>(F, (cplx<T>*)Z, (T*)real_out, real_kind, C, n_slices, nfft / 2 + 1, st);
-              });
-        });
+        [&] { return stft_hipfft<T>(device, rq, x, w, (cplx<T>*)Z, (T*)real_out, (char*)scratch, st); });
   });
 }
 

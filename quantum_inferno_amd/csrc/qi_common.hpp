@@ -127,14 +127,7 @@ struct EpiArgs {
 };
 template <typename T>
 int launch_epilogue(const EpiArgs<T>& a, hipStream_t st);
-// sliding-window STFT in scipy.signal.ShortTimeFFT's convention (qi_stft_sliding.hip)
-template <typename T>
-int launch_sliding_frames(const T* sig, const T* win, T* frames, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                          int64_t nfft, int64_t nseg, int64_t first, int pad_mode, int detrend, int64_t roll,
-                          hipStream_t st);
-template <typename T>
-int launch_sliding_transpose(const cplx<T>* F, cplx<T>* Z, T* R, int kind, int64_t C, int64_t nseg, int64_t nf,
-                             hipStream_t st);
+// the inverse of the ShortTimeFFT-convention transform on hipFFT (qi_stft_hipfft.hip)
 template <typename T>
 int launch_sliding_untranspose(const cplx<T>* S, cplx<T>* F, int64_t C, int64_t nseg, int64_t nf, hipStream_t st);
 template <typename T>
@@ -154,16 +147,15 @@ int launch_fft_marginal(const cplx<T>* X, int64_t C, int64_t nf, T* angle, T* ma
 int launch_finalize(const double* part_band, const double* part_stat, double* power_band, double* stats, int64_t C,
                     int64_t B, int64_t nblk, int64_t nstat, hipStream_t st, const int32_t* band_slots = nullptr);
 
-template <typename T>
-int launch_stft_frames(const T* sig, const T* win, T* frames, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                       int64_t nfft, int64_t nseg, int64_t lead, hipStream_t st, int64_t stride = -1);  // stride < 0: rows of n
 // fused STFT (qi_stft_fused.hip): frames, transform and [frequency][time] store in one kernel
 bool stft_fused_supported(int dtype, int64_t seg, int64_t hop, int64_t nfft);
 // segment groups (workgroups) per record of a fused launch; 0: the transform length has no fused shape
 // (pool_factor > 0: of a launch that pools windows of that many segments)
 int64_t stft_fused_groups(int dtype, int64_t nfft, int64_t nseg, int64_t pool_factor = 0);
-// One forward call of the fused kernel.  The mode fields default to qi_stft's own call (zeros past the record, segment mean
-// removed, coefficient and log2-bits panels); Welch, the ShortTimeFFT convention and the reductions set only what they mean.
+// One forward call of the family, on either engine.  The mode fields default to qi_stft's own call (zeros past the record,
+// segment mean removed, coefficient and log2-bits panels); Welch, the ShortTimeFFT convention and the reductions set only what
+// they mean.  (The hipFFT engine reads the geometry, scale, eps and the ShortTimeFFT fields; its reductions are kernels of
+// their own on the panel.)
 struct StftRequest {
   int64_t C, n, seg, hop, nfft, nseg;
   // samples of extension in front of the record (seg / 2 for the STFT, 0 Welch, -first sliding; a segment range: the signed
@@ -197,16 +189,18 @@ int launch_stft_fused(const StftRequest& rq, const T* sig, const T* win, cplx<T>
 template <typename T>
 int launch_istft_fused(const cplx<T>* S, const T* dual, T* out, int64_t C, int64_t seg, int64_t hop, int64_t nfft, int64_t first,
                        int64_t nseg, int64_t roll, int64_t k0, int64_t k1, hipStream_t st);
-// Welch mean on the fused kernel (`part`: [C][stft_fused_groups()][nfft / 2 + 1] doubles of scratch)
+// Welch mean on the fused kernel (`part`: [C][stft_fused_groups()][nfft / 2 + 1] doubles of scratch; rq.scale: 1 / sum(window))
 template <typename T>
-int launch_welch_fused(const T* sig, const T* win, T* pxx, double* part, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                       int64_t nfft, int64_t nseg, double scale2, hipStream_t st);
+int launch_welch_fused(const StftRequest& rq, const T* sig, const T* win, T* pxx, double* part, hipStream_t st);
+// the hipFFT engine's forward kernels (qi_stft_hipfft.hip).  frames [C][nseg][nfft]: the request's segments (extension,
+// mean removal, window, roll); F [C][nseg][nfft / 2 + 1] spectra -> rq.scale F as [C][nfft / 2 + 1][nseg] in Z and / or
+// its real panel by rq.real_kind in R (either may be null), or -> Welch's mean pxx [C][nfft / 2 + 1]
 template <typename T>
-int launch_welch_mean(const cplx<T>* F, T* pxx, int64_t C, int64_t nseg, int64_t nf, int64_t nfft, T scale2,
-                      hipStream_t st);
+int launch_hipfft_frames(const StftRequest& rq, const T* sig, const T* win, T* frames, hipStream_t st);
 template <typename T>
-int launch_stft_transpose(const cplx<T>* F, cplx<T>* Z, T* bits, int64_t C, int64_t nseg, int64_t nf, T scale, T eps,
-                          hipStream_t st);
+int launch_hipfft_transpose(const StftRequest& rq, const cplx<T>* F, cplx<T>* Z, T* R, hipStream_t st);
+template <typename T>
+int launch_welch_mean(const StftRequest& rq, const cplx<T>* F, T* pxx, hipStream_t st);
 
 template <typename T>
 int launch_power_marginals(const T* P, int64_t C, int64_t B, int64_t n, T* power_time, double* part_band,

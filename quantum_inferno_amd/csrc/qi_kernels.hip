@@ -1,5 +1,5 @@
 // Hand-written gfx950 kernels around the FFT passes: packing, Gabor bank construction,
-// spectrum multiply, Stockwell shift x Gaussian, crop / power / entropy epilogue, STFT framing,
+// spectrum multiply, Stockwell shift x Gaussian, crop / power / entropy epilogue,
 // tfr_info reductions.  Wave = 64 lanes everywhere.
 #include <map>
 #include <mutex>
@@ -166,86 +166,6 @@ __global__ void __launch_bounds__(256) k_finalize(const double* __restrict__ par
 }
 
 // ------------------------------------------------------------------------------------------------
-// STFT framing: zero-extended segment, mean removal, window (scipy.signal._spectral_helper with
-// boundary='zeros', padded=True, detrend='constant').  One workgroup per (segment, channel).
-template <typename T>
-__global__ void __launch_bounds__(256) k_stft_frames(const T* __restrict__ sig, const T* __restrict__ win,
-                                                     T* __restrict__ frames, int64_t n, int64_t stride, int64_t seg,
-                                                     int64_t hop, int64_t nfft, int64_t nseg, int64_t lead) {
-  __shared__ double s[256 / kWave];
-  __shared__ double s_mean;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  const int64_t m = blockIdx.x, c = blockIdx.y;
-  const int64_t base = m * hop - lead;  // lead = seg/2 zero-extended samples (stft), 0 (welch), a range's signed origin
-  const T* x = sig + c * stride;  // rows of `stride` samples, the first n of them the record's
-  double acc = 0.0;
-  for (int64_t i = tid; i < seg; i += 256) {
-    int64_t k = base + i;
-    if (k >= 0 && k < n) acc += (double)x[k];
-  }
-  acc = wave_sum(acc);
-  if (lane == 0) s[wv] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int w = 0; w < 256 / kWave; ++w) t += s[w];
-    s_mean = t / (double)seg;
-  }
-  __syncthreads();
-  const T mean = (T)s_mean;
-  T* f = frames + (c * nseg + m) * nfft;
-  for (int64_t i = tid; i < nfft; i += 256) {
-    T v = T(0);
-    if (i < seg) {
-      int64_t k = base + i;
-      T xv = (k >= 0 && k < n) ? x[k] : T(0);
-      v = (xv - mean) * win[i];
-    }
-    f[i] = v;
-  }
-}
-
-// F [C*nseg][nf] -> Z [C][nf][nseg] (frequency x time as the reference returns it), scaled; bits optional.
-template <typename T>
-__global__ void k_stft_transpose(const cplx<T>* __restrict__ F, cplx<T>* __restrict__ Z, T* __restrict__ bits,
-                                 int64_t nseg, int64_t nf, T scale, T eps) {
-  __shared__ cplx<T> tile[32][33];
-  const int64_t c = blockIdx.z;
-  const int64_t f0 = (int64_t)blockIdx.x * 32, m0 = (int64_t)blockIdx.y * 32;
-  for (int r = threadIdx.y; r < 32; r += blockDim.y) {
-    int64_t m = m0 + r, f = f0 + threadIdx.x;
-    if (m < nseg && f < nf) tile[r][threadIdx.x] = F[(c * nseg + m) * nf + f];
-  }
-  __syncthreads();
-  for (int r = threadIdx.y; r < 32; r += blockDim.y) {
-    int64_t f = f0 + r, m = m0 + threadIdx.x;
-    if (m < nseg && f < nf) {
-      cplx<T> z = tile[threadIdx.x][r];
-      z.x *= scale;
-      z.y *= scale;
-      Z[(c * nf + f) * nseg + m] = z;
-      if (bits) bits[(c * nf + f) * nseg + m] = log2_t(sqrt_t(z.x * z.x + z.y * z.y) + eps);
-    }
-  }
-}
-
-// Welch: Pxx[c][f] = w_f * scale^2 * mean over segments of |F[c][m][f]|^2, w_f = 2 except at DC and (even nfft) Nyquist
-// (scipy.signal.welch, scaling="spectrum", average="mean", one-sided; call site styx_fft.py:253-266).
-template <typename T>
-__global__ void k_welch_mean(const cplx<T>* __restrict__ F, T* __restrict__ pxx, int64_t nseg, int64_t nf, int64_t nfft,
-                             T scale2) {
-  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
-  if (f >= nf) return;
-  double acc = 0.0;
-  for (int64_t m = 0; m < nseg; ++m) {
-    const cplx<T> z = F[(c * nseg + m) * nf + f];
-    acc += (double)(z.x * z.x + z.y * z.y);
-  }
-  const bool paired = f > 0 && !(nfft % 2 == 0 && f == nf - 1);
-  pxx[c * nf + f] = (T)(acc / (double)nseg) * scale2 * (paired ? T(2) : T(1));
-}
-
-// ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void k_log2_offset(const T* __restrict__ in, T* __restrict__ out, int64_t count, T eps,
                               const double* __restrict__ ref) {
@@ -361,33 +281,6 @@ int launch_finalize(const double* part_band, const double* part_stat, double* po
 }
 
 template <typename T>
-int launch_stft_frames(const T* sig, const T* win, T* frames, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                       int64_t nfft, int64_t nseg, int64_t lead, hipStream_t st, int64_t stride) {
-  dim3 g((unsigned)nseg, (unsigned)C);
-  k_stft_frames<T><<<g, 256, 0, st>>>(sig, win, frames, n, stride < 0 ? n : stride, seg, hop, nfft, nseg, lead);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
-}
-
-template <typename T>
-int launch_stft_transpose(const cplx<T>* F, cplx<T>* Z, T* bits, int64_t C, int64_t nseg, int64_t nf, T scale, T eps,
-                          hipStream_t st) {
-  dim3 g((unsigned)ceil_div(nf, 32), (unsigned)ceil_div(nseg, 32), (unsigned)C);
-  k_stft_transpose<T><<<g, dim3(32, 8), 0, st>>>(F, Z, bits, nseg, nf, scale, eps);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
-}
-
-template <typename T>
-int launch_welch_mean(const cplx<T>* F, T* pxx, int64_t C, int64_t nseg, int64_t nf, int64_t nfft, T scale2,
-                      hipStream_t st) {
-  dim3 g((unsigned)ceil_div(nf, 256), (unsigned)C);
-  k_welch_mean<T><<<g, 256, 0, st>>>(F, pxx, nseg, nf, nfft, scale2);
-  QI_LAUNCH_CHECK();
-  return QI_OK;
-}
-
-template <typename T>
 int launch_power_marginals(const T* P, int64_t C, int64_t B, int64_t n, T* power_time, double* part_band,
                            double* part_stat, hipStream_t st) {
   EpiArgs<T> a{};
@@ -493,11 +386,6 @@ int launch_shannon(const T* P, const T* mult, int mode, int64_t C, int64_t B, in
   template int launch_stx_window<T>(const cplx<T>*, cplx<T>*, int64_t, int64_t, int64_t, const int64_t*,           \
                                     const double*, hipStream_t);                                                   \
   template int launch_epilogue<T>(const EpiArgs<T>&, hipStream_t);                                                 \
-  template int launch_stft_frames<T>(const T*, const T*, T*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, \
-                                     int64_t, hipStream_t, int64_t);                                               \
-  template int launch_welch_mean<T>(const cplx<T>*, T*, int64_t, int64_t, int64_t, int64_t, T, hipStream_t);       \
-  template int launch_stft_transpose<T>(const cplx<T>*, cplx<T>*, T*, int64_t, int64_t, int64_t, T, T,             \
-                                        hipStream_t);                                                              \
   template int launch_power_marginals<T>(const T*, int64_t, int64_t, int64_t, T*, double*, double*, hipStream_t);  \
   template int launch_log2_offset<T>(const T*, T*, int64_t, int64_t, T, const double*, hipStream_t);               \
   template int launch_shannon<T>(const T*, const T*, int, int64_t, int64_t, int64_t, double, T*, T*, T*, T*,       \

@@ -49,7 +49,7 @@ __device__ __forceinline__ cplx<T> csub(cplx<T> a, cplx<T> b) {
   return mk<T>(a.x - b.x, a.y - b.y);
 }
 
-// sample k of the record extended past its ends (np.pad: constant 0 / edge / reflect even / odd; qi_stft_sliding.hip)
+// sample k of the record extended past its ends (np.pad: constant 0 / edge / reflect even / odd; qi_stft_hipfft.hip)
 template <typename T>
 __device__ __forceinline__ T stft_sample(const T* __restrict__ x, int64_t n, int64_t k, int mode) {
   if (k >= 0 && k < n) return x[k];
@@ -970,21 +970,19 @@ template int launch_stft_fused<double>(const StftRequest&, const double*, const 
 // Welch power spectrum on the fused kernel: partial sums per segment group in `part` ([C][groups][nfft / 2 + 1] doubles),
 // then the mean over the segments with scipy's one-sided "spectrum" weights
 template <typename T>
-int launch_welch_fused(const T* sig, const T* win, T* pxx, double* part, int64_t C, int64_t n, int64_t seg, int64_t hop,
-                       int64_t nfft, int64_t nseg, double scale2, hipStream_t st) {
-  StftRequest rq{C, n, seg, hop, nfft, nseg, 0};
-  rq.welch_part = part;
-  QI_TRY(launch_stft_fused<T>(rq, sig, win, nullptr, nullptr, st));
-  const int nf = (int)(nfft / 2 + 1);
-  dim3 g((unsigned)ceil_div(nf, 256), (unsigned)C);
-  k_welch_reduce<T><<<g, 256, 0, st>>>(part, pxx, (int)StftShape(nfft, sizeof(T) == 8).groups(nseg), nseg, nf, (T)scale2);
+int launch_welch_fused(const StftRequest& rq, const T* sig, const T* win, T* pxx, double* part, hipStream_t st) {
+  StftRequest w = rq;
+  w.welch_part = part;
+  QI_TRY(launch_stft_fused<T>(w, sig, win, nullptr, nullptr, st));
+  const int nf = (int)(rq.nfft / 2 + 1);
+  dim3 g((unsigned)ceil_div(nf, 256), (unsigned)rq.C);
+  k_welch_reduce<T><<<g, 256, 0, st>>>(part, pxx, (int)StftShape(rq.nfft, sizeof(T) == 8).groups(rq.nseg), rq.nseg, nf,
+                                       (T)(rq.scale * rq.scale));
   QI_LAUNCH_CHECK();
   return QI_OK;
 }
-template int launch_welch_fused<float>(const float*, const float*, float*, double*, int64_t, int64_t, int64_t, int64_t, int64_t,
-                                       int64_t, double, hipStream_t);
-template int launch_welch_fused<double>(const double*, const double*, double*, double*, int64_t, int64_t, int64_t, int64_t,
-                                        int64_t, int64_t, double, hipStream_t);
+template int launch_welch_fused<float>(const StftRequest&, const float*, const float*, float*, double*, hipStream_t);
+template int launch_welch_fused<double>(const StftRequest&, const double*, const double*, double*, double*, hipStream_t);
 
 // the fused inverse: supported for the forward kernel's geometries with hop <= seg when a workgroup's LDS holds at least one
 // owned hop beside the halo slices

@@ -122,6 +122,21 @@ class TfrResult:
         return b - b.max(dim=1, keepdim=True).values
 
 
+def out_descriptor(res, eps):
+    """The C-ABI descriptor of the outputs `res` (a TfrResult) holds buffers for, at its power_scale."""
+    return _lib.TfrOut(coef=_lib.ptr(res.coef), bits=_lib.ptr(res.bits), power_band=_lib.ptr(res.power_band),
+                       power_time=_lib.ptr(res.power_time), stats=_lib.ptr(res.stats), power_scale=float(res.power_scale),
+                       eps=float(eps))
+
+
+def check_pooled_methods(methods, name="pooled_methods"):
+    """-> the tuple of the pooling methods the device folds beside a transform, or the ValueError of another choice."""
+    methods = tuple(methods)
+    if not methods or any(m not in ("average", "max") for m in methods) or len(set(methods)) != len(methods):
+        raise ValueError(f'{name} must be a subset of ("average", "max"), got {methods!r}')
+    return methods
+
+
 def reduced_views(n_ch, n_b, n, rdtype, device, reductions=True, reduced_out=None):
     """(reduced, power_band [C, B] f64, power_time [C, n], stats [C, 4] f64) of one transform: views into ONE float64 buffer
     for the whole reduced product (the message of dist.gather_reduced; layout dist.reduced_slots), new or the caller's
@@ -308,16 +323,7 @@ class TfrPlan:
             if reductions:
                 res.reduced, res.power_band, res.power_time, res.stats = reduced_views(
                     n_ch, n_b, self.n, self.rdtype, dev, reductions, reduced_out)
-        desc = _lib.TfrOut(
-            coef=_lib.ptr(res.coef),
-            bits=_lib.ptr(res.bits),
-            power_band=_lib.ptr(res.power_band),
-            power_time=_lib.ptr(res.power_time),
-            stats=_lib.ptr(res.stats),
-            power_scale=float(power_scale),
-            eps=float(eps),
-        )
-        return res, desc
+        return res, out_descriptor(res, eps)
 
     def _run(self, which, sig, coef, bits, reductions, power_scale, eps, out=None, reduced_out=None):
         sig = self._signal(sig)
@@ -414,9 +420,7 @@ class TfrPlan:
         staging tensor as pooled(); per tile one transform into the stage and ONE kernel (qi_pool_strip) that reads the range
         once for every output; the statistics are folded over the bands on the device (qi_pool_strip_stats).  Nothing is
         synchronised on the host."""
-        methods = tuple(methods)
-        if not methods or any(m not in ("average", "max") for m in methods) or len(set(methods)) != len(methods):
-            raise ValueError(f'methods must be a subset of ("average", "max"), got {methods!r}')
+        methods = check_pooled_methods(methods, "methods")
         factor, first, windows = int(factor), int(first), int(windows)
         if factor < 2:
             raise ValueError(f"pooling factor {factor}: 2 or more")

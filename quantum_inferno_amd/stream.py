@@ -187,13 +187,6 @@ class _Staging:
         self.used[j] = True
 
 
-def _merge_sums(mine, other):
-    """power_band and stats of two assemblers: sums added, maxima compared"""
-    mine.power_band += other.power_band
-    mine.stats[:, 1:3] += other.stats[:, 1:3]
-    mine.stats[:, 0] = torch.maximum(mine.stats[:, 0], other.stats[:, 0])
-
-
 def _merge_panels(mine, other):
     """What `other` filled where `mine` holds NaN (nobody added there), in place"""
     for m in mine:
@@ -201,7 +194,71 @@ def _merge_panels(mine, other):
         mine[m][gap] = other[m].to(mine[m].device)[gap]
 
 
-class PooledRecord:
+def _host_records(host_records):
+    """The records of a stream as [channels, n_total]: an ndarray / memmap, or any object with a 2-D `shape` that answers
+    [channel slice, sample slice] with an array (a rank of the 24 h job materialises only the records it owns)."""
+    sig = host_records if hasattr(host_records, "shape") and hasattr(host_records, "__getitem__") else np.asarray(host_records)
+    return sig[None, :] if len(sig.shape) == 1 else sig
+
+
+def _pump(staging, items, host_rows, launch, device):
+    """The double-buffered walk of `items` through `staging`: host_rows(item) are the host rows an item carries,
+    launch(item, device buffer) queues its work on the current stream of `device` once the rows are there.  Yields (position,
+    item, what launch returned) after the NEXT item has been staged: its host gather (a 134 MB memcpy at 16 float64 records of
+    2^20 samples: milliseconds of host time) and its copy to the device run after this item's launches are queued, so they
+    overlap its transforms even when the consumer waits for every item before asking for the next."""
+    if not items:
+        return
+    compute = torch.cuda.current_stream(device) if staging.gpu else None
+    staging.stage(0, host_rows(items[0]))
+    for k, item in enumerate(items):
+        j = k & 1
+        if staging.gpu:
+            compute.wait_event(staging.copied[j])
+        out = launch(item, staging.dev[j])
+        if staging.gpu:
+            staging.consumed[j].record(compute)
+        if k + 1 < len(items):
+            staging.stage(j ^ 1, host_rows(items[k + 1]))
+        yield k, item, out
+
+
+class _RecordSums:
+    """What the assemblers of a streamed record set share: power_band [n_channels, n_bands] and stats [n_channels, 4] float64
+    added up over the items (sums added, maxima compared), the pooled strips side by side in `panel[method]` [n_channels,
+    n_bands, n_windows] (NaN where nothing was added), and the frequency_hz / power_scale the items carry."""
+
+    def __init__(self, n_channels, n_bands, n_windows, methods, dtype, device):
+        self.methods = tuple(methods)
+        self.panel = {m: torch.full((n_channels, n_bands, n_windows), float("nan"), dtype=dtype, device=device) for m in self.methods}
+        self.power_band = torch.zeros((n_channels, n_bands), dtype=torch.float64, device=device)
+        self.stats = torch.zeros((n_channels, 4), dtype=torch.float64, device=device)
+        self.frequency_hz = None
+        self.power_scale = 1.0
+
+    def _add(self, item, res):
+        """The strips and sums of one item's result `res`; -> the item's channel slice"""
+        ch = slice(item.first_channel, item.first_channel + item.channels)
+        for m in self.methods:
+            self.panel[m][ch, :, item.window0 : item.window0 + item.windows] = res.pooled[m]
+        self.power_band[ch] += res.power_band
+        self.stats[ch, 1:3] += res.stats[:, 1:3]
+        self.stats[ch, 0] = torch.maximum(self.stats[ch, 0], res.stats[:, 0])
+        self.frequency_hz, self.power_scale = res.frequency_hz, res.power_scale
+        return ch
+
+    def _merge(self, other):
+        """Another assembler of the same record set (the caller has compared the shapes) into this one"""
+        _merge_panels(self.panel, other.panel)
+        self.power_band += other.power_band
+        self.stats[:, 1:3] += other.stats[:, 1:3]
+        self.stats[:, 0] = torch.maximum(self.stats[:, 0], other.stats[:, 0])
+        if self.frequency_hz is None:
+            self.frequency_hz, self.power_scale = other.frequency_hz, other.power_scale
+        return self
+
+
+class PooledRecord(_RecordSums):
     """Assembles the items of a `StreamPipeline(pooled=factor)` run into the pooled panel and the reductions of the whole
     record set: `add(item, "cwt")` puts the item's strips at [first_channel : first_channel + channels, :, window0 :
     window0 + windows], adds its band powers, sum P and sum P log2 P, and keeps the larger maximum.  `panel[method]` is
@@ -215,33 +272,18 @@ class PooledRecord:
     every record's items came from one rank)."""
 
     def __init__(self, n_channels, n_bands, n_windows, methods=("average",), dtype=torch.float32, device=None):
-        self.methods = tuple(methods)
-        self.panel = {m: torch.full((n_channels, n_bands, n_windows), float("nan"), dtype=dtype, device=device) for m in self.methods}
-        self.power_band = torch.zeros((n_channels, n_bands), dtype=torch.float64, device=device)
-        self.stats = torch.zeros((n_channels, 4), dtype=torch.float64, device=device)
-        self.frequency_hz = None
-        self.power_scale = 1.0
+        super().__init__(n_channels, n_bands, n_windows, methods, dtype, device)
 
     def add(self, item: "StreamItem", which: str = "cwt"):
         res = {"cwt": item.cwt, "stx": item.stx}[which]
         if res is None or res.pooled is None or item.windows is None:
             raise ValueError(f"item {item.index} carries no pooled {which} strips (StreamPipeline(pooled=factor))")
-        ch = slice(item.first_channel, item.first_channel + item.channels)
-        for m in self.methods:
-            self.panel[m][ch, :, item.window0 : item.window0 + item.windows] = res.pooled[m]
-        self.power_band[ch] += res.power_band
-        self.stats[ch, 1:3] += res.stats[:, 1:3]
-        self.stats[ch, 0] = torch.maximum(self.stats[ch, 0], res.stats[:, 0])
-        self.frequency_hz, self.power_scale = res.frequency_hz, res.power_scale
+        self._add(item, res)
 
     def merge(self, other: "PooledRecord"):
         if self.methods != other.methods or any(self.panel[m].shape != other.panel[m].shape for m in self.methods):
             raise ValueError("the assemblers are not of one record set: methods or panel shapes differ")
-        _merge_panels(self.panel, other.panel)
-        _merge_sums(self, other)
-        if self.frequency_hz is None:
-            self.frequency_hz, self.power_scale = other.frequency_hz, other.power_scale
-        return self
+        return self._merge(other)
 
     def result(self) -> engine.TfrResult:
         return engine.TfrResult(frequency_hz=self.frequency_hz, power_band=self.power_band, stats=self.stats,
@@ -270,11 +312,7 @@ class StreamPipeline:
                  power_scale: float = 1.0, keep_time: bool = True, pooled: Optional[int] = None, pooled_methods=("average",)):
         self.plan, self.hop, self.block = plan, int(hop), int(block)
         self.pooled, self.pooled_methods = (None if pooled is None else int(pooled)), tuple(pooled_methods)
-        # an ndarray / memmap, or any object with a 2-D `shape` that answers [channel slice, sample slice] with an array
-        # (a rank of the 24 h job materialises only the records it owns)
-        self.sig = host_records if hasattr(host_records, "shape") and hasattr(host_records, "__getitem__") else np.asarray(host_records)
-        if len(self.sig.shape) == 1:
-            self.sig = self.sig[None, :]
+        self.sig = _host_records(host_records)
         self.transforms = tuple(transforms)
         for t in self.transforms:
             if t not in ("cwt", "stx"):
@@ -284,64 +322,46 @@ class StreamPipeline:
         self._reductions = True if keep_time else "band"
         self.items = work_items(self.sig.shape[0], self.block, self.sig.shape[1], plan.n, self.hop)
         if self.pooled is not None:
-            if not self.pooled_methods or any(m not in ("average", "max") for m in self.pooled_methods):
-                raise ValueError(f'pooled_methods must be a subset of ("average", "max"), got {self.pooled_methods!r}')
+            engine.check_pooled_methods(self.pooled_methods)
             self._starts, self._edges = owned_windows(self.sig.shape[1], plan.n, self.hop, self.pooled)
         # (a plan on the CPU exists only as the stand-in of bench.py --stub: the item walk without streams or pinning)
         self._staging = _Staging(self.block, plan.n, plan.rdtype, plan.device)
-        self._gpu, self._dev = self._staging.gpu, self._staging.dev
-        self._copied, self._consumed = self._staging.copied, self._staging.consumed
         self._out = {}  # (transform, channels) -> result buffers reused item after item
 
-    def _stage(self, j, item):
-        """Host gather of one item into pinned buffer j and its asynchronous copy to device buffer j."""
-        c0, cb, _, s = item
-        self._staging.stage(j, self.sig[c0 : c0 + cb, s : s + self.plan.n])
+    def _launch(self, item, dev):
+        """The transforms of one item on its rows in device buffer `dev`: -> ({transform: result}, window0, windows)"""
+        _, cb, chunk, s = item
+        x = dev[:cb]
+        res = {}
+        if self.pooled is not None:
+            e0, e1 = int(self._edges[chunk]), int(self._edges[chunk + 1])
+            w0, nw = e0 // self.pooled, (e1 - e0) // self.pooled
+            for t in self.transforms:
+                which = engine._lib.QI_BANK_STYX if t == "cwt" else engine._lib.QI_TABLE_STX
+                strips, band, stats = self.plan.pooled_strip(which, x, self.pooled, e0 - s, nw, self.pooled_methods, self.power_scale)
+                res[t] = engine.TfrResult(frequency_hz=self.plan.freq[which], power_band=band, stats=stats,
+                                          power_scale=self.power_scale, pooled=strips)
+            return res, w0, nw
+        if self.transforms == ("cwt", "stx"):
+            key = ("both", cb)
+            self._out[key] = self.plan.cwt_stx(x, coef=False, reductions=self._reductions, power_scale=self.power_scale,
+                                               out=self._out.get(key))
+            res["cwt"], res["stx"] = self._out[key]
+        else:
+            for t in self.transforms:
+                key = (t, cb)
+                fn = self.plan.cwt if t == "cwt" else self.plan.stx
+                self._out[key] = fn(x, coef=False, reductions=self._reductions, power_scale=self.power_scale, out=self._out.get(key))
+                res[t] = self._out[key]
+        return res, None, None
 
     def run(self, rank: int = 0, world: int = 1, first_item: int = 0) -> Iterator[StreamItem]:
         mine = rank_items(self.items, rank, world)[first_item:]
-        if not mine:
-            return
-        compute = torch.cuda.current_stream(self.plan.device) if self._gpu else None
-        self._stage(0, mine[0])
-        for k, item in enumerate(mine):
-            j = k & 1
-            c0, cb, chunk, s = item
-            if self._gpu:
-                compute.wait_event(self._copied[j])
-            x = self._dev[j][:cb]
-            res = {}
-            if self.pooled is not None:
-                e0, e1 = int(self._edges[chunk]), int(self._edges[chunk + 1])
-                w0, nw = e0 // self.pooled, (e1 - e0) // self.pooled
-                for t in self.transforms:
-                    strips, band, stats = self.plan.pooled_strip(engine._lib.QI_BANK_STYX if t == "cwt" else engine._lib.QI_TABLE_STX,
-                                                                 x, self.pooled, e0 - s, nw, self.pooled_methods, self.power_scale)
-                    res[t] = engine.TfrResult(frequency_hz=self.plan.freq[engine._lib.QI_BANK_STYX if t == "cwt" else engine._lib.QI_TABLE_STX],
-                                              power_band=band, stats=stats, power_scale=self.power_scale, pooled=strips)
-            elif self.transforms == ("cwt", "stx"):
-                key = ("both", cb)
-                self._out[key] = self.plan.cwt_stx(x, coef=False, reductions=self._reductions, power_scale=self.power_scale,
-                                                   out=self._out.get(key))
-                res["cwt"], res["stx"] = self._out[key]
-            else:
-                for t in self.transforms:
-                    key = (t, cb)
-                    fn = self.plan.cwt if t == "cwt" else self.plan.stx
-                    self._out[key] = fn(x, coef=False, reductions=self._reductions, power_scale=self.power_scale, out=self._out.get(key))
-                    res[t] = self._out[key]
-            if self._gpu:
-                self._consumed[j].record(compute)
-            # the next item's host gather (a 134 MB memcpy at 16 float64 records: milliseconds of host time) and its copy to
-            # the device run AFTER this item's launches are queued: they overlap its transforms even when the consumer
-            # waits for every item before asking for the next (round 3 staged first: the GPU idled through the gather)
-            if k + 1 < len(mine):
-                self._stage(j ^ 1, mine[k + 1])
-            if self.pooled is not None:  # (pooled_strip's outputs are new tensors: the item owns them)
-                yield StreamItem(first_item + k, c0, cb, chunk, s, res.get("cwt"), res.get("stx"), w0, nw)
-                continue
-            kept = {t: self._keep(r) for t, r in res.items()}
-            yield StreamItem(first_item + k, c0, cb, chunk, s, kept.get("cwt"), kept.get("stx"))
+        rows = lambda item: self.sig[item[0] : item[0] + item[1], item[3] : item[3] + self.plan.n]
+        for k, (c0, cb, chunk, s), (res, w0, nw) in _pump(self._staging, mine, rows, self._launch, self.plan.device):
+            if self.pooled is None:  # (pooled_strip's outputs are new tensors: the item owns them; these are the plan's buffers)
+                res = {t: self._keep(r) for t, r in res.items()}
+            yield StreamItem(first_item + k, c0, cb, chunk, s, res.get("cwt"), res.get("stx"), w0, nw)
 
     def _keep(self, res):
         if self.keep_time:
@@ -406,17 +426,14 @@ class StftStream:
         self.plan, self.block, self.per = stft_plan, int(block), int(segments_per_item)
         self.pooled, self.pooled_methods = (None if pooled is None else int(pooled)), tuple(pooled_methods)
         self.keep_time, self.power_scale = keep_time, power_scale
-        self.sig = host_records if hasattr(host_records, "shape") and hasattr(host_records, "__getitem__") else np.asarray(host_records)
-        if len(self.sig.shape) == 1:
-            self.sig = self.sig[None, :]
+        self.sig = _host_records(host_records)
         if self.sig.shape[1] != stft_plan.n_total:
             raise ValueError(f"records of {self.sig.shape[1]} samples, the plan is for {stft_plan.n_total}")
         if self.block < 1:
             raise ValueError(f"block {block}: 1 or more")
         self.ranges = segment_items(stft_plan.n_total, stft_plan.seg, stft_plan.hop, self.per)
         if self.pooled is not None:
-            if not self.pooled_methods or any(m not in ("average", "max") for m in self.pooled_methods):
-                raise ValueError(f'pooled_methods must be a subset of ("average", "max"), got {self.pooled_methods!r}')
+            engine.check_pooled_methods(self.pooled_methods)
             if self.pooled < 2:
                 raise ValueError(f"pooling factor {self.pooled}: 2 or more")
             if self.per % self.pooled:
@@ -428,37 +445,22 @@ class StftStream:
         self._width = max(1, max(r[3] for r in self.ranges))
         self._staging = None  # (the pinned and device buffers are made by the first run)
 
-    def _stage(self, j, item):
-        c0, cb, _, _, s0, n_avail = item
-        self._staging.stage(j, self.sig[c0 : c0 + cb, s0 : s0 + n_avail])
+    def _launch(self, item, dev):
+        _, cb, first, count, s0, n_avail = item
+        return self.plan.segment_range(dev[:cb], first, count, s0, reductions=True if self.keep_time else "band", pooled=self.pooled,
+                                       pooled_methods=self.pooled_methods, power_scale=self.power_scale, n_avail=n_avail)
 
     def run(self, rank: int = 0, world: int = 1, first_item: int = 0) -> Iterator[StftItem]:
         mine = rank_items(self.items, rank, world)[first_item:]
-        if not mine:
-            return
-        if self._staging is None:
+        if mine and self._staging is None:
             self._staging = _Staging(self.block, self._width, self.plan.rdtype, self.device)
-        st = self._staging
-        compute = torch.cuda.current_stream(self.device) if st.gpu else None
-        self._stage(0, mine[0])
-        for k, item in enumerate(mine):
-            j = k & 1
-            c0, cb, first, count, s0, n_avail = item
-            if st.gpu:
-                compute.wait_event(st.copied[j])
-            res = self.plan.segment_range(st.dev[j][:cb], first, count, s0, reductions=True if self.keep_time else "band",
-                                          pooled=self.pooled, pooled_methods=self.pooled_methods, power_scale=self.power_scale,
-                                          n_avail=n_avail)
-            if st.gpu:
-                st.consumed[j].record(compute)
-            # (the next item's host gather and copy run after this item's launches are queued, as in StreamPipeline)
-            if k + 1 < len(mine):
-                self._stage(j ^ 1, mine[k + 1])
+        rows = lambda item: self.sig[item[0] : item[0] + item[1], item[4] : item[4] + item[5]]
+        for k, (c0, cb, first, count, s0, n_avail), res in _pump(self._staging, mine, rows, self._launch, self.device):
             w0, nw = (None, None) if self.pooled is None else (first // self.pooled, count // self.pooled)
             yield StftItem(first_item + k, c0, cb, first, count, s0, n_avail, res, w0, nw)  # (segment_range's outputs are new tensors)
 
 
-class StftRecord:
+class StftRecord(_RecordSums):
     """Assembles the items of an `StftStream` run into the products of the whole record set: `add(item)` puts the item's
     pooled strips at [channels, :, window0 : window0 + windows] and its per-time power at [channels, first_segment :
     first_segment + segments], adds its band powers, sum P and sum P log2 P, and keeps the larger maximum (PooledRecord's
@@ -468,33 +470,22 @@ class StftRecord:
 
     def __init__(self, n_channels, n_f, n_segments, pooled=None, methods=("average",), keep_time=True, dtype=torch.float32,
                  device=None):
-        self.pooled, self.methods = (None if pooled is None else int(pooled)), (tuple(methods) if pooled is not None else ())
-        n_windows = 0 if pooled is None else n_segments // self.pooled
-        self.panel = {m: torch.full((n_channels, n_f, n_windows), float("nan"), dtype=dtype, device=device) for m in self.methods}
+        self.pooled = None if pooled is None else int(pooled)
+        super().__init__(n_channels, n_f, 0 if pooled is None else n_segments // self.pooled, methods if pooled is not None else (),
+                         dtype, device)
         self.power_time = torch.full((n_channels, n_segments), float("nan"), dtype=dtype, device=device) if keep_time else None
-        self.power_band = torch.zeros((n_channels, n_f), dtype=torch.float64, device=device)
-        self.stats = torch.zeros((n_channels, 4), dtype=torch.float64, device=device)
-        self.frequency_hz = None
-        self.power_scale = 1.0
 
     def add(self, item: "StftItem"):
         res = item.stft
         if res is None or res.power_band is None:
             raise ValueError(f"item {item.index} carries no reductions")
-        ch = slice(item.first_channel, item.first_channel + item.channels)
-        if self.methods:
-            if res.pooled is None or item.windows is None:
-                raise ValueError(f"item {item.index} carries no pooled strips (StftStream(pooled=factor))")
-            for m in self.methods:
-                self.panel[m][ch, :, item.window0 : item.window0 + item.windows] = res.pooled[m]
+        if self.methods and (res.pooled is None or item.windows is None):
+            raise ValueError(f"item {item.index} carries no pooled strips (StftStream(pooled=factor))")
+        if self.power_time is not None and res.power_time is None:
+            raise ValueError(f"item {item.index} carries no per-time power (StftStream(keep_time=True))")
+        ch = self._add(item, res)
         if self.power_time is not None:
-            if res.power_time is None:
-                raise ValueError(f"item {item.index} carries no per-time power (StftStream(keep_time=True))")
             self.power_time[ch, item.first_segment : item.first_segment + item.segments] = res.power_time
-        self.power_band[ch] += res.power_band
-        self.stats[ch, 1:3] += res.stats[:, 1:3]
-        self.stats[ch, 0] = torch.maximum(self.stats[ch, 0], res.stats[:, 0])
-        self.frequency_hz, self.power_scale = res.frequency_hz, res.power_scale
 
     def merge(self, other: "StftRecord"):
         if (self.methods != other.methods or self.power_band.shape != other.power_band.shape
@@ -502,13 +493,9 @@ class StftRecord:
                 or (self.power_time is None) != (other.power_time is None)
                 or (self.power_time is not None and self.power_time.shape != other.power_time.shape)):
             raise ValueError("the assemblers are not of one record set: methods or shapes differ")
-        _merge_panels(self.panel, other.panel)
         if self.power_time is not None:
             _merge_panels({"t": self.power_time}, {"t": other.power_time})
-        _merge_sums(self, other)
-        if self.frequency_hz is None:
-            self.frequency_hz, self.power_scale = other.frequency_hz, other.power_scale
-        return self
+        return self._merge(other)
 
     def result(self) -> engine.TfrResult:
         return engine.TfrResult(frequency_hz=self.frequency_hz, power_band=self.power_band, power_time=self.power_time,

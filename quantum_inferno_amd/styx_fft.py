@@ -4,7 +4,7 @@ Short-time Fourier transform on the GPU behind the reference's signatures
 detrend="constant", return_onesided=True); here the zero-extended segments are mean-removed and
 windowed by a HIP kernel, transformed as one batched real FFT and written frequency x time.
 """
-from typing import Tuple
+from dataclasses import dataclass
 
 import ctypes as C
 import numpy as np
@@ -92,20 +92,81 @@ def butter_lowpass(sig_wf, frequency_sample_rate_hz: float, frequency_cut_high_h
     return _butter_filtfilt(sig_wf, filter_order, [edge_high], "lowpass", tukey_alpha)
 
 
-def _stft_out(lib, sig, window, seg, hop, nfft, scale, res, scratch=None):
-    """qi_stft_out on a [C, n] device tensor into the buffers of `res` (a TfrResult: any of coef, bits, the reductions);
-    `scratch`: a kept buffer of qi_stft_out_scratch_bytes for this request, or None."""
+def _frame_count(n, seg, hop):
+    """Segments of scipy.signal.stft(boundary="zeros", padded=True), as qi_stft_segments counts them: host arithmetic."""
+    if n <= 0 or seg <= 0 or not 0 < hop <= seg:
+        return 0
+    length = n + 2 * (seg // 2)
+    length += (-(length - seg) % hop) % seg
+    return (length - seg) // hop + 1
+
+
+def _run_window(window64, rdtype):
+    """The window as a run in `rdtype` holds it: SciPy rounds it to the output precision before using and summing it
+    (_spectral_helper)."""
+    win = np.asarray(window64, dtype=np.float64)
+    return np.ascontiguousarray(win if rdtype == torch.float64 else win.astype(np.float32))
+
+
+def _order_segment(n, fs, band_order_nth, center_frequency_hz=None, octaves_below_center=4):
+    """stft_from_sig's segment for a record of n samples, or its refusal."""
+    seg = stft_segment_points(fs, band_order_nth, center_frequency_hz, octaves_below_center)
+    if n < seg:
+        raise ValueError(f"Signal length: {n} is less than time_fft_nd: {seg}")
+    return seg
+
+
+@dataclass(frozen=True, eq=False)
+class StftGeometry:
+    """What scipy.signal.stft(boundary="zeros", padded=True, scaling="spectrum") makes of a record length and a window, once
+    for every caller: host arithmetic, no device and no library.  `window` is the host array in the run's precision, `scale`
+    1 / sum(window) of that array times the caller's factor, `n_seg` the segments, `n_f` = nfft // 2 + 1."""
+
+    seg: int
+    hop: int
+    nfft: int
+    n_seg: int
+    n_f: int
+    scale: float
+    window: np.ndarray
+    time_s: np.ndarray
+    frequency_hz: np.ndarray
+
+    @classmethod
+    def from_window(cls, n, fs, window64, overlap_points, nfft_points, extra_scale=1.0, rdtype=torch.float32):
+        """A float64 `window` [seg] with overlap and transform length as stft_complex_pow2 hands them to SciPy."""
+        n, fs, seg, nfft = int(n), float(fs), len(window64), int(nfft_points)
+        hop = seg - int(overlap_points)
+        if not 0 < hop <= seg:
+            raise ValueError("noverlap must be less than nperseg.")
+        if nfft < seg:
+            raise ValueError("nfft must be greater than or equal to nperseg.")
+        win = _run_window(window64, engine._real_dtype(rdtype))
+        scale = float(np.sqrt(1.0 / np.sum(win.astype(np.float64)) ** 2)) * extra_scale
+        padded = n + 2 * (seg // 2)
+        padded += (-(padded - seg) % hop) % seg
+        time_s = np.arange(seg / 2, padded - seg / 2 + 1, hop) / fs - (seg / 2) / fs
+        return cls(seg, hop, nfft, _frame_count(n, seg, hop), nfft // 2 + 1, float(scale), win, time_s, np.fft.rfftfreq(nfft, 1 / fs))
+
+    @classmethod
+    def from_order(cls, n, fs, band_order_nth, center_frequency_hz=None, octaves_below_center=4, rdtype=torch.float32):
+        """stft_from_sig's: periodic Hann of the order's segment, half overlap, scale 2 sqrt(pi) / segment."""
+        seg = _order_segment(int(n), fs, band_order_nth, center_frequency_hz, octaves_below_center)
+        return cls.from_window(n, fs, tukey_window_periodic(seg, 1.0), seg // 2, seg, 2 * np.sqrt(np.pi) / seg, rdtype)
+
+
+def _stft_out(lib, sig, window, g, res, scratch=None):
+    """qi_stft_out of geometry `g` on a [C, n] device tensor into the buffers of `res` (a TfrResult: any of coef, bits, the
+    reductions); `scratch`: a kept buffer of qi_stft_out_scratch_bytes for this request, or None."""
     n_ch, n = sig.shape
     dev = sig.device
     code = _lib.dtype_code(sig.dtype)
     if scratch is None:
-        scratch, _ = _lib.scratch(lib.qi_stft_out_scratch_bytes, dev, code, n_ch, n, seg, hop, nfft, res.coef is not None,
+        scratch, _ = _lib.scratch(lib.qi_stft_out_scratch_bytes, dev, code, n_ch, n, g.seg, g.hop, g.nfft, res.coef is not None,
                                   res.bits is not None)
-    desc = _lib.TfrOut(coef=_lib.ptr(res.coef), bits=_lib.ptr(res.bits), power_band=_lib.ptr(res.power_band),
-                       power_time=_lib.ptr(res.power_time), stats=_lib.ptr(res.stats), power_scale=float(res.power_scale),
-                       eps=float(get_epsilon()))
-    _lib.call(lib.qi_stft_out, dev, code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(window), seg, hop, nfft, scale, C.byref(desc),
-              _lib.ptr(scratch), scratch.numel())
+    desc = engine.out_descriptor(res, get_epsilon())
+    _lib.call(lib.qi_stft_out, dev, code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(window), g.seg, g.hop, g.nfft, g.scale,
+              C.byref(desc), _lib.ptr(scratch), scratch.numel())
     return res
 
 
@@ -122,43 +183,43 @@ def _stft_result(frequency_hz, n_ch, n_f, n_seg, rdtype, dev, coef, bits, reduct
     return res
 
 
-def _stft_windowed(sig_wf, fs, window64, segment_points, overlap_points, nfft_points, extra_scale=1.0, want_bits=False,
-                   _reduce=None):
-    """_reduce: None, or the options of a reduced product -- dict(coef=True, bits=want_bits, reductions=True,
-    power_scale=1.0) -- and the return value is then (frequency_hz, time_s, TfrResult) with device tensors [C, ...]."""
+def _stft_call(sig_wf, geometry, want_bits=False, _reduce=None):
+    """One transform of `sig_wf`; geometry: (n, rdtype) -> the StftGeometry of such records.  -> (frequency_hz, time_s, z, bits);
+    _reduce: None, or the options of a reduced product -- dict(coef=True, bits=want_bits, reductions=True, power_scale=1.0)
+    -- and the return value is then (frequency_hz, time_s, TfrResult) with device tensors [C, ...]."""
     lib = _lib.require_gpu()
     sig, was_numpy, was_1d = engine.as_signal(sig_wf)
     n_ch, n = sig.shape
-    seg, nfft = int(segment_points), int(nfft_points)
-    hop = seg - int(overlap_points)
-    if not 0 < hop <= seg:
-        raise ValueError("noverlap must be less than nperseg.")
-    if nfft < seg:
-        raise ValueError("nfft must be greater than or equal to nperseg.")
+    g = geometry(n, sig.dtype)
     dev = sig.device
-    f64 = sig.dtype == torch.float64
-    # SciPy rounds the window to the output precision before using and summing it (_spectral_helper)
-    win = window64 if f64 else window64.astype(np.float32)
-    scale = float(np.sqrt(1.0 / np.sum(win.astype(np.float64)) ** 2)) * extra_scale
-    win_d = torch.from_numpy(np.ascontiguousarray(win)).to(dev)
-    n_seg = int(lib.qi_stft_segments(n, seg, hop))
-    n_f = nfft // 2 + 1
-    padded = n + 2 * (seg // 2)
-    padded += (-(padded - seg) % hop) % seg
-    time_s = np.arange(seg / 2, padded - seg / 2 + 1, hop) / float(fs) - (seg / 2) / fs
-    freq_hz = np.fft.rfftfreq(nfft, 1 / fs)
+    win_d = torch.from_numpy(g.window).to(dev)
     if _reduce is not None:
-        res = _stft_result(freq_hz, n_ch, n_f, n_seg, sig.dtype, dev, _reduce.get("coef", True), _reduce.get("bits", want_bits),
-                           _reduce.get("reductions", True), _reduce.get("power_scale", 1.0))
-        return freq_hz, time_s, _stft_out(lib, sig, win_d, seg, hop, nfft, scale, res)
-    cdt = torch.complex128 if f64 else torch.complex64
-    z = torch.empty((n_ch, n_f, n_seg), dtype=cdt, device=dev)
-    bits = torch.empty((n_ch, n_f, n_seg), dtype=sig.dtype, device=dev) if want_bits else None
+        res = _stft_result(g.frequency_hz, n_ch, g.n_f, g.n_seg, sig.dtype, dev, _reduce.get("coef", True),
+                           _reduce.get("bits", want_bits), _reduce.get("reductions", True), _reduce.get("power_scale", 1.0))
+        return g.frequency_hz, g.time_s, _stft_out(lib, sig, win_d, g, res)
+    z = torch.empty((n_ch, g.n_f, g.n_seg), dtype=engine._complex_of(sig.dtype), device=dev)
+    bits = torch.empty((n_ch, g.n_f, g.n_seg), dtype=sig.dtype, device=dev) if want_bits else None
     code = _lib.dtype_code(sig.dtype)
-    scratch, nbytes = _lib.scratch(lib.qi_stft_scratch_bytes, dev, code, n_ch, n, seg, hop, nfft)
-    _lib.call(lib.qi_stft, dev, code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale, _lib.ptr(z),
+    scratch, nbytes = _lib.scratch(lib.qi_stft_scratch_bytes, dev, code, n_ch, n, g.seg, g.hop, g.nfft)
+    _lib.call(lib.qi_stft, dev, code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), g.seg, g.hop, g.nfft, g.scale, _lib.ptr(z),
               _lib.ptr(bits), float(get_epsilon()), _lib.ptr(scratch), nbytes)
-    return freq_hz, time_s, engine.finish(z, was_numpy, was_1d), engine.finish(bits, was_numpy, was_1d)
+    return g.frequency_hz, g.time_s, engine.finish(z, was_numpy, was_1d), engine.finish(bits, was_numpy, was_1d)
+
+
+def _stft_windowed(sig_wf, fs, window64, segment_points, overlap_points, nfft_points, extra_scale=1.0, want_bits=False,
+                   _reduce=None):
+    """_stft_call with the geometry of a float64 window [segment_points]."""
+    if len(window64) != int(segment_points):
+        raise ValueError(f"a window of {len(window64)} points for segments of {int(segment_points)}")
+    return _stft_call(sig_wf, lambda n, rdtype: StftGeometry.from_window(n, fs, window64, overlap_points, nfft_points, extra_scale,
+                                                                         rdtype), want_bits, _reduce)
+
+
+def _stft_from_order(sig_wf, order_args, **options):
+    """_stft_call with stft_from_sig's geometry; order_args: (fs, band_order_nth, center_frequency_hz, octaves_below_center).
+    A record shorter than the segment is refused before the device is asked for."""
+    _order_segment(sig_wf.shape[-1] if hasattr(sig_wf, "shape") else len(sig_wf), *order_args)
+    return _stft_call(sig_wf, lambda n, rdtype: StftGeometry.from_order(n, *order_args, rdtype=rdtype), **options)
 
 
 def _shrunk_segment(sig_wf, segment_points):
@@ -181,30 +242,19 @@ class StftPlan:
     def __init__(self, n, channels, frequency_sample_rate_hz, band_order_nth, dtype=torch.float32, device=None):
         self._lib = _lib.require_gpu()
         self.n, self.channels, self.fs = int(n), int(channels), float(frequency_sample_rate_hz)
-        self.seg = stft_segment_points(self.fs, band_order_nth)
-        if self.n < self.seg:
-            raise ValueError(f"Signal length: {self.n} is less than time_fft_nd: {self.seg}")
-        self.hop, self.nfft = self.seg // 2, self.seg
         self.rdtype = engine._real_dtype(dtype)
+        self._geometry = g = StftGeometry.from_order(self.n, self.fs, band_order_nth, rdtype=self.rdtype)
+        self.seg, self.hop, self.nfft, self.n_seg, self.n_f, self.scale = g.seg, g.hop, g.nfft, g.n_seg, g.n_f, g.scale
+        self.time_s, self.frequency_hz = g.time_s, g.frequency_hz
         self.device = torch.device(device) if device is not None else engine.default_device()
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        f64 = self.rdtype == torch.float64
-        win64 = tukey_window_periodic(self.seg, 1.0)
-        win = win64 if f64 else win64.astype(np.float32)
-        self.scale = float(np.sqrt(1.0 / np.sum(win.astype(np.float64)) ** 2)) * 2 * np.sqrt(np.pi) / self.seg
-        self.window = torch.from_numpy(np.ascontiguousarray(win)).to(self.device)
-        self.n_seg = int(self._lib.qi_stft_segments(self.n, self.seg, self.hop))
-        self.n_f = self.nfft // 2 + 1
+        self.window = torch.from_numpy(g.window).to(self.device)
         self.code = _lib.dtype_code(self.rdtype)
         self.z = torch.empty((self.channels, self.n_f, self.n_seg), dtype=engine._complex_of(self.rdtype), device=self.device)
         self.bits = torch.empty((self.channels, self.n_f, self.n_seg), dtype=self.rdtype, device=self.device)
         self.scratch_bytes = int(self._lib.qi_stft_scratch_bytes(self.code, self.channels, self.n, self.seg, self.hop, self.nfft))
         self.scratch = torch.empty(max(self.scratch_bytes, 1), dtype=torch.uint8, device=self.device)
-        padded = self.n + 2 * (self.seg // 2)
-        padded += (-(padded - self.seg) % self.hop) % self.seg
-        self.time_s = np.arange(self.seg / 2, padded - self.seg / 2 + 1, self.hop) / float(self.fs) - (self.seg / 2) / self.fs
-        self.frequency_hz = np.fft.rfftfreq(self.nfft, 1 / self.fs)
         self._reduced, self._out_scratch = {}, None  # buffers of `reduce`, made on its first call
 
     @property
@@ -243,16 +293,7 @@ class StftPlan:
             if nbytes > self.scratch.numel():
                 self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             self._out_scratch = self.scratch
-        return _stft_out(self._lib, sig, self.window, self.seg, self.hop, self.nfft, self.scale, res, self._out_scratch)
-
-
-def _frame_count(n, seg, hop):
-    """qi_stft_segments restated (scipy.signal.stft, boundary="zeros", padded=True): host arithmetic, no library."""
-    if n <= 0 or seg <= 0 or not 0 < hop <= seg:
-        return 0
-    length = n + 2 * (seg // 2)
-    length += (-(length - seg) % hop) % seg
-    return (length - seg) // hop + 1
+        return _stft_out(self._lib, sig, self.window, self._geometry, res, self._out_scratch)
 
 
 def range_samples(n_total, seg, hop, first_segment, segments):
@@ -278,38 +319,24 @@ class StftRangePlan:
         self.n_total, self.fs = int(n_total), float(frequency_sample_rate_hz)
         if (band_order_nth is None) == (window is None):
             raise ValueError("give band_order_nth (stft_from_sig's geometry) or a window, not both")
+        self.rdtype = engine._real_dtype(dtype)
         if window is None:
-            self.seg = stft_segment_points(self.fs, band_order_nth)
-            if self.n_total < self.seg:
-                raise ValueError(f"Signal length: {self.n_total} is less than time_fft_nd: {self.seg}")
-            win64 = tukey_window_periodic(self.seg, 1.0)
-            self.hop, self.nfft = self.seg // 2, self.seg
-            extra_scale = 2 * np.sqrt(np.pi) / self.seg
+            g = StftGeometry.from_order(self.n_total, self.fs, band_order_nth, rdtype=self.rdtype)
         else:
             win64 = np.asarray(window, dtype=np.float64)
             if win64.ndim != 1 or len(win64) < 1:
                 raise ValueError("window must be 1-D")
-            self.seg = len(win64)
-            if self.n_total < self.seg:
-                raise ValueError(f"record of {self.n_total} samples is shorter than the segment of {self.seg}")
-            self.hop = self.seg - (int(self.seg / 2) if overlap_points is None else int(overlap_points))
-            self.nfft = int(2 ** np.ceil(np.log2(self.seg))) if nfft_points is None else int(nfft_points)
-            if not 0 < self.hop <= self.seg:
-                raise ValueError("noverlap must be less than nperseg.")
-            if self.nfft < self.seg:
-                raise ValueError("nfft must be greater than or equal to nperseg.")
-        self.rdtype = engine._real_dtype(dtype)
+            seg = len(win64)
+            if self.n_total < seg:
+                raise ValueError(f"record of {self.n_total} samples is shorter than the segment of {seg}")
+            g = StftGeometry.from_window(self.n_total, self.fs, win64, int(seg / 2) if overlap_points is None else overlap_points,
+                                         int(2 ** np.ceil(np.log2(seg))) if nfft_points is None else nfft_points, extra_scale,
+                                         self.rdtype)
+        self._geometry = g
+        self.seg, self.hop, self.nfft, self.n_seg, self.n_f, self.scale = g.seg, g.hop, g.nfft, g.n_seg, g.n_f, g.scale
+        self.time_s, self.frequency_hz = g.time_s, g.frequency_hz
         self._device = device
-        win = win64 if self.rdtype == torch.float64 else win64.astype(np.float32)
-        self._win_host = np.ascontiguousarray(win)
-        self.scale = float(np.sqrt(1.0 / np.sum(win.astype(np.float64)) ** 2)) * extra_scale
-        self.n_seg = _frame_count(self.n_total, self.seg, self.hop)
-        self.n_f = self.nfft // 2 + 1
         self.code = _lib.dtype_code(self.rdtype)
-        padded = self.n_total + 2 * (self.seg // 2)
-        padded += (-(padded - self.seg) % self.hop) % self.seg
-        self.time_s = np.arange(self.seg / 2, padded - self.seg / 2 + 1, self.hop) / self.fs - (self.seg / 2) / self.fs
-        self.frequency_hz = np.fft.rfftfreq(self.nfft, 1 / self.fs)
         self._lib, self.device, self.window, self._scratch = None, None, None, None
 
     def check_range(self, first_segment, segments, sample0, n_avail, pooled=None, pooled_methods=("average",)):
@@ -324,9 +351,8 @@ class StftRangePlan:
             raise ValueError(f"the range needs the record samples {lo} .. {lo + need - 1}, the rows hold {sample0} .. {sample0 + n_avail - 1}")
         if pooled is None:
             return 0
-        pooled, methods = int(pooled), tuple(pooled_methods)
-        if not methods or any(m not in ("average", "max") for m in methods) or len(set(methods)) != len(methods):
-            raise ValueError(f'pooled_methods must be a subset of ("average", "max"), got {methods!r}')
+        pooled = int(pooled)
+        engine.check_pooled_methods(pooled_methods)
         if pooled < 2:
             raise ValueError(f"pooling factor {pooled}: 2 or more")
         if first_segment % pooled:
@@ -368,7 +394,7 @@ class StftRangePlan:
             raise ValueError("rows must be a CUDA tensor")
         if self.window is None or self.device != rows.device:
             self.device = rows.device
-            self.window = torch.from_numpy(self._win_host).to(self.device)
+            self.window = torch.from_numpy(self._geometry.window).to(self.device)
         dev = self.device
         res = _stft_result(self.frequency_hz, n_ch, self.n_f, segments, self.rdtype, dev, coef, bits, reductions, power_scale)
         rng = _lib.StftRange(n_total=self.n_total, first_segment=first_segment, segments=segments, sample0=sample0, n_avail=n_avail,
@@ -382,9 +408,7 @@ class StftRangePlan:
             _lib.check(nbytes)
         if self._scratch is None or self._scratch.numel() < nbytes or self._scratch.device != dev:
             self._scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        desc = _lib.TfrOut(coef=_lib.ptr(res.coef), bits=_lib.ptr(res.bits), power_band=_lib.ptr(res.power_band),
-                           power_time=_lib.ptr(res.power_time), stats=_lib.ptr(res.stats), power_scale=float(power_scale),
-                           eps=float(get_epsilon()))
+        desc = engine.out_descriptor(res, get_epsilon())
         _lib.call(self._lib.qi_stft_out_range, dev, self.code, dev.index, _lib.ptr(rows), n_ch, _lib.ptr(self.window), self.seg,
                   self.hop, self.nfft, self.scale, C.byref(rng), C.byref(desc), _lib.ptr(self._scratch), self._scratch.numel())
         return res
@@ -441,15 +465,8 @@ def stft_from_sig(
     """Order-N standardised STFT: periodic-Hann segments sized from N, scaled by 2 sqrt(pi) / segment,
     with its log2 amplitude bits (ref styx_fft.py:14-57).
     :return: stft_complex, stft_bits, time_stft_s, frequency_stft_hz  (note the order)"""
-    seg = stft_segment_points(frequency_sample_rate_hz, band_order_nth, center_frequency_hz, octaves_below_center)
-    n = sig_wf.shape[-1] if hasattr(sig_wf, "shape") else len(sig_wf)
-    if n < seg:
-        raise ValueError(f"Signal length: {n} is less than time_fft_nd: {seg}")
-    window = tukey_window_periodic(seg, 1.0)
-    f, t, z, bits = _stft_windowed(
-        sig_wf, frequency_sample_rate_hz, window, seg, seg // 2, seg, extra_scale=2 * np.sqrt(np.pi) / seg,
-        want_bits=True,
-    )
+    f, t, z, bits = _stft_from_order(sig_wf, (frequency_sample_rate_hz, band_order_nth, center_frequency_hz, octaves_below_center),
+                                     want_bits=True)
     return z, bits, t, f
 
 
@@ -466,15 +483,8 @@ def stft_reductions_from_sig(
     sig_wf: [n] or [C, n], NumPy or CUDA tensor.
     :return: TfrResult (device tensors power_band [C, n_f], power_time [C, n_seg], stats [C, 4]), time_stft_s,
         frequency_stft_hz"""
-    seg = stft_segment_points(frequency_sample_rate_hz, band_order_nth, center_frequency_hz, octaves_below_center)
-    n = sig_wf.shape[-1] if hasattr(sig_wf, "shape") else len(sig_wf)
-    if n < seg:
-        raise ValueError(f"Signal length: {n} is less than time_fft_nd: {seg}")
-    window = tukey_window_periodic(seg, 1.0)
-    f, t, res = _stft_windowed(
-        sig_wf, frequency_sample_rate_hz, window, seg, seg // 2, seg, extra_scale=2 * np.sqrt(np.pi) / seg,
-        _reduce=dict(coef=False, bits=False, power_scale=power_scale),
-    )
+    f, t, res = _stft_from_order(sig_wf, (frequency_sample_rate_hz, band_order_nth, center_frequency_hz, octaves_below_center),
+                                 _reduce=dict(coef=False, bits=False, power_scale=power_scale))
     return res, t, f
 
 
@@ -501,11 +511,9 @@ def welch_power_pow2(
         raise ValueError(f"Signal length: {n} is less than the segment: {seg}")
     if not 0 < hop <= seg:
         raise ValueError("noverlap must be less than nperseg.")
-    f64 = sig.dtype == torch.float64
-    win64 = tukey_window_periodic(seg, alpha)
-    win = win64 if f64 else win64.astype(np.float32)
+    win = _run_window(tukey_window_periodic(seg, alpha), sig.dtype)
     scale = float(1.0 / np.sum(win.astype(np.float64)))
-    win_d = torch.from_numpy(np.ascontiguousarray(win)).to(sig.device)
+    win_d = torch.from_numpy(win).to(sig.device)
     code = _lib.dtype_code(sig.dtype)
     pxx = torch.empty((n_ch, nfft // 2 + 1), dtype=sig.dtype, device=sig.device)
     scratch, nbytes = _lib.scratch(lib.qi_welch_scratch_bytes, sig.device, code, n_ch, n, seg, hop, nfft)

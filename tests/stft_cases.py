@@ -195,11 +195,12 @@ def welch_reference(case, dtype):
 # ---- 4. ShortTimeFFT convention -----------------------------------------------------------------------------------------
 ALPHA = 0.25
 PADDINGS = ("zeros", "edge", "even", "odd")
-SLIDING_SEGS = (64, 200, 512, 1000, 2048, 4096)  # overlap 3 / 4 of the segment
+# overlap 3 / 4 of the segment; 24 (nfft 32, below every fused shape: 73 samples, 15 slices) takes the hipFFT path in both precisions
+SLIDING_SEGS = (24, 64, 200, 512, 1000, 2048, 4096)
 BOTH_SCALINGS_AT = (200, 2048)  # "magnitude" and "psd" there, "magnitude" elsewhere
 # the complex output: its roll phase exp(2 pi i k (seg // 2) / nfft) is (-1)^k when seg = nfft (512, 2048: a conjugated ramp is the
 # same ramp there) and a ramp with an imaginary part below it (200 in 256, 1000 in 1024; 3000 in 4096: fused in float32,
-# the rotation of k_sliding_frames before hipFFT in float64; 24 in 32: hipFFT in both)
+# the rotation of the framing kernel before hipFFT in float64; 24 in 32: hipFFT in both)
 SLIDING_COMPLEX_SEGS = (24, 200, 512, 1000, 2048, 3000)
 # (seg, hop) of the inverse.  Halo ceil(seg / hop) - 1 = 1, 3, 7, 15; launch_istft_fused holds
 # G = min(16, (80 KiB / sizeof(complex) - M - 1) / tile) slices per workgroup and needs G - halo >= 1:

@@ -2,7 +2,7 @@
 
 tests/stft_cases.py holds the rows and their references (the oracle in float64 on the same three-channel record; for
 float32 on the rounded record, widened, with the window rounded as the wrappers round it).  Which branch of
-qi_stft_fused.hip / qi_stft_sliding.hip / qi_api_ops.hip each group is there for:
+qi_stft_fused.hip / qi_stft_hipfft.hip / qi_api_ops.hip each group is there for:
 
   test_stft_from_sig_every_segment_length
       k_stft_fused<T, R, C, PLAIN = true>, all seven <2,3> .. <5,6> (float64: six) -- nfft 64 with NP * kWave != M (half a
@@ -31,7 +31,8 @@ qi_stft_fused.hip / qi_stft_sliding.hip / qi_api_ops.hip each group is there for
       PLAIN = false with pad_mode 0 .. 3 (stft_sample), detrend on / off, real_kind 1 / 2, the roll phase ramp
       (`a.roll`: complex output compared directly, not through the inverse -- at seg = nfft the ramp is (-1)^k and a
       conjugated ramp passes, so the complex rows include seg 200 / 1000 / 3000 below nfft), at <2,3> .. <5,6>; float64 at
-      4096 and seg 24 (nfft 32): launch_sliding_frames (its rotation in time) -> hipFFT -> launch_sliding_transpose.
+      4096 and seg 24 (nfft 32) in both precisions: the request through launch_hipfft_frames (every padding, detrend on /
+      off, its rotation in time) -> hipFFT -> launch_hipfft_transpose (real_kind 1 / 2, the complex panel).
   test_istft_random_spectrum_vs_oracle
       k_istft_fused at halo 1, 3, 7, 15 where G - halo >= 1 and the three-kernel path (untranspose -> hipFFT C2R ->
       overlap-add) past it (stft_cases.ISTFT_SHAPES has the table), a hop that does not divide the segment, and the
