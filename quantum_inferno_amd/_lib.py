@@ -1,4 +1,4 @@
-"""ctypes binding of libqi_tfr.so (include/qi_tfr.h).  There is no CPU fallback: if the
+"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, include/qi_array.h).  There is no CPU fallback: if the
 library is missing or no HIP device is present, every transform raises."""
 import ctypes as C
 import os
@@ -159,6 +159,14 @@ PROTOTYPES = {
     "qi_stft_out_range": (_int, [_int, _int, _P, _i64, _P, _i64, _i64, _i64, _dbl, C.POINTER(StftRange), C.POINTER(TfrOut), _P, _i64, _P]),
 }
 
+# include/qi_array.h (operations across the records of a batch), one to one
+ARRAY_PROTOTYPES = {
+    "qi_cross_spectra_scratch_bytes": (_i64, [_int, _i64, _i64, _i64]),
+    "qi_cross_spectra": (_int, [_int, _int, _P, _i64, _i64, _i64, _D, _P, _P, _P, _i64, _P]),
+    "qi_csd_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
+    "qi_csd": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _i64, _dbl, _P, _P, _P, _i64, _P]),
+}
+
 _lib = None
 
 
@@ -181,7 +189,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,6 +1,7 @@
 // C ABI of libqi_tfr.so, plan-less entry points: STFT / Welch / sliding STFT, tfr_info on caller panels, the 1-D Shannon
 // family, widening and log2 helpers, Gabor atoms.
 #include "qi_host.hpp"
+#include "qi_array.h"
 
 using namespace qi;
 using qi::host::align_up;
@@ -333,6 +334,60 @@ int qi_welch(int dtype, int device, const void* sig, int64_t C, int64_t n, const
           return via_hipfft<T>(device, rq, x, w, (char*)scratch, st,
                                [&](const cplx<T>* F) { return launch_welch_mean<T>(rq, F, (T*)pxx, st); });
         });
+  });
+}
+
+// ---- cross-spectra of the Welch segments (include/qi_array.h) -----------------------------------------------------------
+// Scratch of qi_csd: [0] the three-kernel path's frames and spectra | [1] the coefficient panel [C][nfft / 2 + 1][nseg] | [2]
+// the contraction's own (cross_spectra_scratch)
+struct CsdLayout {
+  size_t panel, cross, total;
+  CsdLayout(int dtype, int64_t C, int64_t nseg, int64_t nfft) {
+    const int64_t nf = nfft / 2 + 1;
+    panel = FftScratch(dtype, C, nseg, nfft).total;
+    cross = panel + align_up((size_t)C * nf * nseg * 2 * elem_size(dtype));
+    total = cross + cross_spectra_scratch(dtype, C, nf);
+  }
+};
+static int csd_check(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(C > 0 && seg > 0 && n >= seg && hop > 0 && hop <= seg && nfft >= seg, "bad Welch geometry");
+  // (the shape refusals of the contraction, before anything is launched)
+  const int64_t bytes = qi_cross_spectra_scratch_bytes(dtype, C, nfft / 2 + 1, (n - seg) / hop + 1);
+  return bytes < 0 ? (int)bytes : QI_OK;
+}
+
+int64_t qi_csd_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {
+  QI_TRY(csd_check(dtype, C, n, seg, hop, nfft));
+  return (int64_t)CsdLayout(dtype, C, (n - seg) / hop + 1, nfft).total;
+}
+
+int qi_csd(int dtype, int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop,
+           int64_t nfft, double scale, void* csd, void* coherence, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_REQUIRE(sig && window && scratch, "null argument");
+  QI_REQUIRE(csd || coherence, "nothing to produce");
+  QI_TRY(csd_check(dtype, C, n, seg, hop, nfft));
+  const int64_t nseg = (n - seg) / hop + 1, nf = nfft / 2 + 1;
+  const CsdLayout l(dtype, C, nseg, nfft);
+  QI_TRY(require_scratch(scratch_bytes, (int64_t)l.total));
+  QI_REQUIRE(aligned(scratch, 16), "misaligned scratch");
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  StftRequest rq{C, n, seg, hop, nfft, nseg, 0};  // qi_welch's segments; the panel unscaled: the weight carries scale^2
+  CsdWeight w;
+  w.edge = scale * scale / (double)nseg;
+  w.paired = 2.0 * w.edge;
+  w.nfft = nfft;
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    const T *x = (const T*)sig, *win = (const T*)window;
+    char* s = (char*)scratch;
+    cplx<T>* Z = reinterpret_cast<cplx<T>*>(s + l.panel);
+    QI_TRY(fused_or_hipfft(
+        stft_fused_supported(dtype, seg, hop, nfft),
+        [&] { return launch_stft_fused<T>(rq, x, win, Z, (T*)nullptr, st); },  // the storing form with lead = 0
+        [&] { return stft_hipfft<T>(device, rq, x, win, Z, (T*)nullptr, s, st); }));
+    return launch_cross_spectra<T>(Z, C, nf, nseg, w, (cplx<T>*)csd, (T*)coherence, s + l.cross + align_up((size_t)nf * 8), st);
   });
 }
 

@@ -202,6 +202,20 @@ int launch_hipfft_transpose(const StftRequest& rq, const cplx<T>* F, cplx<T>* Z,
 template <typename T>
 int launch_welch_mean(const StftRequest& rq, const cplx<T>* F, T* pxx, hipStream_t st);
 
+// cross-spectra of a panel (qi_csd.hip; include/qi_array.h).  The weight of bin f: table[f] (a DEVICE array) when there is
+// one, else `paired` for the bins a one-sided spectrum doubles (0 < f, and f < nfft / 2 for an even nfft) and `edge` for the rest
+struct CsdWeight {
+  const double* table = nullptr;
+  double edge = 1.0, paired = 1.0;
+  int64_t nfft = 0;
+};
+// bytes of launch_cross_spectra's scratch: nf doubles (a caller's weights) | [nf][C][C] complex (the matrices when csd is null)
+size_t cross_spectra_scratch(int dtype, int64_t C, int64_t nf);
+// Z [C][nf][nseg] -> csd [nf][C][C] and / or coherence [nf][C][C] (either may be null); `matrices`: the second region of the scratch
+template <typename T>
+int launch_cross_spectra(const cplx<T>* Z, int64_t C, int64_t nf, int64_t nseg, const CsdWeight& w, cplx<T>* csd, T* coherence,
+                         void* matrices, hipStream_t st);
+
 template <typename T>
 int launch_power_marginals(const T* P, int64_t C, int64_t B, int64_t n, T* power_time, double* part_band,
                            double* part_stat, hipStream_t st);

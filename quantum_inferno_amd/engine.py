@@ -587,6 +587,36 @@ def gabor_atoms(n, p_re, p_im, omega, amp, device=None, x=None):
 
 
 # ---- plan-less record calls: records [n] or [C, n] in, one library call on the current stream, `finish` out ----
+def cross_spectra(panel, weight=None, coherence=False):
+    """Cross-spectra between the records of a stored coefficient panel [C, n_bands, n_time] (an STFT, CWT or Stockwell panel:
+    complex64 or complex128): csd[f, i, j] = weight[f] sum_t conj(panel[i, f, t]) panel[j, f, t], one Hermitian matrix per
+    band, summed on the matrix cores in the panel's precision (qi_cross_spectra).  weight: [n_bands] host values or None (1).
+    -> csd [n_bands, C, C], or (csd, coherence [n_bands, C, C] = |S_ij|^2 / (S_ii S_jj)) with coherence=True.  NumPy in ->
+    NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    was_numpy = not isinstance(panel, torch.Tensor)
+    z = torch.from_numpy(np.ascontiguousarray(panel)) if was_numpy else panel
+    if z.dim() != 3 or z.dtype not in (torch.complex64, torch.complex128) or 0 in z.shape:
+        raise ValueError(f"panel must be a non-empty complex64 / complex128 [C, bands, time], got {z.dtype} {tuple(z.shape)}")
+    z = z.to(z.device if z.is_cuda else default_device()).contiguous()
+    n_ch, n_f, n_t = z.shape
+    rdtype = torch.float32 if z.dtype == torch.complex64 else torch.float64
+    w_host, w_ptr = (None, None)
+    if weight is not None:
+        w_host, w_ptr = _lib.darr(weight)
+        if w_host.shape != (n_f,):
+            raise ValueError(f"weight must hold one value per band ({n_f}), got shape {w_host.shape}")
+    dev, code = z.device, _lib.dtype_code(rdtype)
+    csd = torch.empty((n_f, n_ch, n_ch), dtype=z.dtype, device=dev)
+    coh = torch.empty((n_f, n_ch, n_ch), dtype=rdtype, device=dev) if coherence else None
+    scratch, nbytes = _lib.scratch(lib.qi_cross_spectra_scratch_bytes, dev, code, n_ch, n_f, n_t)
+    _lib.call(lib.qi_cross_spectra, dev, code, dev.index, _lib.ptr(z), n_ch, n_f, n_t, w_ptr, _lib.ptr(csd), _lib.ptr(coh),
+              _lib.ptr(scratch), nbytes)
+    if coherence:
+        return finish(csd, was_numpy, False), finish(coh, was_numpy, False)
+    return finish(csd, was_numpy, False)
+
+
 def _record_shape(a, what="signal", nonempty=True):
     """Shape (n,) or (C, n) of records, NumPy or tensor, checked before anything needs the device; n is its last entry."""
     shape = tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)

@@ -520,3 +520,120 @@ def welch_power_pow2(
     _lib.call(lib.qi_welch, sig.device, code, sig.device.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale,
               _lib.ptr(pxx), _lib.ptr(scratch), nbytes)
     return np.fft.rfftfreq(nfft, 1 / frequency_sample_rate_hz), engine.finish(pxx, was_numpy, was_1d)
+
+
+def _csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, scaling, want_csd, want_coherence):
+    """qi_csd on a [C, n] device tensor with welch_power_pow2's conventions -> (frequency_hz, csd [nf, C, C] or None,
+    coherence [nf, C, C] or None), device tensors in the records' precision."""
+    lib = _lib.require_gpu()
+    if nfft_points is None:
+        nfft_points = int(2 ** np.ceil(np.log2(segment_points)))
+    if overlap_points is None:
+        overlap_points = int(segment_points / 2)
+    n_ch, n = sig.shape
+    seg, nfft = int(segment_points), int(nfft_points)
+    hop = seg - int(overlap_points)
+    if n < seg:
+        raise ValueError(f"Signal length: {n} is less than the segment: {seg}")
+    if not 0 < hop <= seg:
+        raise ValueError("noverlap must be less than nperseg.")
+    if nfft < seg:
+        raise ValueError("nfft must be greater than or equal to nperseg.")
+    fs = float(frequency_sample_rate_hz)
+    win = _run_window(tukey_window_periodic(seg, alpha), sig.dtype)
+    win64 = win.astype(np.float64)
+    if scaling == "spectrum":
+        scale = float(1.0 / np.sum(win64))
+    elif scaling == "density":
+        scale = float(np.sqrt(1.0 / (fs * np.sum(win64 * win64))))
+    else:
+        raise ValueError(f"Unknown scaling: {scaling!r}")
+    dev, n_f = sig.device, nfft // 2 + 1
+    win_d = torch.from_numpy(win).to(dev)
+    code = _lib.dtype_code(sig.dtype)
+    csd = torch.empty((n_f, n_ch, n_ch), dtype=engine._complex_of(sig.dtype), device=dev) if want_csd else None
+    coherence = torch.empty((n_f, n_ch, n_ch), dtype=sig.dtype, device=dev) if want_coherence else None
+    scratch, nbytes = _lib.scratch(lib.qi_csd_scratch_bytes, dev, code, n_ch, n, seg, hop, nfft)
+    _lib.call(lib.qi_csd, dev, code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale, _lib.ptr(csd),
+              _lib.ptr(coherence), _lib.ptr(scratch), nbytes)
+    return np.fft.rfftfreq(nfft, 1 / fs), csd, coherence
+
+
+def csd_matrix_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    segment_points: int,
+    nfft_points: int = None,
+    overlap_points: int = None,
+    alpha: float = 0.25,
+    scaling: str = "spectrum",
+):
+    """Cross-spectral matrix of the records of one batch [C x n]: scipy.signal.csd(x_i, x_j) of every pair with
+    welch_power_pow2's segments (Tukey window, 50 % overlap by default, mean removed, one-sided, average="mean");
+    scaling "spectrum" (1 / sum(w)^2) or "density" (1 / (fs sum(w^2))).  The diagonal is the Welch spectrum of each record.
+    :return: frequency_hz, csd [(nfft/2+1) x C x C] complex, Hermitian per bin (csd[f, j, i] is conj(csd[f, i, j]) bit for bit)"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    f, csd, _ = _csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, scaling, True, False)
+    return f, engine.finish(csd, was_numpy, False)
+
+
+def coherence_matrix_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    segment_points: int,
+    nfft_points: int = None,
+    overlap_points: int = None,
+    alpha: float = 0.25,
+):
+    """Magnitude-squared coherence |S_ij|^2 / (S_ii S_jj) between the records of one batch [C x n]: scipy.signal.coherence of
+    every pair, with csd_matrix_pow2's segments.  A bin whose auto-power is 0 is NaN; one segment gives 1.
+    :return: frequency_hz, coherence [(nfft/2+1) x C x C]"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    f, _, coh = _csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, "spectrum", False, True)
+    return f, engine.finish(coh, was_numpy, False)
+
+
+def _csd_pairs(sig_x, sig_y, want_coherence, *args):
+    """The pair forms: row c of sig_x against row c of sig_y, from the matrices of the stacked records [x ; y] -- the entries
+    (c, C + c), which are the matrix forms' bits (an entry is a function of its two records alone)."""
+    x, x_numpy, was_1d = engine.as_signal(sig_x)
+    y, y_numpy, _ = engine.as_signal(sig_y, device=x.device)
+    if x.shape != y.shape or np.ndim(sig_x) != np.ndim(sig_y):
+        raise ValueError(f"sig_x and sig_y must have the same shape, got {tuple(np.shape(sig_x))} and {tuple(np.shape(sig_y))}")
+    if x.dtype != y.dtype:
+        x, y = x.to(torch.float64), y.to(torch.float64)
+    n_ch = x.shape[0]
+    f, csd, coh = _csd_matrices(torch.cat([x, y]), *args, not want_coherence, want_coherence)
+    full = coh if want_coherence else csd
+    rows = torch.arange(n_ch, device=full.device)
+    pairs = full[:, rows, rows + n_ch].transpose(0, 1).contiguous()  # [C, nf]
+    return f, engine.finish(pairs, x_numpy and y_numpy, was_1d)
+
+
+def csd_pow2(
+    sig_x,
+    sig_y,
+    frequency_sample_rate_hz: float,
+    segment_points: int,
+    nfft_points: int = None,
+    overlap_points: int = None,
+    alpha: float = 0.25,
+    scaling: str = "spectrum",
+):
+    """scipy.signal.csd(sig_x, sig_y) with csd_matrix_pow2's conventions: a 1-D pair, or two equal-shaped batches [C x n]
+    paired row by row.  :return: frequency_hz, csd [nfft/2+1] (or [C x ...]) complex"""
+    return _csd_pairs(sig_x, sig_y, False, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, scaling)
+
+
+def coherence_pow2(
+    sig_x,
+    sig_y,
+    frequency_sample_rate_hz: float,
+    segment_points: int,
+    nfft_points: int = None,
+    overlap_points: int = None,
+    alpha: float = 0.25,
+):
+    """scipy.signal.coherence(sig_x, sig_y) with coherence_matrix_pow2's conventions: a 1-D pair, or two equal-shaped batches
+    paired row by row.  :return: frequency_hz, coherence [nfft/2+1] (or [C x ...])"""
+    return _csd_pairs(sig_x, sig_y, True, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, "spectrum")
