@@ -2,7 +2,9 @@
  * qi_array.h -- C ABI of libqi_tfr.so, part two: operations ACROSS the records of a batch (a sensor array's channels).
  *
  * Everything of qi_tfr.h holds here: its types and status codes, caller-owned device pointers, asynchronous calls on the
- * given stream with no host synchronisation and no allocation, qi_last_error() for the message.  The reference
+ * given stream with no host synchronisation and no allocation, qi_last_error() for the message (per thread).  Both calls are
+ * plan-less: they may be made from several host threads at once, each on its own stream and buffers (qi_csd shares the
+ * per-device hipFFT handles of qi_tfr.h's short-time family, locked inside).  The reference
  * (quantum-inferno) has no cross-channel product; the calls below restate scipy.signal.csd and scipy.signal.coherence,
  * the siblings of the scipy.signal.welch call behind styx_fft.welch_power_pow2 (styx_fft.py:230-266).
  *

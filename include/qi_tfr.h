@@ -14,7 +14,14 @@
  *    because band and index selection stays on the host in float64 (bit-exact with the
  *    reference, scales_dyadic.py:355-393, styx_stx.py:233).
  *  - every call returns 0 on success or a negative qi_status; qi_last_error() gives the
- *    message for the calling thread.  Nothing throws, nothing aborts.
+ *    message for the calling thread (qi_last_error is per thread: a refusal on another thread
+ *    never changes it).  Nothing throws, nothing aborts.
+ *  - host threads: the plan-less entry points (everything that takes no qi_plan) may be called
+ *    from several host threads at once, each on its own stream and its own buffers; what they
+ *    keep per device (hipFFT handles and a work area per stream, strip partials per stream,
+ *    twiddle tables) is locked inside.  A plan belongs to ONE host thread and stream at a time:
+ *    it has one scratch; threads each make their own plan, and different plans may be created,
+ *    used and destroyed side by side (tests/test_gpu_threads.py, tests/sanitize_threads/).
  *  - transforms are asynchronous on the given stream and do no host synchronisation;
  *    a plan is thread-compatible (one plan per host thread / stream).  The calls that upload
  *    host tables -- qi_plan_set_gabor_bank, qi_gabor_atoms, qi_gabor_atoms_at -- wait for the

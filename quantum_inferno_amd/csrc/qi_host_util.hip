@@ -88,6 +88,7 @@ std::map<int, FftCache> g_stft_fft;  // per device
 }  // namespace qi
 
 #ifdef QI_HOST_SANITIZE
+#include <atomic>
 // Host sanitizer build only (tests/sanitize): the regions a run carves out of the plan's scratch, checked as they are reported.
 namespace qi {
 namespace host {
@@ -98,9 +99,11 @@ struct LayoutRegion {
   std::string what;
   int gen;
 };
-std::vector<LayoutRegion> g_regions;
-int g_layout_gen = 0;
-size_t g_layout_checked = 0;
+// (a run's regions belong to the plan of the calling thread -- a plan has one thread at a time --, so they are per thread;
+// the count is read by the walker at its end)
+thread_local std::vector<LayoutRegion> g_regions;
+thread_local int g_layout_gen = 0;
+std::atomic<size_t> g_layout_checked{0};
 }  // namespace
 
 void layout_begin(const qi_plan* p, const char* run, bool keep_previous) {
@@ -130,5 +133,5 @@ void layout_note(const qi_plan* p, const char* what, const void* ptr, size_t byt
 }
 }  // namespace host
 }  // namespace qi
-extern "C" size_t qi_layout_regions_checked() { return qi::host::g_layout_checked; }
+extern "C" size_t qi_layout_regions_checked() { return qi::host::g_layout_checked.load(); }
 #endif

@@ -163,8 +163,8 @@ def cwt_chirp_complex(
         plan.set_gabor_bank(which, f_hz, *_atom_tables(order, f_hz, fs, index_shift, scale_base, dictionary_type))
         return plan
 
-    plan = engine.cached_plan(key, make)
-    res = plan._run(which, sig, True, True, False, 1.0, 0.0)
+    with engine.borrowed_plan(key, make) as plan:
+        res = plan._run(which, sig, True, True, False, 1.0, 0.0)
     return (
         engine.finish(res.coef, was_numpy, was_1d, widen=True),
         engine.finish(res.bits, was_numpy, was_1d, widen=True),

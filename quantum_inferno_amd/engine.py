@@ -9,6 +9,7 @@ runs in libqi_tfr.so.  Signals are [channels, n]; panels are [channels, bands, n
 PyTorch is used for device memory and streams only.
 """
 import collections
+import contextlib
 import ctypes as C
 import operator
 import os
@@ -530,25 +531,81 @@ class PlanRing:
 
 
 # ---- small LRU of plans for the reference-signature wrappers (each call there is one record) ----
-_PLANS = collections.OrderedDict()
+# Safe from several host threads and streams.  A plan has one scratch (include/qi_tfr.h: one plan per host thread and stream at
+# a time), so a caller BORROWS a plan and returns it behind its last launch: nobody else holds it meanwhile, and a plan in use
+# is never closed.  A second concurrent caller of one key does not wait, it pays for a plan of its own.
+_PLANS = collections.OrderedDict()  # the IDLE plans: serial -> _Idle, least recently returned first
 _MAX_PLANS = 3
+_PLANS_LOCK = threading.Lock()  # all bookkeeping; factory() and close() run outside it
+_PLANS_SERIAL = 0
+_PLANS_EPOCH = 0  # raised by clear_plans(): a plan borrowed in an earlier epoch is closed when it comes back
+
+_Idle = collections.namedtuple("_Idle", "key plan done stream")  # done: event behind the last borrower's launches, on `stream`
 
 
-def cached_plan(key, factory):
-    plan = _PLANS.pop(key, None)
-    if plan is None:
+def _close_idle(entries):
+    for e in entries:
+        if e.done is not None:
+            e.done.synchronize()  # the last borrower's launches still use the scratch that close() frees
+        e.plan.close()
+
+
+@contextlib.contextmanager
+def borrowed_plan(key, factory):
+    """`with borrowed_plan(key, factory) as plan:` -- the idle plan of `key` returned last, or a new one from `factory()` when
+    none is idle (another borrower holds it, or it was evicted).  Leave the block once the last launch that uses the plan has
+    been queued: the cache then records an event on the current stream, and the next borrower's current stream waits for it on
+    the device (nothing for the same stream; the host never waits).  Idle plans beyond _MAX_PLANS are closed, least recently
+    returned first."""
+    global _PLANS_SERIAL
+    found = None
+    with _PLANS_LOCK:
+        epoch = _PLANS_EPOCH
+        for serial in reversed(_PLANS):
+            if _PLANS[serial].key == key:
+                found = _PLANS.pop(serial)
+                break
+    if found is None:
         plan = factory()
-        while len(_PLANS) >= _MAX_PLANS:
-            _, old = _PLANS.popitem(last=False)
-            old.close()
-    _PLANS[key] = plan
-    return plan
+    else:
+        plan = found.plan
+        if found.done is not None:
+            stream = torch.cuda.current_stream(plan.device)
+            if stream.cuda_stream != found.stream:
+                stream.wait_event(found.done)
+    try:
+        yield plan
+    finally:
+        done = stream_id = None
+        device = getattr(plan, "device", None)
+        if device is not None:
+            stream = torch.cuda.current_stream(device)
+            if found is not None and found.done is not None and found.stream == stream.cuda_stream:
+                done = found.done  # (the event is the plan's: recorded again, it stands for the later launches)
+            else:
+                done = torch.cuda.Event()
+            done.record(stream)
+            stream_id = stream.cuda_stream
+        doomed = []
+        with _PLANS_LOCK:
+            if epoch != _PLANS_EPOCH:
+                doomed.append(_Idle(key, plan, done, stream_id))
+            else:
+                _PLANS_SERIAL += 1
+                _PLANS[_PLANS_SERIAL] = _Idle(key, plan, done, stream_id)
+                while len(_PLANS) > _MAX_PLANS:
+                    doomed.append(_PLANS.popitem(last=False)[1])
+        _close_idle(doomed)
 
 
 def clear_plans():
-    while _PLANS:
-        _, old = _PLANS.popitem()
-        old.close()
+    """Close the idle plans; a plan that is borrowed now is closed when it comes back."""
+    global _PLANS_EPOCH
+    with _PLANS_LOCK:
+        _PLANS_EPOCH += 1
+        doomed = list(_PLANS.values())
+        _PLANS.clear()
+    _close_idle(doomed)
 
 
 def gabor_atoms(n, p_re, p_im, omega, amp, device=None, x=None):

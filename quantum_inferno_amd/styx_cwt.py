@@ -124,7 +124,7 @@ def cwt_complex_any_scale_pow2(
         plan.set_styx_bank(band_order_nth, fs, dictionary_type)
         return plan
 
-    plan = engine.cached_plan(key, make)
-    res = plan.cwt(sig, coef=True)
+    with engine.borrowed_plan(key, make) as plan:
+        res = plan.cwt(sig, coef=True)
     time_cwt_s = np.arange(n) / fs
     return res.frequency_hz, time_cwt_s, engine.finish(res.coef, was_numpy, was_1d, widen=True)

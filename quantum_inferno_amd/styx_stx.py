@@ -28,8 +28,8 @@ def stx_complex_any_scale_pow2(band_order_nth: float, sig_wf, frequency_sample_r
         plan.set_stx_bands(band_order_nth, fs)
         return plan
 
-    plan = engine.cached_plan(key, make)
-    res = plan.stx(sig, coef=True)
+    with engine.borrowed_plan(key, make) as plan:
+        res = plan.stx(sig, coef=True)
     return res.frequency_hz, np.arange(n) / fs, engine.finish(res.coef, was_numpy, was_1d, widen=True)
 
 

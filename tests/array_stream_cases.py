@@ -35,6 +35,10 @@ def named_functions():
     return sorted({f for c in CASES for f in c.functions})
 
 
+def plan_less_ids():
+    return [c.id for c in CASES if c.engine is None]  # (all of them: qi_array.h has no plans)
+
+
 def _build_csd(shape):
     """csd and coherence of RECORDS float32 records at stream_cases' fused / hipFFT STFT shape (Welch segments)."""
     torch, _lib, lib, dev = sc._gpu()

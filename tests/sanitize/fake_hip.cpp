@@ -9,6 +9,7 @@
 #include <hipfft/hipfft.h>
 #include <sys/mman.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,11 +21,12 @@ constexpr size_t kMapFrom = (size_t)32 << 20;  // allocations from 32 MiB are ad
 std::mutex g_mu;
 std::map<void*, size_t> g_mapped;   // mmap'ed "device" buffers
 std::map<void*, size_t> g_malloced;
-size_t g_launches = 0;
-int g_fft_handles = 0;
+std::atomic<size_t> g_launches{0};  // (counters of every thread of a walker)
+std::atomic<int> g_fft_handles{0};
 }  // namespace
 
-extern "C" size_t qi_fake_hip_launches() { return g_launches; }
+extern "C" size_t qi_fake_hip_launches() { return g_launches.load(); }
+extern "C" int qi_fake_hip_fft_handles() { return g_fft_handles.load(); }
 // is [ptr, ptr + bytes) inside one live "device" allocation?  (the driver's bounds check for argument blocks)
 extern "C" int qi_fake_hip_inside(const void* ptr, size_t bytes) {
   std::lock_guard<std::mutex> lk(g_mu);

@@ -36,8 +36,12 @@ SYN_RECORDS = [1, 4, 16, 0]
 EXPECT = {None: 0, "native": 1, "fallback": 2}
 
 
-def write_config(fh, order, log2n, dtype, records, gabor, stx, flags):
-    n = 1 << log2n
+def write_config(fh, order, log2n, dtype, records, gabor, stx, flags, n=None):
+    """n: the record length itself goes into the log2n field (format 3: engine_layouts)."""
+    if n is None:
+        n = 1 << log2n
+    else:
+        log2n = n
     idx, sigma = stx
     nb = max(len(gabor["p_re"]), len(sigma))
     td = torch.float64 if dtype else torch.float32
@@ -97,5 +101,26 @@ def main(path):
     print(json.dumps({"synthetic_plans": len(syn) * used, "synthetic_on_native_at_least": both * used}))
 
 
+def engine_layouts(path):
+    """`--engines`: one layout per engine of tests/stream_cases.py's ENGINES (float32 at 2^14, float64 at 2^15, 2^11 in both
+    precisions, 3000 samples on the hipFFT engine) at its order, for 1 and 8 records (RECORD_COUNTS) -- the tables of
+    tests/sanitize_threads/walk_threads.cpp.  Format 3: the field that holds log2n elsewhere holds the record length."""
+    import stream_cases as sc
+
+    fs = sc.FS
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<4i", 0x51495354, len(sc.ENGINES), len(sc.RECORD_COUNTS), 3))
+        for dtype, n, _ in sc.ENGINES.values():
+            f_hz, p_re, p_im, omega, amp, _ = engine.styx_bank_tables(sc.ORDER, n, fs)
+            idx = scales.stx_shift_indices(f_hz, n, fs).astype(np.int64)
+            sigma = (scales.cycles_from_order(sc.ORDER) / (2 * np.pi * f_hz / fs)).astype(np.float64)
+            write_config(fh, sc.ORDER, 0, int(dtype == "float64"), list(sc.RECORD_COUNTS), dict(p_re=p_re, p_im=p_im, omega=omega, amp=amp),
+                         (idx, sigma), 0, n=n)
+    print(json.dumps({"layouts": [[dtype, n] for dtype, n, _ in sc.ENGINES.values()], "records": list(sc.RECORD_COUNTS)}))
+
+
 if __name__ == "__main__":
-    main(sys.argv[1])
+    if sys.argv[1] == "--engines":
+        engine_layouts(sys.argv[2])
+    else:
+        main(sys.argv[1])

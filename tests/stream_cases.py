@@ -26,16 +26,19 @@ FS = 1000.0
 ORDER = 3
 FILL = 0.3125  # finite, exactly representable, and no result of any case
 
-Case = collections.namedtuple("Case", "id functions asynchronous reason build")
+# engine: the key of the plan a plan case runs on (ENGINES, PASS2_ENGINE or a plan of the case's own), None for a plan-less case --
+# the two groups of the host-thread tests (tests/test_gpu_threads.py): a plan belongs to one thread at a time, a plan-less op may
+# be called from several at once
+Case = collections.namedtuple("Case", "id functions asynchronous reason build engine", defaults=(None,))
 Built = collections.namedtuple("Built", "op a b note")  # a, b: NumPy record sets; note: what the build asserted, for the log
 
 CASES = []
 
 
-def _case(cid, functions, build, asynchronous=True, reason=""):
+def _case(cid, functions, build, asynchronous=True, reason="", engine=None):
     assert asynchronous or reason, cid
     assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build))
+    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build, engine))
 
 
 def ids():
@@ -48,6 +51,10 @@ def by_id(cid):
 
 def named_functions():
     return sorted({f for c in CASES for f in c.functions})
+
+
+def plan_less_ids():
+    return [c.id for c in CASES if c.engine is None]
 
 
 def noise(seed, shape, dtype, offset=0.75):
@@ -234,12 +241,12 @@ for _key in ENGINES:
         for _full in (True, False):
             for _records in RECORD_COUNTS:
                 _case(f"{_transform}-{_key}-{'all' if _full else 'band'}-r{_records}", _functions,
-                      functools.partial(_build_transform, _key, _transform, _full, _records))
+                      functools.partial(_build_transform, _key, _transform, _full, _records), engine=_key)
 
 
 for _full, _records in PASS2_FORMS:
     _case(f"cwt_styx-{PASS2_ENGINE[0]}-{'all' if _full else 'band'}-r{_records}", ("qi_cwt",),
-          functools.partial(_build_transform, PASS2_ENGINE[0], "cwt_styx", _full, _records))
+          functools.partial(_build_transform, PASS2_ENGINE[0], "cwt_styx", _full, _records), engine=PASS2_ENGINE[0])
 
 
 def _build_pooled(key, strip):
@@ -262,8 +269,9 @@ def _build_pooled(key, strip):
     return Built(op, a, b, note + f"; strip partials per row S = {segments}")
 
 
-_case("pooled-average-f32_n2048", ("qi_cwt", "qi_pool_panel"), functools.partial(_build_pooled, "f32_n2048", False))
-_case("pooled_strip-f32_n2048", ("qi_cwt", "qi_pool_strip", "qi_pool_strip_stats"), functools.partial(_build_pooled, "f32_n2048", True))
+_case("pooled-average-f32_n2048", ("qi_cwt", "qi_pool_panel"), functools.partial(_build_pooled, "f32_n2048", False), engine="f32_n2048")
+_case("pooled_strip-f32_n2048", ("qi_cwt", "qi_pool_strip", "qi_pool_strip_stats"), functools.partial(_build_pooled, "f32_n2048", True),
+      engine="f32_n2048")
 
 
 def _build_set_bank():
@@ -285,7 +293,8 @@ def _build_set_bank():
 
 
 _case("set_gabor_bank-then-cwt", ("qi_plan_set_gabor_bank", "qi_cwt"), _build_set_bank, asynchronous=False,
-      reason="qi_plan_set_gabor_bank uploads the tables and ends with hipStreamSynchronize(st) (qi_api.hip: build_gabor_bank)")
+      reason="qi_plan_set_gabor_bank uploads the tables and ends with hipStreamSynchronize(st) (qi_api.hip: build_gabor_bank)",
+      engine="set_bank")
 
 
 # ---- the short-time family: _lib calls, one fused and one hipFFT shape --------------------------------------------------------

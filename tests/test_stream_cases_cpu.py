@@ -73,6 +73,32 @@ def test_every_promised_path_is_in_the_table():
     assert len(ids) == 125, len(ids)  # a case that leaves the table fails here even where its function keeps another case
 
 
+def test_every_case_is_in_one_thread_group():
+    """tests/test_gpu_threads.py runs the plan-less cases from several host threads at once and the plan cases with one plan
+    per thread.  Which group a case is in is told by the header: a case reaches a function that takes a `qi_plan*` exactly
+    when it names the plan it runs on (`engine`), and the names are those of the plans stream_cases builds."""
+    import array_stream_cases as asc
+
+    plan_functions = {name for name, params in header_functions().items() if re.search(r"\bqi_plan\s*\*", params)}
+    assert {"qi_cwt", "qi_stx", "qi_cwt_stx", "qi_plan_set_gabor_bank"} <= plan_functions and "qi_stft_out_range" not in plan_functions
+    keys = set(sc.ENGINES) | {sc.PASS2_ENGINE[0], "set_bank"}
+    for case in sc.CASES:
+        takes_plan = any(f in plan_functions for f in case.functions)
+        assert (case.engine is not None) == takes_plan, case.id
+        assert case.engine is None or case.engine in keys, case.id
+        if case.engine in sc.ENGINES or case.engine == sc.PASS2_ENGINE[0]:
+            assert case.engine in case.id, case.id
+    plan_cases = [c.id for c in sc.CASES if c.engine is not None]
+    assert len(plan_cases) + len(sc.plan_less_ids()) == len(sc.CASES) == 125 and not set(plan_cases) & set(sc.plan_less_ids())
+    # each engine's transforms, the two-pass forms, the two pooled forms, the bank upload; the rest is plan-less
+    assert len(plan_cases) == len(sc.ENGINES) * 16 + len(sc.PASS2_FORMS) + 2 + 1 and len(sc.plan_less_ids()) == 39
+    assert set(sc.SHARED_STATE) <= set(sc.plan_less_ids())
+    for key in ("f32_n16384", "f64_n32768", "f32_n2048", "f32_n3000"):  # test_threads_one_plan_each: a thread per key
+        assert sc.by_id(f"cwt_stx-{key}-all-r1").engine == key
+    assert asc.plan_less_ids() == asc.ids() and len(asc.ids()) == 4  # include/qi_array.h has no plans
+    assert all(len(c) == len(sc.Case._fields) for c in asc.CASES)
+
+
 def test_strip_shapes_fold_partials():
     s = sc.STRIP
     assert sc.strip_segments(s["records"] * s["bands"], s["windows"], s["factor"]) == 5
