@@ -142,6 +142,12 @@ int64_t qi_plan_stage_bands(const qi_plan* plan, int which, int stage);
  * `which` with every bin its bands read inside (-K, K), K <= Lf / 64. */
 int64_t qi_plan_forward_low(const qi_plan* plan, int which /* as qi_plan_bands */);
 
+/* Per-time planes table `which` (QI_BANK_STYX or 2, the Stockwell table) writes in a joint one-record qi_cwt_stx call of a
+ * float32 plan on the native engines: the planes the summing tail reads for that table (two-pass chunks, the block
+ * launch's planes under the dealing in effect, the zoom launch's rows).  0 when the plan runs no joint call.  Builds the
+ * joint launch's item lists on first use, like the call itself. */
+int64_t qi_plan_joint_planes(qi_plan* plan, int which);
+
 /* Which kernels produce row `band` of table `which` in a call of `records` records (a read-only query: tests and
  * diagnostics use it to tell which path a band takes; it changes nothing).  `records` means the records that go through
  * together: a call whose records do not fit the plan's scratch runs in tiles, and each tile takes the route of its own

@@ -108,6 +108,7 @@ PROTOTYPES = {
     "qi_plan_bands": (_i64, [_P, _int]),
     "qi_plan_stage_bands": (_i64, [_P, _int, _int]),
     "qi_plan_forward_low": (_i64, [_P, _int]),
+    "qi_plan_joint_planes": (_i64, [_P, _int]),
     "qi_plan_band_route": (_int, [_P, _int, _i32, _i64, C.POINTER(BandRoute)]),
     "qi_plan_profile": (_int, [_P, _int]),
     "qi_plan_profile_read": (_int, [_P, _D, _I64, _i32]),

@@ -46,6 +46,7 @@ int qi_plan_create(qi_plan** plan, const qi_plan_desc* desc) {
   if (const char* e = tune_env("QI_NATIVE_DEBUG")) p->native_debug = atoi(e);
   if (const char* e = tune_env("QI_NATIVE_FWD")) p->native_fwd = atoi(e);
   if (const char* e = tune_env("QI_NATIVE_FWD_LOW")) p->native_fwd_low = atoi(e);
+  if (const char* e = tune_env("QI_NATIVE_JOINT_DEAL")) p->native_joint_deal = atoi(e);
 #ifdef QI_NATIVE_STAMPS
   if (tune_env("QI_NATIVE_STAMPS")) {
     if (hipMalloc((void**)&p->stamps, 65536 * 8 * sizeof(unsigned long long)) != hipSuccess) p->stamps = nullptr;
@@ -328,6 +329,12 @@ int64_t qi_plan_bands(const qi_plan* p, int which) {
 int64_t qi_plan_forward_low(const qi_plan* p, int which) {
   if (!p || which < 0 || which > 2 || !forward_low(p)) return 0;
   return table_low_bins(p, which);
+}
+
+int64_t qi_plan_joint_planes(qi_plan* p, int which) {
+  if (!p || (which != QI_BANK_STYX && which != 2)) return 0;
+  DeviceGuard g(p->d.device);  // (the item lists of the joint dealing are built on first use)
+  return g.ok ? joint_planes(p, which) : 0;
 }
 
 int64_t qi_plan_stage_bands(const qi_plan* p, int which, int stage) {

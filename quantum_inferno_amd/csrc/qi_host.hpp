@@ -355,10 +355,16 @@ struct qi_plan {
       int32_t nedge_items = 0;  // edge pieces of the split bands, appended to the item list (styx bank)
       bool edge_merged = false;  // one edge item per block for all split bands (k_block_edge) instead of one per band and block
       std::vector<native::BlockItem> h_items;  // host copy of d_items (the joint launch list is made from it)
+      std::vector<std::pair<int32_t, int32_t>> h_groups;  // (first band, bands) of every reach group in d_bands
     } var[2];
+    // qi_cwt_stx below batch_from records (native_joint_deal): this table's items of the joint dealing (build_joint_items,
+    // on first use).  A copy of var[0] -- the same bands, the tables borrowed from it -- with its own d_items / h_items,
+    // nitems, nplanes, nlong and nedge_items; a complete item list of the table, so it also serves a launch of its own.
+    ItemList joint;
     int64_t max_blocks = 0;  // partial slots a band row needs
     void release() {
       free_device(bank);
+      free_device(joint.d_items);
       for (auto& v : var) {
         free_device(v.d_bands);
         free_device(v.d_demod_pow);
@@ -418,10 +424,13 @@ struct qi_plan {
   std::vector<int32_t> h_split_bands;
   int32_t nsplit = 0;
   FusedCarry carry;
-  native::DualItem* d_dual[2] = {nullptr, nullptr};  // joint block launch of qi_cwt_stx (styx + Stockwell tables) per item cut, built on first use
-  int32_t n_dual[2] = {0, 0};
-  int32_t n_dual_long[2] = {0, 0};  // long-block items at the front of d_dual
-  bool dual_valid[2] = {false, false};
+  // joint block launch of qi_cwt_stx (styx + Stockwell tables), built on first use: [0], [1] the tables' item lists of that cut
+  // paired chunk by chunk; [kDualJoint] cut 0 dealt table-first (BlockTable::joint)
+  static constexpr int kDualJoint = 2;
+  native::DualItem* d_dual[3] = {nullptr, nullptr, nullptr};
+  int32_t n_dual[3] = {0, 0, 0};
+  int32_t n_dual_long[3] = {0, 0, 0};  // long-block items at the front of d_dual
+  bool dual_valid[3] = {false, false, false};
   int native_fuse = 4;         // qi_cwt_stx: 1 the block launches and the tails of the two transforms go out back to back, 2 as one
                                // launch each, 3 also the gather and the coarse stage of the zoom engine, 4 and its interpolation
   native::EdgeBand* d_edge = nullptr;  // short-atom bands of table 3
@@ -431,6 +440,8 @@ struct qi_plan {
   int native_debug = 0;
   int native_fwd = 1;          // forward transform of the records on the native kernels (0: hipFFT)
   int native_fwd_low = 1;      // ... only the bins near DC when nothing reads the others (forward_low); 0: always every bin
+  int native_joint_deal = 1;   // qi_cwt_stx below batch_from records: the joint block launch deals a reach group's styx and Stockwell
+                               // bands as one sequence (build_joint_items); 0: the tables' own item lists, paired chunk by chunk
   unsigned long long* stamps = nullptr;  // diagnostic builds: phase cycle counters of the last pass-2 launch
   unsigned long long* blk_stamps = nullptr;  // idem, last block launch
   int native_group = 0;        // wide bands per launch group (0: all in one group)
@@ -484,6 +495,9 @@ template <typename T>
 int build_bank(qi_plan* p, int bank, int32_t B, const double* d_par, hipStream_t st);
 // the Stockwell table of a plan (native classification, block picks; nat[2] / blk[2]); `sigma`, `shift_index`: host [B]
 int build_stx_tables(qi_plan* p, int32_t B, const int64_t* shift_index, const double* sigma, const std::vector<double>& coef);
+// Table-first dealing of the joint block launch (item cut 0 of the styx and the Stockwell table, both ready): fills
+// blk[0].joint and blk[2].joint and returns the launch's band items in generation order (no edge items; the caller sorts)
+int build_joint_items(qi_plan* p, std::vector<native::DualItem>* dual);
 
 // the small-record engine's rule: does table `kind` (0 styx bank, 1 atoms bank, 2 Stockwell) of this plan run on it?  (A
 // property of the plan alone; on_small: ... and the table is set)
@@ -506,6 +520,9 @@ int run_small(qi_plan* p, int njobs, const int* kinds, const qi_tfr_out* const* 
               bool* ran);
 int run_native64(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_out* out, hipStream_t st);
 int flush_carry(qi_plan* p, FusedCarry* c, hipStream_t st);
+// per-time planes of table `kind` (0 styx, 2 Stockwell) in a joint one-record qi_cwt_stx call: two-pass chunks, block planes
+// of the dealing in effect, zoom rows (0: the plan runs no joint call); builds the joint item lists when they are the ones used
+int64_t joint_planes(qi_plan* p, int kind);
 
 }  // namespace host
 }  // namespace qi

@@ -706,7 +706,7 @@ int finish_block_table(qi_plan* p, int kind, int demod, const std::vector<BlockP
   constexpr bool F64 = sizeof(T) == 8;
   auto& bt = p->blk[kind];
   bt.release();
-  p->dual_valid[0] = p->dual_valid[1] = false;
+  for (bool& valid : p->dual_valid) valid = false;
   if (picks.empty()) return QI_OK;
   const int32_t rows = (int32_t)picks.size();
   QI_TRY(fft_c2c<double>(p->fft, taps, native::kBlk, rows, HIPFFT_FORWARD, st));
@@ -733,6 +733,7 @@ int finish_block_table(qi_plan* p, int kind, int demod, const std::vector<BlockP
         QI_TRY(block_band_desc<T>(p, picks[r], r, is_long, &list.back()));
       }
       group_count[g] = (int32_t)list.size() - group_first[g];
+      il.h_groups.push_back({group_first[g], group_count[g]});
       if (group_count[g] == 0) continue;
       const int64_t nblocks = ceil_div(p->n, native::block_valid(kBlockGroupWq[g]));
       if (nblocks > bt.max_blocks) bt.max_blocks = nblocks;
@@ -751,6 +752,87 @@ int finish_block_table(qi_plan* p, int kind, int demod, const std::vector<BlockP
   }
   QI_HIP(hipStreamSynchronize(st));
   bt.ready = true;
+  return QI_OK;
+}
+
+// Table-first dealing of the joint block launch of qi_cwt_stx, item cut 0.  A reach group with c0 styx and c2 Stockwell
+// bands keeps the workgroups per block of the chunk-by-chunk pairing, W = max of the two tables' chunk counts, but its
+// bands are dealt as ONE sequence, styx bands first: W runs whose lengths differ by at most one, a run = one workgroup
+// per block with a contiguous styx part and a contiguous Stockwell part (either may be empty).  A table owns one
+// per-time plane per run that holds any of its bands: 7 + 7 bands are runs of 7 styx and 7 Stockwell bands, one plane per
+// table, where chunks of 4 + 4 and 3 + 3 need two.  The rule depends on the tables alone.  Each table's share is a complete
+// item list of its own (BlockTable::joint: planes, statistics slots, long-block items first, the styx table's edge
+// items at the end with planes of their own).
+int build_joint_items(qi_plan* p, std::vector<native::DualItem>* dual) {
+  qi_plan::BlockTable* bt[2] = {&p->blk[0], &p->blk[2]};
+  std::vector<native::BlockItem> items[2];
+  for (auto* t : bt) {
+    if (!t->ready || t->var[0].h_groups.size() != (size_t)kBlockGroups) {
+      set_error("block engine: the joint dealing needs both block tables");
+      return QI_ERR_STATE;
+    }
+    free_device(t->joint.d_items);
+    t->joint = t->var[0];  // (the bands and their tables stay var[0]'s)
+    t->joint.d_items = nullptr;
+    t->joint.h_items.clear();
+    t->joint.nitems = t->joint.nplanes = t->joint.nlong = t->joint.nedge_items = 0;
+  }
+  dual->clear();
+  for (int g = 0; g < kBlockGroups; ++g) {
+    const int32_t f[2] = {bt[0]->var[0].h_groups[g].first, bt[1]->var[0].h_groups[g].first};
+    const int32_t c[2] = {bt[0]->var[0].h_groups[g].second, bt[1]->var[0].h_groups[g].second};
+    const int32_t total = c[0] + c[1];
+    if (total == 0) continue;
+    const int32_t W = (int32_t)std::max(ceil_div(c[0], kBlockBandsPerWg), ceil_div(c[1], kBlockBandsPerWg));
+    const int64_t nblocks = ceil_div(p->n, native::block_valid(kBlockGroupWq[g]));
+    const int32_t planes_before[2] = {bt[0]->joint.nplanes, bt[1]->joint.nplanes};
+    for (int32_t r = 0; r < W; ++r) {
+      const int32_t lo = (int32_t)((int64_t)total * r / W), hi = (int32_t)((int64_t)total * (r + 1) / W);
+      // the run's part of each table: [lo, hi) cut at c0, the Stockwell part counted from its own first band
+      const int32_t first[2] = {f[0] + std::min(lo, c[0]), f[1] + std::max(lo, c[0]) - c[0]};
+      const int32_t count[2] = {std::min(hi, c[0]) - std::min(lo, c[0]), std::max(hi, c[0]) - std::max(lo, c[0])};
+      int32_t plane[2] = {0, 0};
+      for (int q = 0; q < 2; ++q)
+        if (count[q] > 0) plane[q] = bt[q]->joint.nplanes++;
+      for (int64_t b = 0; b < nblocks; ++b) {
+        native::DualItem d{kBlockGroupWq[g], (int32_t)b, 0, 0, 0, 0, 0, 0, 0, 0};
+        int32_t slot[2] = {0, 0};
+        for (int q = 0; q < 2; ++q) {
+          if (count[q] == 0) continue;
+          slot[q] = (int32_t)items[q].size();  // (dense and unique: the order of the statistics slots is the generation order)
+          items[q].push_back({kBlockGroupWq[g], (int32_t)b, first[q], count[q], plane[q], slot[q]});
+        }
+        if (count[0] > 0) d.first0 = first[0], d.count0 = count[0], d.plane0 = plane[0], d.slot0 = slot[0];
+        if (count[1] > 0) d.first2 = first[1], d.count2 = count[1], d.plane2 = plane[1], d.slot2 = slot[1];
+        dual->push_back(d);
+      }
+    }
+    if (tune_env("QI_NATIVE_VERBOSE"))
+      fprintf(stderr, "[qi plan] joint dealing, reach group %d: %d styx + %d Stockwell bands in %d workgroups x %lld blocks; planes %d + %d (chunk by chunk: %d + %d)\n",
+              kBlockGroupWq[g], c[0], c[1], W, (long long)nblocks, bt[0]->joint.nplanes - planes_before[0],
+              bt[1]->joint.nplanes - planes_before[1], (int)ceil_div(c[0], kBlockBandsPerWg), (int)ceil_div(c[1], kBlockBandsPerWg));
+  }
+  for (int q = 0; q < 2; ++q) {
+    auto& il = bt[q]->joint;
+    std::stable_sort(items[q].begin(), items[q].end(), [](const native::BlockItem& x, const native::BlockItem& y) {
+      const bool lx = x.wq == native::kBlkLongWq, ly = y.wq == native::kBlkLongWq;
+      return lx != ly ? lx : x.band_count > y.band_count;
+    });
+    il.nitems = (int32_t)items[q].size();
+    il.nlong = (int32_t)std::count_if(items[q].begin(), items[q].end(), [](const native::BlockItem& x) { return x.wq == native::kBlkLongWq; });
+    // the edge items of the split bands (styx table): as in var[0], their planes behind the band items' planes
+    const auto& src = bt[q]->var[0];
+    for (int32_t i = src.nitems; i < src.nitems + src.nedge_items; ++i) {
+      native::BlockItem e = src.h_items[(size_t)i];
+      e.plane = il.nplanes + (e.plane - src.h_items[(size_t)src.nitems].plane);
+      e.stat_slot = (int32_t)items[q].size();
+      items[q].push_back(e);
+    }
+    il.nedge_items = src.nedge_items;
+    if (src.nedge_items > 0) il.nplanes += src.nplanes - src.h_items[(size_t)src.nitems].plane;
+    il.h_items = items[q];
+    if (!il.h_items.empty()) QI_TRY(upload_table(&il.d_items, il.h_items));
+  }
   return QI_OK;
 }
 

@@ -282,20 +282,31 @@ int run_stx_leftover(qi_plan* p, const void* sig_v, int64_t C, const qi_tfr_out*
 template int run_stx_leftover<float>(qi_plan*, const void*, int64_t, const qi_tfr_out*, hipStream_t);
 template int run_stx_leftover<double>(qi_plan*, const void*, int64_t, const qi_tfr_out*, hipStream_t);
 
+// the item list of table `kind` behind joint launch list `cut` (an item cut, or qi_plan::kDualJoint: BlockTable::joint)
+const qi_plan::BlockTable::ItemList& dual_list(const qi_plan* p, int kind, int cut) {
+  return cut == qi_plan::kDualJoint ? p->blk[kind].joint : p->blk[kind].var[cut];
+}
+// does a run of table `kind` take its share of the table-first dealing?  joint_call: it is a half of a qi_cwt_stx tile
+bool joint_deal_wanted(const qi_plan* p, int kind, int cut, bool joint_call) {
+  return joint_call && cut == 0 && kind != 1 && p->native_joint_deal != 0 && p->blk[0].ready && p->blk[2].ready;
+}
 // Work items of the joint block launch: the items of the styx table (0) and of the Stockwell table (2) on the same
 // (reach group, block) are paired chunk by chunk -- one forward transform serves both; what has no partner stays single;
-// the edge items of the styx table keep their place at the end.
+// the edge items of the styx table keep their place at the end.  cut = qi_plan::kDualJoint: item cut 0 dealt table-first
+// (build_joint_items), the tables' shares in BlockTable::joint.
 int build_dual_items(qi_plan* p, int cut) {
   if (p->dual_valid[cut]) return QI_OK;
   free_device(p->d_dual[cut]);
   p->n_dual[cut] = 0;
   std::map<std::pair<int32_t, int32_t>, std::pair<std::vector<native::BlockItem>, std::vector<native::BlockItem>>> at;
   std::vector<native::DualItem> dual, edge;
-  for (const auto& it : p->blk[0].var[cut].h_items) {
+  if (cut == qi_plan::kDualJoint) QI_TRY(build_joint_items(p, &dual));
+  for (const auto& it : dual_list(p, 0, cut).h_items) {
     if (it.wq < 0) edge.push_back({it.wq, it.block, it.band_first, it.band_count, it.plane, it.stat_slot, 0, 0, 0, 0});
-    else at[{it.wq, it.block}].first.push_back(it);
+    else if (cut != qi_plan::kDualJoint) at[{it.wq, it.block}].first.push_back(it);
   }
-  for (const auto& it : p->blk[2].var[cut].h_items) at[{it.wq, it.block}].second.push_back(it);
+  if (cut != qi_plan::kDualJoint)
+    for (const auto& it : p->blk[2].var[cut].h_items) at[{it.wq, it.block}].second.push_back(it);
   for (const auto& kv : at) {
     const auto& a = kv.second.first;
     const auto& b = kv.second.second;
@@ -832,7 +843,7 @@ int launch_block_stage(qi_plan* p, const native::BlockArgs<float>& b, int demod,
   if (joint) {
     QI_TRY(build_dual_items(p, cut));
     QI_TRY(native::launch_block_dual<T>(finish->blk, b, p->d_dual[cut], p->n_dual[cut], p->n_dual_long[cut],
-                                        p->blk[0].var[cut].nedge_items, ct, st));
+                                        dual_list(p, 0, cut).nedge_items, ct, st));
   } else {
     if (finish) QI_TRY(native::launch_block<T>(finish->blk, finish->demod, finish->ct, st));
     QI_TRY(native::launch_block<T>(b, demod, ct, st));
@@ -873,7 +884,14 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
   const auto& bt = p->blk[kind];
   const bool blocks = kind != 1 && bt.ready;
   const int cut = C >= batch_from(p) ? 1 : 0;  // (both halves of a joint tile see the same C and the same tables)
-  const auto& il = bt.var[cut];
+  // qi_cwt_stx (either half of a joint tile, probes included) at item cut 0, asked for the per-time sums and a reduction (the
+  // requests whose block launches can go out as one and whose tail reads per-time planes): the table's share of the
+  // table-first dealing -- its planes, statistics slots and items, whatever becomes of the joint launch later (the share is
+  // a complete item list)
+  const bool joint_deal = joint_deal_wanted(p, kind, cut, (defer || finish) && out->power_time && (out->power_band || out->stats));
+  const int list = joint_deal ? qi_plan::kDualJoint : cut;
+  if (joint_deal) QI_TRY(build_dual_items(p, list));
+  const auto& il = dual_list(p, kind, list);
   int64_t blk_stats = 0, blk_slots = 0;
   if (blocks) {
     chunk_total += il.nplanes;
@@ -980,7 +998,7 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
     if (blocks) {
       native::BlockArgs<T> b = block_args<T>(p, bt, il, v, sig_t, s.zadd, nsplit, p2_stats, chunk_p2);
       b.nlong = il.nlong;
-      QI_TRY(launch_block_stage(p, b, bt.demod, cut, deferring ? defer : nullptr, finishing ? finish : nullptr, ct, st));
+      QI_TRY(launch_block_stage(p, b, bt.demod, list, deferring ? defer : nullptr, finishing ? finish : nullptr, ct, st));
     }
     p->prof.begin(st, QI_STAGE_EPILOGUE);
     if (shorts) QI_TRY(launch_edges<T>(p, v, s, sig_t, ct, st));
@@ -999,6 +1017,21 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
     p->prof.end(QI_STAGE_EPILOGUE, st);
   }
   return QI_OK;
+}
+
+// (the chunk count of run_native for one record of a joint tile, without a run)
+int64_t joint_planes(qi_plan* p, int kind) {
+  if ((kind != 0 && kind != 2) || p->d.dtype != QI_F32 || !p->native_fuse || !p->nat[0].ready || !p->nat[2].ready || p->stx_left_n != 0)
+    return 0;
+  const int64_t C = 1;
+  const int cut = C >= batch_from(p) ? 1 : 0;
+  int64_t planes = plan_two_pass(p, kind, C, p->native_rows).chunk_total + plan_zoom_rows(p, kind, C, true).planes;
+  if (p->blk[kind].ready) {
+    const bool joint_deal = joint_deal_wanted(p, kind, cut, true);
+    if (joint_deal && build_dual_items(p, qi_plan::kDualJoint) != QI_OK) return 0;
+    planes += dual_list(p, kind, joint_deal ? qi_plan::kDualJoint : cut).nplanes;
+  }
+  return planes;
 }
 
 // ---- float64 only: the float64 zoom's rows and launches, the block launch with its side stream ----

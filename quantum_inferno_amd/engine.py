@@ -281,6 +281,11 @@ class TfrPlan:
         of two K with every spectrum bin table `which` reads inside (-K, K) (qi_plan_forward_low)."""
         return int(self._lib.qi_plan_forward_low(self._handle, which))
 
+    def joint_planes(self, which):
+        """Per-time planes table `which` (styx or Stockwell) writes in a joint one-record cwt_stx call (qi_plan_joint_planes);
+        0 when the plan runs no joint call."""
+        return int(self._lib.qi_plan_joint_planes(self._handle, which))
+
     def band_route(self, which, band, records=1):
         """(stage name, cls, run_cls, flags) of the kernels that produce row `band` of table `which` in a call of
         `records` records (qi_plan_band_route; the flag bits are _lib.ROUTE_*)."""
