@@ -1,4 +1,4 @@
-"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, include/qi_array.h).  There is no CPU fallback: if the
+"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, include/qi_array.h, include/qi_beam.h).  There is no CPU fallback: if the
 library is missing or no HIP device is present, every transform raises."""
 import ctypes as C
 import os
@@ -168,6 +168,13 @@ ARRAY_PROTOTYPES = {
     "qi_csd": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _i64, _dbl, _P, _P, _P, _i64, _P]),
 }
 
+# include/qi_beam.h (what consumes the cross-spectral matrices), one to one
+BEAM_PROTOTYPES = {
+    "qi_beam_power_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64]),
+    "qi_beam_power": (_int, [_int, _int, _P, _i64, _i64, _D, _P, _i64, _I64, _i64, _int, _P, _P, _P, _P, _i64, _P]),
+}
+BEAM_MAX_SENSORS = 64  # QI_BEAM_MAX_SENSORS
+
 _lib = None
 
 
@@ -190,7 +197,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

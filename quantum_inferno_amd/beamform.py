@@ -1,0 +1,114 @@
+"""
+Frequency-wavenumber (f-k) analysis of a sensor array: steered power of the cross-spectral matrices over a grid of
+slowness vectors (engine.beam_power, include/qi_beam.h).  The reference (quantum-inferno) has no array processing; the
+conventions below are the usual ones of infrasound and seismic array work.
+
+Geometry.  Positions are [C, 2] metres (x east, y north).  A slowness vector s [s/m] points the way the wave TRAVELS; a
+plane wave reaches sensor i later by tau_i = s . r_i seconds.  The back azimuth is where it comes FROM: the direction of
+-s in degrees clockwise from north; the trace velocity is 1 / |s|.
+
+The helpers are host code on torch float64; only plane_wave_delays' result and fk_power_pow2's work are on the device.
+"""
+import numpy as np
+import torch
+
+from . import engine, styx_fft
+
+
+def _host64(a, cols, what):
+    t = a.detach().cpu() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+    t = t.to(torch.float64)
+    if t.dim() != 2 or t.shape[1] != cols or t.shape[0] < 1:
+        raise ValueError(f"{what} must be [count, {cols}], got shape {tuple(t.shape)}")
+    return t
+
+
+def slowness_grid(max_slowness_s_per_m: float, points: int) -> torch.Tensor:
+    """A square grid of points x points slowness vectors from -max to +max on both axes -> [points^2, 2] (s_x, s_y); the
+    x component (east) runs fastest: vector (ix, iy) is row iy * points + ix."""
+    if points < 1 or not max_slowness_s_per_m > 0:
+        raise ValueError("slowness_grid needs points >= 1 and a positive largest slowness")
+    axis = torch.linspace(-float(max_slowness_s_per_m), float(max_slowness_s_per_m), int(points), dtype=torch.float64)
+    if points == 1:
+        axis = torch.zeros(1, dtype=torch.float64)
+    sy, sx = torch.meshgrid(axis, axis, indexing="ij")
+    return torch.stack([sx.reshape(-1), sy.reshape(-1)], dim=1)
+
+
+def polar_slowness_grid(back_azimuth_deg, trace_velocity_m_s) -> torch.Tensor:
+    """Slowness vectors of every (trace velocity, back azimuth) pair -> [len(velocity) * len(azimuth), 2]; the back azimuth
+    runs fastest.  s = -(sin az, cos az) / v: the wave travels away from where it comes from."""
+    az = torch.deg2rad(torch.as_tensor(np.atleast_1d(np.asarray(back_azimuth_deg, dtype=np.float64))))
+    v = torch.as_tensor(np.atleast_1d(np.asarray(trace_velocity_m_s, dtype=np.float64)))
+    if az.numel() < 1 or v.numel() < 1 or not bool((v > 0).all()):
+        raise ValueError("polar_slowness_grid needs back azimuths and positive trace velocities")
+    sx = -torch.sin(az)[None, :] / v[:, None]
+    sy = -torch.cos(az)[None, :] / v[:, None]
+    return torch.stack([sx.reshape(-1), sy.reshape(-1)], dim=1)
+
+
+def plane_wave_delays(positions_m, slowness, device=None) -> torch.Tensor:
+    """tau[g, i] = s_g . r_i seconds -> [G, C] float64 on the device: the delays_s of engine.beam_power."""
+    r = _host64(positions_m, 2, "positions_m")
+    s = _host64(slowness, 2, "slowness")
+    tau = s[:, 0:1] * r[:, 0][None, :] + s[:, 1:2] * r[:, 1][None, :]
+    return tau.contiguous().to(device if device is not None else engine.default_device())
+
+
+def back_azimuth_and_velocity(slowness):
+    """-> (back azimuth in degrees clockwise from north in [0, 360), trace velocity in m/s) of slowness vectors [..., 2]
+    (torch float64 on the host).  A zero vector (vertical incidence) has azimuth 0 and infinite velocity."""
+    s = slowness.detach().cpu() if isinstance(slowness, torch.Tensor) else torch.from_numpy(np.asarray(slowness, dtype=np.float64))
+    s = s.to(torch.float64)
+    if s.shape[-1] != 2:
+        raise ValueError(f"slowness must be [..., 2], got shape {tuple(s.shape)}")
+    az = torch.remainder(torch.rad2deg(torch.atan2(-s[..., 0], -s[..., 1])), 360.0)
+    norm = torch.hypot(s[..., 0], s[..., 1])
+    az = torch.where(norm == 0, torch.zeros_like(az), az)
+    return az, 1.0 / norm
+
+
+def band_offsets(frequency_hz, edges_hz) -> np.ndarray:
+    """Offsets of the bands edges[b] <= f < edges[b + 1] into an ascending frequency table -> int64 [len(edges)], the
+    `bands` of engine.beam_power.  Every band must hold a bin."""
+    f = np.asarray(frequency_hz, dtype=np.float64)
+    edges = np.asarray(edges_hz, dtype=np.float64)
+    if f.ndim != 1 or edges.ndim != 1 or edges.size < 2 or np.any(np.diff(f) <= 0):
+        raise ValueError("band_offsets needs an ascending frequency table and at least two edges")
+    first = np.searchsorted(f, edges, side="left").astype(np.int64)
+    if np.any(np.diff(first) <= 0):
+        raise ValueError(f"a band of {edges.tolist()} Hz holds no bin of the table")
+    return first
+
+
+def fk_power_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    positions_m,
+    slowness,
+    segment_points: int,
+    overlap_points: int = None,
+    nfft_points: int = None,
+    alpha: float = 0.25,
+    band_edges_hz=None,
+    normalize: bool = True,
+):
+    """f-k power of the records of one array [C x n]: styx_fft.csd_matrix_pow2's cross-spectral matrices (Welch segments,
+    Tukey window, spectrum scaling), steered over the slowness vectors [G, 2] and summed over the bands between
+    band_edges_hz (None: every bin its own band).  normalize: the semblance (in [0, 1]) instead of the power.  Neither the
+    segments' panel nor the matrices leave the device.
+    :return: band_frequency_ranges [nb x 2] (first and last bin frequency of every band), power [nb x G], peak_index [nb]
+        (row of `slowness` with the largest power in the band), peak_value [nb]"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    f, csd, _ = styx_fft._csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, "spectrum",
+                                       True, False)
+    if band_edges_hz is None:
+        bands, ranges = None, np.stack([f, f], axis=1)
+    else:
+        bands = band_offsets(f, band_edges_hz)
+        ranges = np.stack([f[bands[:-1]], f[bands[1:] - 1]], axis=1)
+    tau = plane_wave_delays(positions_m, slowness, sig.device)
+    if tau.shape[1] != sig.shape[0]:
+        raise ValueError(f"{tau.shape[1]} positions for {sig.shape[0]} records")
+    power, index, value = engine.beam_power(csd, f, tau, bands=bands, normalize=normalize, peaks=True)
+    return ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False)

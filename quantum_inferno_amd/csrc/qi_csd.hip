@@ -30,6 +30,7 @@
 #include "qi_host.hpp"
 #include "qi_device.hpp"   // kWave
 #include "qi_fft_reg.hpp"  // QI_LAUNCH_CHECK
+#include "qi_mfma.hpp"     // Mx
 #include "qi_array.h"
 
 using namespace qi;
@@ -40,30 +41,6 @@ namespace {
 constexpr int kCsdTile = 16;      // records per tile side (the instruction's M and N)
 constexpr int kCsdWaves = 4;      // waves (bins) per workgroup
 constexpr int kWeightChunk = 256; // host weights per k_csd_put_weights launch (2 KiB of kernel arguments)
-
-typedef float qi_f4 __attribute__((ext_vector_type(4)));
-typedef double qi_d4 __attribute__((ext_vector_type(4)));
-
-// the instruction per precision: accumulator type, one K step of four segments, consecutive segments a lane loads (32 bytes),
-// and the record row inside the tile that register `reg` of lane `lane` holds -- the two C/D maps differ
-template <typename T>
-struct Mx;
-template <>
-struct Mx<float> {
-  using acc = qi_f4;
-  static constexpr int V = 4;
-  static __device__ __forceinline__ acc mac(float a, float b, acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-  // float32 C/D: lane l, register r -> row 4 (l >> 4) + r, column l & 15
-  static __device__ __forceinline__ int row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
-};
-template <>
-struct Mx<double> {
-  using acc = qi_d4;
-  static constexpr int V = 2;
-  static __device__ __forceinline__ acc mac(double a, double b, acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-  // float64 C/D: lane l, register r -> row (l >> 4) + 4 r, column l & 15
-  static __device__ __forceinline__ int row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
-};
 
 struct CsdArgs {
   int64_t C, nf, nseg;

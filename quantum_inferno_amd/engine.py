@@ -679,6 +679,48 @@ def cross_spectra(panel, weight=None, coherence=False):
     return finish(csd, was_numpy, False)
 
 
+def beam_power(csd, frequency_hz, delays_s, bands=None, normalize=False, peaks=False):
+    """Steered (Bartlett) power of cross-spectral matrices over a grid of delay sets (qi_beam_power): with
+    e[f, g, i] = exp(2 pi i frequency_hz[f] delays_s[g, i]), Q[f, g] = Re sum_ij conj(e_i) csd[f, i, j] e_j, summed over the
+    matrices of each band and divided by C^2 -- or, normalize=True, by C sum_f trace(csd[f]): the semblance.
+    csd: [nf, C, C] complex64 / complex128 as cross_spectra and styx_fft.csd_matrix_pow2 return it, C <= 64;
+    frequency_hz: [nf] host values; delays_s: [G, C] seconds, NumPy or tensor, converted to float64 on the device (the
+    phase is formed in double whatever the matrices' precision); bands: nb + 1 strictly ascending offsets into 0..nf or None
+    (every matrix its own band).  -> power [nb, G] real, or (power, peak_index [nb] int64, peak_value [nb]) with peaks=True:
+    np.argmax of every band's row and that entry.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    was_numpy = not isinstance(csd, torch.Tensor)
+    s = torch.from_numpy(np.ascontiguousarray(csd)) if was_numpy else csd
+    if s.dim() != 3 or s.dtype not in (torch.complex64, torch.complex128) or 0 in s.shape or s.shape[1] != s.shape[2]:
+        raise ValueError(f"csd must be a non-empty complex64 / complex128 [nf, C, C], got {s.dtype} {tuple(s.shape)}")
+    s = s.to(s.device if s.is_cuda else default_device()).contiguous()
+    n_f, n_ch, _ = s.shape
+    dev = s.device
+    f_host, f_ptr = _lib.darr(frequency_hz)
+    if f_host.shape != (n_f,):
+        raise ValueError(f"frequency_hz must hold one value per matrix ({n_f}), got shape {f_host.shape}")
+    tau = delays_s if isinstance(delays_s, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(delays_s))
+    if tau.dim() != 2 or tau.shape[0] < 1 or tau.shape[1] != n_ch:
+        raise ValueError(f"delays_s must be [G, {n_ch}], got shape {tuple(tau.shape)}")
+    tau = tau.to(dev).to(torch.float64).contiguous()
+    n_g = tau.shape[0]
+    b_host, b_ptr = (None, None) if bands is None else _lib.iarr(bands)
+    if b_host is not None and (b_host.ndim != 1 or b_host.size < 2):
+        raise ValueError(f"bands must be a list of nb + 1 offsets, got shape {b_host.shape}")
+    n_b = n_f if b_host is None else b_host.size - 1
+    rdtype = torch.float32 if s.dtype == torch.complex64 else torch.float64
+    code = _lib.dtype_code(rdtype)
+    scratch, nbytes = _lib.scratch(lib.qi_beam_power_scratch_bytes, dev, code, n_ch, n_f, n_g, n_b)
+    power = torch.empty((n_b, n_g), dtype=rdtype, device=dev)
+    index = torch.empty(n_b, dtype=torch.int64, device=dev) if peaks else None
+    value = torch.empty(n_b, dtype=rdtype, device=dev) if peaks else None
+    _lib.call(lib.qi_beam_power, dev, code, dev.index, _lib.ptr(s), n_ch, n_f, f_ptr, _lib.ptr(tau), n_g, b_ptr, n_b,
+              int(bool(normalize)), _lib.ptr(power), _lib.ptr(index), _lib.ptr(value), _lib.ptr(scratch), nbytes)
+    if peaks:
+        return finish(power, was_numpy, False), finish(index, was_numpy, False), finish(value, was_numpy, False)
+    return finish(power, was_numpy, False)
+
+
 def _record_shape(a, what="signal", nonempty=True):
     """Shape (n,) or (C, n) of records, NumPy or tensor, checked before anything needs the device; n is its last entry."""
     shape = tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
