@@ -1,4 +1,4 @@
-"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, include/qi_array.h, include/qi_beam.h).  There is no CPU fallback: if the
+"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, include/qi_array.h, include/qi_beam.h, include/qi_adaptive.h).  There is no CPU fallback: if the
 library is missing or no HIP device is present, every transform raises."""
 import ctypes as C
 import os
@@ -175,6 +175,13 @@ BEAM_PROTOTYPES = {
 }
 BEAM_MAX_SENSORS = 64  # QI_BEAM_MAX_SENSORS
 
+# include/qi_adaptive.h (the Capon beamformer: whitening factors of the matrices, and their form over the grid), one to one
+ADAPTIVE_PROTOTYPES = {
+    "qi_csd_whiten": (_int, [_int, _int, _P, _i64, _i64, _dbl, _P, _P, _P]),
+    "qi_beam_capon_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64]),
+    "qi_beam_capon": (_int, [_int, _int, _P, _i64, _i64, _D, _P, _i64, _I64, _i64, _P, _P, _P, _P, _i64, _P]),
+}
+
 _lib = None
 
 
@@ -197,7 +204,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,13 +1,15 @@
 """
 Frequency-wavenumber (f-k) analysis of a sensor array: steered power of the cross-spectral matrices over a grid of
-slowness vectors (engine.beam_power, include/qi_beam.h).  The reference (quantum-inferno) has no array processing; the
-conventions below are the usual ones of infrasound and seismic array work.
+slowness vectors (engine.beam_power, include/qi_beam.h), and Capon's minimum-variance power over the same grid
+(engine.csd_whiten and engine.capon_power, include/qi_adaptive.h).  The reference (quantum-inferno) has no array processing;
+the conventions below are the usual ones of infrasound and seismic array work.
 
 Geometry.  Positions are [C, 2] metres (x east, y north).  A slowness vector s [s/m] points the way the wave TRAVELS; a
 plane wave reaches sensor i later by tau_i = s . r_i seconds.  The back azimuth is where it comes FROM: the direction of
 -s in degrees clockwise from north; the trace velocity is 1 / |s|.
 
-The helpers are host code on torch float64; only plane_wave_delays' result and fk_power_pow2's work are on the device.
+The helpers are host code on torch float64; only plane_wave_delays' result and the work of fk_power_pow2 and
+capon_power_pow2 are on the device.
 """
 import numpy as np
 import torch
@@ -112,3 +114,41 @@ def fk_power_pow2(
         raise ValueError(f"{tau.shape[1]} positions for {sig.shape[0]} records")
     power, index, value = engine.beam_power(csd, f, tau, bands=bands, normalize=normalize, peaks=True)
     return ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False)
+
+
+def capon_power_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    positions_m,
+    slowness,
+    segment_points: int,
+    overlap_points: int = None,
+    nfft_points: int = None,
+    alpha: float = 0.25,
+    band_edges_hz=None,
+    loading: float = 1e-2,
+):
+    """Capon (minimum-variance) f-k power of the records of one array [C x n], fk_power_pow2's twin: the same cross-spectral
+    matrices, loaded on the diagonal with `loading` times their mean auto-power and factored once per bin
+    (engine.csd_whiten), then 1 / (e^H R^-1 e) over the slowness vectors [G, 2], summed over the bands between band_edges_hz
+    (engine.capon_power).  The power has fk_power_pow2's units with normalize=False and never exceeds it; there is no
+    semblance.  Neither the panel, the matrices nor their factors leave the device: only the power, the peaks and info do.
+    A matrix averaged over fewer segments than there are sensors is singular: such records need loading > 0.  A bin whose
+    loaded matrix still does not factor has info != 0, and the band that holds it is NaN (its peak the first NaN).
+    :return: band_frequency_ranges [nb x 2], power [nb x G], peak_index [nb], peak_value [nb] as fk_power_pow2 returns them,
+        info [bins] int32: 0, or the 1-based pivot at which the bin's factorisation failed"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    f, csd, _ = styx_fft._csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, "spectrum",
+                                       True, False)
+    if band_edges_hz is None:
+        bands, ranges = None, np.stack([f, f], axis=1)
+    else:
+        bands = band_offsets(f, band_edges_hz)
+        ranges = np.stack([f[bands[:-1]], f[bands[1:] - 1]], axis=1)
+    tau = plane_wave_delays(positions_m, slowness, sig.device)
+    if tau.shape[1] != sig.shape[0]:
+        raise ValueError(f"{tau.shape[1]} positions for {sig.shape[0]} records")
+    whitener, info = engine.csd_whiten(csd, loading=loading, info=True)
+    power, index, value = engine.capon_power(whitener, f, tau, bands=bands, peaks=True)
+    return (ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False),
+            engine.finish(info, was_numpy, False))

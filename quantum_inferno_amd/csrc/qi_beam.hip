@@ -29,24 +29,9 @@
 // grid point g lies in whatever grid, in any band table that holds the band (NW is a matter of occupancy, not of results).
 //
 // The peaks are a second launch over the finished power: a workgroup per band, np.argmax's rules.
-#include "qi_host.hpp"
-#include "qi_device.hpp"   // kWave
-#include "qi_fft_reg.hpp"  // QI_LAUNCH_CHECK
-#include "qi_mfma.hpp"     // Mx
-#include "qi_beam.h"
-
-using namespace qi;
-using qi::host::align_up;
+#include "qi_beam_common.hpp"  // the tile constants, beam_ld, beam_sincospi, the peaks, put_words, the verdicts, the scratch
 
 namespace {
-
-constexpr int kBeamTile = 16;     // grid points of a wave, sensors of a row tile (the instruction's N and M)
-constexpr int kBeamMaxTiles = QI_BEAM_MAX_SENSORS / kBeamTile;
-constexpr int kBeamWavesFew = 2;  // waves per workgroup: few where the workgroups would not fill the chip otherwise
-constexpr int kBeamWavesMany = 8;
-constexpr int64_t kBeamFill = 512;  // workgroups from which the larger workgroup is taken
-constexpr int kPeakThreads = 256;
-constexpr int kWordChunk = 256;  // host values per k_beam_put_words launch (2 KiB of kernel arguments)
 
 template <typename T>
 struct BeamArgs {
@@ -59,15 +44,6 @@ struct BeamArgs {
   int64_t gparts;  // workgroups per band
   int normalize;
 };
-
-// entries a row of the matrix takes in LDS
-template <typename T>
-__host__ __device__ constexpr int beam_ld(int ntile) {
-  return ntile * kBeamTile + (sizeof(T) == 4 ? 4 : 0);
-}
-
-__device__ __forceinline__ void beam_sincospi(float x, float* s, float* c) { sincospif(x, s, c); }
-__device__ __forceinline__ void beam_sincospi(double x, double* s, double* c) { sincospi(x, s, c); }
 
 template <typename T, int NW, int NT>
 __global__ void __launch_bounds__(NW* kWave) k_beam_power(BeamArgs<T> a) {
@@ -142,79 +118,6 @@ __global__ void __launch_bounds__(NW* kWave) k_beam_power(BeamArgs<T> a) {
   if (on && lane < kBeamTile) a.power[b * a.G + g] = (T)((double)q / den);
 }
 
-// np.argmax's order: a NaN before every number, a larger value before a smaller one, a lower index before a higher one
-template <typename T>
-__device__ __forceinline__ bool beam_before(T va, int64_t ia, T vb, int64_t ib) {
-  const bool na = va != va, nb = vb != vb;
-  if (na || nb) return na && (!nb || ia < ib);
-  return va > vb || (va == vb && ia < ib);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(kPeakThreads) k_beam_peaks(const T* __restrict__ power, int64_t G, int64_t* __restrict__ index,
-                                                            T* __restrict__ value) {
-  __shared__ T sv[kPeakThreads];
-  __shared__ int64_t si[kPeakThreads];
-  const int tid = threadIdx.x;
-  const T* __restrict__ row = power + (int64_t)blockIdx.x * G;
-  T bv = T(0);
-  int64_t bi = -1;  // (none yet: G may be below the thread count)
-  for (int64_t g = tid; g < G; g += kPeakThreads) {
-    const T v = row[g];
-    if (bi < 0 || beam_before(v, g, bv, bi)) {
-      bv = v;
-      bi = g;
-    }
-  }
-  sv[tid] = bv;
-  si[tid] = bi;
-  __syncthreads();
-  for (int s = kPeakThreads / 2; s > 0; s >>= 1) {
-    if (tid < s && si[tid + s] >= 0 && (si[tid] < 0 || beam_before(sv[tid + s], si[tid + s], sv[tid], si[tid]))) {
-      sv[tid] = sv[tid + s];
-      si[tid] = si[tid + s];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    if (index) index[blockIdx.x] = si[0];
-    if (value) value[blockIdx.x] = sv[0];
-  }
-}
-
-// 8-byte host values (frequencies, band offsets) to the device as kernel arguments: stream-ordered, the caller's array is
-// free at return
-struct WordChunk {
-  uint64_t w[kWordChunk];
-};
-__global__ void __launch_bounds__(kWordChunk) k_beam_put_words(uint64_t* __restrict__ dst, WordChunk c, int count) {
-  if ((int)threadIdx.x < count) dst[threadIdx.x] = c.w[threadIdx.x];
-}
-int put_words(void* dst, const void* src, int64_t count, hipStream_t st) {
-  for (int64_t k0 = 0; k0 < count; k0 += kWordChunk) {
-    WordChunk c{};
-    const int n = (int)std::min<int64_t>(kWordChunk, count - k0);
-    std::memcpy(c.w, static_cast<const uint64_t*>(src) + k0, (size_t)n * sizeof(uint64_t));
-    k_beam_put_words<<<1, kWordChunk, 0, st>>>(static_cast<uint64_t*>(dst) + k0, c, n);
-    QI_LAUNCH_CHECK();
-  }
-  return QI_OK;
-}
-
-// what the size query and the call refuse of a shape (the index arithmetic and the grid stay inside their types)
-int beam_shape_check(int dtype, int64_t C, int64_t nf, int64_t G, int64_t nb) {
-  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
-  QI_REQUIRE(C >= 1 && C <= QI_BEAM_MAX_SENSORS, "%lld sensors: 1 to %d", (long long)C, QI_BEAM_MAX_SENSORS);
-  QI_REQUIRE(nf >= 1 && G >= 1 && nb >= 1, "bad shape: %lld matrices, %lld grid points, %lld bands", (long long)nf, (long long)G,
-             (long long)nb);
-  QI_REQUIRE(nb <= nf, "%lld bands of %lld matrices", (long long)nb, (long long)nf);
-  QI_REQUIRE(nf < (1ll << 40) && G < (1ll << 40) && nb * ceil_div(G, kBeamTile * kBeamWavesFew) < (1ll << 31), "request too large");
-  return QI_OK;
-}
-
-size_t beam_freq_bytes(int64_t nf) { return align_up((size_t)nf * sizeof(double)); }
-size_t beam_scratch(int64_t nf, int64_t nb) { return beam_freq_bytes(nf) + align_up((size_t)(nb + 1) * sizeof(int64_t)); }
-
 template <typename T, int NW>
 int launch_beam_power(const BeamArgs<T>& a, int ntile, int64_t nb, hipStream_t st) {
   const dim3 grid((unsigned)(nb * a.gparts));
@@ -241,33 +144,18 @@ int64_t qi_beam_power_scratch_bytes(int dtype, int64_t C, int64_t nf, int64_t G,
 int qi_beam_power(int dtype, int device, const void* csd, int64_t C, int64_t nf, const double* freq_hz, const void* delays_s,
                   int64_t G, const int64_t* band_first, int64_t nb, int normalize, void* power, void* peak_index,
                   void* peak_value, void* scratch, int64_t scratch_bytes, qi_stream stream) {
-  QI_TRY(beam_shape_check(dtype, C, nf, G, nb));
-  QI_REQUIRE(csd && freq_hz && delays_s && scratch, "null argument");
-  QI_REQUIRE(power, "power is null: nothing to produce");
-  if (band_first) {
-    QI_REQUIRE(band_first[0] >= 0 && band_first[0] < nf, "band offsets start at %lld: outside 0..%lld", (long long)band_first[0],
-               (long long)nf);
-    for (int64_t b = 0; b < nb; ++b)
-      QI_REQUIRE(band_first[b + 1] > band_first[b], "band offsets are not strictly ascending at band %lld", (long long)b);
-    QI_REQUIRE(band_first[nb] <= nf, "band offsets end at %lld, past the %lld matrices", (long long)band_first[nb], (long long)nf);
-  } else {
-    QI_REQUIRE(nb == nf, "no band table: every matrix is its own band, nb must be nf");
-  }
-  QI_TRY(require_scratch(scratch_bytes, (int64_t)beam_scratch(nf, nb)));
-  QI_REQUIRE(aligned(csd, 2 * elem_size(dtype)) && aligned(delays_s, 8) && aligned(power, elem_size(dtype)) &&
-                 aligned(peak_index, 8) && aligned(peak_value, elem_size(dtype)) && aligned(scratch, 16),
-             "misaligned pointer");
+  QI_TRY(beam_call_check(dtype, C, nf, G, nb, csd, freq_hz, delays_s, band_first, power, peak_index, peak_value, scratch,
+                         scratch_bytes));
   DeviceGuard guard(device);
   hipStream_t st = (hipStream_t)stream;
-  double* freq = static_cast<double*>(scratch);
-  int64_t* first = band_first ? reinterpret_cast<int64_t*>(static_cast<char*>(scratch) + beam_freq_bytes(nf)) : nullptr;
-  QI_TRY(put_words(freq, freq_hz, nf, st));
-  if (band_first) QI_TRY(put_words(first, band_first, nb + 1, st));
+  double* freq;
+  int64_t* first;
+  QI_TRY(beam_put_tables(scratch, freq_hz, nf, band_first, nb, st, &freq, &first));
   return by_dtype(dtype, [&](auto t) -> int {
     using T = decltype(t);
     const int ntile = (int)ceil_div(C, kBeamTile);
     const int64_t tiles = ceil_div(G, kBeamTile);
-    const bool many = nb * ceil_div(tiles, kBeamWavesMany) >= kBeamFill;
+    const bool many = beam_many(G, nb);
     BeamArgs<T> a{};
     a.S = static_cast<const cplx<T>*>(csd);
     a.tau = static_cast<const double*>(delays_s);

@@ -721,6 +721,73 @@ def beam_power(csd, frequency_hz, delays_s, bands=None, normalize=False, peaks=F
     return finish(power, was_numpy, False)
 
 
+def _matrix_stack(a, what):
+    """A non-empty [nf, C, C] complex64 / complex128 stack, NumPy or tensor -> (contiguous device tensor, was_numpy)."""
+    was_numpy = not isinstance(a, torch.Tensor)
+    s = torch.from_numpy(np.ascontiguousarray(a)) if was_numpy else a
+    if s.dim() != 3 or s.dtype not in (torch.complex64, torch.complex128) or 0 in s.shape or s.shape[1] != s.shape[2]:
+        raise ValueError(f"{what} must be a non-empty complex64 / complex128 [nf, C, C], got {s.dtype} {tuple(s.shape)}")
+    return s.to(s.device if s.is_cuda else default_device()).contiguous(), was_numpy
+
+
+def csd_whiten(csd, loading=0.0, info=False):
+    """Whitening factors of Hermitian cross-spectral matrices (qi_csd_whiten), what capon_power consumes: for every matrix
+    R = csd[f] + loading * mean(diag csd[f]) I = L L^H (Cholesky), whitener[f] = V = L^-H -- upper triangular, R^-1 = V V^H,
+    V^H R V = I.  csd: [nf, C, C] complex64 / complex128 as cross_spectra and styx_fft.csd_matrix_pow2 return it, C <= 64;
+    only the lower triangle and the real part of the diagonal are read.  loading >= 0, relative to the mean auto-power.
+    -> whitener [nf, C, C], or (whitener, info [nf] int32) with info=True: 0, or the 1-based index of the first pivot that is
+    not a positive finite number (LAPACK's potrf); such a matrix's whitener is NaN on and above the diagonal.  NumPy in ->
+    NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    s, was_numpy = _matrix_stack(csd, "csd")
+    n_f, n_ch, _ = s.shape
+    dev = s.device
+    code = _lib.dtype_code(torch.float32 if s.dtype == torch.complex64 else torch.float64)
+    whitener = torch.empty_like(s)
+    flags = torch.empty(n_f, dtype=torch.int32, device=dev) if info else None
+    _lib.call(lib.qi_csd_whiten, dev, code, dev.index, _lib.ptr(s), n_ch, n_f, float(loading), _lib.ptr(whitener), _lib.ptr(flags))
+    if info:
+        return finish(whitener, was_numpy, False), finish(flags, was_numpy, False)
+    return finish(whitener, was_numpy, False)
+
+
+def capon_power(whitener, frequency_hz, delays_s, bands=None, peaks=False):
+    """Capon (minimum-variance) power of whitened cross-spectral matrices over a grid of delay sets (qi_beam_capon): with
+    e[f, g, i] = exp(2 pi i frequency_hz[f] delays_s[g, i]) and V = whitener[f], D[f, g] = sum_j |sum_i conj(V[i, j]) e_i|^2
+    = e^H R^-1 e, and power[b, g] = sum over the band's matrices of 1 / D -- in the units of beam_power with normalize=False,
+    and never above it on the same loaded matrices.  whitener: [nf, C, C] complex64 / complex128 as csd_whiten returns it,
+    C <= 64; frequency_hz, delays_s, bands and peaks: as in beam_power.  A band that holds a matrix csd_whiten flagged is NaN,
+    and its peak the first NaN.  -> power [nb, G] real, or (power, peak_index [nb] int64, peak_value [nb]) with peaks=True.
+    NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    v, was_numpy = _matrix_stack(whitener, "whitener")
+    n_f, n_ch, _ = v.shape
+    dev = v.device
+    f_host, f_ptr = _lib.darr(frequency_hz)
+    if f_host.shape != (n_f,):
+        raise ValueError(f"frequency_hz must hold one value per matrix ({n_f}), got shape {f_host.shape}")
+    tau = delays_s if isinstance(delays_s, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(delays_s))
+    if tau.dim() != 2 or tau.shape[0] < 1 or tau.shape[1] != n_ch:
+        raise ValueError(f"delays_s must be [G, {n_ch}], got shape {tuple(tau.shape)}")
+    tau = tau.to(dev).to(torch.float64).contiguous()
+    n_g = tau.shape[0]
+    b_host, b_ptr = (None, None) if bands is None else _lib.iarr(bands)
+    if b_host is not None and (b_host.ndim != 1 or b_host.size < 2):
+        raise ValueError(f"bands must be a list of nb + 1 offsets, got shape {b_host.shape}")
+    n_b = n_f if b_host is None else b_host.size - 1
+    rdtype = torch.float32 if v.dtype == torch.complex64 else torch.float64
+    code = _lib.dtype_code(rdtype)
+    scratch, nbytes = _lib.scratch(lib.qi_beam_capon_scratch_bytes, dev, code, n_ch, n_f, n_g, n_b)
+    power = torch.empty((n_b, n_g), dtype=rdtype, device=dev)
+    index = torch.empty(n_b, dtype=torch.int64, device=dev) if peaks else None
+    value = torch.empty(n_b, dtype=rdtype, device=dev) if peaks else None
+    _lib.call(lib.qi_beam_capon, dev, code, dev.index, _lib.ptr(v), n_ch, n_f, f_ptr, _lib.ptr(tau), n_g, b_ptr, n_b,
+              _lib.ptr(power), _lib.ptr(index), _lib.ptr(value), _lib.ptr(scratch), nbytes)
+    if peaks:
+        return finish(power, was_numpy, False), finish(index, was_numpy, False), finish(value, was_numpy, False)
+    return finish(power, was_numpy, False)
+
+
 def _record_shape(a, what="signal", nonempty=True):
     """Shape (n,) or (C, n) of records, NumPy or tensor, checked before anything needs the device; n is its last entry."""
     shape = tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
