@@ -47,6 +47,7 @@ int qi_plan_create(qi_plan** plan, const qi_plan_desc* desc) {
   if (const char* e = tune_env("QI_NATIVE_FWD")) p->native_fwd = atoi(e);
   if (const char* e = tune_env("QI_NATIVE_FWD_LOW")) p->native_fwd_low = atoi(e);
   if (const char* e = tune_env("QI_NATIVE_JOINT_DEAL")) p->native_joint_deal = atoi(e);
+  if (const char* e = tune_env("QI_NATIVE_ZOOM_MERGE")) p->native_zoom_merge = atoi(e);
 #ifdef QI_NATIVE_STAMPS
   if (tune_env("QI_NATIVE_STAMPS")) {
     if (hipMalloc((void**)&p->stamps, 65536 * 8 * sizeof(unsigned long long)) != hipSuccess) p->stamps = nullptr;

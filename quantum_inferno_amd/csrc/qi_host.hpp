@@ -442,6 +442,8 @@ struct qi_plan {
   int native_fwd_low = 1;      // ... only the bins near DC when nothing reads the others (forward_low); 0: always every bin
   int native_joint_deal = 1;   // qi_cwt_stx below batch_from records: the joint block launch deals a reach group's styx and Stockwell
                                // bands as one sequence (build_joint_items); 0: the tables' own item lists, paired chunk by chunk
+  int native_zoom_merge = 1;   // qi_cwt_stx below batch_from records: a table's zoom classes of equal zoom_steps run as one merged
+                               // row with one per-time plane (plan_zoom_rows); 0: a row (and a plane) per class
   unsigned long long* stamps = nullptr;  // diagnostic builds: phase cycle counters of the last pass-2 launch
   unsigned long long* blk_stamps = nullptr;  // idem, last block launch
   int native_group = 0;        // wide bands per launch group (0: all in one group)

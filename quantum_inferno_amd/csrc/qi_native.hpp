@@ -229,6 +229,9 @@ constexpr int zoom_steps(int cls) { return zoom_grid(cls) <= 2 ? 16 : (64 >> zoo
 constexpr int kZoomOversample = 4;
 // classes 5 and 6 run on their own in calls (tiles) of at least this many records; below, as part of the 10-tap class 0
 constexpr int kZoomShortFrom = 4;
+// Merged rows (qi_cwt_stx with few records, plan_zoom_rows): the classes of zoom_steps 16 of a table share their rows, one
+// workgroup per time tile walking its bands of each class in class order into one per-time plane and one statistics slot.
+constexpr int kZoomMergeClasses = 0x67;  // classes 0, 1, 2, 5, 6
 template <typename T>
 struct ZoomArgs {
   int64_t n, Lf;
@@ -241,6 +244,11 @@ struct ZoomArgs {
   // bands [lvl_first[g], lvl_first[g] + lvl_count[g]) of `bands`, and writes per-time plane chunk_base + blockIdx.y
   int32_t lvl_first[kZoomClasses], lvl_count[kZoomClasses], lvl_chunk0[kZoomClasses], lvl_nchunk[kZoomClasses];
   int64_t lvl_stat_base[kZoomClasses];
+  // merge_mask != 0: rows [0, merge_nchunk) are the merged rows of the classes in the mask (their lvl_nchunk is 0); row c
+  // walks bands c, c + merge_nchunk, ... of each class, writes plane chunk_base + c and stat slots merge_stat_base +
+  // c * groups + group; its bands fill the partial slots they fill in rows of their own
+  int32_t merge_mask, merge_nchunk;
+  int64_t merge_stat_base;
   const float* lvl_weights[kZoomClasses];  // [taps][64] interpolation weights of the lanes, per class
   const cplx<T>* X;        // [C][x_mask + 1] spectra of the records: bin k of Lf at (k << x_shift) & x_mask
   int32_t x_shift;         // 1: X is the spectrum of the records zero-padded to twice Lf (bin k of Lf = bin 2k)

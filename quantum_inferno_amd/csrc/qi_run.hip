@@ -286,9 +286,12 @@ template int run_stx_leftover<double>(qi_plan*, const void*, int64_t, const qi_t
 const qi_plan::BlockTable::ItemList& dual_list(const qi_plan* p, int kind, int cut) {
   return cut == qi_plan::kDualJoint ? p->blk[kind].joint : p->blk[kind].var[cut];
 }
-// does a run of table `kind` take its share of the table-first dealing?  joint_call: it is a half of a qi_cwt_stx tile
+// the requests whose tail reads per-time planes of both tables of a joint call with few records: a half of a qi_cwt_stx tile
+// (joint_call: with the per-time sums and a reduction) at item cut 0
+bool joint_planes_wanted(int kind, int cut, bool joint_call) { return joint_call && cut == 0 && kind != 1; }
+// does such a run of table `kind` take its share of the table-first dealing of the block launch?
 bool joint_deal_wanted(const qi_plan* p, int kind, int cut, bool joint_call) {
-  return joint_call && cut == 0 && kind != 1 && p->native_joint_deal != 0 && p->blk[0].ready && p->blk[2].ready;
+  return joint_planes_wanted(kind, cut, joint_call) && p->native_joint_deal != 0 && p->blk[0].ready && p->blk[2].ready;
 }
 // Work items of the joint block launch: the items of the styx table (0) and of the Stockwell table (2) on the same
 // (reach group, block) are paired chunk by chunk -- one forward transform serves both; what has no partner stays single;
@@ -646,13 +649,19 @@ struct ZoomRows {
   int64_t stat_base[native::kZoomClasses] = {}, groups[native::kZoomClasses] = {};
   int planes = 0;                // rows of all classes
   int64_t stats = 0, slots = 0;  // stat slots of the launch; most partial slots a band fills
+  // the merged rows (rows 0 .. merge_nchunk - 1, when merge_mask != 0): the classes of the mask run in them and have no
+  // rows of their own; their stat slots come first
+  int merge_mask = 0, merge_nchunk = 0;
 };
 
 constexpr int kZoomWaves = 2048;    // waves each level of a zoom launch of one table should have at least
 constexpr int kZoomWgsJoint = 768;  // workgroups per table in the joint launch of qi_cwt_stx (512 .. 1024 measured within 1.5 %)
 
-// joint: the launch is one half of a joint launch of qi_cwt_stx
-ZoomRows plan_zoom_rows(const qi_plan* p, int kind, int64_t C, bool joint) {
+// joint: the launch is one half of a joint launch of qi_cwt_stx; merge: a half of a qi_cwt_stx tile at item cut 0 (fewer
+// than batch_from records) that is asked for the per-time sums and a reduction (joint_planes_wanted) -- then the classes
+// of kZoomMergeClasses, whose rows tile the record alike, run in merged rows when there are two or more of them: one
+// per-time plane where each class had one.  A rule of the tables and of that condition alone.
+ZoomRows plan_zoom_rows(const qi_plan* p, int kind, int64_t C, bool joint, bool merge) {
   constexpr int NL = native::kZoomClasses;
   const auto& zt = p->nat[kind];
   const int64_t n = p->n;
@@ -712,6 +721,22 @@ ZoomRows plan_zoom_rows(const qi_plan* p, int kind, int64_t C, bool joint) {
       r.nchunk[g] = nc;
     }
   }
+  // merged rows: the classes of kZoomMergeClasses the call uses, when there are two or more, give up their rows for as many
+  // merged rows as the class with the most had (one each at 2^20 samples: one merged row); merged row c walks bands
+  // c, c + merge_nchunk, ... of every class of the mask
+  int merged = 0;
+  for (int g = 0; g < NL; ++g)
+    if (r.count[g] > 0 && (native::kZoomMergeClasses >> g & 1)) merged += 1;
+  if (merge && p->native_zoom_merge != 0 && merged >= 2) {
+    for (int g = 0; g < NL; ++g) {
+      if (r.count[g] <= 0 || !(native::kZoomMergeClasses >> g & 1)) continue;
+      r.merge_mask |= 1 << g;
+      if (r.nchunk[g] > r.merge_nchunk) r.merge_nchunk = r.nchunk[g];
+      r.nchunk[g] = 0;
+    }
+    r.planes = r.merge_nchunk;
+    r.stats = (int64_t)r.merge_nchunk * native::zoom_groups(n, 0);  // (every class of the mask has class 0's groups)
+  }
   for (int g = 0; g < NL; ++g) {
     if (r.count[g] <= 0) continue;
     r.planes += r.nchunk[g];
@@ -720,9 +745,10 @@ ZoomRows plan_zoom_rows(const qi_plan* p, int kind, int64_t C, bool joint) {
     if (r.groups[g] > r.slots) r.slots = r.groups[g];
   }
   if (tune_env("QI_NATIVE_VERBOSE"))
-    fprintf(stderr, "[qi run] zoom launch of table %d: bands per class %d %d %d %d %d | 6-tap %d 4-tap %d in rows %d %d %d %d %d | %d %d\n", kind,
+    fprintf(stderr, "[qi run] zoom launch of table %d: bands per class %d %d %d %d %d | 6-tap %d 4-tap %d in rows %d %d %d %d %d | %d %d, %d merged rows of classes 0x%x, %d planes\n", kind,
             r.count[0], r.count[1], r.count[2], r.count[3], r.count[4], r.count[5],
-            r.count[6], r.nchunk[0], r.nchunk[1], r.nchunk[2], r.nchunk[3], r.nchunk[4], r.nchunk[5], r.nchunk[6]);
+            r.count[6], r.nchunk[0], r.nchunk[1], r.nchunk[2], r.nchunk[3], r.nchunk[4], r.nchunk[5], r.nchunk[6], r.merge_nchunk,
+            r.merge_mask, r.planes);
   return r;
 }
 
@@ -733,6 +759,7 @@ int upload_band_slots(qi_plan* p, int kind, int cut, int64_t nblk_max, bool bloc
   if (p->d_band_slots[kind][cut]) return QI_OK;
   std::vector<int32_t> slots((size_t)p->nat[kind].nbands, 0);
   for (int32_t r : p->nat[kind].h_rows) slots[r] = (int32_t)nblk_max;
+  // (a merged row has the groups of its classes' own rows: the same slots under either layout)
   for (const auto& z : p->nat[kind].h_zoom) slots[z.first] = (int32_t)native::zoom_groups(p->n, z.second);
   if (blocks)
     for (const auto& b : p->blk[kind].var[cut].h_bands) slots[b.first] = b.second;
@@ -770,7 +797,10 @@ native::ZoomArgs<float> zoom_args(const qi_plan* p, int kind, const ZoomRows& r,
   z.split_part = s.zadd;
   z.split_rows = nsplit;
   z.debug = p->native_debug;
-  int chunk0 = 0;
+  z.merge_mask = r.merge_mask;
+  z.merge_nchunk = r.merge_nchunk;
+  z.merge_stat_base = stat_base;  // (the merged rows' slots come first)
+  int chunk0 = r.merge_nchunk;
   for (int g = 0; g < native::kZoomClasses; ++g) {
     z.lvl_count[g] = r.count[g];
     z.lvl_chunk0[g] = chunk0;
@@ -901,7 +931,8 @@ int run_native(qi_plan* p, int kind, const void* sig_v, int64_t C, const qi_tfr_
   // zoom engine launch (narrow bands of the main table): its chunks come last
   const auto& zt = p->nat[kind];
   const bool zoom = zt.nzoom > 0;
-  const ZoomRows zr = plan_zoom_rows(p, kind, C, defer || (finish && (finish->active || probe)));
+  const ZoomRows zr = plan_zoom_rows(p, kind, C, defer || (finish && (finish->active || probe)),
+                                     joint_planes_wanted(kind, cut, (defer || finish) && out->power_time && (out->power_band || out->stats)));
   const int chunk_z0 = chunk_total;
   chunk_total += zr.planes;
   int64_t nbk = tp.nblk_max + (shorts ? 1 : 0);  // partial slots per band (last one: edge samples)
@@ -1025,9 +1056,9 @@ int64_t joint_planes(qi_plan* p, int kind) {
     return 0;
   const int64_t C = 1;
   const int cut = C >= batch_from(p) ? 1 : 0;
-  int64_t planes = plan_two_pass(p, kind, C, p->native_rows).chunk_total + plan_zoom_rows(p, kind, C, true).planes;
+  const bool joint_deal = joint_deal_wanted(p, kind, cut, true);
+  int64_t planes = plan_two_pass(p, kind, C, p->native_rows).chunk_total + plan_zoom_rows(p, kind, C, true, joint_planes_wanted(kind, cut, true)).planes;
   if (p->blk[kind].ready) {
-    const bool joint_deal = joint_deal_wanted(p, kind, cut, true);
     if (joint_deal && build_dual_items(p, qi_plan::kDualJoint) != QI_OK) return 0;
     planes += dual_list(p, kind, joint_deal ? qi_plan::kDualJoint : cut).nplanes;
   }

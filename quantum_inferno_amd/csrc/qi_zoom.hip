@@ -31,39 +31,62 @@ __device__ __forceinline__ float lane_value(float v, int lane) {
   return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), lane));
 }
 
-// Fine stage of one level.  PHASOR: multiply by the carrier exp(2 pi i k_c f / Lf) (Gabor banks; the Stockwell bands
-// are at baseband already).  Output sample t is the full-length sample f = t + off, off = 64 A - e (e = 0 or 1).
+// What the band loops of one row share (zoom_prologue): the lane's place along time, the per-time sums of its outputs
+// over the row's bands (colp: one per wave-step), the row's statistics and the parity of the double-buffered s_red.
+template <typename T, int STEPS>
+struct ZoomLane {
+  int tid, lane, wv;
+  int64_t ch;
+  uint32_t step_a;  // first wave-step of this wave
+  uint32_t t_base;  // output sample of wave-step s: t_base + 64 s
+  T colp[STEPS];
+  T mx;
+  double plogp;
+  int par;  // s_red is double-buffered so that one barrier per band is enough
+};
+
+// wave gw of a row with STEPS wave-steps per wave covers wave-steps STEPS gw ..., lane l of wave-step s is output 64 s + l
+template <typename T, int STEPS>
+__device__ __forceinline__ void zoom_prologue(ZoomLane<T, STEPS>& w) {
+  constexpr int NW = kZoomThreads / kWave;
+  w.tid = threadIdx.x;
+  w.lane = w.tid & (kWave - 1);
+  w.wv = w.tid / kWave;
+  w.ch = blockIdx.z;
+  const int64_t gw = (int64_t)blockIdx.x * NW + w.wv;  // wave index along time
+  w.step_a = (uint32_t)gw * STEPS;
+  w.t_base = w.step_a * kZoomD + (uint32_t)w.lane;
+#pragma unroll
+  for (int s = 0; s < STEPS; ++s) w.colp[s] = T(0);
+  w.mx = T(0);
+  w.plogp = 0.0;
+  w.par = 0;
+}
+
+// Fine stage of one class: bands chunk, chunk + nchunk, ... of the class's list, added into the row's sums.  STEPS: the
+// wave-steps per wave of the row (a row of the class's own: zoom_steps(LEVEL)).  PHASOR: multiply by the carrier
+// exp(2 pi i k_c f / Lf) (Gabor banks; the Stockwell bands are at baseband already).  Output sample t is the full-length
+// sample f = t + off, off = 64 A - e (e = 0 or 1).
 // SDESC: the band descriptors by scalar loads (load_uniform: no vector registers for the descriptor fetched a band ahead;
 // -3 % of the interpolation launch at 64 records).  With one or two records a workgroup has few bands and the first
 // descriptor's scalar-cache miss shows (+1 % of the step): those calls keep the vector loads.
-template <typename T, int LEVEL, bool PHASOR, bool COEF, bool BITS, bool SDESC>
-__device__ __forceinline__ void zoom_level(const ZoomArgs<T>& a, int chunk, int row, double (*s_red)[kZoomThreads / kWave],
-                                           double (*s_fin)[kZoomThreads / kWave]) {
-  constexpr int NW = kZoomThreads / kWave, S = zoom_span(LEVEL), TAPS = zoom_taps(LEVEL), STEPS = zoom_steps(LEVEL);
-  if ((int64_t)blockIdx.x >= a.n / ((int64_t)kZoomD * STEPS * NW)) return;  // this level has fewer groups along time
-  const int nchunk = a.lvl_nchunk[LEVEL];
+template <typename T, int LEVEL, int STEPS, bool PHASOR, bool COEF, bool BITS, bool SDESC>
+__device__ __forceinline__ void zoom_bands(const ZoomArgs<T>& a, int chunk, int nchunk, ZoomLane<T, STEPS>& w,
+                                           double (*s_red)[kZoomThreads / kWave]) {
+  constexpr int NW = kZoomThreads / kWave, S = zoom_span(LEVEL), TAPS = zoom_taps(LEVEL);
   const float* __restrict__ weights = a.lvl_weights[LEVEL];
   constexpr int GRID = zoom_grid(LEVEL), HALF = zoom_ntap(LEVEL) / 2 - 1;
   constexpr int WIN = (STEPS - 1) * S + TAPS;  // coarse samples one wave needs per band
   static_assert(WIN <= 2 * kWave, "the window of one wave must fit two registers of its lanes");
   constexpr bool TWO = WIN > kWave;  // the window spills into a second vector register
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  const int64_t ch = blockIdx.z;
-  const int64_t gw = (int64_t)blockIdx.x * NW + wv;  // wave index along time
-  const uint32_t step_a = (uint32_t)gw * STEPS;      // first wave-step of this wave
+  const int tid = w.tid, lane = w.lane, wv = w.wv;
+  const int64_t ch = w.ch;
+  const uint32_t step_a = w.step_a, t_base = w.t_base;
   const uint32_t mmask = (uint32_t)((a.Lf / kZoomD) << GRID) - 1u, lmask = (uint32_t)a.Lf - 1u;
   const int plog2 = ilog2((int)(((a.Lf / kZoomD) << GRID) / kBlk));  // log2 of the planes per band
   float wgt[TAPS];
 #pragma unroll
   for (int j = 0; j < TAPS; ++j) wgt[j] = weights[j * kWave + lane];  // [tap][lane]: coalesced
-  T colp[STEPS];
-#pragma unroll
-  for (int s = 0; s < STEPS; ++s) colp[s] = T(0);
-  T mx = T(0);
-  double plogp = 0.0;
-  const uint32_t t_base = step_a * kZoomD + (uint32_t)lane;  // output sample of wave-step s: t_base + 64 s
-  int par = 0;  // s_red is double-buffered so that one barrier per band is enough
-
   // lane i holds coarse sample S (step_a + A) - HALF + i of the band: wave-step s interpolates from lanes s S ..
   // s S + TAPS - 1.  Coarse sample tau = P tau2 + tau1 sits at plane tau1, position tau2 (the coarse stage's layout).
   // The samples (and the descriptor) of the next band are requested a band ahead.
@@ -150,37 +173,42 @@ __device__ __forceinline__ void zoom_level(const ZoomArgs<T>& a, int chunk, int 
       const T m2 = norm2(z.x, z.y);
       if (BITS) *reinterpret_cast<T*>(bits_row + (size_t)(tt * (uint32_t)sizeof(T))) = log2_t(sqrt_t(m2) + a.eps);
       const T p = mul_rn(pscale, m2);
-      colp[s] += p;
+      w.colp[s] += p;
       rowacc += p;
-      mx = max_t(mx, p);
+      w.mx = max_t(w.mx, p);
       pl += plog2p(p);
     }
-    plogp += (double)pl;
+    w.plogp += (double)pl;
     if (a.part_band) {
       // one partial per workgroup and band: wave sums through LDS
       const double r = wave_sum((double)rowacc);
-      if (lane == 0) s_red[par][wv] = r;
+      if (lane == 0) s_red[w.par][wv] = r;
       __syncthreads();
       if (tid == 0 && !part)
-        a.part_band[((int64_t)ch * a.panel_bands + bd.out_band) * a.nblk + blockIdx.x] = fold_band_sum<NW>(s_red[par]);
-      par ^= 1;
+        a.part_band[((int64_t)ch * a.panel_bands + bd.out_band) * a.nblk + blockIdx.x] = fold_band_sum<NW>(s_red[w.par]);
+      w.par ^= 1;
     }
   }
+}
 
+// the row's per-time plane `plane` of the tile and its statistics slot `stat` of the launch's
+template <typename T, int STEPS>
+__device__ __forceinline__ void zoom_epilogue(const ZoomArgs<T>& a, const ZoomLane<T, STEPS>& w, int plane, int64_t stat,
+                                              double (*s_fin)[kZoomThreads / kWave]) {
+  constexpr int NW = kZoomThreads / kWave;
   T tot = T(0);
   char* __restrict__ time_row = reinterpret_cast<char*>(
-      a.time_part ? a.time_part + ((int64_t)ch * a.chunk_total + a.chunk_base + row) * a.n : nullptr);
+      a.time_part ? a.time_part + ((int64_t)w.ch * a.chunk_total + a.chunk_base + plane) * a.n : nullptr);
 #pragma unroll
   for (int s = 0; s < STEPS; ++s) {
-    tot += colp[s];
-    const uint32_t tt = t_base + (uint32_t)(kZoomD * s);
-    if (time_row) *reinterpret_cast<T*>(time_row + (size_t)(tt * (uint32_t)sizeof(T))) = colp[s];
+    tot += w.colp[s];
+    const uint32_t tt = w.t_base + (uint32_t)(kZoomD * s);
+    if (time_row) *reinterpret_cast<T*>(time_row + (size_t)(tt * (uint32_t)sizeof(T))) = w.colp[s];
   }
   if (a.part_stat) {
-    const PanelStats ps = fold_stats<NW>(mx, tot, plogp, s_fin, tid);
-    if (tid == 0) {
-      const int64_t groups = a.n / ((int64_t)kZoomD * STEPS * NW);
-      double* o = a.part_stat + ((int64_t)ch * a.stat_stride + a.lvl_stat_base[LEVEL] + (int64_t)chunk * groups + blockIdx.x) * 3;
+    const PanelStats ps = fold_stats<NW>(w.mx, tot, w.plogp, s_fin, w.tid);
+    if (w.tid == 0) {
+      double* o = a.part_stat + ((int64_t)w.ch * a.stat_stride + stat) * 3;
       o[0] = ps.mx;
       o[1] = ps.sum;
       o[2] = ps.plogp;
@@ -188,11 +216,48 @@ __device__ __forceinline__ void zoom_level(const ZoomArgs<T>& a, int chunk, int 
   }
 }
 
-// row y of a table's fine launch = (level, chunk of the level's band list)
+// a row of one class: chunk `chunk` of its band list
+template <typename T, int LEVEL, bool PHASOR, bool COEF, bool BITS, bool SDESC>
+__device__ __forceinline__ void zoom_level(const ZoomArgs<T>& a, int chunk, int row, double (*s_red)[kZoomThreads / kWave],
+                                           double (*s_fin)[kZoomThreads / kWave]) {
+  constexpr int NW = kZoomThreads / kWave, STEPS = zoom_steps(LEVEL);
+  const int64_t groups = a.n / ((int64_t)kZoomD * STEPS * NW);
+  if ((int64_t)blockIdx.x >= groups) return;  // this level has fewer groups along time
+  ZoomLane<T, STEPS> w;
+  zoom_prologue(w);
+  zoom_bands<T, LEVEL, STEPS, PHASOR, COEF, BITS, SDESC>(a, chunk, a.lvl_nchunk[LEVEL], w, s_red);
+  zoom_epilogue(a, w, row, a.lvl_stat_base[LEVEL] + (int64_t)chunk * groups + blockIdx.x, s_fin);
+}
+
+// Merged row `chunk` (the first merge_nchunk rows of a table whose merge_mask is set, see plan_zoom_rows): the band loops of
+// every class in the mask, in class order, into one per-time plane and one statistics slot.  The classes of the mask share
+// zoom_steps, so their rows would tile the record alike; a band's arithmetic is that of its own row.
 template <typename T, bool PHASOR, bool COEF, bool BITS, bool SDESC>
+__device__ __forceinline__ void zoom_merged(const ZoomArgs<T>& a, int chunk, double (*s_red)[kZoomThreads / kWave],
+                                            double (*s_fin)[kZoomThreads / kWave]) {
+  constexpr int NW = kZoomThreads / kWave, STEPS = zoom_steps(0);
+  static_assert(STEPS == zoom_steps(1) && STEPS == zoom_steps(2) && STEPS == zoom_steps(5) && STEPS == zoom_steps(6),
+                "the classes of a merged row tile the record alike");
+  const int64_t groups = a.n / ((int64_t)kZoomD * STEPS * NW);
+  if ((int64_t)blockIdx.x >= groups) return;
+  const int nchunk = a.merge_nchunk;
+  ZoomLane<T, STEPS> w;
+  zoom_prologue(w);
+  if (a.merge_mask & 1) zoom_bands<T, 0, STEPS, PHASOR, COEF, BITS, SDESC>(a, chunk, nchunk, w, s_red);
+  if (a.merge_mask & 2) zoom_bands<T, 1, STEPS, PHASOR, COEF, BITS, SDESC>(a, chunk, nchunk, w, s_red);
+  if (a.merge_mask & 4) zoom_bands<T, 2, STEPS, PHASOR, COEF, BITS, SDESC>(a, chunk, nchunk, w, s_red);
+  if (a.merge_mask & 32) zoom_bands<T, 5, STEPS, PHASOR, COEF, BITS, SDESC>(a, chunk, nchunk, w, s_red);
+  if (a.merge_mask & 64) zoom_bands<T, 6, STEPS, PHASOR, COEF, BITS, SDESC>(a, chunk, nchunk, w, s_red);
+  zoom_epilogue(a, w, chunk, a.merge_stat_base + (int64_t)chunk * groups + blockIdx.x, s_fin);
+}
+
+// row y of a table's fine launch = (level, chunk of the level's band list); MERGED: a table of the launch has a merged row
+// (its first rows; the classes of its mask have no rows of their own)
+template <typename T, bool PHASOR, bool COEF, bool BITS, bool SDESC, bool MERGED>
 __device__ __forceinline__ void zoom_row(const ZoomArgs<T>& a, int y, double (*s_red)[kZoomThreads / kWave],
                                          double (*s_fin)[kZoomThreads / kWave]) {
-  if (y < a.lvl_chunk0[0] + a.lvl_nchunk[0]) zoom_level<T, 0, PHASOR, COEF, BITS, SDESC>(a, y - a.lvl_chunk0[0], y, s_red, s_fin);
+  if (MERGED && y < a.merge_nchunk) zoom_merged<T, PHASOR, COEF, BITS, SDESC>(a, y, s_red, s_fin);
+  else if (y < a.lvl_chunk0[0] + a.lvl_nchunk[0]) zoom_level<T, 0, PHASOR, COEF, BITS, SDESC>(a, y - a.lvl_chunk0[0], y, s_red, s_fin);
   else if (y < a.lvl_chunk0[1] + a.lvl_nchunk[1]) zoom_level<T, 1, PHASOR, COEF, BITS, SDESC>(a, y - a.lvl_chunk0[1], y, s_red, s_fin);
   else if (y < a.lvl_chunk0[2] + a.lvl_nchunk[2]) zoom_level<T, 2, PHASOR, COEF, BITS, SDESC>(a, y - a.lvl_chunk0[2], y, s_red, s_fin);
   else if (y < a.lvl_chunk0[3] + a.lvl_nchunk[3]) zoom_level<T, 3, PHASOR, COEF, BITS, SDESC>(a, y - a.lvl_chunk0[3], y, s_red, s_fin);
@@ -206,22 +271,45 @@ template <typename T, bool PHASOR, bool COEF, bool BITS>
 __global__ void __launch_bounds__(kZoomThreads) k_zoom(ZoomArgs<T> a) {
   __shared__ double s_red[2][kZoomThreads / kWave];
   __shared__ double s_fin[3][kZoomThreads / kWave];
-  zoom_row<T, PHASOR, COEF, BITS, false>(a, blockIdx.y, s_red, s_fin);
+  zoom_row<T, PHASOR, COEF, BITS, false, false>(a, blockIdx.y, s_red, s_fin);
 }
 
-// qi_cwt_stx: the rows of the styx table (a0, with carrier) and of the Stockwell table (a2) in one launch
-template <typename T, bool COEF, bool BITS, bool SDESC>
-__global__ void __launch_bounds__(kZoomThreads) k_zoom2(ZoomArgs<T> a0, ZoomArgs<T> a2, int rows0) {
+// qi_cwt_stx: the rows of the styx table (a0, with carrier) and of the Stockwell table (a2) in one launch; rows0 = 0 or
+// every row of the grid: one table alone (a half of a joint tile with merged rows that is launched on its own).
+// Calls of few records that write coefficients (COEF, !SDESC) are held to four waves per SIMD: the 1536 workgroups of a
+// launch with a row per class run 10 % longer at five (99.8 against 90.8 us at 2^20 samples, order 3), and the band loop sits
+// at 95-97 registers, on the boundary between the two.  The merged rows' 512 workgroups are two waves per SIMD either way;
+// every other instantiation keeps what its register count gives it.
+template <typename T, bool COEF, bool BITS, bool SDESC, bool MERGED>
+__global__ void __launch_bounds__(kZoomThreads) __attribute__((amdgpu_waves_per_eu(1, COEF && !SDESC ? 4 : 8)))
+k_zoom2(ZoomArgs<T> a0, ZoomArgs<T> a2, int rows0) {
   __shared__ double s_red[2][kZoomThreads / kWave];
   __shared__ double s_fin[3][kZoomThreads / kWave];
-  if ((int)blockIdx.y < rows0) zoom_row<T, true, COEF, BITS, SDESC>(a0, blockIdx.y, s_red, s_fin);
-  else zoom_row<T, false, COEF, BITS, SDESC>(a2, (int)blockIdx.y - rows0, s_red, s_fin);
+  if ((int)blockIdx.y < rows0) zoom_row<T, true, COEF, BITS, SDESC, MERGED>(a0, blockIdx.y, s_red, s_fin);
+  else zoom_row<T, false, COEF, BITS, SDESC, MERGED>(a2, (int)blockIdx.y - rows0, s_red, s_fin);
 }
 
 template <typename T, bool PHASOR>
 int launch_zoom_v(const ZoomArgs<T>& a, dim3 grid, hipStream_t st) {
   with_panels(a.coef != nullptr, a.bits != nullptr, [&](auto C, auto B) {
     k_zoom<T, PHASOR, C.value, B.value><<<grid, kZoomThreads, 0, st>>>(a);
+  });
+  QI_LAUNCH_CHECK();
+  return QI_OK;
+}
+
+// the joint kernel on `grid`: rows [0, rows0) are a0's, the rest a2's
+int launch_zoom2_v(const ZoomArgs<float>& a0, const ZoomArgs<float>& a2, int rows0, dim3 grid, hipStream_t st) {
+  const bool sdesc = grid.z >= 4;  // (see zoom_bands)
+  const bool merged = a0.merge_mask != 0 || a2.merge_mask != 0;
+  with_panels(a0.coef != nullptr, a0.bits != nullptr, [&](auto C, auto B) {
+    if (merged) {
+      if (sdesc) k_zoom2<float, C.value, B.value, true, true><<<grid, kZoomThreads, 0, st>>>(a0, a2, rows0);
+      else k_zoom2<float, C.value, B.value, false, true><<<grid, kZoomThreads, 0, st>>>(a0, a2, rows0);
+    } else {
+      if (sdesc) k_zoom2<float, C.value, B.value, true, false><<<grid, kZoomThreads, 0, st>>>(a0, a2, rows0);
+      else k_zoom2<float, C.value, B.value, false, false><<<grid, kZoomThreads, 0, st>>>(a0, a2, rows0);
+    }
   });
   QI_LAUNCH_CHECK();
   return QI_OK;
@@ -236,9 +324,9 @@ int64_t zoom_groups(int64_t n, int level) {
 // grid of a table's fine launch: workgroups along time (the level with the most) x rows
 static int zoom_grid(const ZoomArgs<float>& a, int64_t* groups_out, int* rows_out) {
   int64_t groups = 0;
-  int chunks = 0;
+  int chunks = a.merge_nchunk;  // (the merged rows come first; their classes have lvl_nchunk 0)
   for (int g = 0; g < kZoomClasses; ++g) {
-    if (a.lvl_nchunk[g] <= 0) continue;
+    if (a.lvl_nchunk[g] <= 0 && !(a.merge_mask >> g & 1)) continue;
     const int64_t gg = zoom_groups(a.n, g);
     if (gg < 1 || gg * kZoomD * zoom_steps(g) * (kZoomThreads / kWave) != a.n) {
       set_error("zoom engine: record length %lld is not a multiple of %d samples", (long long)a.n,
@@ -246,7 +334,7 @@ static int zoom_grid(const ZoomArgs<float>& a, int64_t* groups_out, int* rows_ou
       return QI_ERR_UNSUPPORTED;
     }
     if (gg > groups) groups = gg;
-    chunks = a.lvl_chunk0[g] + a.lvl_nchunk[g];
+    if (a.lvl_nchunk[g] > 0) chunks = a.lvl_chunk0[g] + a.lvl_nchunk[g];
   }
   *groups_out = groups;
   *rows_out = chunks;
@@ -260,6 +348,7 @@ int launch_zoom<float>(const ZoomArgs<float>& a, int64_t n_channels, hipStream_t
   if (int rc = zoom_grid(a, &groups, &chunks)) return rc;
   if (chunks <= 0) return QI_OK;
   dim3 grid((unsigned)groups, (unsigned)chunks, (unsigned)n_channels);
+  if (a.merge_mask != 0) return launch_zoom2_v(a, a, a.stx ? 0 : chunks, grid, st);  // (merged rows: the joint kernel's)
   return a.stx ? launch_zoom_v<float, false>(a, grid, st) : launch_zoom_v<float, true>(a, grid, st);
 }
 
@@ -275,13 +364,7 @@ int launch_zoom2<float>(const ZoomArgs<float>& a0, const ZoomArgs<float>& a2, in
     return QI_ERR_STATE;
   }
   dim3 grid((unsigned)(g0 > g2 ? g0 : g2), (unsigned)(r0 + r2), (unsigned)n_channels);
-  const bool sdesc = n_channels >= 4;  // (see zoom_level)
-  with_panels(coef, bits, [&](auto C, auto B) {
-    if (sdesc) k_zoom2<float, C.value, B.value, true><<<grid, kZoomThreads, 0, st>>>(a0, a2, r0);
-    else k_zoom2<float, C.value, B.value, false><<<grid, kZoomThreads, 0, st>>>(a0, a2, r0);
-  });
-  QI_LAUNCH_CHECK();
-  return QI_OK;
+  return launch_zoom2_v(a0, a2, r0, grid, st);
 }
 
 // N <= 16 taps (nodes -N/2 + 1 .. N/2) of the interpolator to the fraction x in [0, 1) that is exact for the tones at the
