@@ -83,6 +83,25 @@ def band_offsets(frequency_hz, edges_hz) -> np.ndarray:
     return first
 
 
+def _array_matrices(sig_wf, frequency_sample_rate_hz, positions_m, slowness, segment_points, overlap_points, nfft_points, alpha,
+                    band_edges_hz):
+    """What the two *_pow2 functions do before their form: records [C x n] -> (was_numpy, bin frequencies, cross-spectral
+    matrices on the device, band offsets or None, band_frequency_ranges, delays on the device), the positions checked against
+    the records."""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    f, csd, _ = styx_fft._csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, "spectrum",
+                                       True, False)
+    if band_edges_hz is None:
+        bands, ranges = None, np.stack([f, f], axis=1)
+    else:
+        bands = band_offsets(f, band_edges_hz)
+        ranges = np.stack([f[bands[:-1]], f[bands[1:] - 1]], axis=1)
+    tau = plane_wave_delays(positions_m, slowness, sig.device)
+    if tau.shape[1] != sig.shape[0]:
+        raise ValueError(f"{tau.shape[1]} positions for {sig.shape[0]} records")
+    return was_numpy, f, csd, bands, ranges, tau
+
+
 def fk_power_pow2(
     sig_wf,
     frequency_sample_rate_hz: float,
@@ -101,17 +120,8 @@ def fk_power_pow2(
     segments' panel nor the matrices leave the device.
     :return: band_frequency_ranges [nb x 2] (first and last bin frequency of every band), power [nb x G], peak_index [nb]
         (row of `slowness` with the largest power in the band), peak_value [nb]"""
-    sig, was_numpy, _ = engine.as_signal(sig_wf)
-    f, csd, _ = styx_fft._csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, "spectrum",
-                                       True, False)
-    if band_edges_hz is None:
-        bands, ranges = None, np.stack([f, f], axis=1)
-    else:
-        bands = band_offsets(f, band_edges_hz)
-        ranges = np.stack([f[bands[:-1]], f[bands[1:] - 1]], axis=1)
-    tau = plane_wave_delays(positions_m, slowness, sig.device)
-    if tau.shape[1] != sig.shape[0]:
-        raise ValueError(f"{tau.shape[1]} positions for {sig.shape[0]} records")
+    was_numpy, f, csd, bands, ranges, tau = _array_matrices(sig_wf, frequency_sample_rate_hz, positions_m, slowness, segment_points,
+                                                            overlap_points, nfft_points, alpha, band_edges_hz)
     power, index, value = engine.beam_power(csd, f, tau, bands=bands, normalize=normalize, peaks=True)
     return ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False)
 
@@ -137,17 +147,8 @@ def capon_power_pow2(
     loaded matrix still does not factor has info != 0, and the band that holds it is NaN (its peak the first NaN).
     :return: band_frequency_ranges [nb x 2], power [nb x G], peak_index [nb], peak_value [nb] as fk_power_pow2 returns them,
         info [bins] int32: 0, or the 1-based pivot at which the bin's factorisation failed"""
-    sig, was_numpy, _ = engine.as_signal(sig_wf)
-    f, csd, _ = styx_fft._csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, "spectrum",
-                                       True, False)
-    if band_edges_hz is None:
-        bands, ranges = None, np.stack([f, f], axis=1)
-    else:
-        bands = band_offsets(f, band_edges_hz)
-        ranges = np.stack([f[bands[:-1]], f[bands[1:] - 1]], axis=1)
-    tau = plane_wave_delays(positions_m, slowness, sig.device)
-    if tau.shape[1] != sig.shape[0]:
-        raise ValueError(f"{tau.shape[1]} positions for {sig.shape[0]} records")
+    was_numpy, f, csd, bands, ranges, tau = _array_matrices(sig_wf, frequency_sample_rate_hz, positions_m, slowness, segment_points,
+                                                            overlap_points, nfft_points, alpha, band_edges_hz)
     whitener, info = engine.csd_whiten(csd, loading=loading, info=True)
     power, index, value = engine.capon_power(whitener, f, tau, bands=bands, peaks=True)
     return (ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False),

@@ -40,7 +40,6 @@ namespace {
 
 constexpr int kCsdTile = 16;      // records per tile side (the instruction's M and N)
 constexpr int kCsdWaves = 4;      // waves (bins) per workgroup
-constexpr int kWeightChunk = 256; // host weights per k_csd_put_weights launch (2 KiB of kernel arguments)
 
 struct CsdArgs {
   int64_t C, nf, nseg;
@@ -186,13 +185,6 @@ __global__ void __launch_bounds__(256) k_coherence(const cplx<T>* __restrict__ S
   coh[at] = (T)(num / den);
 }
 
-struct WeightChunk {
-  double w[kWeightChunk];
-};
-__global__ void __launch_bounds__(kWeightChunk) k_csd_put_weights(double* __restrict__ dst, WeightChunk c, int count) {
-  if ((int)threadIdx.x < count) dst[threadIdx.x] = c.w[threadIdx.x];
-}
-
 // what both entry points refuse of a shape (the matrices' index arithmetic and the grid stay inside their types)
 int csd_shape_check(int dtype, int64_t C, int64_t nf, int64_t nseg) {
   QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
@@ -265,15 +257,9 @@ int qi_cross_spectra(int dtype, int device, const void* Z, int64_t C, int64_t nf
   hipStream_t st = (hipStream_t)stream;
   CsdWeight w;
   if (weight) {
-    // the host array rides in kernel arguments, chunk by chunk: stream-ordered, and the caller's array is free at return
+    // the host array rides in kernel arguments: stream-ordered, and the caller's array is free at return
     double* table = static_cast<double*>(scratch);
-    for (int64_t f0 = 0; f0 < nf; f0 += kWeightChunk) {
-      WeightChunk c{};
-      const int count = (int)std::min<int64_t>(kWeightChunk, nf - f0);
-      std::memcpy(c.w, weight + f0, (size_t)count * sizeof(double));
-      k_csd_put_weights<<<1, kWeightChunk, 0, st>>>(table + f0, c, count);
-      QI_LAUNCH_CHECK();
-    }
+    QI_TRY(qi::host::put_words(table, weight, nf, st));
     w.table = table;
   }
   void* matrices = static_cast<char*>(scratch) + align_up((size_t)nf * 8);

@@ -454,6 +454,9 @@ namespace qi {
 namespace host {
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+// qi_host_util.hip: `count` 8-byte host values (doubles and offsets alike, bit for bit) to device memory as kernel arguments,
+// 256 per launch: stream-ordered, and the caller's array is free at return
+int put_words(void* dst, const void* src, int64_t count, hipStream_t st);
 // a request (qi_tfr_out, the plan-less entry points) that leaves power_scale / eps at zero asks for the defaults
 inline double power_scale_or_default(double power_scale) { return power_scale == 0.0 ? 1.0 : power_scale; }
 inline double eps_or_default(double eps) { return eps == 0.0 ? 2.220446049250313e-16 : eps; }

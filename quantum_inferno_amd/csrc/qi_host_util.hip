@@ -1,5 +1,7 @@
-// Error text, development switches and the hipFFT wrappers shared by the host files of libqi_tfr.so.
+// Error text, development switches, the hipFFT wrappers and the upload of small host tables shared by the host files of
+// libqi_tfr.so.
 #include "qi_host.hpp"
+#include "qi_fft_reg.hpp"  // QI_LAUNCH_CHECK
 
 namespace qi {
 
@@ -84,6 +86,27 @@ int fft_c2r<double>(FftCache& fc, double2* in, double* out, int64_t len, int64_t
 
 std::mutex g_stft_mu;
 std::map<int, FftCache> g_stft_fft;  // per device
+
+namespace {
+constexpr int kWordChunk = 256;  // host values per k_put_words launch (2 KiB of kernel arguments)
+struct WordChunk {
+  uint64_t w[kWordChunk];
+};
+__global__ void __launch_bounds__(kWordChunk) k_put_words(uint64_t* __restrict__ dst, WordChunk c, int count) {
+  if ((int)threadIdx.x < count) dst[threadIdx.x] = c.w[threadIdx.x];
+}
+}  // namespace
+
+int host::put_words(void* dst, const void* src, int64_t count, hipStream_t st) {
+  for (int64_t k0 = 0; k0 < count; k0 += kWordChunk) {
+    WordChunk c{};
+    const int n = (int)std::min<int64_t>(kWordChunk, count - k0);
+    std::memcpy(c.w, static_cast<const uint64_t*>(src) + k0, (size_t)n * sizeof(uint64_t));
+    k_put_words<<<1, kWordChunk, 0, st>>>(static_cast<uint64_t*>(dst) + k0, c, n);
+    QI_LAUNCH_CHECK();
+  }
+  return QI_OK;
+}
 
 }  // namespace qi
 

@@ -1,10 +1,13 @@
-// The 16 x 16 x 4 matrix-core instruction per precision (qi_csd.hip, qi_beam.hip): D = A B + C with A [16 x 4], B [4 x 16].
-// Lane l supplies A[l & 15][l >> 4] and B[l >> 4][l & 15] -- the two operands have the same lane layout: entry l & 15 of
-// the 16-side at slot l >> 4 of the K side -- and holds four entries of column l & 15 of C/D, whose rows differ by precision.
+// The 16 x 16 x 4 matrix-core instruction per precision (qi_csd.hip, qi_beam.hip; qi_whiten.hip pads to its tile): D = A B + C
+// with A [16 x 4], B [4 x 16].  Lane l supplies A[l & 15][l >> 4] and B[l >> 4][l & 15] -- the two operands have the same lane
+// layout: entry l & 15 of the 16-side at slot l >> 4 of the K side -- and holds four entries of column l & 15 of C/D, whose rows
+// differ by precision.
 #pragma once
 #include "qi_common.hpp"
 
 namespace qi {
+
+constexpr int kMxTile = 16;  // M and N of the instruction: the side of a result tile
 
 typedef float qi_f4 __attribute__((ext_vector_type(4)));
 typedef double qi_d4 __attribute__((ext_vector_type(4)));

@@ -649,6 +649,17 @@ def gabor_atoms(n, p_re, p_im, omega, amp, device=None, x=None):
 
 
 # ---- plan-less record calls: records [n] or [C, n] in, one library call on the current stream, `finish` out ----
+def _matrix_stack(a, what, layout="[nf, C, C]", square=True):
+    """A non-empty 3-d complex64 / complex128 stack, NumPy or tensor -> (contiguous device tensor, was_numpy, real dtype);
+    square: its last two sides are equal (a stack of matrices)."""
+    was_numpy = not isinstance(a, torch.Tensor)
+    s = torch.from_numpy(np.ascontiguousarray(a)) if was_numpy else a
+    if s.dim() != 3 or s.dtype not in (torch.complex64, torch.complex128) or 0 in s.shape or (square and s.shape[1] != s.shape[2]):
+        raise ValueError(f"{what} must be a non-empty complex64 / complex128 {layout}, got {s.dtype} {tuple(s.shape)}")
+    rdtype = torch.float32 if s.dtype == torch.complex64 else torch.float64
+    return s.to(s.device if s.is_cuda else default_device()).contiguous(), was_numpy, rdtype
+
+
 def cross_spectra(panel, weight=None, coherence=False):
     """Cross-spectra between the records of a stored coefficient panel [C, n_bands, n_time] (an STFT, CWT or Stockwell panel:
     complex64 or complex128): csd[f, i, j] = weight[f] sum_t conj(panel[i, f, t]) panel[j, f, t], one Hermitian matrix per
@@ -656,13 +667,8 @@ def cross_spectra(panel, weight=None, coherence=False):
     -> csd [n_bands, C, C], or (csd, coherence [n_bands, C, C] = |S_ij|^2 / (S_ii S_jj)) with coherence=True.  NumPy in ->
     NumPy out, CUDA tensor in -> CUDA tensor out."""
     lib = _lib.require_gpu()
-    was_numpy = not isinstance(panel, torch.Tensor)
-    z = torch.from_numpy(np.ascontiguousarray(panel)) if was_numpy else panel
-    if z.dim() != 3 or z.dtype not in (torch.complex64, torch.complex128) or 0 in z.shape:
-        raise ValueError(f"panel must be a non-empty complex64 / complex128 [C, bands, time], got {z.dtype} {tuple(z.shape)}")
-    z = z.to(z.device if z.is_cuda else default_device()).contiguous()
+    z, was_numpy, rdtype = _matrix_stack(panel, "panel", "[C, bands, time]", square=False)
     n_ch, n_f, n_t = z.shape
-    rdtype = torch.float32 if z.dtype == torch.complex64 else torch.float64
     w_host, w_ptr = (None, None)
     if weight is not None:
         w_host, w_ptr = _lib.darr(weight)
@@ -679,21 +685,11 @@ def cross_spectra(panel, weight=None, coherence=False):
     return finish(csd, was_numpy, False)
 
 
-def beam_power(csd, frequency_hz, delays_s, bands=None, normalize=False, peaks=False):
-    """Steered (Bartlett) power of cross-spectral matrices over a grid of delay sets (qi_beam_power): with
-    e[f, g, i] = exp(2 pi i frequency_hz[f] delays_s[g, i]), Q[f, g] = Re sum_ij conj(e_i) csd[f, i, j] e_j, summed over the
-    matrices of each band and divided by C^2 -- or, normalize=True, by C sum_f trace(csd[f]): the semblance.
-    csd: [nf, C, C] complex64 / complex128 as cross_spectra and styx_fft.csd_matrix_pow2 return it, C <= 64;
-    frequency_hz: [nf] host values; delays_s: [G, C] seconds, NumPy or tensor, converted to float64 on the device (the
-    phase is formed in double whatever the matrices' precision); bands: nb + 1 strictly ascending offsets into 0..nf or None
-    (every matrix its own band).  -> power [nb, G] real, or (power, peak_index [nb] int64, peak_value [nb]) with peaks=True:
-    np.argmax of every band's row and that entry.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+def _delay_grid_form(name, matrices, what, frequency_hz, delays_s, bands, peaks, *form_args):
+    """What beam_power and capon_power share: the checks of the stack `what`, of frequency_hz, delays_s and bands, the scratch
+    of qi_<name>_scratch_bytes, the outputs, the call of qi_<name> (form_args: what it takes between nb and power) and finish."""
     lib = _lib.require_gpu()
-    was_numpy = not isinstance(csd, torch.Tensor)
-    s = torch.from_numpy(np.ascontiguousarray(csd)) if was_numpy else csd
-    if s.dim() != 3 or s.dtype not in (torch.complex64, torch.complex128) or 0 in s.shape or s.shape[1] != s.shape[2]:
-        raise ValueError(f"csd must be a non-empty complex64 / complex128 [nf, C, C], got {s.dtype} {tuple(s.shape)}")
-    s = s.to(s.device if s.is_cuda else default_device()).contiguous()
+    s, was_numpy, rdtype = _matrix_stack(matrices, what)
     n_f, n_ch, _ = s.shape
     dev = s.device
     f_host, f_ptr = _lib.darr(frequency_hz)
@@ -708,26 +704,28 @@ def beam_power(csd, frequency_hz, delays_s, bands=None, normalize=False, peaks=F
     if b_host is not None and (b_host.ndim != 1 or b_host.size < 2):
         raise ValueError(f"bands must be a list of nb + 1 offsets, got shape {b_host.shape}")
     n_b = n_f if b_host is None else b_host.size - 1
-    rdtype = torch.float32 if s.dtype == torch.complex64 else torch.float64
     code = _lib.dtype_code(rdtype)
-    scratch, nbytes = _lib.scratch(lib.qi_beam_power_scratch_bytes, dev, code, n_ch, n_f, n_g, n_b)
+    scratch, nbytes = _lib.scratch(getattr(lib, f"qi_{name}_scratch_bytes"), dev, code, n_ch, n_f, n_g, n_b)
     power = torch.empty((n_b, n_g), dtype=rdtype, device=dev)
     index = torch.empty(n_b, dtype=torch.int64, device=dev) if peaks else None
     value = torch.empty(n_b, dtype=rdtype, device=dev) if peaks else None
-    _lib.call(lib.qi_beam_power, dev, code, dev.index, _lib.ptr(s), n_ch, n_f, f_ptr, _lib.ptr(tau), n_g, b_ptr, n_b,
-              int(bool(normalize)), _lib.ptr(power), _lib.ptr(index), _lib.ptr(value), _lib.ptr(scratch), nbytes)
+    _lib.call(getattr(lib, f"qi_{name}"), dev, code, dev.index, _lib.ptr(s), n_ch, n_f, f_ptr, _lib.ptr(tau), n_g, b_ptr, n_b,
+              *form_args, _lib.ptr(power), _lib.ptr(index), _lib.ptr(value), _lib.ptr(scratch), nbytes)
     if peaks:
         return finish(power, was_numpy, False), finish(index, was_numpy, False), finish(value, was_numpy, False)
     return finish(power, was_numpy, False)
 
 
-def _matrix_stack(a, what):
-    """A non-empty [nf, C, C] complex64 / complex128 stack, NumPy or tensor -> (contiguous device tensor, was_numpy)."""
-    was_numpy = not isinstance(a, torch.Tensor)
-    s = torch.from_numpy(np.ascontiguousarray(a)) if was_numpy else a
-    if s.dim() != 3 or s.dtype not in (torch.complex64, torch.complex128) or 0 in s.shape or s.shape[1] != s.shape[2]:
-        raise ValueError(f"{what} must be a non-empty complex64 / complex128 [nf, C, C], got {s.dtype} {tuple(s.shape)}")
-    return s.to(s.device if s.is_cuda else default_device()).contiguous(), was_numpy
+def beam_power(csd, frequency_hz, delays_s, bands=None, normalize=False, peaks=False):
+    """Steered (Bartlett) power of cross-spectral matrices over a grid of delay sets (qi_beam_power): with
+    e[f, g, i] = exp(2 pi i frequency_hz[f] delays_s[g, i]), Q[f, g] = Re sum_ij conj(e_i) csd[f, i, j] e_j, summed over the
+    matrices of each band and divided by C^2 -- or, normalize=True, by C sum_f trace(csd[f]): the semblance.
+    csd: [nf, C, C] complex64 / complex128 as cross_spectra and styx_fft.csd_matrix_pow2 return it, C <= 64;
+    frequency_hz: [nf] host values; delays_s: [G, C] seconds, NumPy or tensor, converted to float64 on the device (the
+    phase is formed in double whatever the matrices' precision); bands: nb + 1 strictly ascending offsets into 0..nf or None
+    (every matrix its own band).  -> power [nb, G] real, or (power, peak_index [nb] int64, peak_value [nb]) with peaks=True:
+    np.argmax of every band's row and that entry.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    return _delay_grid_form("beam_power", csd, "csd", frequency_hz, delays_s, bands, peaks, int(bool(normalize)))
 
 
 def csd_whiten(csd, loading=0.0, info=False):
@@ -739,10 +737,10 @@ def csd_whiten(csd, loading=0.0, info=False):
     not a positive finite number (LAPACK's potrf); such a matrix's whitener is NaN on and above the diagonal.  NumPy in ->
     NumPy out, CUDA tensor in -> CUDA tensor out."""
     lib = _lib.require_gpu()
-    s, was_numpy = _matrix_stack(csd, "csd")
+    s, was_numpy, rdtype = _matrix_stack(csd, "csd")
     n_f, n_ch, _ = s.shape
     dev = s.device
-    code = _lib.dtype_code(torch.float32 if s.dtype == torch.complex64 else torch.float64)
+    code = _lib.dtype_code(rdtype)
     whitener = torch.empty_like(s)
     flags = torch.empty(n_f, dtype=torch.int32, device=dev) if info else None
     _lib.call(lib.qi_csd_whiten, dev, code, dev.index, _lib.ptr(s), n_ch, n_f, float(loading), _lib.ptr(whitener), _lib.ptr(flags))
@@ -759,33 +757,7 @@ def capon_power(whitener, frequency_hz, delays_s, bands=None, peaks=False):
     C <= 64; frequency_hz, delays_s, bands and peaks: as in beam_power.  A band that holds a matrix csd_whiten flagged is NaN,
     and its peak the first NaN.  -> power [nb, G] real, or (power, peak_index [nb] int64, peak_value [nb]) with peaks=True.
     NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
-    lib = _lib.require_gpu()
-    v, was_numpy = _matrix_stack(whitener, "whitener")
-    n_f, n_ch, _ = v.shape
-    dev = v.device
-    f_host, f_ptr = _lib.darr(frequency_hz)
-    if f_host.shape != (n_f,):
-        raise ValueError(f"frequency_hz must hold one value per matrix ({n_f}), got shape {f_host.shape}")
-    tau = delays_s if isinstance(delays_s, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(delays_s))
-    if tau.dim() != 2 or tau.shape[0] < 1 or tau.shape[1] != n_ch:
-        raise ValueError(f"delays_s must be [G, {n_ch}], got shape {tuple(tau.shape)}")
-    tau = tau.to(dev).to(torch.float64).contiguous()
-    n_g = tau.shape[0]
-    b_host, b_ptr = (None, None) if bands is None else _lib.iarr(bands)
-    if b_host is not None and (b_host.ndim != 1 or b_host.size < 2):
-        raise ValueError(f"bands must be a list of nb + 1 offsets, got shape {b_host.shape}")
-    n_b = n_f if b_host is None else b_host.size - 1
-    rdtype = torch.float32 if v.dtype == torch.complex64 else torch.float64
-    code = _lib.dtype_code(rdtype)
-    scratch, nbytes = _lib.scratch(lib.qi_beam_capon_scratch_bytes, dev, code, n_ch, n_f, n_g, n_b)
-    power = torch.empty((n_b, n_g), dtype=rdtype, device=dev)
-    index = torch.empty(n_b, dtype=torch.int64, device=dev) if peaks else None
-    value = torch.empty(n_b, dtype=rdtype, device=dev) if peaks else None
-    _lib.call(lib.qi_beam_capon, dev, code, dev.index, _lib.ptr(v), n_ch, n_f, f_ptr, _lib.ptr(tau), n_g, b_ptr, n_b,
-              _lib.ptr(power), _lib.ptr(index), _lib.ptr(value), _lib.ptr(scratch), nbytes)
-    if peaks:
-        return finish(power, was_numpy, False), finish(index, was_numpy, False), finish(value, was_numpy, False)
-    return finish(power, was_numpy, False)
+    return _delay_grid_form("beam_capon", whitener, "whitener", frequency_hz, delays_s, bands, peaks)
 
 
 def _record_shape(a, what="signal", nonempty=True):

@@ -111,6 +111,28 @@ def test_equal_delay_rows_give_equal_bits_and_the_lower_peak(dtype):
         assert index[b] == lo and value[b] == got[b, lo]
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_host_tables_of_more_than_one_upload_chunk(dtype):
+    """257 matrices, every one its own band: the frequency table goes to the device in two chunks of kernel arguments, 256
+    values and one (an explicit band table of 258 offsets: 256 and two).  A band's power depends on its own matrices alone
+    (include/qi_beam.h), so the call has the bits of the calls on matrices 0 .. 255 and on matrix 256."""
+    nf, C, G = 257, 5, 15
+    rng = np.random.default_rng([31, nf, C, G])
+    a = rng.standard_normal((nf, C, C)) + 1j * rng.standard_normal((nf, C, C))
+    s = (a @ np.conj(a.transpose(0, 2, 1)) + np.eye(C)).astype(bc.complex_of(dtype))
+    freq = rng.uniform(1.0, 40.0, nf)  # (no two alike: a value of the wrong chunk shows)
+    tau = rng.uniform(-bc.MAX_DELAY_S, bc.MAX_DELAY_S, (G, C))
+    for normalize in (False, True):
+        whole = engine.beam_power(s, freq, tau, normalize=normalize, peaks=True)
+        head = engine.beam_power(s[:256], freq[:256], tau, normalize=normalize, peaks=True)
+        last = engine.beam_power(s[256:], freq[256:], tau, normalize=normalize, peaks=True)
+        assert whole[0].shape == (nf, G) and np.isfinite(whole[0]).all()
+        for w, h, t in zip(whole, head, last):
+            assert same_bits(w, np.concatenate([h, t])), normalize
+        table = engine.beam_power(s, freq, tau, bands=np.arange(nf + 1), normalize=normalize, peaks=True)
+        assert all(same_bits(t, w) for t, w in zip(table, whole)), normalize
+
+
 # ---- peaks ------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_peak_rules_with_nan(dtype):

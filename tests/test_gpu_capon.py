@@ -125,6 +125,29 @@ def test_a_matrix_has_the_same_whitener_wherever_it_is_factored(dtype):
         assert same_bits(engine.csd_whiten(hurt, loading=cpc.LOADING), full)
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_host_tables_of_more_than_one_upload_chunk(dtype):
+    """257 matrices A A^H + I, every one its own band: the frequency table goes to the device in two chunks of kernel
+    arguments, 256 values and one (an explicit band table of 258 offsets: 256 and two).  A band's power depends on its own
+    matrices alone (include/qi_adaptive.h), so the call has the bits of the calls on matrices 0 .. 255 and on matrix 256."""
+    nf, C, G = 257, 5, 15
+    rng = np.random.default_rng([37, nf, C, G])
+    a = rng.standard_normal((nf, C, C)) + 1j * rng.standard_normal((nf, C, C))
+    s = (a @ np.conj(a.transpose(0, 2, 1)) + np.eye(C)).astype(bc.complex_of(dtype))
+    freq = rng.uniform(1.0, 40.0, nf)  # (no two alike: a value of the wrong chunk shows)
+    tau = rng.uniform(-bc.MAX_DELAY_S, bc.MAX_DELAY_S, (G, C))
+    v, info = engine.csd_whiten(s, info=True)
+    assert not info.any()
+    whole = engine.capon_power(v, freq, tau, peaks=True)
+    head = engine.capon_power(v[:256], freq[:256], tau, peaks=True)
+    last = engine.capon_power(v[256:], freq[256:], tau, peaks=True)
+    assert whole[0].shape == (nf, G) and np.isfinite(whole[0]).all() and whole[0].min() > 0
+    for w, h, t in zip(whole, head, last):
+        assert same_bits(w, np.concatenate([h, t]))
+    table = engine.capon_power(v, freq, tau, bands=np.arange(nf + 1), peaks=True)
+    assert all(same_bits(t, w) for t, w in zip(table, whole))
+
+
 def test_tensors_in_tensors_out_and_both_workgroup_sizes():
     """CUDA tensors stay on the device; a grid that takes the larger workgroup agrees bit for bit with a part of it that
     takes the smaller one."""

@@ -107,6 +107,22 @@ def test_exact_integer_panels(dtype, weighted):
                     assert np.all((want_coh == 1) | np.isnan(want_coh))
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_weights_of_more_than_one_upload_chunk(dtype):
+    """257 host weights go to the device in two chunks of kernel arguments, 256 values and one.  A bin's matrix depends on its
+    own rows and weight alone, so the call has the bits of the calls on bins 0 .. 255 and on bin 256."""
+    C, nf, nseg = 5, 257, 12
+    rng = np.random.default_rng([41, C, nf, nseg])
+    panel = (rng.standard_normal((C, nf, nseg)) + 1j * rng.standard_normal((C, nf, nseg))).astype(np.complex64 if dtype == "float32" else np.complex128)
+    weight = rng.uniform(0.5, 1.5, nf)  # (no two alike: a value of the wrong chunk shows)
+    whole = engine.cross_spectra(panel, weight=weight, coherence=True)
+    head = engine.cross_spectra(panel[:, :256], weight=weight[:256], coherence=True)
+    last = engine.cross_spectra(panel[:, 256:], weight=weight[256:], coherence=True)
+    assert whole[0].shape == (nf, C, C) and np.isfinite(whole[0]).all()
+    for w, h, t in zip(whole, head, last):
+        assert same_bits(w, np.concatenate([h, t]))
+
+
 def test_cross_spectra_without_matrices_or_without_coherence():
     """Either output alone: the coherence alone goes through the scratch matrices and has the same bits."""
     zr, zi = integer_panel(17, 3, 67)
