@@ -182,6 +182,13 @@ ADAPTIVE_PROTOTYPES = {
     "qi_beam_capon": (_int, [_int, _int, _P, _i64, _i64, _D, _P, _i64, _I64, _i64, _P, _P, _P, _P, _i64, _P]),
 }
 
+# include/qi_subspace.h (the eigenpairs of the matrices, and the MUSIC form of their noise subspace over the grid), one to one
+SUBSPACE_PROTOTYPES = {
+    "qi_csd_eigh": (_int, [_int, _int, _P, _i64, _i64, _P, _P, _P, _P]),
+    "qi_beam_music_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64]),
+    "qi_beam_music": (_int, [_int, _int, _P, _i64, _i64, _i64, _D, _P, _i64, _I64, _i64, _P, _P, _P, _P, _i64, _P]),
+}
+
 _lib = None
 
 
@@ -204,7 +211,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES, **SUBSPACE_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

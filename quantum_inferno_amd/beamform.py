@@ -1,15 +1,16 @@
 """
 Frequency-wavenumber (f-k) analysis of a sensor array: steered power of the cross-spectral matrices over a grid of
-slowness vectors (engine.beam_power, include/qi_beam.h), and Capon's minimum-variance power over the same grid
-(engine.csd_whiten and engine.capon_power, include/qi_adaptive.h).  The reference (quantum-inferno) has no array processing;
+slowness vectors (engine.beam_power, include/qi_beam.h), Capon's minimum-variance power over the same grid
+(engine.csd_whiten and engine.capon_power, include/qi_adaptive.h), and the MUSIC power of the matrices' noise subspaces
+(engine.csd_eigh and engine.music_power, include/qi_subspace.h).  The reference (quantum-inferno) has no array processing;
 the conventions below are the usual ones of infrasound and seismic array work.
 
 Geometry.  Positions are [C, 2] metres (x east, y north).  A slowness vector s [s/m] points the way the wave TRAVELS; a
 plane wave reaches sensor i later by tau_i = s . r_i seconds.  The back azimuth is where it comes FROM: the direction of
 -s in degrees clockwise from north; the trace velocity is 1 / |s|.
 
-The helpers are host code on torch float64; only plane_wave_delays' result and the work of fk_power_pow2 and
-capon_power_pow2 are on the device.
+The helpers are host code on torch float64; only plane_wave_delays' result and the work of fk_power_pow2,
+capon_power_pow2 and music_power_pow2 are on the device.
 """
 import numpy as np
 import torch
@@ -85,7 +86,7 @@ def band_offsets(frequency_hz, edges_hz) -> np.ndarray:
 
 def _array_matrices(sig_wf, frequency_sample_rate_hz, positions_m, slowness, segment_points, overlap_points, nfft_points, alpha,
                     band_edges_hz):
-    """What the two *_pow2 functions do before their form: records [C x n] -> (was_numpy, bin frequencies, cross-spectral
+    """What the *_pow2 functions do before their form: records [C x n] -> (was_numpy, bin frequencies, cross-spectral
     matrices on the device, band offsets or None, band_frequency_ranges, delays on the device), the positions checked against
     the records."""
     sig, was_numpy, _ = engine.as_signal(sig_wf)
@@ -151,5 +152,36 @@ def capon_power_pow2(
                                                             overlap_points, nfft_points, alpha, band_edges_hz)
     whitener, info = engine.csd_whiten(csd, loading=loading, info=True)
     power, index, value = engine.capon_power(whitener, f, tau, bands=bands, peaks=True)
+    return (ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False),
+            engine.finish(info, was_numpy, False))
+
+
+def music_power_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    positions_m,
+    slowness,
+    segment_points: int,
+    overlap_points: int = None,
+    nfft_points: int = None,
+    alpha: float = 0.25,
+    band_edges_hz=None,
+    n_sources: int = 1,
+):
+    """MUSIC f-k power of the records of one array [C x n], capon_power_pow2's twin: the same cross-spectral matrices,
+    diagonalised once per bin (engine.csd_eigh), then C / (e^H P e) over the slowness vectors [G, 2] with P the projector onto
+    the eigenvectors of the C - n_sources smallest eigenvalues, averaged over the bands between band_edges_hz
+    (engine.music_power).  The power is dimensionless, at least 1 and large where a steering vector leaves the noise subspace:
+    it locates up to n_sources < C uncorrelated sources and says nothing of their strength.  There is no loading: a matrix
+    averaged over fewer segments than there are sensors has zero eigenvalues, which belong to the noise subspace as they are.
+    Neither the panel, the matrices nor their eigenpairs leave the device: only the power, the peaks and info do.  A bin whose
+    matrix does not diagonalise (one that holds a value that is not finite) has info != 0, and the band that holds it is NaN
+    (its peak the first NaN).
+    :return: band_frequency_ranges [nb x 2], power [nb x G], peak_index [nb], peak_value [nb] as fk_power_pow2 returns them,
+        info [bins] int32: 0, or 1 where the bin's matrix did not converge"""
+    was_numpy, f, csd, bands, ranges, tau = _array_matrices(sig_wf, frequency_sample_rate_hz, positions_m, slowness, segment_points,
+                                                            overlap_points, nfft_points, alpha, band_edges_hz)
+    _, vectors, info = engine.csd_eigh(csd, info=True)
+    power, index, value = engine.music_power(vectors, n_sources, f, tau, bands=bands, peaks=True)
     return (ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False),
             engine.finish(info, was_numpy, False))

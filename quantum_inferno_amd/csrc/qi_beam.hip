@@ -1,4 +1,4 @@
-// The two forms of cross-spectral matrices over a grid of delay sets: one walk over a band's matrices, two forms at its ends.
+// The forms of cross-spectral matrices over a grid of delay sets: one walk over a band's matrices, three forms at its ends.
 // With the phase factors e_i = exp(2 pi i freq[f] tau[g][i]) of matrix f and grid point g:
 //
 // Bartlett, the steered power (include/qi_beam.h, k_beam_power):
@@ -10,6 +10,12 @@
 // k_csd_whiten (qi_whiten.hip) factors every matrix once, R = L L^H, and stores V = L^-H, so that R^-1 = V V^H and
 //   D = e^H R^-1 e = |V^H e|^2 = sum_j | sum_i conj(V[i][j]) e_i |^2
 // is a sum of squares: never negative, and its rounding error goes with the condition number of L, the square root of R's.
+//
+// MUSIC, the reciprocal of the null spectrum (include/qi_subspace.h, k_beam_music):
+//   C / (e^H P e),  P = U_n U_n^H the projector onto the noise subspace.
+// k_csd_eigh (qi_eigh.hip) diagonalises every matrix once, S = U diag(w) U^H with w ascending, so that with m = C - n_sources
+//   D = e^H P e = sum_{j < m} | sum_i conj(U[i][j]) e_i |^2
+// is Capon's sum of squares over the first m columns of a full matrix.
 //
 // The walk (beam_walk).  The inner sum is, for one matrix and 16 grid points, a complex product of a [C x C] and a [C x 16]
 // matrix, K = C -- Bartlett: W = S_f^T conj(E); Capon: W = V^H E -- and runs on the matrix cores in the matrices' precision
@@ -35,7 +41,9 @@
 // i: S[f][i][i] over f, then the lanes by a fixed tree), and the quotient is taken in double.  Capon: V is upper triangular,
 // row tile tj of W needs the K steps t < 4 (tj + 1) alone, 10 of the 16 tile products at 64 sensors.  There is no closing
 // product: a lane squares and adds its own result registers, the four K slots are added once per matrix, the reciprocal is
-// taken in double and summed in double over the band in ascending f.
+// taken in double and summed in double over the band in ascending f.  MUSIC: U is full, every row tile takes all K steps as
+// Bartlett's; a lane squares and adds its result registers as Capon's, those of the columns j < m alone (it knows the column
+// each register holds); D is summed in double over the band and C n_b is divided by the sum, once.
 //
 // Work split.  A workgroup of NW waves takes one band and NW tiles of grid points and walks the band's matrices in order:
 // matrix -> LDS (padded to whole tiles, float32 rows 4 entries longer: the four K slots then read different banks), barrier,
@@ -46,7 +54,7 @@
 //
 // The peaks are a second launch over the finished power: a workgroup per band, np.argmax's rules.
 //
-// Host side, once for both forms: the verdicts on a shape, a band table and a call, the scratch layout (the frequency table,
+// Host side, once for all forms: the verdicts on a shape, a band table and a call, the scratch layout (the frequency table,
 // then the band offsets), the upload of the two host tables (qi::host::put_words), the choice of the workgroup size, the
 // dispatch on the tile count and the peaks launch.
 #include <type_traits>
@@ -57,6 +65,7 @@
 #include "qi_mfma.hpp"     // Mx, kMxTile
 #include "qi_beam.h"
 #include "qi_adaptive.h"
+#include "qi_subspace.h"
 
 namespace {
 
@@ -80,7 +89,7 @@ __device__ __forceinline__ void beam_sincospi(double x, double* s, double* c) { 
 
 template <typename T>
 struct BeamArgs {
-  const cplx<T>* M;      // [nf][C][C]: the matrices S (Bartlett), the whiteners V (Capon)
+  const cplx<T>* M;      // [nf][C][C]: the matrices S (Bartlett), the whiteners V (Capon), the eigenvectors U (MUSIC)
   const double* tau;     // [G][C]
   const double* freq;    // [nf] (scratch)
   const int64_t* first;  // [nb + 1] (scratch), or null: band b is matrix b
@@ -88,9 +97,10 @@ struct BeamArgs {
   int64_t C, G;
   int64_t gparts;  // workgroups per band
   int normalize;   // (Bartlett alone)
+  int n_sources;   // (MUSIC alone)
 };
 
-// A form: the state of a lane over its band; matrix_in, once the matrix lies in LDS; the K steps row tile tj takes, a
+// A form: the state of a lane over its band; begin, before the first matrix; matrix_in, once the matrix lies in LDS; the K steps row tile tj takes, a
 // compile-time function of the unrolled tj (the factors stay in registers); tile, on the finished products of a row tile
 // (result row reg of tile tj is sensor sigma(4 tj + reg): the lane holds its factor); matrix_out, after the last tile; result,
 // what the lanes of the first K slot store.
@@ -99,6 +109,7 @@ struct BartlettForm {
   using acc = typename Mx<T>::acc;
   T q = T(0), trace = T(0);
   static constexpr int ksteps(int tj, int nt) { return 4 * nt; }
+  __device__ __forceinline__ void begin(const BeamArgs<T>&, int) {}
   __device__ __forceinline__ void matrix_in(const cplx<T>* sm, int ld, int lane, int C) {
     if (lane < C) trace += sm[lane * ld + lane].x;
   }
@@ -130,6 +141,7 @@ struct CaponForm {
   double sum = 0.0;  // of 1 / D over the band
   T d;
   static constexpr int ksteps(int tj, int nt) { return 4 * (tj + 1); }  // V[i][j] = 0 for i > j: the sensors of the tiles up to tj
+  __device__ __forceinline__ void begin(const BeamArgs<T>&, int) {}
   __device__ __forceinline__ void matrix_in(const cplx<T>*, int, int, int) { d = T(0); }
   __device__ __forceinline__ void tile(int, const acc& rr, const acc& ii, const acc& ir, const acc& ri, const T*, const T*) {
 #pragma unroll
@@ -145,6 +157,36 @@ struct CaponForm {
     sum += 1.0 / (double)d;
   }
   __device__ __forceinline__ T result(const BeamArgs<T>&, int) { return (T)sum; }
+};
+
+template <typename T>
+struct SubspaceForm {
+  using acc = typename Mx<T>::acc;
+  double sum = 0.0;  // of D over the band
+  T d;
+  int count = 0;  // matrices of the band
+  int left[4];    // noise columns from the lane's result row `reg` of tile 0 on: m - row
+  static constexpr int ksteps(int tj, int nt) { return 4 * nt; }  // U is full
+  __device__ __forceinline__ void begin(const BeamArgs<T>& a, int lane) {
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) left[reg] = (int)a.C - a.n_sources - Mx<T>::row(lane, reg);
+  }
+  __device__ __forceinline__ void matrix_in(const cplx<T>*, int, int, int) { d = T(0); }
+  __device__ __forceinline__ void tile(int tj, const acc& rr, const acc& ii, const acc& ir, const acc& ri, const T*, const T*) {
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const T wr = rr[reg] + ii[reg], wi = ri[reg] - ir[reg];
+      if (kBeamTile * tj < left[reg]) d += wr * wr + wi * wi;  // column j = 16 tj + row < m
+    }
+  }
+  __device__ __forceinline__ void matrix_out() {
+    // the four K slots of a grid point: (0 + 1) + (2 + 3), the same value in all four
+    d += __shfl_xor(d, 16);
+    d += __shfl_xor(d, 32);
+    sum += (double)d;
+    ++count;
+  }
+  __device__ __forceinline__ T result(const BeamArgs<T>&, int C) { return (T)(((double)C * (double)count) / sum); }
 };
 
 template <typename T, int NW, int NT, typename Form>
@@ -170,6 +212,7 @@ __device__ __forceinline__ void beam_walk(const BeamArgs<T>& a) {
     tau[t] = on && s < C ? a.tau[g * C + s] : 0.0;
   }
   Form form;
+  form.begin(a, lane);
   for (int64_t f = f0; f < f1; ++f) {
     __syncthreads();  // the previous matrix has been read (first: the zeros are written)
     const cplx<T>* __restrict__ Mf = a.M + f * C * C;
@@ -216,6 +259,10 @@ __global__ void __launch_bounds__(NW* kWave) k_beam_power(BeamArgs<T> a) {
 template <typename T, int NW, int NT>
 __global__ void __launch_bounds__(NW* kWave) k_beam_capon(BeamArgs<T> a) {
   beam_walk<T, NW, NT, CaponForm<T>>(a);
+}
+template <typename T, int NW, int NT>
+__global__ void __launch_bounds__(NW* kWave) k_beam_music(BeamArgs<T> a) {
+  beam_walk<T, NW, NT, SubspaceForm<T>>(a);
 }
 
 // np.argmax's order: a NaN before every number, a larger value before a smaller one, a lower index before a higher one
@@ -305,6 +352,7 @@ int beam_call_check(int dtype, int64_t C, int64_t nf, int64_t G, int64_t nb, con
 template <typename Form, typename T, int NW, int NT>
 constexpr auto form_kernel() {
   if constexpr (std::is_same<Form, CaponForm<T>>::value) return &k_beam_capon<T, NW, NT>;
+  else if constexpr (std::is_same<Form, SubspaceForm<T>>::value) return &k_beam_music<T, NW, NT>;
   else return &k_beam_power<T, NW, NT>;
 }
 
@@ -325,8 +373,8 @@ int launch_form(const BeamArgs<T>& a, int ntile, int64_t nb, hipStream_t st) {
 // a form's call: the refusals, the two host tables into the scratch in stream order, the form over every band, the peaks
 template <template <typename> class Form>
 int beam_form(int dtype, int device, const void* matrices, int64_t C, int64_t nf, const double* freq_hz, const void* delays_s,
-              int64_t G, const int64_t* band_first, int64_t nb, int normalize, void* power, void* peak_index, void* peak_value,
-              void* scratch, int64_t scratch_bytes, qi_stream stream) {
+              int64_t G, const int64_t* band_first, int64_t nb, int normalize, int n_sources, void* power, void* peak_index,
+              void* peak_value, void* scratch, int64_t scratch_bytes, qi_stream stream) {
   QI_TRY(beam_call_check(dtype, C, nf, G, nb, matrices, freq_hz, delays_s, band_first, power, peak_index, peak_value, scratch,
                          scratch_bytes));
   DeviceGuard guard(device);
@@ -351,6 +399,7 @@ int beam_form(int dtype, int device, const void* matrices, int64_t C, int64_t nf
     a.G = G;
     a.gparts = ceil_div(tiles, many ? kBeamWavesMany : kBeamWavesFew);
     a.normalize = normalize != 0;
+    a.n_sources = n_sources;
     QI_TRY((many ? launch_form<Form<T>, T, kBeamWavesMany>(a, ntile, nb, st) : launch_form<Form<T>, T, kBeamWavesFew>(a, ntile, nb, st)));
     if (peak_index || peak_value) {
       k_beam_peaks<T><<<dim3((unsigned)nb), kPeakThreads, 0, st>>>(a.power, G, static_cast<int64_t*>(peak_index),
@@ -373,7 +422,7 @@ int64_t qi_beam_power_scratch_bytes(int dtype, int64_t C, int64_t nf, int64_t G,
 int qi_beam_power(int dtype, int device, const void* csd, int64_t C, int64_t nf, const double* freq_hz, const void* delays_s,
                   int64_t G, const int64_t* band_first, int64_t nb, int normalize, void* power, void* peak_index,
                   void* peak_value, void* scratch, int64_t scratch_bytes, qi_stream stream) {
-  return beam_form<BartlettForm>(dtype, device, csd, C, nf, freq_hz, delays_s, G, band_first, nb, normalize, power, peak_index,
+  return beam_form<BartlettForm>(dtype, device, csd, C, nf, freq_hz, delays_s, G, band_first, nb, normalize, 0, power, peak_index,
                                  peak_value, scratch, scratch_bytes, stream);
 }
 
@@ -385,8 +434,23 @@ int64_t qi_beam_capon_scratch_bytes(int dtype, int64_t C, int64_t nf, int64_t G,
 int qi_beam_capon(int dtype, int device, const void* whitener, int64_t C, int64_t nf, const double* freq_hz, const void* delays_s,
                   int64_t G, const int64_t* band_first, int64_t nb, void* power, void* peak_index, void* peak_value, void* scratch,
                   int64_t scratch_bytes, qi_stream stream) {
-  return beam_form<CaponForm>(dtype, device, whitener, C, nf, freq_hz, delays_s, G, band_first, nb, 0, power, peak_index, peak_value,
+  return beam_form<CaponForm>(dtype, device, whitener, C, nf, freq_hz, delays_s, G, band_first, nb, 0, 0, power, peak_index, peak_value,
                               scratch, scratch_bytes, stream);
+}
+
+int64_t qi_beam_music_scratch_bytes(int dtype, int64_t C, int64_t nf, int64_t G, int64_t nb) {
+  QI_TRY(beam_shape_check(dtype, C, nf, G, nb));
+  return (int64_t)beam_scratch(nf, nb);
+}
+
+int qi_beam_music(int dtype, int device, const void* eigenvectors, int64_t C, int64_t nf, int64_t n_sources, const double* freq_hz,
+                  const void* delays_s, int64_t G, const int64_t* band_first, int64_t nb, void* power, void* peak_index,
+                  void* peak_value, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_TRY(beam_shape_check(dtype, C, nf, G, nb));
+  QI_REQUIRE(n_sources >= 0 && n_sources < C, "%lld sources for %lld sensors: 0 to %lld", (long long)n_sources, (long long)C,
+             (long long)(C - 1));
+  return beam_form<SubspaceForm>(dtype, device, eigenvectors, C, nf, freq_hz, delays_s, G, band_first, nb, 0, (int)n_sources, power,
+                                 peak_index, peak_value, scratch, scratch_bytes, stream);
 }
 
 }  // extern "C"

@@ -685,9 +685,10 @@ def cross_spectra(panel, weight=None, coherence=False):
     return finish(csd, was_numpy, False)
 
 
-def _delay_grid_form(name, matrices, what, frequency_hz, delays_s, bands, peaks, *form_args):
-    """What beam_power and capon_power share: the checks of the stack `what`, of frequency_hz, delays_s and bands, the scratch
-    of qi_<name>_scratch_bytes, the outputs, the call of qi_<name> (form_args: what it takes between nb and power) and finish."""
+def _delay_grid_form(name, matrices, what, frequency_hz, delays_s, bands, peaks, *form_args, form_first=()):
+    """What beam_power, capon_power and music_power share: the checks of the stack `what`, of frequency_hz, delays_s and bands,
+    the scratch of qi_<name>_scratch_bytes, the outputs, the call of qi_<name> (form_first: what it takes between nf and
+    freq_hz; form_args: between nb and power) and finish."""
     lib = _lib.require_gpu()
     s, was_numpy, rdtype = _matrix_stack(matrices, what)
     n_f, n_ch, _ = s.shape
@@ -709,8 +710,8 @@ def _delay_grid_form(name, matrices, what, frequency_hz, delays_s, bands, peaks,
     power = torch.empty((n_b, n_g), dtype=rdtype, device=dev)
     index = torch.empty(n_b, dtype=torch.int64, device=dev) if peaks else None
     value = torch.empty(n_b, dtype=rdtype, device=dev) if peaks else None
-    _lib.call(getattr(lib, f"qi_{name}"), dev, code, dev.index, _lib.ptr(s), n_ch, n_f, f_ptr, _lib.ptr(tau), n_g, b_ptr, n_b,
-              *form_args, _lib.ptr(power), _lib.ptr(index), _lib.ptr(value), _lib.ptr(scratch), nbytes)
+    _lib.call(getattr(lib, f"qi_{name}"), dev, code, dev.index, _lib.ptr(s), n_ch, n_f, *form_first, f_ptr, _lib.ptr(tau), n_g, b_ptr,
+              n_b, *form_args, _lib.ptr(power), _lib.ptr(index), _lib.ptr(value), _lib.ptr(scratch), nbytes)
     if peaks:
         return finish(power, was_numpy, False), finish(index, was_numpy, False), finish(value, was_numpy, False)
     return finish(power, was_numpy, False)
@@ -758,6 +759,42 @@ def capon_power(whitener, frequency_hz, delays_s, bands=None, peaks=False):
     and its peak the first NaN.  -> power [nb, G] real, or (power, peak_index [nb] int64, peak_value [nb]) with peaks=True.
     NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
     return _delay_grid_form("beam_capon", whitener, "whitener", frequency_hz, delays_s, bands, peaks)
+
+
+def csd_eigh(csd, info=False):
+    """Eigenpairs of Hermitian cross-spectral matrices (qi_csd_eigh), what music_power consumes: for every matrix
+    csd[f] = U diag(w) U^H with w ascending and U^H U = I -- numpy.linalg.eigh's layout, column j of U the unit eigenvector of
+    w[j]; the phase of a column is the iteration's, a function of the matrix alone.  csd: [nf, C, C] complex64 / complex128 as
+    cross_spectra and styx_fft.csd_matrix_pow2 return it, C <= 64; only the lower triangle and the real part of the diagonal
+    are read.  -> (eigenvalues [nf, C] real, eigenvectors [nf, C, C]), or (eigenvalues, eigenvectors, info [nf] int32) with
+    info=True: 0, or 1 for a matrix that did not converge within the sweep cap -- every matrix with an entry that is not finite
+    does not; such a matrix's eigenvalues and eigenvectors are NaN.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    s, was_numpy, rdtype = _matrix_stack(csd, "csd")
+    n_f, n_ch, _ = s.shape
+    dev = s.device
+    code = _lib.dtype_code(rdtype)
+    values = torch.empty((n_f, n_ch), dtype=rdtype, device=dev)
+    vectors = torch.empty_like(s)
+    flags = torch.empty(n_f, dtype=torch.int32, device=dev) if info else None
+    _lib.call(lib.qi_csd_eigh, dev, code, dev.index, _lib.ptr(s), n_ch, n_f, _lib.ptr(values), _lib.ptr(vectors), _lib.ptr(flags))
+    out = (finish(values, was_numpy, False), finish(vectors, was_numpy, False))
+    return out + (finish(flags, was_numpy, False),) if info else out
+
+
+def music_power(eigenvectors, n_sources, frequency_hz, delays_s, bands=None, peaks=False):
+    """MUSIC power of diagonalised cross-spectral matrices over a grid of delay sets (qi_beam_music): with
+    e[f, g, i] = exp(2 pi i frequency_hz[f] delays_s[g, i]), U = eigenvectors[f] and m = C - n_sources noise columns,
+    D[f, g] = sum_{j < m} |sum_i conj(U[i, j]) e_i|^2 = e^H P_noise e, and power[b, g] = C n_b / (sum of D over the band's n_b
+    matrices): the reciprocal of the band's mean null spectrum, dimensionless, >= 1 up to rounding and large at a source.
+    eigenvectors: [nf, C, C] complex64 / complex128 as csd_eigh returns it, C <= 64; n_sources: 0 <= n_sources < C, one number
+    for all matrices; frequency_hz, delays_s, bands and peaks: as in beam_power.  A band that holds a matrix csd_eigh flagged
+    is NaN, and its peak the first NaN.  -> power [nb, G] real, or (power, peak_index [nb] int64, peak_value [nb]) with
+    peaks=True.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    n = int(n_sources)
+    if n != n_sources:
+        raise ValueError(f"n_sources must be a whole number, got {n_sources!r}")
+    return _delay_grid_form("beam_music", eigenvectors, "eigenvectors", frequency_hz, delays_s, bands, peaks, form_first=(n,))
 
 
 def _record_shape(a, what="signal", nonempty=True):
