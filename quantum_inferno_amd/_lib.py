@@ -1,4 +1,4 @@
-"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, include/qi_array.h, include/qi_beam.h, include/qi_adaptive.h).  There is no CPU fallback: if the
+"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, qi_array.h, qi_beam.h, qi_adaptive.h, qi_subspace.h, qi_steer.h).  There is no CPU fallback: if the
 library is missing or no HIP device is present, every transform raises."""
 import ctypes as C
 import os
@@ -189,6 +189,13 @@ SUBSPACE_PROTOTYPES = {
     "qi_beam_music": (_int, [_int, _int, _P, _i64, _i64, _i64, _D, _P, _i64, _I64, _i64, _P, _P, _P, _P, _i64, _P]),
 }
 
+# include/qi_steer.h (beam weights over delay rows, Bartlett or MVDR, and their application to a panel), one to one
+STEER_PROTOTYPES = {
+    "qi_beam_weights_scratch_bytes": (_i64, [_int, _i64, _i64, _i64]),
+    "qi_beam_weights": (_int, [_int, _int, _P, _i64, _i64, _D, _P, _i64, _P, _P, _i64, _P]),
+    "qi_beam_steer": (_int, [_int, _int, _P, _i64, _i64, _i64, _P, _i64, _P, _P]),
+}
+
 _lib = None
 
 
@@ -211,7 +218,8 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES, **SUBSPACE_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES, **SUBSPACE_PROTOTYPES,
+                               **STEER_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -2,20 +2,23 @@
 Frequency-wavenumber (f-k) analysis of a sensor array: steered power of the cross-spectral matrices over a grid of
 slowness vectors (engine.beam_power, include/qi_beam.h), Capon's minimum-variance power over the same grid
 (engine.csd_whiten and engine.capon_power, include/qi_adaptive.h), and the MUSIC power of the matrices' noise subspaces
-(engine.csd_eigh and engine.music_power, include/qi_subspace.h).  The reference (quantum-inferno) has no array processing;
-the conventions below are the usual ones of infrasound and seismic array work.
+(engine.csd_eigh and engine.music_power, include/qi_subspace.h) -- and, once the map has a peak, the signal from that
+direction: beam panels and beam waveforms with Bartlett or MVDR weights (engine.beam_weights and engine.beam_steer,
+include/qi_steer.h).  The reference (quantum-inferno) has no array processing; the conventions below are the usual ones of
+infrasound and seismic array work.
 
 Geometry.  Positions are [C, 2] metres (x east, y north).  A slowness vector s [s/m] points the way the wave TRAVELS; a
 plane wave reaches sensor i later by tau_i = s . r_i seconds.  The back azimuth is where it comes FROM: the direction of
 -s in degrees clockwise from north; the trace velocity is 1 / |s|.
 
 The helpers are host code on torch float64; only plane_wave_delays' result and the work of fk_power_pow2,
-capon_power_pow2 and music_power_pow2 are on the device.
+capon_power_pow2, music_power_pow2, beam_stft_pow2 and beam_traces_tukey are on the device.
 """
 import numpy as np
 import torch
 
 from . import engine, styx_fft
+from .utilities import short_time_fft
 
 
 def _host64(a, cols, what):
@@ -185,3 +188,84 @@ def music_power_pow2(
     power, index, value = engine.music_power(vectors, n_sources, f, tau, bands=bands, peaks=True)
     return (ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False),
             engine.finish(info, was_numpy, False))
+
+
+BEAM_METHODS = ("bartlett", "capon")
+
+
+def _panel_weights(panel, frequency_hz, positions_m, slowness, method, loading):
+    """The weights step of beam_stft_pow2 and beam_traces_tukey: panel [C, nf, segments] on the device -> (weights
+    [nf, K, C], info [nf] or None).  bartlett: e / C.  capon: the MVDR weights of the panel's own cross-spectral matrices
+    (engine.cross_spectra with weight 1 / segments), loaded and factored once per bin (engine.csd_whiten)."""
+    if method not in BEAM_METHODS:
+        raise ValueError(f"method must be one of {BEAM_METHODS}, got {method!r}")
+    n_ch, n_f, n_seg = panel.shape
+    tau = plane_wave_delays(positions_m, slowness, panel.device)
+    if tau.shape[1] != n_ch:
+        raise ValueError(f"{tau.shape[1]} positions for {n_ch} records")
+    if method == "bartlett":
+        return engine.beam_weights(frequency_hz, tau, sensors=n_ch, dtype=panel.real.dtype), None
+    csd = engine.cross_spectra(panel, weight=np.full(n_f, 1.0 / n_seg))
+    whitener, info = engine.csd_whiten(csd, loading=loading, info=True)
+    return engine.beam_weights(frequency_hz, tau, whitener=whitener), info
+
+
+def beam_stft_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    positions_m,
+    slowness,
+    segment_points: int,
+    overlap_points: int = None,
+    nfft_points: int = None,
+    alpha: float = 0.25,
+    method: str = "bartlett",
+    loading: float = 1e-2,
+):
+    """Beam panels of the records of one array [C x n]: styx_fft.stft_complex_pow2's panel of every record, mixed per bin with
+    the weights of each slowness vector [K, 2] (engine.beam_steer): beams[k] is the STFT of the signal that travels with
+    slowness[k].  method "bartlett": delay-and-sum, weights e / C with e_i = exp(2 pi i f tau_i), tau = plane_wave_delays.
+    method "capon": the minimum-variance distortionless-response (MVDR) weights R^-1 e / (e^H R^-1 e) of the panel's own
+    cross-spectral matrices (their mean over the segments), loaded on the diagonal with `loading` times the mean auto-power
+    (engine.csd_whiten): unit gain towards slowness[k], the least power from everywhere else.  With fewer segments than a
+    few times the sensors MVDR also cancels part of the wanted signal; raise `loading` towards Bartlett.  The delay is applied
+    as a phase per bin of each segment -- a circular shift inside the windowed segment -- so the delays across the array must
+    be short against the segment.  Neither the panel, the matrices nor the weights leave the device.
+    :return: frequency_hz [nf], time_s [segments], beams [K x nf x segments] complex, info: None (bartlett) or [nf] int32
+        (capon: 0, or the 1-based pivot at which the bin's factorisation failed; such a bin's beams are NaN)"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    f, t, panel = styx_fft.stft_complex_pow2(sig, frequency_sample_rate_hz, segment_points, overlap_points, nfft_points, alpha)
+    weights, info = _panel_weights(panel, f, positions_m, slowness, method, loading)
+    beams = engine.beam_steer(panel, weights)
+    return f, t, engine.finish(beams, was_numpy, False), (None if info is None else engine.finish(info, was_numpy, False))
+
+
+def beam_traces_tukey(
+    sig_wf,
+    sample_rate_hz: float,
+    positions_m,
+    slowness,
+    segment_length: int,
+    overlap_length: int,
+    tukey_alpha: float = 0.25,
+    method: str = "bartlett",
+    loading: float = 1e-2,
+):
+    """Beam waveforms of the records of one array [C x n], one real trace per slowness vector [K, 2]: frequency-domain
+    delay-and-sum through the invertible transform of utilities.short_time_fft.  The complex ShortTimeFFT-convention panel of
+    every record (symmetric Tukey window, zero padding, no detrend), the weights of beam_stft_pow2 (method "bartlett" or
+    "capon" with `loading`), engine.beam_steer, and istft_tukey's inverse of every beam panel.  The delay is a phase ramp per
+    segment: a circular shift inside each windowed segment, not a shift of the record, so the delays across the array must be
+    short against the segment (a plane wave across 60 m at 800 Hz, delays of up to 53 samples: 5 % relative RMS error at
+    segments of 1024 with overlap 768 -- the records' own noise floor is 4.5 % --, 16 % at 256 / 128).  With few segments
+    Capon cancels part of the signal (13 % in the same case at loading 0.1, 19 segments).  Zero delays give the mean of the
+    records.  Nothing but the traces and info leaves the device.
+    :return: timestamps [samples] (istft_tukey's: up to the last window index), traces [K x samples] real, info: None
+        (bartlett) or [bins] int32 as beam_stft_pow2 returns it"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    obj = short_time_fft.get_stft_object_tukey(sample_rate_hz, tukey_alpha, segment_length, overlap_length, "magnitude")
+    panel = short_time_fft._forward(obj, sig, "zeros", False, 0)
+    weights, info = _panel_weights(panel, obj.f, positions_m, slowness, method, loading)
+    beams = engine.beam_steer(panel, weights)
+    timestamps, traces = short_time_fft.istft_tukey(beams, sample_rate_hz, tukey_alpha, segment_length, overlap_length, "magnitude")
+    return timestamps, engine.finish(traces, was_numpy, False), (None if info is None else engine.finish(info, was_numpy, False))

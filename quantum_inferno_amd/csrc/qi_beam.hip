@@ -63,6 +63,7 @@
 #include "qi_device.hpp"   // kWave
 #include "qi_fft_reg.hpp"  // QI_LAUNCH_CHECK
 #include "qi_mfma.hpp"     // Mx, kMxTile
+#include "qi_phase.hpp"    // beam_factor: the phase rule
 #include "qi_beam.h"
 #include "qi_adaptive.h"
 #include "qi_subspace.h"
@@ -83,9 +84,6 @@ template <typename T>
 __host__ __device__ constexpr int beam_ld(int ntile) {
   return ntile * kBeamTile + (sizeof(T) == 4 ? 4 : 0);
 }
-
-__device__ __forceinline__ void beam_sincospi(float x, float* s, float* c) { sincospif(x, s, c); }
-__device__ __forceinline__ void beam_sincospi(double x, double* s, double* c) { sincospi(x, s, c); }
 
 template <typename T>
 struct BeamArgs {
@@ -226,11 +224,7 @@ __device__ __forceinline__ void beam_walk(const BeamArgs<T>& a) {
     const double fr = a.freq[f];
     T er[KT], ei[KT];
 #pragma unroll
-    for (int t = 0; t < KT; ++t) {
-      double turns = fr * tau[t];
-      turns -= rint(turns);  // [-1/2, 1/2]
-      beam_sincospi((T)(2.0 * turns), &ei[t], &er[t]);
-    }
+    for (int t = 0; t < KT; ++t) beam_factor<T>(fr, tau[t], &er[t], &ei[t]);
 #pragma unroll
     for (int tj = 0; tj < NT; ++tj) {
       acc rr{0, 0, 0, 0}, ii{0, 0, 0, 0}, ir{0, 0, 0, 0}, ri{0, 0, 0, 0};

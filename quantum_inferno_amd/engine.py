@@ -797,6 +797,70 @@ def music_power(eigenvectors, n_sources, frequency_hz, delays_s, bands=None, pea
     return _delay_grid_form("beam_music", eigenvectors, "eigenvectors", frequency_hz, delays_s, bands, peaks, form_first=(n,))
 
 
+def beam_weights(frequency_hz, delays_s, whitener=None, sensors=None, dtype=None):
+    """Beam weights of nf bins over nbeam delay rows (qi_beam_weights), what beam_steer applies: with
+    e[f, k, i] = exp(2 pi i frequency_hz[f] delays_s[k, i]), the conventional (Bartlett, delay-and-sum) weights a = e / C, or,
+    with the whiteners V of csd_whiten (R^-1 = V V^H), the minimum-variance distortionless-response (MVDR) weights
+    u = V^H e, D = sum_j |u_j|^2, a = V u / D = R^-1 e / (e^H R^-1 e): the a that minimises a^H R a under e^H a = 1, with
+    a^H R a = 1 / D, the power capon_power gives.  frequency_hz: [nf] host values; delays_s: [nbeam, C] seconds, NumPy or
+    tensor, converted to float64 on the device; whitener: [nf, C, C] complex64 / complex128 or None.  With a whitener C and the
+    precision are its own; without one C is delays_s.shape[1] (sensors, if given, must agree) and dtype float32 (the default) or
+    float64.  A bin whose whitener csd_whiten flagged has NaN weights.  -> weights [nf, nbeam, C] complex.  NumPy in (the
+    whitener, or the delays without one) -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    f_host, f_ptr = _lib.darr(frequency_hz)
+    if f_host.ndim != 1 or f_host.size < 1:
+        raise ValueError(f"frequency_hz must be a non-empty list of bin frequencies, got shape {f_host.shape}")
+    tau = delays_s if isinstance(delays_s, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(delays_s))
+    if whitener is not None:
+        v, was_numpy, rdtype = _matrix_stack(whitener, "whitener")
+        if dtype is not None and _real_dtype(dtype) != rdtype:
+            raise ValueError(f"dtype {dtype} given with a {v.dtype} whitener: the precision is the whitener's")
+        n_f, n_ch, dev = v.shape[0], v.shape[1], v.device
+        if f_host.shape != (n_f,):
+            raise ValueError(f"frequency_hz must hold one value per matrix ({n_f}), got shape {f_host.shape}")
+    else:
+        v, was_numpy = None, not isinstance(delays_s, torch.Tensor)
+        rdtype = torch.float32 if dtype is None else _real_dtype(dtype)
+        if rdtype not in (torch.float32, torch.float64):
+            raise ValueError(f"dtype must be float32 or float64, got {dtype}")
+        n_f, n_ch = f_host.size, (tau.shape[1] if tau.dim() == 2 else -1)
+        dev = tau.device if tau.is_cuda else default_device()
+    if sensors is not None and int(sensors) != n_ch:
+        raise ValueError(f"sensors={sensors}, but the {'whitener' if v is not None else 'delays'} hold {n_ch}")
+    if tau.dim() != 2 or tau.shape[0] < 1 or tau.shape[1] != n_ch:
+        raise ValueError(f"delays_s must be [nbeam, {n_ch if n_ch > 0 else 'C'}], got shape {tuple(tau.shape)}")
+    tau = tau.to(dev).to(torch.float64).contiguous()
+    n_k = tau.shape[0]
+    code = _lib.dtype_code(rdtype)
+    scratch, nbytes = _lib.scratch(lib.qi_beam_weights_scratch_bytes, dev, code, n_ch, n_f, n_k)
+    weights = torch.empty((n_f, n_k, n_ch), dtype=_complex_of(rdtype), device=dev)
+    _lib.call(lib.qi_beam_weights, dev, code, dev.index, _lib.ptr(v), n_ch, n_f, f_ptr, _lib.ptr(tau), n_k, _lib.ptr(weights),
+              _lib.ptr(scratch), nbytes)
+    return finish(weights, was_numpy, False)
+
+
+def beam_steer(panel, weights):
+    """Beams of a stored coefficient panel (qi_beam_steer): out[k, f, t] = sum_i weights[f, k, i] panel[i, f, t], summed on the
+    matrix cores in the panel's precision.  There is no conjugate: with cross_spectra's csd = conj(Z_i) Z_j,
+    mean_t |out|^2 = a^H csd a, and beam_weights' a = e / C aligns a plane wave that reaches sensor i later by delays_s[k, i].
+    panel: [C, n_bands, n_time] complex64 / complex128 (an STFT, CWT or Stockwell panel of C <= 64 records); weights:
+    [n_bands, nbeam, C] of the same dtype -- beam_weights' or any others: the call is a general per-bin mixing of the records.
+    -> beams [nbeam, n_bands, n_time].  NumPy panel in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    z, was_numpy, rdtype = _matrix_stack(panel, "panel", "[C, bands, time]", square=False)
+    n_ch, n_f, n_t = z.shape
+    w, _, w_rdtype = _matrix_stack(weights, "weights", "[bands, beams, C]", square=False)
+    if w_rdtype != rdtype or w.shape[0] != n_f or w.shape[2] != n_ch:
+        raise ValueError(f"weights must be {z.dtype} [{n_f}, beams, {n_ch}] for this panel, got {w.dtype} {tuple(w.shape)}")
+    dev, code = z.device, _lib.dtype_code(rdtype)
+    w = w.to(dev)
+    n_k = w.shape[1]
+    out = torch.empty((n_k, n_f, n_t), dtype=z.dtype, device=dev)
+    _lib.call(lib.qi_beam_steer, dev, code, dev.index, _lib.ptr(z), n_ch, n_f, n_t, _lib.ptr(w), n_k, _lib.ptr(out))
+    return finish(out, was_numpy, False)
+
+
 def _record_shape(a, what="signal", nonempty=True):
     """Shape (n,) or (C, n) of records, NumPy or tensor, checked before anything needs the device; n is its last entry."""
     shape = tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)

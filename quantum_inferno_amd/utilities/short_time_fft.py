@@ -144,7 +144,8 @@ def _as_rows(x, complex_ok=False):
 
 
 def _forward(obj: TukeyStft, timeseries, padding, detrend, real_kind):
-    """|STFT| (real_kind 1) or |STFT|^2 (2) of the record(s): [.., f_pts, p_num]."""
+    """|STFT| (real_kind 1) or |STFT|^2 (2) of the record(s): [.., f_pts, p_num]; real_kind 0: the complex STFT itself
+    (ShortTimeFFT.stft's values and phase convention, what istft_tukey inverts)."""
     lib = _lib.require_gpu()
     x, was_numpy = _as_rows(timeseries)
     one = x.dim() == 1
@@ -155,12 +156,12 @@ def _forward(obj: TukeyStft, timeseries, padding, detrend, real_kind):
     n_slices = p1 - p0
     first = p0 * obj.hop - obj.m_num_mid
     win = torch.from_numpy(obj.win).to(device=x.device, dtype=x.dtype)
-    out = torch.empty((n_ch, obj.f_pts, n_slices), dtype=x.dtype, device=x.device)
+    out = torch.empty((n_ch, obj.f_pts, n_slices), dtype=x.dtype if real_kind else engine._complex_of(x.dtype), device=x.device)
     code = _lib.dtype_code(x.dtype)
     scratch, nbytes = _lib.scratch(lib.qi_sliding_scratch_bytes, x.device, code, n_ch, obj.mfft, n_slices)
     _lib.call(lib.qi_sliding_stft, x.device, code, x.device.index, _lib.ptr(x), n_ch, n, _lib.ptr(win), obj.m_num, obj.hop, obj.mfft,
-              first, n_slices, _PAD_CODE[padding], 1 if detrend else 0, obj.m_num_mid, None, _lib.ptr(out), real_kind,
-              _lib.ptr(scratch), nbytes)
+              first, n_slices, _PAD_CODE[padding], 1 if detrend else 0, obj.m_num_mid, None if real_kind else _lib.ptr(out),
+              _lib.ptr(out) if real_kind else None, real_kind, _lib.ptr(scratch), nbytes)
     if one:
         out = out[0]
     return out.cpu().numpy() if was_numpy else out
