@@ -196,6 +196,14 @@ STEER_PROTOTYPES = {
     "qi_beam_steer": (_int, [_int, _int, _P, _i64, _i64, _i64, _P, _i64, _P, _P]),
 }
 
+# include/qi_windows.h (cross-spectral matrices per sliding window of segments), one to one
+WINDOW_PROTOTYPES = {
+    "qi_cross_spectra_windows_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "qi_cross_spectra_windows": (_int, [_int, _int, _P, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _D, _P, _P, _P, _i64, _P]),
+    "qi_csd_windows_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "qi_csd_windows": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _i64, _dbl, _i64, _i64, _i64, _i64, _P, _P, _P, _i64, _P]),
+}
+
 _lib = None
 
 
@@ -219,7 +227,7 @@ def load():
         )
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES, **SUBSPACE_PROTOTYPES,
-                               **STEER_PROTOTYPES}.items():
+                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -4,15 +4,16 @@ slowness vectors (engine.beam_power, include/qi_beam.h), Capon's minimum-varianc
 (engine.csd_whiten and engine.capon_power, include/qi_adaptive.h), and the MUSIC power of the matrices' noise subspaces
 (engine.csd_eigh and engine.music_power, include/qi_subspace.h) -- and, once the map has a peak, the signal from that
 direction: beam panels and beam waveforms with Bartlett or MVDR weights (engine.beam_weights and engine.beam_steer,
-include/qi_steer.h).  The reference (quantum-inferno) has no array processing; the conventions below are the usual ones of
-infrasound and seismic array work.
+include/qi_steer.h).  fk_timeline_pow2 runs the three power forms per sliding window of the record
+(styx_fft.csd_windows_pow2's matrices, include/qi_windows.h): a detection timeline.  The reference (quantum-inferno) has no
+array processing; the conventions below are the usual ones of infrasound and seismic array work.
 
 Geometry.  Positions are [C, 2] metres (x east, y north).  A slowness vector s [s/m] points the way the wave TRAVELS; a
 plane wave reaches sensor i later by tau_i = s . r_i seconds.  The back azimuth is where it comes FROM: the direction of
 -s in degrees clockwise from north; the trace velocity is 1 / |s|.
 
 The helpers are host code on torch float64; only plane_wave_delays' result and the work of fk_power_pow2,
-capon_power_pow2, music_power_pow2, beam_stft_pow2 and beam_traces_tukey are on the device.
+capon_power_pow2, music_power_pow2, fk_timeline_pow2, beam_stft_pow2 and beam_traces_tukey are on the device.
 """
 import numpy as np
 import torch
@@ -188,6 +189,91 @@ def music_power_pow2(
     power, index, value = engine.music_power(vectors, n_sources, f, tau, bands=bands, peaks=True)
     return (ranges, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False), engine.finish(value, was_numpy, False),
             engine.finish(info, was_numpy, False))
+
+
+TIMELINE_METHODS = ("bartlett", "capon", "music")
+
+
+def fk_timeline_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    positions_m,
+    slowness,
+    segment_points: int,
+    window_segments: int,
+    window_hop_segments: int = None,
+    overlap_points: int = None,
+    nfft_points: int = None,
+    alpha: float = 0.25,
+    band_edges_hz=None,
+    method: str = "bartlett",
+    normalize: bool = True,
+    loading: float = 1e-2,
+    n_sources: int = 1,
+):
+    """Detection timeline of the records of one array [C x n]: fk_power_pow2 (method "bartlett"), capon_power_pow2 ("capon")
+    or music_power_pow2 ("music") per sliding window of the record's Welch segments -- when did something arrive, and from
+    where.  styx_fft.csd_windows_pow2's matrices (window_segments segments every window_hop_segments, None for half a
+    window) are formed in one launch for the bins of the bands only, and the form runs once on the stack of all windows:
+    window w's band b is band w * nb + b of a table in which the frequencies repeat per window.  normalize (bartlett only):
+    the semblance instead of the power; the other methods have none and refuse normalize=False.  Nothing but the results
+    leaves the device.  back_azimuth_and_velocity(slowness[peak_index]) gives the timeline's azimuth and velocity columns,
+    fisher_from_semblance(peak_value, C) its F ratio.
+    :return: window_time_s [nwin], band_frequency_ranges [nb x 2], power [nwin x nb x G], peak_index [nwin x nb],
+        peak_value [nwin x nb], info: None for bartlett, [nwin x bins] int32 for capon / music (as those functions return it)"""
+    if method not in TIMELINE_METHODS:
+        raise ValueError(f"method must be one of {TIMELINE_METHODS}, got {method!r}")
+    if method != "bartlett" and not normalize:
+        raise ValueError(f"normalize belongs to the bartlett method: there is no {method} semblance to leave out")
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    table = {}
+
+    def bins_of(f):
+        # only the bins of the bands are formed: one window's last band is followed by the next window's first
+        table["bands"] = None if band_edges_hz is None else band_offsets(f, band_edges_hz)
+        return (0, f.size) if table["bands"] is None else (int(table["bands"][0]), int(table["bands"][-1] - table["bands"][0]))
+
+    f, time_s, csd, _ = styx_fft._csd_window_matrices(sig, frequency_sample_rate_hz, segment_points, window_segments, window_hop_segments,
+                                                      nfft_points, overlap_points, alpha, "spectrum", None, True, False, bins_of=bins_of)
+    n_win, bins, n_ch, _ = csd.shape
+    if table["bands"] is None:
+        bands, n_b, ranges = None, bins, np.stack([f, f], axis=1)
+    else:
+        local = table["bands"] - table["bands"][0]
+        n_b = local.size - 1
+        ranges = np.stack([f[local[:-1]], f[local[1:] - 1]], axis=1)
+        bands = np.concatenate([(np.arange(n_win, dtype=np.int64)[:, None] * bins + local[None, :-1]).reshape(-1), [n_win * bins]])
+    tau = plane_wave_delays(positions_m, slowness, sig.device)
+    if tau.shape[1] != n_ch:
+        raise ValueError(f"{tau.shape[1]} positions for {n_ch} records")
+    stack, f_all, info = csd.reshape(n_win * bins, n_ch, n_ch), np.tile(f, n_win), None
+    if method == "bartlett":
+        power, index, value = engine.beam_power(stack, f_all, tau, bands=bands, normalize=normalize, peaks=True)
+    elif method == "capon":
+        whitener, info = engine.csd_whiten(stack, loading=loading, info=True)
+        power, index, value = engine.capon_power(whitener, f_all, tau, bands=bands, peaks=True)
+    else:
+        _, vectors, info = engine.csd_eigh(stack, info=True)
+        power, index, value = engine.music_power(vectors, n_sources, f_all, tau, bands=bands, peaks=True)
+    return (time_s, ranges, engine.finish(power.reshape(n_win, n_b, -1), was_numpy, False),
+            engine.finish(index.reshape(n_win, n_b), was_numpy, False), engine.finish(value.reshape(n_win, n_b), was_numpy, False),
+            None if info is None else engine.finish(info.reshape(n_win, bins), was_numpy, False))
+
+
+def fisher_from_semblance(semblance, sensors: int):
+    """The frequency-domain F ratio of a steered band from its semblance s (fk_power_pow2's and fk_timeline_pow2's
+    normalize=True value): F = (C - 1) s / (1 - s), the beam's power over the residual's per degree of freedom, for C sensors.
+    s = 0 gives 0, s = 1 / C (uncorrelated records) gives 1, s = 1 gives inf, NaN stays NaN.  Host or device arithmetic on
+    whatever came in: a NumPy array, a tensor or a number.  With back_azimuth_and_velocity(slowness[peak_index]) these are
+    the columns of a detection timeline."""
+    c = int(sensors)
+    if c < 2:
+        raise ValueError(f"the F ratio needs at least two sensors, got {sensors}")
+    if isinstance(semblance, torch.Tensor):
+        return (c - 1) * semblance / (1 - semblance)
+    s = np.asarray(semblance, dtype=np.float64) if not isinstance(semblance, np.ndarray) else semblance
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (c - 1) * s / (1 - s)
 
 
 BEAM_METHODS = ("bartlett", "capon")

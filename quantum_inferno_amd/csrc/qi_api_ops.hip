@@ -2,6 +2,7 @@
 // family, widening and log2 helpers, Gabor atoms.
 #include "qi_host.hpp"
 #include "qi_array.h"
+#include "qi_windows.h"
 
 using namespace qi;
 using qi::host::align_up;
@@ -338,28 +339,47 @@ int qi_welch(int dtype, int device, const void* sig, int64_t C, int64_t n, const
 }
 
 // ---- cross-spectra of the Welch segments (include/qi_array.h) -----------------------------------------------------------
-// Scratch of qi_csd: [0] the three-kernel path's frames and spectra | [1] the coefficient panel [C][nfft / 2 + 1][nseg] | [2]
-// the contraction's own (cross_spectra_scratch)
+// Scratch of qi_csd and qi_csd_windows: [0] the three-kernel path's frames and spectra | [1] the coefficient panel
+// [C][nfft / 2 + 1][nseg] | [2] the contraction's own (cross_spectra_scratch, cross_spectra_windows_scratch)
 struct CsdLayout {
   size_t panel, cross, total;
-  CsdLayout(int dtype, int64_t C, int64_t nseg, int64_t nfft) {
+  CsdLayout(int dtype, int64_t C, int64_t nseg, int64_t nfft, size_t contraction) {
     const int64_t nf = nfft / 2 + 1;
     panel = FftScratch(dtype, C, nseg, nfft).total;
     cross = panel + align_up((size_t)C * nf * nseg * 2 * elem_size(dtype));
-    total = cross + cross_spectra_scratch(dtype, C, nf);
+    total = cross + contraction;
   }
 };
-static int csd_check(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {
+static int csd_geometry_check(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {
   QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
   QI_REQUIRE(C > 0 && seg > 0 && n >= seg && hop > 0 && hop <= seg && nfft >= seg, "bad Welch geometry");
+  return QI_OK;
+}
+static int csd_check(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {
+  QI_TRY(csd_geometry_check(dtype, C, n, seg, hop, nfft));
   // (the shape refusals of the contraction, before anything is launched)
   const int64_t bytes = qi_cross_spectra_scratch_bytes(dtype, C, nfft / 2 + 1, (n - seg) / hop + 1);
   return bytes < 0 ? (int)bytes : QI_OK;
 }
+// the first step of both: qi_welch's segments as the UNSCALED coefficient panel [C][nfft / 2 + 1][nseg] in the layout's second
+// region (the weight of the contraction carries scale^2)
+static int csd_panel(int dtype, int device, const StftRequest& rq, const CsdLayout& l, const void* sig, const void* window,
+                     void* scratch, hipStream_t st) {
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    const T *x = (const T*)sig, *win = (const T*)window;
+    char* s = (char*)scratch;
+    cplx<T>* Z = reinterpret_cast<cplx<T>*>(s + l.panel);
+    return fused_or_hipfft(
+        stft_fused_supported(dtype, rq.seg, rq.hop, rq.nfft),
+        [&] { return launch_stft_fused<T>(rq, x, win, Z, (T*)nullptr, st); },  // the storing form with lead = 0
+        [&] { return stft_hipfft<T>(device, rq, x, win, Z, (T*)nullptr, s, st); });
+  });
+}
 
 int64_t qi_csd_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft) {
   QI_TRY(csd_check(dtype, C, n, seg, hop, nfft));
-  return (int64_t)CsdLayout(dtype, C, (n - seg) / hop + 1, nfft).total;
+  return (int64_t)CsdLayout(dtype, C, (n - seg) / hop + 1, nfft, cross_spectra_scratch(dtype, C, nfft / 2 + 1)).total;
 }
 
 int qi_csd(int dtype, int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop,
@@ -368,26 +388,64 @@ int qi_csd(int dtype, int device, const void* sig, int64_t C, int64_t n, const v
   QI_REQUIRE(csd || coherence, "nothing to produce");
   QI_TRY(csd_check(dtype, C, n, seg, hop, nfft));
   const int64_t nseg = (n - seg) / hop + 1, nf = nfft / 2 + 1;
-  const CsdLayout l(dtype, C, nseg, nfft);
+  const CsdLayout l(dtype, C, nseg, nfft, cross_spectra_scratch(dtype, C, nf));
   QI_TRY(require_scratch(scratch_bytes, (int64_t)l.total));
   QI_REQUIRE(aligned(scratch, 16), "misaligned scratch");
   DeviceGuard g(device);
   hipStream_t st = (hipStream_t)stream;
-  StftRequest rq{C, n, seg, hop, nfft, nseg, 0};  // qi_welch's segments; the panel unscaled: the weight carries scale^2
+  StftRequest rq{C, n, seg, hop, nfft, nseg, 0};  // qi_welch's segments
   CsdWeight w;
   w.edge = scale * scale / (double)nseg;
   w.paired = 2.0 * w.edge;
   w.nfft = nfft;
+  QI_TRY(csd_panel(dtype, device, rq, l, sig, window, scratch, st));
   return by_dtype(dtype, [&](auto t) -> int {
     using T = decltype(t);
-    const T *x = (const T*)sig, *win = (const T*)window;
     char* s = (char*)scratch;
-    cplx<T>* Z = reinterpret_cast<cplx<T>*>(s + l.panel);
-    QI_TRY(fused_or_hipfft(
-        stft_fused_supported(dtype, seg, hop, nfft),
-        [&] { return launch_stft_fused<T>(rq, x, win, Z, (T*)nullptr, st); },  // the storing form with lead = 0
-        [&] { return stft_hipfft<T>(device, rq, x, win, Z, (T*)nullptr, s, st); }));
-    return launch_cross_spectra<T>(Z, C, nf, nseg, w, (cplx<T>*)csd, (T*)coherence, s + l.cross + align_up((size_t)nf * 8), st);
+    return launch_cross_spectra<T>(reinterpret_cast<const cplx<T>*>(s + l.panel), C, nf, nseg, w, (cplx<T>*)csd, (T*)coherence,
+                                   s + l.cross + align_up((size_t)nf * 8), st);
+  });
+}
+
+// ---- the same per sliding window of segments (include/qi_windows.h) -----------------------------------------------------
+static int csd_windows_check(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft, int64_t bin_first,
+                             int64_t bin_count, int64_t win, int64_t win_hop, int64_t* contraction) {
+  QI_TRY(csd_geometry_check(dtype, C, n, seg, hop, nfft));
+  *contraction = qi_cross_spectra_windows_scratch_bytes(dtype, C, nfft / 2 + 1, (n - seg) / hop + 1, bin_first, bin_count, win, win_hop);
+  return *contraction < 0 ? (int)*contraction : QI_OK;
+}
+
+int64_t qi_csd_windows_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t seg, int64_t hop, int64_t nfft, int64_t bin_first,
+                                     int64_t bin_count, int64_t win, int64_t win_hop) {
+  int64_t contraction = 0;
+  QI_TRY(csd_windows_check(dtype, C, n, seg, hop, nfft, bin_first, bin_count, win, win_hop, &contraction));
+  return (int64_t)CsdLayout(dtype, C, (n - seg) / hop + 1, nfft, (size_t)contraction).total;
+}
+
+int qi_csd_windows(int dtype, int device, const void* sig, int64_t C, int64_t n, const void* window, int64_t seg, int64_t hop,
+                   int64_t nfft, double scale, int64_t bin_first, int64_t bin_count, int64_t win, int64_t win_hop, void* csd,
+                   void* coherence, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_REQUIRE(sig && window && scratch, "null argument");
+  QI_REQUIRE(csd || coherence, "nothing to produce");
+  int64_t contraction = 0;
+  QI_TRY(csd_windows_check(dtype, C, n, seg, hop, nfft, bin_first, bin_count, win, win_hop, &contraction));
+  const int64_t nseg = (n - seg) / hop + 1, nf = nfft / 2 + 1;
+  const CsdLayout l(dtype, C, nseg, nfft, (size_t)contraction);
+  QI_TRY(require_scratch(scratch_bytes, (int64_t)l.total));
+  QI_REQUIRE(aligned(scratch, 16) && aligned(csd, 2 * elem_size(dtype)) && aligned(coherence, elem_size(dtype)), "misaligned pointer");
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  StftRequest rq{C, n, seg, hop, nfft, nseg, 0};  // qi_welch's segments
+  CsdWeight w;  // every window averages its own `win` segments
+  w.edge = scale * scale / (double)win;
+  w.paired = 2.0 * w.edge;
+  w.nfft = nfft;
+  QI_TRY(csd_panel(dtype, device, rq, l, sig, window, scratch, st));
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    char* s = (char*)scratch;
+    return launch_cross_spectra_windows<T>(reinterpret_cast<const cplx<T>*>(s + l.panel), C, nf, nseg, bin_first, bin_count, win, win_hop,
+                                           w, (cplx<T>*)csd, (T*)coherence, s + l.cross + align_up((size_t)bin_count * 8), st);
   });
 }
 

@@ -215,6 +215,12 @@ size_t cross_spectra_scratch(int dtype, int64_t C, int64_t nf);
 template <typename T>
 int launch_cross_spectra(const cplx<T>* Z, int64_t C, int64_t nf, int64_t nseg, const CsdWeight& w, cplx<T>* csd, T* coherence,
                          void* matrices, hipStream_t st);
+// the windowed form (include/qi_windows.h): csd / coherence [nwin][bin_count][C][C], nwin = (nseg - win) / hop + 1; w.table
+// holds one weight per FORMED bin, w.edge / w.paired go by the absolute bin.  Scratch: bin_count doubles | the matrices
+size_t cross_spectra_windows_scratch(int dtype, int64_t C, int64_t bin_count, int64_t nwin);
+template <typename T>
+int launch_cross_spectra_windows(const cplx<T>* Z, int64_t C, int64_t nf, int64_t nseg, int64_t bin_first, int64_t bin_count, int64_t win,
+                                 int64_t hop, const CsdWeight& w, cplx<T>* csd, T* coherence, void* matrices, hipStream_t st);
 
 template <typename T>
 int launch_power_marginals(const T* P, int64_t C, int64_t B, int64_t n, T* power_time, double* part_band,

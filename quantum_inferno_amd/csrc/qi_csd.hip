@@ -27,11 +27,17 @@
 // wave per bin; no wave shares a sum with another, so there are no partial sums to combine.  The K order of an entry depends
 // on nseg alone and each output element of the instruction is its own chain: an entry is a function of its two records,
 // whatever the batch, their places in it and the tiles a wave takes.
+//
+// Windows (include/qi_windows.h).  k_cross_spectra_windows forms one matrix per (window of segments, formed bin) with the same
+// wave: the body is qi_csd_wave.inc, included by both kernels, with the window's first segment and length where the panel's 0
+// and nseg stand -- a window's sums are k_cross_spectra's on the contiguous slice bit for bit, and what the panel holds past
+// the window's end is a zero operand.
 #include "qi_host.hpp"
 #include "qi_device.hpp"   // kWave
 #include "qi_fft_reg.hpp"  // QI_LAUNCH_CHECK
 #include "qi_mfma.hpp"     // Mx
 #include "qi_array.h"
+#include "qi_windows.h"
 
 using namespace qi;
 using qi::host::align_up;
@@ -68,106 +74,41 @@ __device__ __forceinline__ void csd_load(const cplx<T>* __restrict__ row, bool o
 // groups of up to `nj` tiles in row ti of the upper triangle of a matrix of `ntile` tiles a side
 __host__ __device__ inline int64_t csd_row_groups(int64_t ntile, int64_t ti, int nj) { return (ntile - ti + nj - 1) / nj; }
 
-// NJ: tiles of one tile row a wave takes -- they share the A operand's loads; a matter of registers and traffic, not of results
+// NJ: tiles of one tile row a wave takes -- they share the A operand's loads; a matter of registers and traffic, not of results.
+// The wave's work is qi_csd_wave.inc, the text that the windowed kernel below shares.
 template <typename T, int NJ>
 __global__ void __launch_bounds__(kCsdWaves* kWave) k_cross_spectra(const cplx<T>* __restrict__ Z, cplx<T>* __restrict__ S, CsdArgs a) {
-  using M = Mx<T>;
-  using acc = typename M::acc;
-  constexpr int V = M::V, STEP = 4 * V;  // segments of one iteration
-  const int lane = threadIdx.x & (kWave - 1);
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int64_t f = ((int64_t)blockIdx.x % a.nfb) * kCsdWaves + wv;
   if (f >= a.nf) return;  // (the whole wave)
-  // item -> tile row ti and its group of up to NJ tiles tj0 .. tj0 + nj - 1, tj0 >= ti: the groups row by row of the upper triangle
-  int64_t p = (int64_t)blockIdx.x / a.nfb, ti = 0;
-  while (p >= csd_row_groups(a.ntile, ti, NJ)) {
-    p -= csd_row_groups(a.ntile, ti, NJ);
-    ++ti;
-  }
-  const int64_t tj0 = ti + p * NJ;
-  const int nj = (int)(a.ntile - tj0 < NJ ? a.ntile - tj0 : NJ);
-  const bool diag0 = tj0 == ti;  // the group's first tile lies on the diagonal: its B operand is the A operand
-  const int r = lane & 15, g = lane >> 4;
-  // (a record past C: the pointer stays inside the panel, the operand is zero)
-  const int64_t ci = ti * kCsdTile + r;
-  const bool oni = ci < a.C;
-  const cplx<T>* __restrict__ zi = Z + ((oni ? ci : 0) * a.nf + f) * a.nseg;
-  const cplx<T>* zj[NJ];
-  bool onj[NJ];
-#pragma unroll
-  for (int q = 0; q < NJ; ++q) {
-    const int64_t cj = (tj0 + q) * kCsdTile + r;
-    onj[q] = q < nj && cj < a.C;
-    zj[q] = Z + ((onj[q] ? cj : 0) * a.nf + f) * a.nseg;
-  }
-  acc rr[NJ], ii[NJ], ri[NJ], ir[NJ];
-#pragma unroll
-  for (int q = 0; q < NJ; ++q) rr[q] = ii[q] = ri[q] = ir[q] = acc{0, 0, 0, 0};
-  // one iteration's operands: V segments from `s` of the A record and of the B record of every tile of the group
-  auto load = [&](auto check, int64_t s, cplx<T>* x, cplx<T>(*y)[V]) {
-    constexpr bool CHECK = decltype(check)::value;
-    csd_load<T, CHECK>(zi, oni, s, a.nseg, x);
-#pragma unroll
-    for (int q = 0; q < NJ; ++q) {
-      if (q >= nj) break;
-      if (q > 0 || !diag0) csd_load<T, CHECK>(zj[q], onj[q], s, a.nseg, y[q]);
-    }
-  };
-  auto tile_steps = [&](int q, const cplx<T>* x, const cplx<T>* y) {
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      rr[q] = M::mac(x[v].x, y[v].x, rr[q]);
-      ii[q] = M::mac(x[v].y, y[v].y, ii[q]);
-      ri[q] = M::mac(x[v].x, y[v].y, ri[q]);
-      ir[q] = M::mac(x[v].y, y[v].x, ir[q]);
-    }
-  };
-  auto steps = [&](const cplx<T>* x, const cplx<T>(*y)[V]) {
-    if (diag0) tile_steps(0, x, x);  // the diagonal tile: the A operand's registers twice
-    else tile_steps(0, x, y[0]);
-#pragma unroll
-    for (int q = 1; q < NJ; ++q) {
-      if (q >= nj) break;
-      tile_steps(q, x, y[q]);
-    }
-  };
-  const int64_t full = a.nseg / STEP * STEP, s_lane = g * V;
-  cplx<T> xa[V], ya[NJ][V], xb[V], yb[NJ][V];
-  int64_t s0 = 0;
-  // two iterations' loads are in flight before the first one's products: a wave alone on its SIMD (few records) is bound
-  // by the latency of its loads
-  for (; s0 + 2 * STEP <= full; s0 += 2 * STEP) {
-    load(std::false_type{}, s0 + s_lane, xa, ya);
-    load(std::false_type{}, s0 + STEP + s_lane, xb, yb);
-    steps(xa, ya);
-    steps(xb, yb);
-  }
-  if (s0 < full) {
-    load(std::false_type{}, s0 + s_lane, xa, ya);
-    steps(xa, ya);
-    s0 += STEP;
-  }
-  if (s0 < a.nseg) {
-    load(std::true_type{}, s0 + s_lane, xa, ya);
-    steps(xa, ya);
-  }
-  const T w = (T)csd_weight(a.w, f, a.nf);
-  cplx<T>* __restrict__ Sf = S + f * a.C * a.C;
-#pragma unroll
-  for (int q = 0; q < NJ; ++q) {
-    if (q >= nj) break;
-    const bool diag = q == 0 && diag0;
-    const int64_t j = (tj0 + q) * kCsdTile + (lane & 15);
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t i = ti * kCsdTile + M::row(lane, reg);
-      if (i >= a.C || j >= a.C || (diag && j < i)) continue;
-      const T re = (rr[q][reg] + ii[q][reg]) * w;
-      const T im = i == j ? T(0) : (ri[q][reg] - ir[q][reg]) * w;
-      Sf[i * a.C + j] = mk<T>(re, im);
-      if (i != j) Sf[j * a.C + i] = mk<T>(re, -im);
-    }
-  }
+  int64_t p = (int64_t)blockIdx.x / a.nfb;
+  const int64_t first = 0, len = a.nseg, m = f;
+  auto weight = [&] { return csd_weight(a.w, f, a.nf); };
+#include "qi_csd_wave.inc"
+}
+
+// The windowed form (include/qi_windows.h): matrix [w][fr] is the sum over the segments w hop .. w hop + win - 1 of bin
+// bin_first + fr.  p.nfb counts the workgroups of the FORMED bins.  The window index runs fastest in the grid: workgroups that
+// are resident together read overlapping segments of the same rows, so a line that several windows share is still in cache
+// when the next one asks for it (workgroups b and b + 8 share an XCD's L2; neighbours meet in the Infinity Cache).
+struct CsdWindowArgs {
+  CsdArgs p;
+  int64_t bin_first, bin_count, win, hop, nwin;
+};
+
+template <typename T, int NJ>
+__global__ void __launch_bounds__(kCsdWaves* kWave) k_cross_spectra_windows(const cplx<T>* __restrict__ Z, cplx<T>* __restrict__ S,
+                                                                            CsdWindowArgs aw) {
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int64_t wi = (int64_t)blockIdx.x % aw.nwin, rest = (int64_t)blockIdx.x / aw.nwin;
+  const int64_t fr = (rest % aw.p.nfb) * kCsdWaves + wv;
+  if (fr >= aw.bin_count) return;  // (the whole wave)
+  const CsdArgs& a = aw.p;
+  int64_t p = rest / a.nfb;
+  const int64_t f = aw.bin_first + fr, first = wi * aw.hop, len = aw.win, m = wi * aw.bin_count + fr;
+  // a table holds one weight per FORMED bin; without one the one-sided doubling goes by the absolute bin
+  auto weight = [&] { return a.w.table ? a.w.table[fr] : csd_weight(a.w, f, a.nf); };
+#include "qi_csd_wave.inc"
 }
 
 // coherence[f][i][j] = |S_ij|^2 / (S_ii S_jj) of the finished matrices, the quotient in double; one segment: the identity's
@@ -197,6 +138,39 @@ int csd_shape_check(int dtype, int64_t C, int64_t nf, int64_t nseg) {
   return QI_OK;
 }
 
+// tiles of a tile row a wave takes: one where there is one; else what the accumulators leave room for (4 x 4 registers a
+// tile, 8 in float64)
+template <typename T>
+int csd_tiles_per_wave(int64_t ntile) {
+  return ntile == 1 ? 1 : (sizeof(T) == 8 ? 2 : 4);
+}
+int64_t csd_groups(int64_t ntile, int nj) {
+  int64_t groups = 0;
+  for (int64_t ti = 0; ti < ntile; ++ti) groups += csd_row_groups(ntile, ti, nj);
+  return groups;
+}
+
+// what the windowed entry points refuse of a shape, and the number of windows
+int csd_windows_check(int dtype, int64_t C, int64_t nf, int64_t nseg, int64_t bin_first, int64_t bin_count, int64_t win, int64_t hop,
+                      int64_t* nwin_out) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(C > 0 && nf > 0 && nseg > 0, "bad panel shape");
+  QI_REQUIRE(win > 0 && hop > 0, "bad window: %lld segments, hop %lld", (long long)win, (long long)hop);
+  QI_REQUIRE(win <= nseg, "window of %lld segments is longer than the panel's %lld", (long long)win, (long long)nseg);
+  QI_REQUIRE(bin_count > 0 && bin_first >= 0 && bin_first <= nf - bin_count, "bin range %lld + %lld leaves the panel's %lld bins",
+             (long long)bin_first, (long long)bin_count, (long long)nf);
+  const int64_t nwin = (nseg - win) / hop + 1;
+  QI_REQUIRE(C < (1ll << 20) && bin_count < (1ll << 40) / (C * C) && nwin <= (1ll << 40) / (C * C) / bin_count,
+             "cross-spectral matrices of %lld windows x %lld bins x %lld^2 records are too large", (long long)nwin, (long long)bin_count,
+             (long long)C);
+  const int64_t ntile = ceil_div(C, kCsdTile);
+  const int64_t items = ntile * (ntile + 1) / 2 * ceil_div(bin_count, kCsdWaves);  // (>= the tile groups; < 2^40)
+  QI_REQUIRE(items < (1ll << 31) && nwin < (1ll << 31) / items, "request too large");
+  QI_REQUIRE(C * nf < (1ll << 62) / nseg / 16, "panel too large");
+  *nwin_out = nwin;
+  return QI_OK;
+}
+
 }  // namespace
 
 namespace qi {
@@ -216,11 +190,8 @@ int launch_cross_spectra(const cplx<T>* Z, int64_t C, int64_t nf, int64_t nseg, 
   a.nfb = ceil_div(nf, kCsdWaves);
   a.w = w;
   cplx<T>* S = csd ? csd : static_cast<cplx<T>*>(matrices);
-  // tiles a wave takes: one where there is one; else what the accumulators leave room for (4 x 4 registers a tile, 8 in float64)
-  const int nj = a.ntile == 1 ? 1 : (sizeof(T) == 8 ? 2 : 4);
-  int64_t groups = 0;
-  for (int64_t ti = 0; ti < a.ntile; ++ti) groups += csd_row_groups(a.ntile, ti, nj);
-  const dim3 grid((unsigned)(groups * a.nfb));
+  const int nj = csd_tiles_per_wave<T>(a.ntile);
+  const dim3 grid((unsigned)(csd_groups(a.ntile, nj) * a.nfb));
   if (nj == 1) k_cross_spectra<T, 1><<<grid, kCsdWaves * kWave, 0, st>>>(Z, S, a);
   else if (nj == 2) k_cross_spectra<T, 2><<<grid, kCsdWaves * kWave, 0, st>>>(Z, S, a);
   else k_cross_spectra<T, 4><<<grid, kCsdWaves * kWave, 0, st>>>(Z, S, a);
@@ -234,6 +205,43 @@ int launch_cross_spectra(const cplx<T>* Z, int64_t C, int64_t nf, int64_t nseg, 
 template int launch_cross_spectra<float>(const float2*, int64_t, int64_t, int64_t, const CsdWeight&, float2*, float*, void*, hipStream_t);
 template int launch_cross_spectra<double>(const double2*, int64_t, int64_t, int64_t, const CsdWeight&, double2*, double*, void*,
                                           hipStream_t);
+
+size_t cross_spectra_windows_scratch(int dtype, int64_t C, int64_t bin_count, int64_t nwin) {
+  return align_up((size_t)bin_count * 8) + align_up((size_t)nwin * bin_count * C * C * 2 * elem_size(dtype));
+}
+
+template <typename T>
+int launch_cross_spectra_windows(const cplx<T>* Z, int64_t C, int64_t nf, int64_t nseg, int64_t bin_first, int64_t bin_count, int64_t win,
+                                 int64_t hop, const CsdWeight& w, cplx<T>* csd, T* coherence, void* matrices, hipStream_t st) {
+  CsdWindowArgs a{};
+  a.p.C = C;
+  a.p.nf = nf;
+  a.p.nseg = nseg;
+  a.p.ntile = ceil_div(C, kCsdTile);
+  a.p.nfb = ceil_div(bin_count, kCsdWaves);
+  a.p.w = w;
+  a.bin_first = bin_first;
+  a.bin_count = bin_count;
+  a.win = win;
+  a.hop = hop;
+  a.nwin = (nseg - win) / hop + 1;
+  cplx<T>* S = csd ? csd : static_cast<cplx<T>*>(matrices);
+  const int nj = csd_tiles_per_wave<T>(a.p.ntile);
+  const dim3 grid((unsigned)(csd_groups(a.p.ntile, nj) * a.p.nfb * a.nwin));
+  if (nj == 1) k_cross_spectra_windows<T, 1><<<grid, kCsdWaves * kWave, 0, st>>>(Z, S, a);
+  else if (nj == 2) k_cross_spectra_windows<T, 2><<<grid, kCsdWaves * kWave, 0, st>>>(Z, S, a);
+  else k_cross_spectra_windows<T, 4><<<grid, kCsdWaves * kWave, 0, st>>>(Z, S, a);
+  QI_LAUNCH_CHECK();
+  if (!coherence) return QI_OK;
+  const int64_t count = a.nwin * bin_count * C * C;
+  k_coherence<T><<<dim3((unsigned)ceil_div(count, 256)), 256, 0, st>>>(S, coherence, C, count, win == 1);
+  QI_LAUNCH_CHECK();
+  return QI_OK;
+}
+template int launch_cross_spectra_windows<float>(const float2*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                                                 const CsdWeight&, float2*, float*, void*, hipStream_t);
+template int launch_cross_spectra_windows<double>(const double2*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                                                  const CsdWeight&, double2*, double*, void*, hipStream_t);
 
 }  // namespace qi
 
@@ -266,6 +274,41 @@ int qi_cross_spectra(int dtype, int device, const void* Z, int64_t C, int64_t nf
   return by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     return launch_cross_spectra<T>((const cplx<T>*)Z, C, nf, nseg, w, (cplx<T>*)csd, (T*)coherence, matrices, st);
+  });
+}
+
+int64_t qi_cross_spectra_windows_scratch_bytes(int dtype, int64_t C, int64_t nf, int64_t nseg, int64_t bin_first, int64_t bin_count,
+                                               int64_t win, int64_t hop) {
+  int64_t nwin = 0;
+  QI_TRY(csd_windows_check(dtype, C, nf, nseg, bin_first, bin_count, win, hop, &nwin));
+  return (int64_t)cross_spectra_windows_scratch(dtype, C, bin_count, nwin);
+}
+
+int qi_cross_spectra_windows(int dtype, int device, const void* Z, int64_t C, int64_t nf, int64_t nseg, int64_t bin_first,
+                             int64_t bin_count, int64_t win, int64_t hop, const double* weight, void* csd, void* coherence,
+                             void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_REQUIRE(Z && scratch, "null argument");
+  QI_REQUIRE(csd || coherence, "nothing to produce");
+  int64_t nwin = 0;
+  QI_TRY(csd_windows_check(dtype, C, nf, nseg, bin_first, bin_count, win, hop, &nwin));
+  QI_TRY(require_scratch(scratch_bytes, (int64_t)cross_spectra_windows_scratch(dtype, C, bin_count, nwin)));
+  QI_REQUIRE(aligned(Z, 2 * elem_size(dtype)) && aligned(csd, 2 * elem_size(dtype)) && aligned(coherence, elem_size(dtype)) &&
+                 aligned(scratch, 16),
+             "misaligned pointer");
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  CsdWeight w;
+  if (weight) {
+    // one weight per formed bin; as qi_cross_spectra's, the host array rides in kernel arguments
+    double* table = static_cast<double*>(scratch);
+    QI_TRY(qi::host::put_words(table, weight, bin_count, st));
+    w.table = table;
+  }
+  void* matrices = static_cast<char*>(scratch) + align_up((size_t)bin_count * 8);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_cross_spectra_windows<T>((const cplx<T>*)Z, C, nf, nseg, bin_first, bin_count, win, hop, w, (cplx<T>*)csd,
+                                           (T*)coherence, matrices, st);
   });
 }
 

@@ -685,6 +685,39 @@ def cross_spectra(panel, weight=None, coherence=False):
     return finish(csd, was_numpy, False)
 
 
+def cross_spectra_windows(panel, window_segments, hop_segments=None, weight=None, bins=None, coherence=False):
+    """cross_spectra per sliding window of the panel's time axis (qi_cross_spectra_windows): window w holds the columns
+    w * hop_segments .. w * hop_segments + window_segments - 1 of panel [C, n_bands, n_time]; n_windows =
+    (n_time - window_segments) // hop_segments + 1, columns after the last window are ignored.  hop_segments: None for
+    max(1, window_segments // 2).  bins: (first, count) of the bands that are formed, or None (all).  weight: [count] host
+    values, one per FORMED band, or None (1).  Window w equals cross_spectra(panel[:, first:first + count,
+    w * hop:w * hop + window_segments], weight) bit for bit.
+    -> csd [n_windows, count, C, C], or (csd, coherence [n_windows, count, C, C]) with coherence=True.  NumPy in -> NumPy out,
+    CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    z, was_numpy, rdtype = _matrix_stack(panel, "panel", "[C, bands, time]", square=False)
+    n_ch, n_f, n_t = z.shape
+    win = int(window_segments)
+    hop = max(1, win // 2) if hop_segments is None else int(hop_segments)
+    first, count = (0, n_f) if bins is None else (int(bins[0]), int(bins[1]))
+    w_host, w_ptr = (None, None)
+    if weight is not None:
+        w_host, w_ptr = _lib.darr(weight)
+        if w_host.shape != (count,):
+            raise ValueError(f"weight must hold one value per formed band ({count}), got shape {w_host.shape}")
+    dev, code = z.device, _lib.dtype_code(rdtype)
+    # (the library refuses what is wrong with the windows and the bin range, before the outputs are shaped by them)
+    scratch, nbytes = _lib.scratch(lib.qi_cross_spectra_windows_scratch_bytes, dev, code, n_ch, n_f, n_t, first, count, win, hop)
+    n_win = (n_t - win) // hop + 1
+    csd = torch.empty((n_win, count, n_ch, n_ch), dtype=z.dtype, device=dev)
+    coh = torch.empty((n_win, count, n_ch, n_ch), dtype=rdtype, device=dev) if coherence else None
+    _lib.call(lib.qi_cross_spectra_windows, dev, code, dev.index, _lib.ptr(z), n_ch, n_f, n_t, first, count, win, hop, w_ptr,
+              _lib.ptr(csd), _lib.ptr(coh), _lib.ptr(scratch), nbytes)
+    if coherence:
+        return finish(csd, was_numpy, False), finish(coh, was_numpy, False)
+    return finish(csd, was_numpy, False)
+
+
 def _delay_grid_form(name, matrices, what, frequency_hz, delays_s, bands, peaks, *form_args, form_first=()):
     """What beam_power, capon_power and music_power share: the checks of the stack `what`, of frequency_hz, delays_s and bands,
     the scratch of qi_<name>_scratch_bytes, the outputs, the call of qi_<name> (form_first: what it takes between nf and

@@ -522,10 +522,9 @@ def welch_power_pow2(
     return np.fft.rfftfreq(nfft, 1 / frequency_sample_rate_hz), engine.finish(pxx, was_numpy, was_1d)
 
 
-def _csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, scaling, want_csd, want_coherence):
-    """qi_csd on a [C, n] device tensor with welch_power_pow2's conventions -> (frequency_hz, csd [nf, C, C] or None,
-    coherence [nf, C, C] or None), device tensors in the records' precision."""
-    lib = _lib.require_gpu()
+def _csd_request(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, scaling):
+    """The argument checks of qi_csd and qi_csd_windows on a [C, n] device tensor, with welch_power_pow2's conventions ->
+    (seg, hop, nfft, fs, the window on the device, scale)."""
     if nfft_points is None:
         nfft_points = int(2 ** np.ceil(np.log2(segment_points)))
     if overlap_points is None:
@@ -548,8 +547,17 @@ def _csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, ov
         scale = float(np.sqrt(1.0 / (fs * np.sum(win64 * win64))))
     else:
         raise ValueError(f"Unknown scaling: {scaling!r}")
+    return seg, hop, nfft, fs, torch.from_numpy(win).to(sig.device), scale
+
+
+def _csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, scaling, want_csd, want_coherence):
+    """qi_csd on a [C, n] device tensor with welch_power_pow2's conventions -> (frequency_hz, csd [nf, C, C] or None,
+    coherence [nf, C, C] or None), device tensors in the records' precision."""
+    lib = _lib.require_gpu()
+    seg, hop, nfft, fs, win_d, scale = _csd_request(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha,
+                                                    scaling)
+    n_ch, n = sig.shape
     dev, n_f = sig.device, nfft // 2 + 1
-    win_d = torch.from_numpy(win).to(dev)
     code = _lib.dtype_code(sig.dtype)
     csd = torch.empty((n_f, n_ch, n_ch), dtype=engine._complex_of(sig.dtype), device=dev) if want_csd else None
     coherence = torch.empty((n_f, n_ch, n_ch), dtype=sig.dtype, device=dev) if want_coherence else None
@@ -591,6 +599,84 @@ def coherence_matrix_pow2(
     sig, was_numpy, _ = engine.as_signal(sig_wf)
     f, _, coh = _csd_matrices(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha, "spectrum", False, True)
     return f, engine.finish(coh, was_numpy, False)
+
+
+def _csd_window_matrices(sig, frequency_sample_rate_hz, segment_points, window_segments, window_hop_segments, nfft_points, overlap_points,
+                         alpha, scaling, frequency_range_hz, want_csd, want_coherence, bins_of=None):
+    """qi_csd_windows on a [C, n] device tensor, _csd_matrices' twin -> (frequency_hz [bins] of the formed bins,
+    window_time_s [nwin], csd [nwin, bins, C, C] or None, coherence [nwin, bins, C, C] or None).  bins_of: instead of
+    frequency_range_hz, a function of the whole frequency table -> (first, count) of the bins to form."""
+    lib = _lib.require_gpu()
+    seg, hop, nfft, fs, win_d, scale = _csd_request(sig, frequency_sample_rate_hz, segment_points, nfft_points, overlap_points, alpha,
+                                                    scaling)
+    n_ch, n = sig.shape
+    n_seg = (n - seg) // hop + 1
+    win = int(window_segments)
+    win_hop = max(1, win // 2) if window_hop_segments is None else int(window_hop_segments)
+    if win < 1 or win_hop < 1 or win > n_seg:
+        raise ValueError(f"a window of {win} segments every {win_hop} does not fit the record's {n_seg} segments")
+    f = np.fft.rfftfreq(nfft, 1 / fs)
+    first, count = (0, f.size) if bins_of is None else bins_of(f)
+    if frequency_range_hz is not None:
+        lo, hi = (float(v) for v in frequency_range_hz)
+        first, last = np.searchsorted(f, [lo, hi], side="left")  # lo <= f < hi
+        first, count = int(first), int(last - first)
+        if count < 1:
+            raise ValueError(f"no bin of the {f.size} lies in {lo} <= f < {hi} Hz")
+    n_win = (n_seg - win) // win_hop + 1
+    dev, code = sig.device, _lib.dtype_code(sig.dtype)
+    scratch, nbytes = _lib.scratch(lib.qi_csd_windows_scratch_bytes, dev, code, n_ch, n, seg, hop, nfft, first, count, win, win_hop)
+    csd = torch.empty((n_win, count, n_ch, n_ch), dtype=engine._complex_of(sig.dtype), device=dev) if want_csd else None
+    coherence = torch.empty((n_win, count, n_ch, n_ch), dtype=sig.dtype, device=dev) if want_coherence else None
+    _lib.call(lib.qi_csd_windows, dev, code, dev.index, _lib.ptr(sig), n_ch, n, _lib.ptr(win_d), seg, hop, nfft, scale, first, count,
+              win, win_hop, _lib.ptr(csd), _lib.ptr(coherence), _lib.ptr(scratch), nbytes)
+    # the centre of the samples a window spans: its first sample w win_hop hop, its length (win - 1) hop + seg
+    time_s = (np.arange(n_win, dtype=np.float64) * (win_hop * hop) + ((win - 1) * hop + seg) / 2) / fs
+    return f[first:first + count], time_s, csd, coherence
+
+
+def csd_windows_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    segment_points: int,
+    window_segments: int,
+    window_hop_segments: int = None,
+    nfft_points: int = None,
+    overlap_points: int = None,
+    alpha: float = 0.25,
+    scaling: str = "spectrum",
+    frequency_range_hz=None,
+):
+    """csd_matrix_pow2 per sliding window of the record's Welch segments: window w is scipy.signal.csd of the sub-record
+    that the segments w * window_hop_segments .. + window_segments - 1 span (window_hop_segments: None for
+    max(1, window_segments // 2)); segments after the last window are ignored.  frequency_range_hz: (lo, hi) -- only the bins
+    lo <= f < hi are formed -- or None (all).  One window over every segment is csd_matrix_pow2 bit for bit.
+    :return: frequency_hz [bins], window_time_s [nwin] (the centre of the samples each window spans),
+        csd [nwin x bins x C x C] complex, Hermitian per window and bin"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    f, t, csd, _ = _csd_window_matrices(sig, frequency_sample_rate_hz, segment_points, window_segments, window_hop_segments, nfft_points,
+                                        overlap_points, alpha, scaling, frequency_range_hz, True, False)
+    return f, t, engine.finish(csd, was_numpy, False)
+
+
+def coherence_windows_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    segment_points: int,
+    window_segments: int,
+    window_hop_segments: int = None,
+    nfft_points: int = None,
+    overlap_points: int = None,
+    alpha: float = 0.25,
+    frequency_range_hz=None,
+):
+    """coherence_matrix_pow2 per sliding window of the record's Welch segments, with csd_windows_pow2's windows and bins.
+    One segment per window gives 1.
+    :return: frequency_hz [bins], window_time_s [nwin], coherence [nwin x bins x C x C]"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    f, t, _, coh = _csd_window_matrices(sig, frequency_sample_rate_hz, segment_points, window_segments, window_hop_segments, nfft_points,
+                                        overlap_points, alpha, "spectrum", frequency_range_hz, False, True)
+    return f, t, engine.finish(coh, was_numpy, False)
 
 
 def _csd_pairs(sig_x, sig_y, want_coherence, *args):
