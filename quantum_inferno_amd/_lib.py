@@ -1,4 +1,5 @@
-"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, qi_array.h, qi_beam.h, qi_adaptive.h, qi_subspace.h, qi_steer.h).  There is no CPU fallback: if the
+"""ctypes binding of libqi_tfr.so (include/qi_tfr.h, qi_array.h, qi_beam.h, qi_adaptive.h, qi_subspace.h, qi_steer.h, qi_windows.h,
+qi_lags.h).  There is no CPU fallback: if the
 library is missing or no HIP device is present, every transform raises."""
 import ctypes as C
 import os
@@ -204,6 +205,13 @@ WINDOW_PROTOTYPES = {
     "qi_csd_windows": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _i64, _dbl, _i64, _i64, _i64, _i64, _P, _P, _P, _i64, _P]),
 }
 
+# include/qi_lags.h (pair correlations of the matrices: lag windows and sub-sample peaks), one to one
+LAG_PROTOTYPES = {
+    "qi_pair_lags_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64]),
+    "qi_pair_lags": (_int, [_int, _int, _P, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _i64, _i64, _P, _P, _P, _P, _i64, _P]),
+}
+LAG_WEIGHTINGS = ("plain", "phat", "scot")  # QI_LAG_PLAIN, QI_LAG_PHAT, QI_LAG_SCOT
+
 _lib = None
 
 
@@ -227,7 +235,7 @@ def load():
         )
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES, **SUBSPACE_PROTOTYPES,
-                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES}.items():
+                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES, **LAG_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -5,7 +5,9 @@ slowness vectors (engine.beam_power, include/qi_beam.h), Capon's minimum-varianc
 (engine.csd_eigh and engine.music_power, include/qi_subspace.h) -- and, once the map has a peak, the signal from that
 direction: beam panels and beam waveforms with Bartlett or MVDR weights (engine.beam_weights and engine.beam_steer,
 include/qi_steer.h).  fk_timeline_pow2 runs the three power forms per sliding window of the record
-(styx_fft.csd_windows_pow2's matrices, include/qi_windows.h): a detection timeline.  The reference (quantum-inferno) has no
+(styx_fft.csd_windows_pow2's matrices, include/qi_windows.h): a detection timeline.  Without a grid, slowness_from_lags
+fits the slowness vector to the pair delays of styx_fft.pair_lags_pow2 (the peaks of the generalized cross-correlations,
+include/qi_lags.h) and lag_closure is their consistency check.  The reference (quantum-inferno) has no
 array processing; the conventions below are the usual ones of infrasound and seismic array work.
 
 Geometry.  Positions are [C, 2] metres (x east, y north).  A slowness vector s [s/m] points the way the wave TRAVELS; a
@@ -274,6 +276,54 @@ def fisher_from_semblance(semblance, sensors: int):
     s = np.asarray(semblance, dtype=np.float64) if not isinstance(semblance, np.ndarray) else semblance
     with np.errstate(divide="ignore", invalid="ignore"):
         return (c - 1) * s / (1 - s)
+
+
+def _lags64(lags_s, what="lags_s"):
+    t = lags_s if isinstance(lags_s, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(lags_s, dtype=np.float64)))
+    if t.dim() < 1 or t.shape[-1] < 1:
+        raise ValueError(f"{what} must be [..., pairs], got shape {tuple(t.shape)}")
+    return t.to(torch.float64)
+
+
+def slowness_from_lags(lags_s, positions_m, weights=None):
+    """The slowness vector that fits the pair delays of styx_fft.pair_lags_pow2 in the weighted least-squares sense:
+    lag_ij = s . (r_j - r_i) for every pair i < j in the order (0, 1), (0, 2) .. (C - 2, C - 1) -- two unknowns, the 2 x 2
+    normal equations solved in closed form.  lags_s: [..., C (C - 1) / 2] seconds, NumPy or a tensor on any device (leading
+    dimensions, the windows of a timeline, are a batch); positions_m: [C, 2]; weights: None (1), or non-negative values
+    [pairs] or [..., pairs] (peak values, say).  Collinear sensors leave s undetermined: NaN.
+    -> (slowness [..., 2], rms_residual_s [...]: the root of the weighted mean squared lag_ij - s . (r_j - r_i)), torch float64
+    on the device of the lags.  back_azimuth_and_velocity takes the slowness."""
+    lag = _lags64(lags_s)
+    r = _host64(positions_m, 2, "positions_m")
+    rows, cols = np.triu_indices(r.shape[0], 1)
+    if lag.shape[-1] != rows.size:
+        raise ValueError(f"{r.shape[0]} positions make {rows.size} pairs, lags_s holds {lag.shape[-1]}")
+    d = (r[cols] - r[rows]).to(lag.device)  # [pairs, 2]
+    w = torch.ones_like(lag) if weights is None else torch.broadcast_to(_lags64(weights, "weights").to(lag.device), lag.shape)
+    dx, dy = d[:, 0], d[:, 1]
+    axx, axy, ayy = (w * dx * dx).sum(-1), (w * dx * dy).sum(-1), (w * dy * dy).sum(-1)
+    bx, by = (w * dx * lag).sum(-1), (w * dy * lag).sum(-1)
+    det = axx * ayy - axy * axy
+    det = torch.where(det == 0, torch.full_like(det, float("nan")), det)
+    s = torch.stack([(ayy * bx - axy * by) / det, (axx * by - axy * bx) / det], dim=-1)
+    res = lag - (s[..., 0:1] * dx + s[..., 1:2] * dy)
+    return s, torch.sqrt((w * res * res).sum(-1) / w.sum(-1))
+
+
+def lag_closure(lags_s, sensors: int):
+    """The closure of pair delays around every triplet of sensors i < j < k: tau_ij + tau_jk - tau_ik, 0 for the delays of
+    one plane wave and for any set of delays that are differences of per-sensor times -- the consistency check of the PMCC
+    family.  lags_s: [..., C (C - 1) / 2] in styx_fft.pair_lags_pow2's pair order, NumPy or tensor.
+    -> [..., C (C - 1) (C - 2) / 6] torch float64 on the device of the lags, triplets in the order (0, 1, 2), (0, 1, 3) .."""
+    c = int(sensors)
+    lag = _lags64(lags_s)
+    if c < 3 or lag.shape[-1] != c * (c - 1) // 2:
+        raise ValueError(f"a closure needs three sensors and their C (C - 1) / 2 delays, got {sensors} sensors and {lag.shape[-1]} delays")
+    pair = lambda i, j: i * c - i * (i + 1) // 2 + (j - i - 1)  # noqa: E731
+    trip = [(i, j, k) for i in range(c) for j in range(i + 1, c) for k in range(j + 1, c)]
+    ij, jk, ik = (torch.tensor([pair(*t) for t in sel], dtype=torch.int64, device=lag.device)
+                  for sel in ([(i, j) for i, j, k in trip], [(j, k) for i, j, k in trip], [(i, k) for i, j, k in trip]))
+    return lag[..., ij] + lag[..., jk] - lag[..., ik]
 
 
 BEAM_METHODS = ("bartlett", "capon")

@@ -3,6 +3,7 @@
 #include "qi_host.hpp"
 #include "qi_array.h"
 #include "qi_windows.h"
+#include "qi_lags.h"
 
 using namespace qi;
 using qi::host::align_up;
@@ -446,6 +447,48 @@ int qi_csd_windows(int dtype, int device, const void* sig, int64_t C, int64_t n,
     char* s = (char*)scratch;
     return launch_cross_spectra_windows<T>(reinterpret_cast<const cplx<T>*>(s + l.panel), C, nf, nseg, bin_first, bin_count, win, win_hop,
                                            w, (cplx<T>*)csd, (T*)coherence, s + l.cross + align_up((size_t)bin_count * 8), st);
+  });
+}
+
+// ---- time delays between the records from their matrices (include/qi_lags.h) --------------------------------------------
+static int pair_lags_shape_check(int dtype, int64_t nstack, int64_t C, int64_t nfft, int64_t upsample) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(nstack >= 1 && C >= 2, "bad stack shape: %lld stacks of %lld records (a pair needs two)", (long long)nstack, (long long)C);
+  QI_REQUIRE(upsample == 1 || upsample == 2 || upsample == 4 || upsample == 8, "bad upsample %lld (1, 2, 4 or 8)", (long long)upsample);
+  QI_REQUIRE(is_pow2(nfft) && nfft * upsample >= 64 && nfft * upsample <= 8192,
+             "bad transform length: nfft %lld x upsample %lld must be a power of two in 64 .. 8192", (long long)nfft, (long long)upsample);
+  QI_REQUIRE(C <= (1 << 20) && nstack <= (1ll << 40) && (double)nstack * (double)(nfft / 2 + 1) * (double)C * (double)C <= 0x1p40 &&
+                 (double)nstack * (double)(C * (C - 1) / 2) < 0x1p31,
+             "request too large");
+  return QI_OK;
+}
+
+int64_t qi_pair_lags_scratch_bytes(int dtype, int64_t nstack, int64_t C, int64_t nfft, int64_t upsample) {
+  QI_TRY(pair_lags_shape_check(dtype, nstack, C, nfft, upsample));
+  return 0;
+}
+
+int qi_pair_lags(int dtype, int device, const void* csd, int64_t nstack, int64_t C, int64_t nfft, int64_t bin_lo, int64_t bin_hi,
+                 int weighting, int halve_interior, int normalize, int64_t upsample, int64_t max_lag, void* cc, void* peak_lag,
+                 void* peak_value, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_REQUIRE(csd, "null argument");
+  QI_REQUIRE(cc || peak_lag || peak_value, "nothing to produce");
+  QI_TRY(pair_lags_shape_check(dtype, nstack, C, nfft, upsample));
+  QI_REQUIRE(weighting >= 0 && weighting <= 2, "bad weighting %d (0 plain, 1 PHAT, 2 SCOT)", weighting);
+  QI_REQUIRE(bin_lo >= 0 && bin_lo <= bin_hi && bin_hi <= nfft / 2 + 1, "bad bin range %lld .. %lld of %lld bins", (long long)bin_lo,
+             (long long)bin_hi, (long long)(nfft / 2 + 1));
+  QI_REQUIRE(max_lag >= 0 && max_lag <= nfft * upsample / 2 - 1, "bad max_lag %lld (0 .. %lld)", (long long)max_lag,
+             (long long)(nfft * upsample / 2 - 1));
+  QI_TRY(require_scratch(scratch_bytes, 0));
+  const size_t e = elem_size(dtype);
+  QI_REQUIRE(aligned(csd, 2 * e) && aligned(cc, e) && aligned(peak_lag, e) && aligned(peak_value, e) && aligned(scratch, 16),
+             "misaligned pointer");
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return launch_pair_lags<T>((const cplx<T>*)csd, nstack, C, nfft, bin_lo, bin_hi, weighting, halve_interior, normalize, upsample,
+                               max_lag, (T*)cc, (T*)peak_lag, (T*)peak_value, st);
   });
 }
 

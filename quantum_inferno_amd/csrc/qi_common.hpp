@@ -221,6 +221,13 @@ size_t cross_spectra_windows_scratch(int dtype, int64_t C, int64_t bin_count, in
 template <typename T>
 int launch_cross_spectra_windows(const cplx<T>* Z, int64_t C, int64_t nf, int64_t nseg, int64_t bin_first, int64_t bin_count, int64_t win,
                                  int64_t hop, const CsdWeight& w, cplx<T>* csd, T* coherence, void* matrices, hipStream_t st);
+// pair correlations and their peaks from a stack of matrices (qi_lags.hip; include/qi_lags.h): csd [nstack][nfft / 2 + 1][C][C]
+// -> cc [nstack][npair][2 max_lag + 1], peak_lag and peak_value [nstack][npair] (any may be null); the arguments are the
+// checked ones of qi_pair_lags.  One launch, a workgroup per (stack, pair), no scratch.
+template <typename T>
+int launch_pair_lags(const cplx<T>* csd, int64_t nstack, int64_t C, int64_t nfft, int64_t bin_lo, int64_t bin_hi, int weighting,
+                     int halve_interior, int normalize, int64_t upsample, int64_t max_lag, T* cc, T* peak_lag, T* peak_value,
+                     hipStream_t st);
 
 template <typename T>
 int launch_power_marginals(const T* P, int64_t C, int64_t B, int64_t n, T* power_time, double* part_band,

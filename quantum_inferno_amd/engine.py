@@ -718,6 +718,49 @@ def cross_spectra_windows(panel, window_segments, hop_segments=None, weight=None
     return finish(csd, was_numpy, False)
 
 
+def pair_lags(csd, *, bins=None, weighting="phat", halve_interior=True, normalize=True, upsample=1, max_lag=None, want_cc=False):
+    """Time delays between every pair of records from their cross-spectral matrices (qi_pair_lags, include/qi_lags.h): the
+    generalized cross-correlation r of pair (i, j), i < j, its first maximum inside +-max_lag and the three-point parabola
+    through it, in one launch.  csd: [nf, C, C] complex64 / complex128 as cross_spectra and styx_fft.csd_matrix_pow2 return
+    it, or a stack [nstack, nf, C, C] (cross_spectra_windows / styx_fft.csd_windows_pow2 with every bin); nf = nfft / 2 + 1
+    with nfft a power of two, nfft * upsample in 64 .. 8192.  bins: (lo, hi) -- the bins lo <= f < hi enter, the rest count
+    as 0 -- or None (all).  weighting: "plain", "phat" (1 / |S_ij|) or "scot" (1 / sqrt(S_ii S_jj)).  halve_interior: halve
+    the bins 0 < f < nfft / 2 (undoes the one-sided doubling of csd_matrix_pow2).  normalize: plain -> the correlation
+    coefficient; phat / scot -> divided by the count of non-zero two-sided bins, a peak of at most 1.  upsample: 1, 2, 4 or 8,
+    the zero padding of the spectrum -- lags of the window and max_lag are in samples of that finer grid.  max_lag: None for
+    the largest, nfft * upsample / 2 - 1.  With csd[f, i, j] = conj(X_i) X_j a positive lag means record j lags record i.
+    -> (peak_lag [npair] in samples of the RECORDS, peak_value [npair], cc [npair, 2 max_lag + 1] or None), npair =
+    C (C - 1) / 2 in the order (0, 1), (0, 2) .. (C - 2, C - 1), with the leading stack dimension when csd has one.  A pair
+    whose band holds a non-finite entry is NaN.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    was_numpy = not isinstance(csd, torch.Tensor)
+    s = torch.from_numpy(np.ascontiguousarray(csd)) if was_numpy else csd
+    if s.dim() not in (3, 4) or s.dtype not in (torch.complex64, torch.complex128) or 0 in s.shape or s.shape[-1] != s.shape[-2]:
+        raise ValueError(f"csd must be a non-empty complex64 / complex128 [nf, C, C] or [nstack, nf, C, C], got {s.dtype} {tuple(s.shape)}")
+    stacked = s.dim() == 4
+    s = s.to(s.device if s.is_cuda else default_device()).contiguous()
+    rdtype = torch.float32 if s.dtype == torch.complex64 else torch.float64
+    n_stack = s.shape[0] if stacked else 1
+    n_f, n_ch = s.shape[-3], s.shape[-1]
+    nfft = 2 * (n_f - 1)
+    if weighting not in _lib.LAG_WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {_lib.LAG_WEIGHTINGS}, got {weighting!r}")
+    lo, hi = (0, n_f) if bins is None else (int(bins[0]), int(bins[1]))
+    up = int(upsample)
+    dev, code = s.device, _lib.dtype_code(rdtype)
+    # (the library refuses what is wrong with the shape, before the outputs are shaped by it)
+    scratch, nbytes = _lib.scratch(lib.qi_pair_lags_scratch_bytes, dev, code, n_stack, n_ch, nfft, up)
+    lag = nfft * up // 2 - 1 if max_lag is None else int(max_lag)
+    n_pair = n_ch * (n_ch - 1) // 2
+    peak_lag = torch.empty((n_stack, n_pair), dtype=rdtype, device=dev)
+    peak_value = torch.empty((n_stack, n_pair), dtype=rdtype, device=dev)
+    cc = torch.empty((n_stack, n_pair, 2 * max(lag, 0) + 1), dtype=rdtype, device=dev) if want_cc else None
+    _lib.call(lib.qi_pair_lags, dev, code, dev.index, _lib.ptr(s), n_stack, n_ch, nfft, lo, hi, _lib.LAG_WEIGHTINGS.index(weighting),
+              int(bool(halve_interior)), int(bool(normalize)), up, lag, _lib.ptr(cc), _lib.ptr(peak_lag), _lib.ptr(peak_value),
+              _lib.ptr(scratch), nbytes)
+    return tuple(finish(t, was_numpy, not stacked) for t in (peak_lag, peak_value, cc))
+
+
 def _delay_grid_form(name, matrices, what, frequency_hz, delays_s, bands, peaks, *form_args, form_first=()):
     """What beam_power, capon_power and music_power share: the checks of the stack `what`, of frequency_hz, delays_s and bands,
     the scratch of qi_<name>_scratch_bytes, the outputs, the call of qi_<name> (form_first: what it takes between nf and

@@ -679,6 +679,57 @@ def coherence_windows_pow2(
     return f, t, engine.finish(coh, was_numpy, False)
 
 
+def pair_lags_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    segment_points: int,
+    nfft_points: int = None,
+    overlap_points: int = None,
+    alpha: float = 0.25,
+    band_hz=None,
+    weighting: str = "phat",
+    upsample: int = 1,
+    max_lag_s: float = None,
+    window_segments: int = None,
+    window_hop_segments: int = None,
+):
+    """Time delays between every pair of records of one batch [C x n] from the peak of their generalized cross-correlation
+    (engine.pair_lags on csd_matrix_pow2's matrices, or on csd_windows_pow2's -- one set of delays per sliding window -- when
+    window_segments is given): the delay of pair (i, j), i < j, is positive when record j lags record i -- tau_j - tau_i of
+    beamform.plane_wave_delays for a plane wave -- and feeds beamform.slowness_from_lags.  band_hz: (lo, hi), the bins
+    lo <= f < hi enter the correlation, or None (all); weighting "plain", "phat" or "scot"; the correlation is normalised
+    (plain: the correlation coefficient; phat / scot: a peak of at most 1).  upsample: 1, 2, 4 or 8, the zero padding of the
+    spectrum: the peak is searched on a grid of 1 / (upsample fs) seconds and refined by a three-point parabola.  max_lag_s:
+    the largest delay searched, None for all of the correlation.
+    The correlation of Welch segments is CIRCULAR over nfft_points: a delay d and the delay d - nfft_points / fs are the same
+    peak, and the two ends of a segment correlate with each other.  nfft_points >= 2 * segment_points makes it linear.
+    :return: lag_s [npair] (or [nwin x npair]) seconds, peak_value of the same shape, pairs [npair x 2] int64 (the (i, j) of
+        every column, in the order (0, 1), (0, 2) .. (C - 2, C - 1)); with window_segments also window_time_s [nwin] last"""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    args = (frequency_sample_rate_hz, segment_points)
+    if window_segments is None:
+        f, csd, _ = _csd_matrices(sig, *args, nfft_points, overlap_points, alpha, "spectrum", True, False)
+        time_s = None
+    else:
+        f, time_s, csd, _ = _csd_window_matrices(sig, *args, window_segments, window_hop_segments, nfft_points, overlap_points, alpha,
+                                                 "spectrum", None, True, False)
+    fs, up = float(frequency_sample_rate_hz), int(upsample)
+    bins = None
+    if band_hz is not None:
+        lo, hi = np.searchsorted(f, [float(band_hz[0]), float(band_hz[1])], side="left")  # lo <= f < hi
+        if hi <= lo:
+            raise ValueError(f"no bin of the {f.size} lies in {band_hz[0]} <= f < {band_hz[1]} Hz")
+        bins = (int(lo), int(hi))
+    largest = (f.size - 1) * up - 1
+    max_lag = largest if max_lag_s is None else min(largest, int(np.floor(float(max_lag_s) * fs * up)))
+    # (the one-sided doubling of the matrices is undone for the plain correlation; under PHAT and SCOT it cancels by itself)
+    lag, value, _ = engine.pair_lags(csd, bins=bins, weighting=weighting, halve_interior=weighting == "plain", normalize=True, upsample=up,
+                                     max_lag=max_lag)
+    rows, cols = np.triu_indices(sig.shape[0], 1)
+    out = (engine.finish(lag / fs, was_numpy, False), engine.finish(value, was_numpy, False), np.stack([rows, cols], axis=1).astype(np.int64))
+    return out if time_s is None else out + (time_s,)
+
+
 def _csd_pairs(sig_x, sig_y, want_coherence, *args):
     """The pair forms: row c of sig_x against row c of sig_y, from the matrices of the stacked records [x ; y] -- the entries
     (c, C + c), which are the matrix forms' bits (an entry is a function of its two records alone)."""
