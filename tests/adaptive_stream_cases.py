@@ -5,9 +5,10 @@ One case for qi_csd_whiten (float32, with info) and one per path of qi_beam_capo
 the power alone, and a host band table with both peak outputs in float32.  The delayed producer's tensor is the matrix stack,
 resp. the whitener stack, as interleaved (re, im) values.  The matrices are Z Z^H / K + I of stream_cases.record_pair's noise
 (K = 2 SENSORS columns): positive definite, so that both A and B factor; the whitener stacks are capon_cases.whiten of them.
-tests/test_capon_cpu.py holds the table against the header; tests/test_gpu_adaptive_streams.py runs each case behind the
-delayed producer of tests/test_gpu_streams.py.  All are asynchronous: the header promises no host synchronisation, the
-frequencies and the band offsets ride in kernel arguments.
+tests/test_capon_cpu.py holds the table against the header; tests/test_gpu_header_streams.py runs each case behind the
+delayed producer of tests/stream_order.py.  All are asynchronous: the header promises no host synchronisation, the
+frequencies and the band offsets ride in kernel arguments.  The first output, the whitener or the power, always differs
+between the two record sets; `info` is 0 on both and a band's peak index may coincide.
 """
 import functools
 
@@ -15,34 +16,14 @@ import numpy as np
 
 import capon_cases as cpc
 import stream_cases as sc
+from stream_table import Built, Table
 
-Case, Built, FILL = sc.Case, sc.Built, sc.FILL
-CASES = []
+# (no plans: every case is plan-less; output 1 of whiten-info is `info`: both record sets factor)
+TABLE = Table("qi_adaptive.h", complex_input=True, power="first", finite=True, zero_outputs={"whiten-info": 1})
+_case = TABLE.case
 SENSORS = 5  # one ragged tile
 MATRICES, GRID = 33, 300
 LOADING = 1e-2
-
-
-def _case(cid, functions, build, asynchronous=True, reason=""):
-    assert asynchronous or reason, cid
-    assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build))
-
-
-def ids():
-    return [c.id for c in CASES]
-
-
-def by_id(cid):
-    return next(c for c in CASES if c.id == cid)
-
-
-def named_functions():
-    return sorted({f for c in CASES for f in c.functions})
-
-
-def plan_less_ids():
-    return [c.id for c in CASES if c.engine is None]  # (all of them: qi_adaptive.h has no plans)
 
 
 def definite_pair(dtype, salt):

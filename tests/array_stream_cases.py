@@ -3,40 +3,20 @@ on the GPU), in the shape of tests/stream_cases.py, whose helpers it uses.
 
 One case per path of every function of qi_array.h that takes a `qi_stream`: qi_csd at a fused and at a hipFFT shape,
 qi_cross_spectra with and without the coherence (and with and without host weights).  tests/test_csd_cpu.py holds the table
-against the header; tests/test_gpu_array_streams.py runs each case behind the delayed producer of tests/test_gpu_streams.py.
-All four are asynchronous: the header promises no host synchronisation, the host weights ride in kernel arguments.
+against the header; tests/test_gpu_header_streams.py runs each case behind the delayed producer of tests/stream_order.py.
+All four are asynchronous: the header promises no host synchronisation, the host weights ride in kernel arguments.  Every
+output differs between the two record sets and is finite.
 """
 import functools
 
 import numpy as np
 
 import stream_cases as sc
+from stream_table import Built, Table
 
-Case, Built, FILL = sc.Case, sc.Built, sc.FILL
-CASES = []
+TABLE = Table("qi_array.h", power="every", finite=True)  # (no plans: every case is plan-less)
+_case = TABLE.case
 RECORDS = 5  # one ragged tile of records
-
-
-def _case(cid, functions, build, asynchronous=True, reason=""):
-    assert asynchronous or reason, cid
-    assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build))
-
-
-def ids():
-    return [c.id for c in CASES]
-
-
-def by_id(cid):
-    return next(c for c in CASES if c.id == cid)
-
-
-def named_functions():
-    return sorted({f for c in CASES for f in c.functions})
-
-
-def plan_less_ids():
-    return [c.id for c in CASES if c.engine is None]  # (all of them: qi_array.h has no plans)
 
 
 def _build_csd(shape):

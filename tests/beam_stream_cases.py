@@ -2,43 +2,22 @@
 on the GPU), in the shape of tests/array_stream_cases.py, with the helpers of tests/stream_cases.py.
 
 One case per path of qi_beam_power: every matrix its own band with the power alone, and a host band table with the
-semblance and both peak outputs.  The delayed producer's tensor is the matrix stack.  tests/test_beam_cpu.py holds the
-table against the header; tests/test_gpu_beam_streams.py runs each case behind the delayed producer of
-tests/test_gpu_streams.py.  Both are asynchronous: the header promises no host synchronisation, the frequencies and the band
-offsets ride in kernel arguments.
+semblance and both peak outputs.  The delayed producer's tensor is the matrix stack, viewed as complex.  tests/test_beam_cpu.py
+holds the table against the header; tests/test_gpu_header_streams.py runs each case behind the delayed producer of
+tests/stream_order.py.  Both are asynchronous: the header promises no host synchronisation, the frequencies and the band
+offsets ride in kernel arguments.  Every output differs between the two record sets and is finite.
 """
 import functools
 
 import numpy as np
 
 import stream_cases as sc
+from stream_table import Built, Table
 
-Case, Built, FILL = sc.Case, sc.Built, sc.FILL
-CASES = []
+TABLE = Table("qi_beam.h", complex_input=True, power="every", finite=True)  # (no plans: every case is plan-less)
+_case = TABLE.case
 SENSORS = 5  # one ragged tile
 MATRICES, GRID = 33, 300
-
-
-def _case(cid, functions, build, asynchronous=True, reason=""):
-    assert asynchronous or reason, cid
-    assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build))
-
-
-def ids():
-    return [c.id for c in CASES]
-
-
-def by_id(cid):
-    return next(c for c in CASES if c.id == cid)
-
-
-def named_functions():
-    return sorted({f for c in CASES for f in c.functions})
-
-
-def plan_less_ids():
-    return [c.id for c in CASES if c.engine is None]  # (all of them: qi_beam.h has no plans)
 
 
 def _build_beam(dtype, bands, normalize, peaks):

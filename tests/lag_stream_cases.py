@@ -5,44 +5,18 @@ qi_pair_lags on a stack [STACKS, 65 bins, RECORDS, RECORDS] of matrices (the pro
 values; only the entries i <= j are read, so noise with a positive mean serves), nfft 128 zero-padded fourfold, the bins
 3 .. 60, in both precisions: unweighted as the correlation coefficient (the auto-powers are read too) with every output, PHAT
 weights with the peaks alone, PHAT weights with the window alone, and unweighted, not normalised, with the window alone.
-tests/test_lags_cpu.py holds the table against the header; tests/test_gpu_lags_streams.py runs each case behind the delayed
-producer of tests/test_gpu_streams.py.  All are asynchronous: the header promises no host synchronisation.
-
-Four cases, and the count matters to a neighbour: every case's test takes one side stream from PyTorch's pool, and the
-positive control of tests/test_gpu_streams.py, which runs later in a whole-suite run, needs a side stream that the default
-stream does not wait for.  With two cases here that control failed in the whole suite on an MI355X ("the default stream
-waited for the side stream"), with four it passes, as it does without this table.  Supposed, not shown: pool streams share the
-runtime's four hardware queues in turn, and a shift of two hands the control the queue the default stream uses.
+tests/test_lags_cpu.py holds the table against the header; tests/test_gpu_header_streams.py runs each case behind the delayed
+producer of tests/stream_order.py.  All are asynchronous: the header promises no host synchronisation.  Every output differs
+between the two record sets, is finite and holds no FILL.
 """
 import functools
 
 import stream_cases as sc
+from stream_table import Built, Table
 
-Case, Built, FILL = sc.Case, sc.Built, sc.FILL
-CASES = []
+TABLE = Table("qi_lags.h", power="every", finite=True, no_fill=True)  # (no plans: every case is plan-less)
+_case = TABLE.case
 STACKS, RECORDS, NFFT, UPSAMPLE, MAX_LAG, BINS = 3, 5, 128, 4, 40, (3, 60)
-
-
-def _case(cid, functions, build, asynchronous=True, reason=""):
-    assert asynchronous or reason, cid
-    assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build))
-
-
-def ids():
-    return [c.id for c in CASES]
-
-
-def by_id(cid):
-    return next(c for c in CASES if c.id == cid)
-
-
-def named_functions():
-    return sorted({f for c in CASES for f in c.functions})
-
-
-def plan_less_ids():
-    return [c.id for c in CASES if c.engine is None]  # (all of them: qi_lags.h has no plans)
 
 
 def _build_pair_lags(dtype, weighting, normalize, outputs):

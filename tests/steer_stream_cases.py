@@ -5,9 +5,9 @@ qi_beam_weights: MVDR weights in float32, where the delayed producer's tensor is
 float64, where it is the delay table -- the call's one device input.  qi_beam_steer in both precisions with 17 beams (a
 second beam tile): the producer's tensor is the panel, the weights are fixed.  Complex tensors are uploaded as interleaved
 (re, im) values.  The matrices are adaptive_stream_cases.definite_pair's; the whitener stacks are capon_cases.whiten of them.
-tests/test_steer_cpu.py holds the table against the header; tests/test_gpu_steer_streams.py runs each case behind the delayed
-producer of tests/test_gpu_streams.py.  All are asynchronous: the header promises no host synchronisation, the frequencies
-ride in kernel arguments.
+tests/test_steer_cpu.py holds the table against the header; tests/test_gpu_header_streams.py runs each case behind the delayed
+producer of tests/stream_order.py.  All are asynchronous: the header promises no host synchronisation, the frequencies
+ride in kernel arguments.  Each case has one output: it differs between the two record sets, is finite and holds no FILL.
 """
 import functools
 
@@ -16,35 +16,14 @@ import numpy as np
 import adaptive_stream_cases as asc
 import capon_cases as cpc
 import stream_cases as sc
+from stream_table import Built, Table
 
-Case, Built, FILL = sc.Case, sc.Built, sc.FILL
-CASES = []
+TABLE = Table("qi_steer.h", power="every", finite=True, no_fill=True)  # (no plans: every case is plan-less)
+_case = TABLE.case
 SENSORS, MATRICES, LOADING = asc.SENSORS, asc.MATRICES, asc.LOADING
 BEAMS = 17  # a second beam tile
 TIMES = 300  # a third chunk of time
 definite_pair, interleaved = asc.definite_pair, asc.interleaved
-
-
-def _case(cid, functions, build, asynchronous=True, reason=""):
-    assert asynchronous or reason, cid
-    assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build))
-
-
-def ids():
-    return [c.id for c in CASES]
-
-
-def by_id(cid):
-    return next(c for c in CASES if c.id == cid)
-
-
-def named_functions():
-    return sorted({f for c in CASES for f in c.functions})
-
-
-def plan_less_ids():
-    return [c.id for c in CASES if c.engine is None]  # (all of them: qi_steer.h has no plans)
 
 
 def _types(torch, dtype):

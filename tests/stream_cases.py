@@ -3,8 +3,8 @@
 One case per C-ABI function of include/qi_tfr.h that takes a `qi_stream`, one per path where a function has several.  A
 case names the functions it reaches (`functions`: tests/test_stream_cases_cpu.py holds the table against the header) and
 builds, on the device, a closure `op(x) -> tuple of device tensors` together with two record sets A and B of one shape,
-both finite and legal for the op: tests/test_gpu_streams.py runs `op` on a buffer that a delayed producer turns from A
-into B and compares with the serial result on B.  The closures go through the Python call path of the other GPU tests:
+both finite and legal for the op: the harness (tests/stream_order.py, for tests/test_gpu_streams.py) runs `op` on a buffer
+that a delayed producer turns from A into B and compares with the serial result on B.  The table is a stream_table.Table.  The closures go through the Python call path of the other GPU tests:
 TfrPlan methods, the engine.* record ops, the public helpers of tfr_info / sampling, and `_lib.call` for the plan-less
 short-time family (whose public wrappers upload a window first, a host synchronisation of their own).  Buffers a closure
 owns are filled with FILL on the current stream before the call, so an output that is read before the library's own work
@@ -20,41 +20,16 @@ import os
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from stream_table import ROOT, Built, Table
+
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FS = 1000.0
 ORDER = 3
 FILL = 0.3125  # finite, exactly representable, and no result of any case
 
-# engine: the key of the plan a plan case runs on (ENGINES, PASS2_ENGINE or a plan of the case's own), None for a plan-less case --
-# the two groups of the host-thread tests (tests/test_gpu_threads.py): a plan belongs to one thread at a time, a plan-less op may
-# be called from several at once
-Case = collections.namedtuple("Case", "id functions asynchronous reason build engine", defaults=(None,))
-Built = collections.namedtuple("Built", "op a b note")  # a, b: NumPy record sets; note: what the build asserted, for the log
-
-CASES = []
-
-
-def _case(cid, functions, build, asynchronous=True, reason="", engine=None):
-    assert asynchronous or reason, cid
-    assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build, engine))
-
-
-def ids():
-    return [c.id for c in CASES]
-
-
-def by_id(cid):
-    return next(c for c in CASES if c.id == cid)
-
-
-def named_functions():
-    return sorted({f for c in CASES for f in c.functions})
-
-
-def plan_less_ids():
-    return [c.id for c in CASES if c.engine is None]
+# a plan case's `engine` is a key of ENGINES, PASS2_ENGINE's or the name of a plan of the case's own
+TABLE = Table("qi_tfr.h")  # power "any": one output that differs between A and B gives a case power
+_case = TABLE.case
 
 
 def noise(seed, shape, dtype, offset=0.75):

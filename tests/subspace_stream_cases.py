@@ -5,8 +5,10 @@ One case for qi_csd_eigh (float32, with info) and one per path of qi_beam_music:
 the power alone, and a host band table with both peak outputs in float32.  The delayed producer's tensor is the matrix stack,
 resp. the eigenvector stack, as interleaved (re, im) values.  The matrices are adaptive_stream_cases.definite_pair's; the
 eigenvector stacks are music_cases.eigh64 of them.  tests/test_music_cpu.py holds the table against the header;
-tests/test_gpu_subspace_streams.py runs each case behind the delayed producer of tests/test_gpu_streams.py.  All are
+tests/test_gpu_header_streams.py runs each case behind the delayed producer of tests/stream_order.py.  All are
 asynchronous: the header promises no host synchronisation, the frequencies and the band offsets ride in kernel arguments.
+The first output, the eigenvalues or the power, always differs between the two record sets; `info` is 0 on both and a
+band's peak index may coincide.
 """
 import functools
 
@@ -15,34 +17,14 @@ import numpy as np
 import adaptive_stream_cases as asc
 import music_cases as mc
 import stream_cases as sc
+from stream_table import Built, Table
 
-Case, Built, FILL = sc.Case, sc.Built, sc.FILL
-CASES = []
+# (no plans: every case is plan-less; output 2 of eigh-info is `info`: both record sets converge)
+TABLE = Table("qi_subspace.h", complex_input=True, power="first", finite=True, zero_outputs={"eigh-info": 2})
+_case = TABLE.case
 SENSORS, MATRICES, GRID = asc.SENSORS, asc.MATRICES, asc.GRID
 SOURCES = 2
 definite_pair, interleaved = asc.definite_pair, asc.interleaved
-
-
-def _case(cid, functions, build, asynchronous=True, reason=""):
-    assert asynchronous or reason, cid
-    assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build))
-
-
-def ids():
-    return [c.id for c in CASES]
-
-
-def by_id(cid):
-    return next(c for c in CASES if c.id == cid)
-
-
-def named_functions():
-    return sorted({f for c in CASES for f in c.functions})
-
-
-def plan_less_ids():
-    return [c.id for c in CASES if c.engine is None]  # (all of them: qi_subspace.h has no plans)
 
 
 def _build_eigh(dtype):

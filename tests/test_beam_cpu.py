@@ -9,25 +9,16 @@ import numpy as np
 import beam_cases as bc
 import beam_stream_cases as bsc
 import csd_cases as cc
+from stream_table import header_functions, stream_functions
 
 ROOT = bc.ROOT
-
-
-def header_functions(name="qi_beam.h"):
-    """{name: parameter text} of every function the header declares (comments removed first)."""
-    with open(os.path.join(ROOT, "include", name)) as fh:
-        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
-    return dict(re.findall(r"\b(qi_\w+)\s*\(([^;{}()]*)\)\s*;", text))
-
-
-def stream_functions():
-    return sorted(name for name, params in header_functions().items() if re.search(r"\bqi_stream\b", params))
+HEADER = "qi_beam.h"
 
 
 def test_library_exports_the_beam_header():
     from quantum_inferno_amd import _lib
 
-    declared = set(header_functions())
+    declared = set(header_functions(HEADER))
     assert declared == {"qi_beam_power_scratch_bytes", "qi_beam_power"}
     assert declared == set(_lib.BEAM_PROTOTYPES)
     assert not declared & set(_lib.PROTOTYPES) and not declared & set(_lib.ARRAY_PROTOTYPES)
@@ -57,13 +48,14 @@ def test_size_query_verdicts_without_a_gpu():
 
 
 def test_every_stream_entry_point_has_a_case_and_nothing_else_is_named():
-    assert stream_functions() == ["qi_beam_power"]
-    assert bsc.named_functions() == stream_functions()
+    assert bsc.TABLE.header == HEADER
+    assert stream_functions(HEADER) == ["qi_beam_power"]
+    assert bsc.TABLE.named_functions() == stream_functions(HEADER)
 
 
 def test_stream_case_table():
-    assert bsc.ids() == ["beam-bins", "beam-bands-semblance-peaks"]
-    for case in bsc.CASES:
+    assert bsc.TABLE.ids() == ["beam-bins", "beam-bands-semblance-peaks"]
+    for case in bsc.TABLE.cases:
         assert case.functions and callable(case.build) and case.asynchronous and case.engine is None, case.id
 
 

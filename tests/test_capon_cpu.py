@@ -4,7 +4,6 @@ restatements of tests/capon_cases.py against their identities (V^H R V = I, 1 / 
 plane-wave case, the float32 restatements' distance from the float64 ones, the exact case's integers and `info`."""
 import ctypes
 import os
-import re
 
 import numpy as np
 
@@ -12,25 +11,16 @@ import adaptive_stream_cases as asc
 import beam_cases as bc
 import capon_cases as cpc
 import csd_cases as cc
+from stream_table import header_functions, stream_functions
 
 ROOT = bc.ROOT
-
-
-def header_functions(name="qi_adaptive.h"):
-    """{name: parameter text} of every function the header declares (comments removed first)."""
-    with open(os.path.join(ROOT, "include", name)) as fh:
-        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
-    return dict(re.findall(r"\b(qi_\w+)\s*\(([^;{}()]*)\)\s*;", text))
-
-
-def stream_functions():
-    return sorted(name for name, params in header_functions().items() if re.search(r"\bqi_stream\b", params))
+HEADER = "qi_adaptive.h"
 
 
 def test_library_exports_the_adaptive_header():
     from quantum_inferno_amd import _lib
 
-    declared = set(header_functions())
+    declared = set(header_functions(HEADER))
     assert declared == {"qi_csd_whiten", "qi_beam_capon_scratch_bytes", "qi_beam_capon"}
     assert declared == set(_lib.ADAPTIVE_PROTOTYPES)
     for table in (_lib.PROTOTYPES, _lib.ARRAY_PROTOTYPES, _lib.BEAM_PROTOTYPES):
@@ -40,20 +30,21 @@ def test_library_exports_the_adaptive_header():
     lib = _lib.load()
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/qi_adaptive.h but not exported"
-        assert len(_lib.ADAPTIVE_PROTOTYPES[name][1]) == len(header_functions()[name].split(",")), name
+        assert len(_lib.ADAPTIVE_PROTOTYPES[name][1]) == len(header_functions(HEADER)[name].split(",")), name
     with open(os.path.join(ROOT, "include", "qi_adaptive.h")) as fh:
         text = fh.read()
     assert '#include "qi_tfr.h"' in text and "LOWER" in text  # the types; that only the lower triangle is read
 
 
 def test_every_stream_entry_point_has_a_case_and_nothing_else_is_named():
-    assert stream_functions() == ["qi_beam_capon", "qi_csd_whiten"]
-    assert asc.named_functions() == stream_functions()
+    assert asc.TABLE.header == HEADER
+    assert stream_functions(HEADER) == ["qi_beam_capon", "qi_csd_whiten"]
+    assert asc.TABLE.named_functions() == stream_functions(HEADER)
 
 
 def test_stream_case_table():
-    assert asc.ids() == ["whiten-info", "capon-bins", "capon-bands-peaks"]
-    for case in asc.CASES:
+    assert asc.TABLE.ids() == ["whiten-info", "capon-bins", "capon-bands-peaks"]
+    for case in asc.TABLE.cases:
         assert case.functions and callable(case.build) and case.asynchronous and case.engine is None, case.id
     for a in asc.definite_pair("float64", (47, 0)):
         assert np.linalg.eigvalsh(a).min() >= 1.0 and np.array_equal(a, np.conj(np.swapaxes(a, 1, 2)))

@@ -1,33 +1,20 @@
 """Cross-spectra without a GPU: the NumPy restatement of qi_csd (tests/csd_cases.py) against the SciPy fixture
 tests/golden/csd.npz, the condition the tolerances rest on, the float32 coherence tolerance's provenance, the exports of
 include/qi_array.h and the census of tests/array_stream_cases.py against that header."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 import array_stream_cases as asc
 import csd_cases as cc
+from stream_table import header_functions, stream_functions
 
-ROOT = cc.ROOT
 COH32_RESTATEMENT, COH32_TOL = cc.COH32_RESTATEMENT, cc.COH32_TOL
+HEADER = "qi_array.h"
 
 
 @pytest.fixture(scope="module")
 def golden():
     return np.load(cc.GOLDEN, allow_pickle=False)
-
-
-def header_functions():
-    """{name: parameter text} of every function include/qi_array.h declares (comments removed first)."""
-    with open(os.path.join(ROOT, "include", "qi_array.h")) as fh:
-        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
-    return dict(re.findall(r"\b(qi_\w+)\s*\(([^;{}()]*)\)\s*;", text))
-
-
-def stream_functions():
-    return sorted(name for name, params in header_functions().items() if re.search(r"\bqi_stream\b", params))
 
 
 def test_case_table_is_the_issue_s():
@@ -97,7 +84,7 @@ def test_bin_weights():
 def test_library_exports_the_array_header():
     from quantum_inferno_amd import _lib
 
-    declared = set(header_functions())
+    declared = set(header_functions(HEADER))
     assert declared == {"qi_cross_spectra_scratch_bytes", "qi_cross_spectra", "qi_csd_scratch_bytes", "qi_csd"}
     assert declared == set(_lib.ARRAY_PROTOTYPES) and not declared & set(_lib.PROTOTYPES)
     lib = _lib.load()
@@ -113,11 +100,12 @@ def test_library_exports_the_array_header():
 
 # ---- the census of tests/array_stream_cases.py against include/qi_array.h ----------------------------------------------------
 def test_every_stream_entry_point_has_a_case_and_nothing_else_is_named():
-    assert stream_functions() == ["qi_cross_spectra", "qi_csd"]
-    assert asc.named_functions() == stream_functions()
+    assert asc.TABLE.header == HEADER
+    assert stream_functions(HEADER) == ["qi_cross_spectra", "qi_csd"]
+    assert asc.TABLE.named_functions() == stream_functions(HEADER)
 
 
 def test_stream_case_table():
-    assert asc.ids() == ["csd-fused", "csd-hipfft", "cross_spectra-coherence", "cross_spectra-matrices"]
-    for case in asc.CASES:
+    assert asc.TABLE.ids() == ["csd-fused", "csd-hipfft", "cross_spectra-coherence", "cross_spectra-matrices"]
+    for case in asc.TABLE.cases:
         assert case.functions and callable(case.build) and case.asynchronous, case.id

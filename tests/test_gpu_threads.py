@@ -12,7 +12,7 @@ The common shape (run_threads): every thread calls torch.cuda.set_device(0) and 
 own instance of a case of tests/stream_cases.py or tests/array_stream_cases.py (a closure makes its outputs, an instance is
 never shared); everything cached -- the cases, their serial results, the delay chain -- is made before the threads start, and
 every buffer exists and holds legal records by then.  A barrier releases the threads together, and each thread's stream first
-waits for one gate event behind Delay.queue(FLOOR_MS), as tests/test_gpu_streams.py's released_together does, so the queued
+waits for one gate event behind Delay.queue(FLOOR_MS), as tests/stream_order.py's released_together does, so the queued
 work is released together on the device as well.  A thread makes CALLS calls, alternating the record sets A and B, keeps a copy
 of every call's outputs and then synchronises its own stream only; what a thread raises is raised again in the main thread.
 Nothing is sampled: every output of every call is compared.
@@ -34,9 +34,8 @@ import torch
 
 import array_stream_cases as asc
 import stream_cases as sc
-import test_gpu_array_streams as tga
-import test_gpu_streams as tgs
-from test_gpu_streams import FLOOR_MS, delay, keep, mismatches, same_bits
+import stream_order as so
+from stream_order import FLOOR_MS, delay, keep, mismatches, same_bits
 
 from quantum_inferno_amd import _lib, cwt_atoms, engine, styx_cwt, styx_stx
 
@@ -47,7 +46,7 @@ CALLS = 8
 THREADS = 4
 LOG_PATH = os.environ.get("QI_HOST_THREADS_LOG") or os.path.join(ROOT, "profiles", "host_threads.txt")
 _LOG = {}
-PLAN_LESS = [(sc, cid) for cid in sc.plan_less_ids()] + [(asc, cid) for cid in asc.plan_less_ids()]
+PLAN_LESS = [(table, cid) for table in (sc.TABLE, asc.TABLE) for cid in table.plan_less_ids()]
 ONE_PLAN_KEYS = ("f32_n16384", "f64_n32768", "f32_n2048", "f32_n3000")
 OTHER_TESTS = ("mixed_shared_state", "one_plan_each", "wrappers_from_threads", "wrapper_on_two_streams", "fft_work_area")
 
@@ -58,8 +57,7 @@ def _plans_and_log():
     torch.cuda.synchronize()
     engine.clear_plans()
     sc.close_plans()
-    for cache in (tgs.serial, tgs.built, tga.serial, tga.built):
-        cache.cache_clear()
+    so.clear_cases()
     expected = [f"same_op[{cid}]" for _, cid in PLAN_LESS] + list(OTHER_TESTS)
     if all(name in _LOG for name in expected):  # (a partial run does not overwrite the record of a whole one)
         lines = ["host threads: several Python threads inside libqi_tfr.so at once (tests/test_gpu_threads.py)",
@@ -146,7 +144,7 @@ def case_job(op, a_dev, b_dev, on_a, on_b):
 
 def reference(table, cid):
     """(result on A, result on B) of the case's shared instance, alone on the default stream."""
-    want, stale, _ = (tgs if table is sc else tga).serial(cid)
+    want, stale, _ = so.serial(table, cid)
     return stale, want
 
 
@@ -170,7 +168,7 @@ def test_threads_mixed_shared_state():
     """One thread per case of stream_cases.SHARED_STATE, all at once: the hipFFT cache meets four transform shapes and the strip
     partials from six threads (below the 16 CPUs a run may use)."""
     assert len(sc.SHARED_STATE) == 6
-    jobs = [case_job(*instance(sc, cid), *reference(sc, cid)) for cid in sc.SHARED_STATE]
+    jobs = [case_job(*instance(sc.TABLE, cid), *reference(sc.TABLE, cid)) for cid in sc.SHARED_STATE]
     run_threads("mixed_shared_state", jobs)
 
 
@@ -182,9 +180,9 @@ def test_threads_one_plan_each():
     jobs = []
     for key in ONE_PLAN_KEYS:
         cid = f"cwt_stx-{key}-all-r1"
-        assert sc.by_id(cid).engine == key
-        b, a_dev, b_dev = tgs.built(cid)
-        jobs.append(case_job(b.op, a_dev, b_dev, *reference(sc, cid)))
+        assert sc.TABLE.by_id(cid).engine == key
+        b, a_dev, b_dev = so.built(sc.TABLE, cid)
+        jobs.append(case_job(b.op, a_dev, b_dev, *reference(sc.TABLE, cid)))
     n = 1 << 10
     nb = len(engine.scales.log_frequency_hz_from_fft_points(sc.FS, n, sc.ORDER))
     ws = engine.TfrPlan.workspace_for(n, nb, torch.float32, 1)

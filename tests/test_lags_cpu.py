@@ -10,24 +10,19 @@ import numpy as np
 
 import lag_cases as lc
 import lag_stream_cases as lsc
+from stream_table import header_functions, stream_functions
 
 ROOT = lc.ROOT
+HEADER = "qi_lags.h"
 OTHER_HEADERS = ("qi_tfr.h", "qi_array.h", "qi_beam.h", "qi_adaptive.h", "qi_subspace.h", "qi_steer.h", "qi_windows.h")
 NAMES = {"qi_pair_lags_scratch_bytes", "qi_pair_lags"}
-
-
-def header_functions(name="qi_lags.h"):
-    """{name: parameter text} of every function the header declares (comments removed first)."""
-    with open(os.path.join(ROOT, "include", name)) as fh:
-        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
-    return dict(re.findall(r"\b(qi_\w+)\s*\(([^;{}()]*)\)\s*;", text))
 
 
 # ---- the header, the exports, the stream census ---------------------------------------------------------------------------------------
 def test_library_exports_the_lags_header():
     from quantum_inferno_amd import _lib
 
-    declared = set(header_functions())
+    declared = set(header_functions(HEADER))
     assert declared == NAMES
     assert declared == set(_lib.LAG_PROTOTYPES)
     for table in (_lib.PROTOTYPES, _lib.ARRAY_PROTOTYPES, _lib.BEAM_PROTOTYPES, _lib.ADAPTIVE_PROTOTYPES, _lib.SUBSPACE_PROTOTYPES,
@@ -39,7 +34,7 @@ def test_library_exports_the_lags_header():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/qi_lags.h but not exported"
         assert getattr(lib, name).argtypes == _lib.LAG_PROTOTYPES[name][1], f"{name}: load() did not attach the table"
-        assert len(_lib.LAG_PROTOTYPES[name][1]) == len(header_functions()[name].split(",")), name
+        assert len(_lib.LAG_PROTOTYPES[name][1]) == len(header_functions(HEADER)[name].split(",")), name
     with open(os.path.join(ROOT, "include", "qi_lags.h")) as fh:
         text = fh.read()
     assert '#include "qi_tfr.h"' in text and '#include "qi_array.h"' in text
@@ -49,11 +44,11 @@ def test_library_exports_the_lags_header():
 
 
 def test_every_stream_entry_point_has_a_case_and_nothing_else_is_named():
-    streams = sorted(name for name, params in header_functions().items() if re.search(r"\bqi_stream\b", params))
-    assert streams == ["qi_pair_lags"]
-    assert lsc.named_functions() == streams
-    assert lsc.ids() == ["pair_lags-f64-plain-all", "pair_lags-f32-phat-peaks", "pair_lags-f64-phat-cc", "pair_lags-f32-plain-cc"]
-    for case in lsc.CASES:
+    assert lsc.TABLE.header == HEADER
+    assert stream_functions(HEADER) == ["qi_pair_lags"]
+    assert lsc.TABLE.named_functions() == stream_functions(HEADER)
+    assert lsc.TABLE.ids() == ["pair_lags-f64-plain-all", "pair_lags-f32-phat-peaks", "pair_lags-f64-phat-cc", "pair_lags-f32-plain-cc"]
+    for case in lsc.TABLE.cases:
         assert case.functions and callable(case.build) and case.asynchronous and case.engine is None, case.id
 
 

@@ -6,7 +6,6 @@ two-wave case, the exact (diagonal) cases and `info`."""
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 
@@ -15,28 +14,19 @@ import capon_cases as cpc
 import csd_cases as cc
 import music_cases as mc
 import subspace_stream_cases as ssc
+from stream_table import header_functions, stream_functions
 
 ROOT = bc.ROOT
+HEADER = "qi_subspace.h"
 OTHER_HEADERS = ("qi_tfr.h", "qi_array.h", "qi_beam.h", "qi_adaptive.h")
 STEPS64_MATRICES = 5  # matrices of a stack the kernel's algorithm is restated on in double (each is solved alone)
-
-
-def header_functions(name="qi_subspace.h"):
-    """{name: parameter text} of every function the header declares (comments removed first)."""
-    with open(os.path.join(ROOT, "include", name)) as fh:
-        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
-    return dict(re.findall(r"\b(qi_\w+)\s*\(([^;{}()]*)\)\s*;", text))
-
-
-def stream_functions():
-    return sorted(name for name, params in header_functions().items() if re.search(r"\bqi_stream\b", params))
 
 
 # ---- 1, 2: the header, the exports, the stream census ---------------------------------------------------------------------------------
 def test_library_exports_the_subspace_header():
     from quantum_inferno_amd import _lib
 
-    declared = set(header_functions())
+    declared = set(header_functions(HEADER))
     assert declared == {"qi_csd_eigh", "qi_beam_music_scratch_bytes", "qi_beam_music"}
     assert declared == set(_lib.SUBSPACE_PROTOTYPES)
     for table in (_lib.PROTOTYPES, _lib.ARRAY_PROTOTYPES, _lib.BEAM_PROTOTYPES, _lib.ADAPTIVE_PROTOTYPES):
@@ -46,24 +36,26 @@ def test_library_exports_the_subspace_header():
     lib = _lib.load()
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/qi_subspace.h but not exported"
-        assert len(_lib.SUBSPACE_PROTOTYPES[name][1]) == len(header_functions()[name].split(",")), name
+        assert len(_lib.SUBSPACE_PROTOTYPES[name][1]) == len(header_functions(HEADER)[name].split(",")), name
     with open(os.path.join(ROOT, "include", "qi_subspace.h")) as fh:
         text = fh.read()
     assert '#include "qi_tfr.h"' in text and '#include "qi_beam.h"' in text and "LOWER" in text  # that only the lower triangle is read
 
 
 def test_every_stream_entry_point_has_a_case_and_nothing_else_is_named():
-    assert stream_functions() == ["qi_beam_music", "qi_csd_eigh"]
-    assert ssc.named_functions() == stream_functions()
+    assert ssc.TABLE.header == HEADER
+    assert stream_functions(HEADER) == ["qi_beam_music", "qi_csd_eigh"]
+    assert ssc.TABLE.named_functions() == stream_functions(HEADER)
 
 
 def test_stream_case_table():
-    assert ssc.ids() == ["eigh-info", "music-bins", "music-bands-peaks"]
-    for case in ssc.CASES:
+    by_id = ssc.TABLE.by_id
+    assert ssc.TABLE.ids() == ["eigh-info", "music-bins", "music-bands-peaks"]
+    for case in ssc.TABLE.cases:
         assert case.functions and callable(case.build) and case.asynchronous and case.engine is None, case.id
-    dtypes = {c.id: c.build.args[0] for c in ssc.CASES}
+    dtypes = {c.id: c.build.args[0] for c in ssc.TABLE.cases}
     assert dtypes == {"eigh-info": "float32", "music-bins": "float64", "music-bands-peaks": "float32"}
-    assert ssc.by_id("music-bins").build.args[1:] == (None, False) and ssc.by_id("music-bands-peaks").build.args[1:] == ((0, 3, 4, 33), True)
+    assert by_id("music-bins").build.args[1:] == (None, False) and by_id("music-bands-peaks").build.args[1:] == ((0, 3, 4, 33), True)
     assert 0 <= ssc.SOURCES < ssc.SENSORS
 
 

@@ -6,7 +6,6 @@ through the oracle's ShortTimeFFT-convention transform."""
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 
@@ -14,28 +13,19 @@ import beam_cases as bc
 import capon_cases as cpc
 import steer_cases as stc
 import steer_stream_cases as ssc
+from stream_table import header_functions, stream_functions
 
 ROOT = bc.ROOT
+HEADER = "qi_steer.h"
 OTHER_HEADERS = ("qi_tfr.h", "qi_array.h", "qi_beam.h", "qi_adaptive.h", "qi_subspace.h")
 IDENTITY_TOL = 1e-12
-
-
-def header_functions(name="qi_steer.h"):
-    """{name: parameter text} of every function the header declares (comments removed first)."""
-    with open(os.path.join(ROOT, "include", name)) as fh:
-        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
-    return dict(re.findall(r"\b(qi_\w+)\s*\(([^;{}()]*)\)\s*;", text))
-
-
-def stream_functions():
-    return sorted(name for name, params in header_functions().items() if re.search(r"\bqi_stream\b", params))
 
 
 # ---- 1, 2: the header, the exports, the stream census ---------------------------------------------------------------------------------
 def test_library_exports_the_steer_header():
     from quantum_inferno_amd import _lib
 
-    declared = set(header_functions())
+    declared = set(header_functions(HEADER))
     assert declared == {"qi_beam_weights_scratch_bytes", "qi_beam_weights", "qi_beam_steer"}
     assert declared == set(_lib.STEER_PROTOTYPES)
     for table in (_lib.PROTOTYPES, _lib.ARRAY_PROTOTYPES, _lib.BEAM_PROTOTYPES, _lib.ADAPTIVE_PROTOTYPES, _lib.SUBSPACE_PROTOTYPES):
@@ -45,23 +35,25 @@ def test_library_exports_the_steer_header():
     lib = _lib.load()
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/qi_steer.h but not exported"
-        assert len(_lib.STEER_PROTOTYPES[name][1]) == len(header_functions()[name].split(",")), name
+        assert len(_lib.STEER_PROTOTYPES[name][1]) == len(header_functions(HEADER)[name].split(",")), name
     with open(os.path.join(ROOT, "include", "qi_steer.h")) as fh:
         text = fh.read()
     assert '#include "qi_tfr.h"' in text and '#include "qi_beam.h"' in text and "NO conjugate" in text
 
 
 def test_every_stream_entry_point_has_a_case_and_nothing_else_is_named():
-    assert stream_functions() == ["qi_beam_steer", "qi_beam_weights"]
-    assert ssc.named_functions() == stream_functions()
+    assert ssc.TABLE.header == HEADER
+    assert stream_functions(HEADER) == ["qi_beam_steer", "qi_beam_weights"]
+    assert ssc.TABLE.named_functions() == stream_functions(HEADER)
 
 
 def test_stream_case_table():
-    assert ssc.ids() == ["weights-capon", "weights-bartlett", "steer-f32", "steer-f64"]
-    for case in ssc.CASES:
+    by_id = ssc.TABLE.by_id
+    assert ssc.TABLE.ids() == ["weights-capon", "weights-bartlett", "steer-f32", "steer-f64"]
+    for case in ssc.TABLE.cases:
         assert case.functions and callable(case.build) and case.asynchronous and case.engine is None, case.id
-    assert ssc.by_id("weights-capon").build.args == ("float32", True) and ssc.by_id("weights-bartlett").build.args == ("float64", False)
-    assert ssc.by_id("steer-f32").build.args == ("float32",) and ssc.by_id("steer-f64").build.args == ("float64",)
+    assert by_id("weights-capon").build.args == ("float32", True) and by_id("weights-bartlett").build.args == ("float64", False)
+    assert by_id("steer-f32").build.args == ("float32",) and by_id("steer-f64").build.args == ("float64",)
     assert ssc.BEAMS == 17
 
 

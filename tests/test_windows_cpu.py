@@ -4,35 +4,25 @@ table's coverage, the NumPy restatement of tests/window_cases.py against its ide
 two-source timeline case restated in float64 for all three methods."""
 import ctypes
 import os
-import re
 
 import numpy as np
 
 import window_cases as wc
 import window_stream_cases as wsc
+from stream_table import header_functions, stream_functions
 
 ROOT = wc.ROOT
+HEADER = "qi_windows.h"
 OTHER_HEADERS = ("qi_tfr.h", "qi_array.h", "qi_beam.h", "qi_adaptive.h", "qi_subspace.h", "qi_steer.h")
 NAMES = {"qi_cross_spectra_windows_scratch_bytes", "qi_cross_spectra_windows", "qi_csd_windows_scratch_bytes", "qi_csd_windows"}
 IDENTITY_TOL = 1e-12
-
-
-def header_functions(name="qi_windows.h"):
-    """{name: parameter text} of every function the header declares (comments removed first)."""
-    with open(os.path.join(ROOT, "include", name)) as fh:
-        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
-    return dict(re.findall(r"\b(qi_\w+)\s*\(([^;{}()]*)\)\s*;", text))
-
-
-def stream_functions():
-    return sorted(name for name, params in header_functions().items() if re.search(r"\bqi_stream\b", params))
 
 
 # ---- the header, the exports, the stream census ---------------------------------------------------------------------------------------
 def test_library_exports_the_windows_header():
     from quantum_inferno_amd import _lib
 
-    declared = set(header_functions())
+    declared = set(header_functions(HEADER))
     assert declared == NAMES
     assert declared == set(_lib.WINDOW_PROTOTYPES)
     for table in (_lib.PROTOTYPES, _lib.ARRAY_PROTOTYPES, _lib.BEAM_PROTOTYPES, _lib.ADAPTIVE_PROTOTYPES, _lib.SUBSPACE_PROTOTYPES,
@@ -43,24 +33,25 @@ def test_library_exports_the_windows_header():
     lib = _lib.load()
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/qi_windows.h but not exported"
-        assert len(_lib.WINDOW_PROTOTYPES[name][1]) == len(header_functions()[name].split(",")), name
+        assert len(_lib.WINDOW_PROTOTYPES[name][1]) == len(header_functions(HEADER)[name].split(",")), name
     with open(os.path.join(ROOT, "include", "qi_windows.h")) as fh:
         text = fh.read()
     assert '#include "qi_tfr.h"' in text and '#include "qi_array.h"' in text and "BIT FOR BIT" in text
 
 
 def test_every_stream_entry_point_has_a_case_and_nothing_else_is_named():
-    assert stream_functions() == ["qi_cross_spectra_windows", "qi_csd_windows"]
-    assert wsc.named_functions() == stream_functions()
+    assert wsc.TABLE.header == HEADER
+    assert stream_functions(HEADER) == ["qi_cross_spectra_windows", "qi_csd_windows"]
+    assert wsc.TABLE.named_functions() == stream_functions(HEADER)
 
 
 def test_stream_case_table():
-    assert wsc.ids() == ["cross_spectra_windows-matrices", "cross_spectra_windows-coherence", "csd_windows-fused-matrices",
-                         "csd_windows-fused-coherence", "csd_windows-hipfft-matrices", "csd_windows-hipfft-coherence"]
-    for case in wsc.CASES:
+    assert wsc.TABLE.ids() == ["cross_spectra_windows-matrices", "cross_spectra_windows-coherence", "csd_windows-fused-matrices",
+                               "csd_windows-fused-coherence", "csd_windows-hipfft-matrices", "csd_windows-hipfft-coherence"]
+    for case in wsc.TABLE.cases:
         assert case.functions and callable(case.build) and case.asynchronous and case.engine is None, case.id
-    assert wsc.by_id("cross_spectra_windows-coherence").build.args == (True,)
-    assert wsc.by_id("csd_windows-hipfft-matrices").build.args == ("hipfft", False)
+    assert wsc.TABLE.by_id("cross_spectra_windows-coherence").build.args == (True,)
+    assert wsc.TABLE.by_id("csd_windows-hipfft-matrices").build.args == ("hipfft", False)
     assert (wsc.COLUMNS - wsc.WINDOW) // wsc.HOP + 1 == 16 and (wsc.COLUMNS - wsc.WINDOW) % wsc.HOP > 0
 
 

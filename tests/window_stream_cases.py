@@ -6,44 +6,24 @@ qi_cross_spectra_windows on a float64 panel [RECORDS, 7 bands, 300 columns] (the
 values), windows of 40 columns every 17, the bands 2 .. 5: once the matrices alone with no weights, once the coherence alone
 with host weights -- the matrices go through scratch.  qi_csd_windows on float32 records at stream_cases' fused and hipFFT
 STFT shapes (five Welch segments, windows of three every one), each with the matrices and with the coherence only.
-tests/test_windows_cpu.py holds the table against the header; tests/test_gpu_windows_streams.py runs each case behind the
-delayed producer of tests/test_gpu_streams.py.  All are asynchronous: the header promises no host synchronisation, the host
-weights ride in kernel arguments.
+tests/test_windows_cpu.py holds the table against the header; tests/test_gpu_header_streams.py runs each case behind the
+delayed producer of tests/stream_order.py.  All are asynchronous: the header promises no host synchronisation, the host
+weights ride in kernel arguments.  Each case has one output: it differs between the two record sets, is finite and holds no
+FILL.
 """
 import functools
 
 import numpy as np
 
 import stream_cases as sc
+from stream_table import Built, Table
 
-Case, Built, FILL = sc.Case, sc.Built, sc.FILL
-CASES = []
+TABLE = Table("qi_windows.h", power="every", finite=True, no_fill=True)  # (no plans: every case is plan-less)
+_case = TABLE.case
 RECORDS = 5  # one ragged tile of records
 BANDS, COLUMNS, BINS = 7, 300, (2, 4)
 WINDOW, HOP = 40, 17  # 16 windows, odd starts, a checked tail in either precision
 CSD_WINDOW, CSD_HOP = 3, 1  # of the five Welch segments: three windows
-
-
-def _case(cid, functions, build, asynchronous=True, reason=""):
-    assert asynchronous or reason, cid
-    assert cid not in {c.id for c in CASES}, cid
-    CASES.append(Case(cid, tuple(functions), asynchronous, reason, build))
-
-
-def ids():
-    return [c.id for c in CASES]
-
-
-def by_id(cid):
-    return next(c for c in CASES if c.id == cid)
-
-
-def named_functions():
-    return sorted({f for c in CASES for f in c.functions})
-
-
-def plan_less_ids():
-    return [c.id for c in CASES if c.engine is None]  # (all of them: qi_windows.h has no plans)
 
 
 def _build_cross_spectra_windows(coherence):
