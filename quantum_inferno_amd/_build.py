@@ -47,6 +47,7 @@ def needs_build():
     deps += [os.path.join(ROOT, "include", "qi_tfr.h"), os.path.join(ROOT, "include", "qi_array.h"), os.path.join(ROOT, "include", "qi_beam.h"),
              os.path.join(ROOT, "include", "qi_adaptive.h"), os.path.join(ROOT, "include", "qi_subspace.h"), os.path.join(ROOT, "include", "qi_steer.h"),
              os.path.join(ROOT, "include", "qi_windows.h"), os.path.join(ROOT, "include", "qi_lags.h"),
+             os.path.join(ROOT, "include", "qi_bands.h"),
              os.path.abspath(__file__)]  # (the flags live in this file)
     return any(os.path.getmtime(d) > t for d in deps)
 

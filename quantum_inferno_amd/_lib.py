@@ -1,5 +1,5 @@
 """ctypes binding of libqi_tfr.so (include/qi_tfr.h, qi_array.h, qi_beam.h, qi_adaptive.h, qi_subspace.h, qi_steer.h, qi_windows.h,
-qi_lags.h).  There is no CPU fallback: if the
+qi_lags.h, qi_bands.h).  There is no CPU fallback: if the
 library is missing or no HIP device is present, every transform raises."""
 import ctypes as C
 import os
@@ -212,6 +212,13 @@ LAG_PROTOTYPES = {
 }
 LAG_WEIGHTINGS = ("plain", "phat", "scot")  # QI_LAG_PLAIN, QI_LAG_PHAT, QI_LAG_SCOT
 
+# include/qi_bands.h (cross-spectral matrices of a constant-Q panel, every band in its own window, hop and stride), one to one
+BAND_PROTOTYPES = {
+    "qi_cross_spectra_bands_layout": (_i64, [_i64, _i64, _I64, _I64, _I64, _I64]),
+    "qi_cross_spectra_bands_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _I64, _I64, _I64]),
+    "qi_cross_spectra_bands": (_int, [_int, _int, _P, _i64, _i64, _i64, _i64, _i64, _I64, _I64, _I64, _D, _P, _P, _P, _i64, _P]),
+}
+
 _lib = None
 
 
@@ -235,7 +242,7 @@ def load():
         )
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES, **SUBSPACE_PROTOTYPES,
-                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES, **LAG_PROTOTYPES}.items():
+                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES, **LAG_PROTOTYPES, **BAND_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -5,7 +5,9 @@ slowness vectors (engine.beam_power, include/qi_beam.h), Capon's minimum-varianc
 (engine.csd_eigh and engine.music_power, include/qi_subspace.h) -- and, once the map has a peak, the signal from that
 direction: beam panels and beam waveforms with Bartlett or MVDR weights (engine.beam_weights and engine.beam_steer,
 include/qi_steer.h).  fk_timeline_pow2 runs the three power forms per sliding window of the record
-(styx_fft.csd_windows_pow2's matrices, include/qi_windows.h): a detection timeline.  Without a grid, slowness_from_lags
+(styx_fft.csd_windows_pow2's matrices, include/qi_windows.h): a detection timeline; fk_timeline_cq is its constant-Q twin on
+the CWT or Stockwell panel, every band in a window of so many of its own periods (constant_q_windows, band_window_times;
+engine.cross_spectra_bands' matrices, include/qi_bands.h).  Without a grid, slowness_from_lags
 fits the slowness vector to the pair delays of styx_fft.pair_lags_pow2 (the peaks of the generalized cross-correlations,
 include/qi_lags.h) and lag_closure is their consistency check.  The reference (quantum-inferno) has no
 array processing; the conventions below are the usual ones of infrasound and seismic array work.
@@ -15,7 +17,7 @@ plane wave reaches sensor i later by tau_i = s . r_i seconds.  The back azimuth 
 -s in degrees clockwise from north; the trace velocity is 1 / |s|.
 
 The helpers are host code on torch float64; only plane_wave_delays' result and the work of fk_power_pow2,
-capon_power_pow2, music_power_pow2, fk_timeline_pow2, beam_stft_pow2 and beam_traces_tukey are on the device.
+capon_power_pow2, music_power_pow2, fk_timeline_pow2, fk_timeline_cq, beam_stft_pow2 and beam_traces_tukey are on the device.
 """
 import numpy as np
 import torch
@@ -260,6 +262,123 @@ def fk_timeline_pow2(
     return (time_s, ranges, engine.finish(power.reshape(n_win, n_b, -1), was_numpy, False),
             engine.finish(index.reshape(n_win, n_b), was_numpy, False), engine.finish(value.reshape(n_win, n_b), was_numpy, False),
             None if info is None else engine.finish(info.reshape(n_win, bins), was_numpy, False))
+
+
+def constant_q_windows(frequency_hz, frequency_sample_rate_hz: float, n: int, window_cycles: float, hop_fraction: float = 0.5,
+                       max_terms: int = 4096):
+    """The window geometry of engine.cross_spectra_bands for a constant-Q band table (host code): band b's window spans
+    window_cycles of its own periods, span = round(window_cycles * fs / f_b) samples (at least 1); it is summed at every
+    stride-th sample, stride = max(1, ceil(span / max_terms)), terms = (span - 1) // stride + 1; windows start every
+    hop = max(1, round(hop_fraction * span)) samples.  max_terms: None for no stride.
+    max_terms is a cap on work, not a measured number.  A window of window_cycles periods of a band of quality Q holds on the
+    order of window_cycles / Q independent samples -- the coefficients of a band decorrelate over the atom's duration, about
+    Q periods -- so 4096 terms oversample it by two orders of magnitude at every order the project uses; the stride thins
+    the low bands' sums (10^5 consecutive samples of a 2^20-sample order-3 panel) and leaves every window of up to 4096
+    samples as it is.
+    :return: bins = (first, count): the contiguous range of bands whose span fits in n; terms, hop, stride [count] int64 of
+        those bands.  Raises ValueError if no band fits or the bands that fit are not contiguous."""
+    f = np.asarray(frequency_hz, dtype=np.float64)
+    fs = float(frequency_sample_rate_hz)
+    if f.ndim != 1 or f.size < 1 or not np.all(f > 0) or not fs > 0 or not window_cycles > 0 or not hop_fraction > 0 or int(n) < 1:
+        raise ValueError("constant_q_windows needs positive band frequencies, a sample rate, window_cycles, hop_fraction and n")
+    if max_terms is not None and int(max_terms) < 1:
+        raise ValueError(f"max_terms must be at least 1 or None, got {max_terms}")
+    span = np.maximum(1, np.rint(float(window_cycles) * fs / f)).astype(np.int64)
+    stride = np.ones_like(span) if max_terms is None else np.maximum(1, -(-span // int(max_terms)))
+    terms = (span - 1) // stride + 1
+    hop = np.maximum(1, np.rint(float(hop_fraction) * span)).astype(np.int64)
+    fits = np.flatnonzero(span <= int(n))
+    if fits.size == 0:
+        raise ValueError(f"no band's window of {window_cycles} periods fits in {n} samples")
+    first, count = int(fits[0]), int(fits.size)
+    if fits[-1] - fits[0] + 1 != count:
+        raise ValueError("the bands whose window fits the record are not a contiguous range of the table")
+    cut = slice(first, first + count)
+    return (first, count), terms[cut].copy(), hop[cut].copy(), stride[cut].copy()
+
+
+def band_window_times(offsets, terms, hop, stride, frequency_sample_rate_hz: float) -> np.ndarray:
+    """The centre, in seconds, of the samples that every matrix of engine.cross_spectra_bands' stack spans: row
+    offsets[b] + w covers the samples w * hop[b] .. w * hop[b] + span[b] - 1, span[b] = (terms[b] - 1) * stride[b] + 1, and
+    its time is (w * hop[b] + span[b] / 2) / fs -- styx_fft.csd_windows_pow2's convention.  -> [total] float64."""
+    off, t, h, s = (np.asarray(a, dtype=np.int64) for a in (offsets, terms, hop, stride))
+    if off.ndim != 1 or off.size < 2 or not (t.shape == h.shape == s.shape == (off.size - 1,)) or off[0] != 0 or np.any(np.diff(off) < 1):
+        raise ValueError("band_window_times needs count + 1 ascending offsets from 0 and three tables of count values")
+    n_win = np.diff(off)
+    w = np.arange(off[-1], dtype=np.int64) - np.repeat(off[:-1], n_win)
+    span = (t - 1) * s + 1
+    return (w * np.repeat(h, n_win) + np.repeat(span, n_win) / 2.0) / float(frequency_sample_rate_hz)
+
+
+def fk_timeline_cq(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    positions_m,
+    slowness,
+    band_order_nth: float,
+    window_cycles: float,
+    hop_fraction: float = 0.5,
+    max_terms: int = 4096,
+    transform: str = "cwt",
+    method: str = "bartlett",
+    normalize: bool = True,
+    loading: float = 1e-2,
+    n_sources: int = 1,
+):
+    """Constant-Q detection timeline of the records of one array [C x n], n a power of two: fk_timeline_pow2 on the order-N
+    CWT (transform "cwt", styx_cwt's atoms with the "norm" dictionary) or Stockwell transform ("stx") instead of the STFT,
+    every band in a window of window_cycles of its own periods (constant_q_windows) -- PMCC's geometry: short windows where
+    the periods are short.  The panel of all records comes from a borrowed plan and stays on the device; the matrices of all
+    bands and windows are one launch (engine.cross_spectra_bands, weight 1 / terms: the window's mean); the form (method
+    "bartlett", "capon" or "music", with fk_timeline_pow2's arguments and checks) runs once on the flat stack, every matrix
+    its own band, with the band's centre frequency repeated per window.  Nothing but the results leaves the device.
+
+    The narrow-band assumption.  A band's matrices are steered by exp(-i 2 pi f_b tau) at its centre frequency f_b alone.
+    That holds while the delays across the array are short against the atom's duration, f_b * max|tau| << Q (Q about
+    0.375 * band_order_nth periods to one standard deviation of the envelope): beyond it the records' atoms no longer overlap, the
+    coherence falls and the peak flattens -- widen the bands' atoms (a higher order) or shrink the array.
+
+    Conjugation.  The atoms are exp(+i omega t) under a Gaussian and the panel is the record's correlation with them, so a
+    record that arrives later by tau has its coefficients multiplied by exp(-i 2 pi f_b tau), as an STFT's are: with
+    csd[i, j] = conj(Z_i) Z_j the form e^H S e of engine.beam_power, e_i = exp(2 pi i f tau_i), peaks at the wave's own
+    slowness, and the delays are passed as plane_wave_delays gives them, not negated (tests/test_bands_cpu.py pins it with the
+    CPU restatement's float64 CWT of a plane wave).
+    :return: frequency_hz [count] of the bands whose window fits the record, offsets [count + 1] (band b's windows are the
+        rows offsets[b] .. offsets[b + 1] - 1 of what follows), window_time_s [total], power [total x G], peak_index [total],
+        peak_value [total], info: None for bartlett, [total] int32 for capon / music"""
+    from . import styx_cwt, styx_stx
+
+    if method not in TIMELINE_METHODS:
+        raise ValueError(f"method must be one of {TIMELINE_METHODS}, got {method!r}")
+    if method != "bartlett" and not normalize:
+        raise ValueError(f"normalize belongs to the bartlett method: there is no {method} semblance to leave out")
+    if transform not in ("cwt", "stx"):
+        raise ValueError(f"transform must be 'cwt' or 'stx', got {transform!r}")
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    n_ch, n = sig.shape
+    tau = plane_wave_delays(positions_m, slowness, sig.device)
+    if tau.shape[1] != n_ch:
+        raise ValueError(f"{tau.shape[1]} positions for {n_ch} records")
+    if transform == "cwt":
+        res = styx_cwt._cwt_panel(band_order_nth, sig, frequency_sample_rate_hz)
+    else:
+        res = styx_stx._stx_panel(band_order_nth, sig, frequency_sample_rate_hz)
+    f_hz = np.asarray(res.frequency_hz, dtype=np.float64)
+    bins, terms, hop, stride = constant_q_windows(f_hz, frequency_sample_rate_hz, n, window_cycles, hop_fraction, max_terms)
+    offsets, stack = engine.cross_spectra_bands(res.coef, terms, hop, stride, weight=1.0 / terms, bins=bins)
+    f_b = f_hz[bins[0]:bins[0] + bins[1]]
+    f_all, info = np.repeat(f_b, np.diff(offsets)), None
+    if method == "bartlett":
+        power, index, value = engine.beam_power(stack, f_all, tau, normalize=normalize, peaks=True)
+    elif method == "capon":
+        whitener, info = engine.csd_whiten(stack, loading=loading, info=True)
+        power, index, value = engine.capon_power(whitener, f_all, tau, peaks=True)
+    else:
+        _, vectors, info = engine.csd_eigh(stack, info=True)
+        power, index, value = engine.music_power(vectors, n_sources, f_all, tau, peaks=True)
+    time_s = band_window_times(offsets, terms, hop, stride, frequency_sample_rate_hz)
+    return (f_b, offsets, time_s, engine.finish(power, was_numpy, False), engine.finish(index, was_numpy, False),
+            engine.finish(value, was_numpy, False), None if info is None else engine.finish(info, was_numpy, False))
 
 
 def fisher_from_semblance(semblance, sensors: int):

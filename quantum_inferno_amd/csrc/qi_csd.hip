@@ -32,12 +32,21 @@
 // wave: the body is qi_csd_wave.inc, included by both kernels, with the window's first segment and length where the panel's 0
 // and nseg stand -- a window's sums are k_cross_spectra's on the contiguous slice bit for bit, and what the panel holds past
 // the window's end is a zero operand.
+//
+// Bands (include/qi_bands.h).  k_cross_spectra_bands forms one matrix per (band, window of that band's own length, hop and
+// sample stride) of a constant-Q panel with the same wave and the same text: term k of a window is the sample first + k stride
+// where the other kernels have segment k, so a window's sums are k_cross_spectra's on the contiguous strided copy bit for
+// bit.  With a stride above 1 a lane's V operands are V separate 8- or 16-byte loads instead of one 32-byte run.
 #include "qi_host.hpp"
 #include "qi_device.hpp"   // kWave
 #include "qi_fft_reg.hpp"  // QI_LAUNCH_CHECK
 #include "qi_mfma.hpp"     // Mx
 #include "qi_array.h"
 #include "qi_windows.h"
+#include "qi_bands.h"
+
+#include <cstring>
+#include <vector>
 
 using namespace qi;
 using qi::host::align_up;
@@ -70,12 +79,24 @@ __device__ __forceinline__ void csd_load(const cplx<T>* __restrict__ row, bool o
     x[v] = in ? row[s + v] : mk<T>(T(0), T(0));
   }
 }
+// the same of a row whose segments lie `step` elements apart (the banded kernel's sample stride)
+template <typename T, bool CHECK>
+__device__ __forceinline__ void csd_load_strided(const cplx<T>* __restrict__ row, bool on, int64_t s, int64_t nseg, int64_t step,
+                                                 cplx<T>* x) {
+  constexpr int V = Mx<T>::V;
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const bool in = on && (!CHECK || s + v < nseg);
+    x[v] = in ? row[(s + v) * step] : mk<T>(T(0), T(0));
+  }
+}
 
 // groups of up to `nj` tiles in row ti of the upper triangle of a matrix of `ntile` tiles a side
 __host__ __device__ inline int64_t csd_row_groups(int64_t ntile, int64_t ti, int nj) { return (ntile - ti + nj - 1) / nj; }
 
 // NJ: tiles of one tile row a wave takes -- they share the A operand's loads; a matter of registers and traffic, not of results.
-// The wave's work is qi_csd_wave.inc, the text that the windowed kernel below shares.
+// The wave's work is qi_csd_wave.inc, the text that the windowed and the banded kernel below share.
+#define CSD_WAVE_LOAD(row, on, out) csd_load<T, CHECK>(row, on, s, len, out)
 template <typename T, int NJ>
 __global__ void __launch_bounds__(kCsdWaves* kWave) k_cross_spectra(const cplx<T>* __restrict__ Z, cplx<T>* __restrict__ S, CsdArgs a) {
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -109,6 +130,53 @@ __global__ void __launch_bounds__(kCsdWaves* kWave) k_cross_spectra_windows(cons
   // a table holds one weight per FORMED bin; without one the one-sided doubling goes by the absolute bin
   auto weight = [&] { return a.w.table ? a.w.table[fr] : csd_weight(a.w, f, a.nf); };
 #include "qi_csd_wave.inc"
+}
+
+// The banded form (include/qi_bands.h): matrix offset[b] + w of the band-major stack is the sum over the samples
+// w hop[b] + k stride[b], k < terms[b], of band band_first + b.  The device tables lie in scratch, put there in stream order
+// before the launch: offset [band_count + 1], terms, hop, stride [band_count] int64 and, where the caller gave weights,
+// weight [band_count] double.  The matrix index runs fastest in the grid and the four waves of a workgroup take four
+// consecutive matrices: adjacent windows of a band read overlapping samples of the same rows.  A wave finds its band by a
+// binary search of offset[]: the matrix index is wave-uniform, so the search runs on scalar loads and no lane diverges.
+struct CsdBandArgs {
+  CsdArgs p;  // C, nf = the panel's bands, nseg = the panel's samples n, ntile; nfb: workgroups per tile group = ceil(total / 4)
+  int64_t band_first, band_count, total;
+  const int64_t *offset, *terms, *hop, *stride;
+  const double* weight;
+};
+
+// Waves per SIMD the register allocator is held to, by precision and NJ (profiles/bands_kernel_resources.txt).  Every strided
+// load keeps a 64-bit address of its own where the contiguous kernels have one address and immediate offsets; held to these
+// counts the kernels stay out of scratch.  The banded launch takes at most two tiles a wave in either precision: at four the
+// float32 kernel would be down to one wave.
+template <typename T, int NJ>
+constexpr int csd_band_waves() {
+  return sizeof(T) == 8 ? (NJ == 1 ? 4 : 2) : (NJ == 1 ? 4 : 3);
+}
+
+template <typename T, int NJ>
+__global__ void __launch_bounds__(kCsdWaves* kWave) __attribute__((amdgpu_waves_per_eu(csd_band_waves<T, NJ>())))
+k_cross_spectra_bands(const cplx<T>* __restrict__ Z, cplx<T>* __restrict__ S,
+                                                                          CsdBandArgs ab) {
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const CsdArgs& a = ab.p;
+  const int64_t m = ((int64_t)blockIdx.x % a.nfb) * kCsdWaves + wv;
+  if (m >= ab.total) return;  // (the whole wave)
+  int64_t p = (int64_t)blockIdx.x / a.nfb;
+  // the band b with offset[b] <= m < offset[b + 1] (every band holds a window: the offsets ascend strictly)
+  int64_t lo = 0, hi = ab.band_count;
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (ab.offset[mid] <= m) lo = mid;
+    else hi = mid;
+  }
+  const int64_t b = lo, f = ab.band_first + b;
+  const int64_t first = (m - ab.offset[b]) * ab.hop[b], len = ab.terms[b], step = ab.stride[b];
+  auto weight = [&] { return ab.weight ? ab.weight[b] : 1.0; };
+#undef CSD_WAVE_LOAD
+#define CSD_WAVE_LOAD(row, on, out) csd_load_strided<T, CHECK>(row, on, s, len, step, out)
+#include "qi_csd_wave.inc"
+#undef CSD_WAVE_LOAD
 }
 
 // coherence[f][i][j] = |S_ij|^2 / (S_ii S_jj) of the finished matrices, the quotient in double; one segment: the identity's
@@ -168,6 +236,96 @@ int csd_windows_check(int dtype, int64_t C, int64_t nf, int64_t nseg, int64_t bi
   QI_REQUIRE(items < (1ll << 31) && nwin < (1ll << 31) / items, "request too large");
   QI_REQUIRE(C * nf < (1ll << 62) / nseg / 16, "panel too large");
   *nwin_out = nwin;
+  return QI_OK;
+}
+
+// what the banded entry points refuse of a geometry (include/qi_bands.h); the offsets of the band-major stack, into
+// offsets_out [band_count + 1] where there is one, and their total
+int csd_bands_layout(int64_t n, int64_t band_count, const int64_t* terms, const int64_t* hop, const int64_t* stride, int64_t* offsets_out,
+                     int64_t* total_out) {
+  QI_REQUIRE(n > 0 && band_count > 0, "bad band geometry: %lld samples, %lld bands", (long long)n, (long long)band_count);
+  QI_REQUIRE(terms && hop && stride, "null band table");
+  int64_t total = 0;
+  for (int64_t b = 0; b < band_count; ++b) {
+    QI_REQUIRE(terms[b] >= 1 && hop[b] >= 1 && stride[b] >= 1, "bad band table: band %lld has %lld terms, hop %lld, stride %lld",
+               (long long)b, (long long)terms[b], (long long)hop[b], (long long)stride[b]);
+    // span = (terms - 1) stride + 1 <= n, asked without forming a product that could overflow
+    QI_REQUIRE(terms[b] - 1 <= (n - 1) / stride[b], "window of band %lld (%lld terms every %lld) is longer than the panel's %lld samples",
+               (long long)b, (long long)terms[b], (long long)stride[b], (long long)n);
+    const int64_t nwin = (n - ((terms[b] - 1) * stride[b] + 1)) / hop[b] + 1;
+    QI_REQUIRE(total <= (1ll << 62) - nwin, "cross-spectral matrices of %lld bands are too large", (long long)band_count);
+    if (offsets_out) offsets_out[b] = total;
+    total += nwin;
+  }
+  if (offsets_out) offsets_out[band_count] = total;
+  *total_out = total;
+  return QI_OK;
+}
+
+// what the banded entry points refuse of a shape, and the number of matrices
+int csd_bands_check(int dtype, int64_t C, int64_t nb, int64_t n, int64_t band_first, int64_t band_count, const int64_t* terms,
+                    const int64_t* hop, const int64_t* stride, int64_t* total_out) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(C > 0 && nb > 0 && n > 0, "bad panel shape");
+  QI_REQUIRE(band_count > 0 && band_first >= 0 && band_first <= nb - band_count, "band range %lld + %lld leaves the panel's %lld bands",
+             (long long)band_first, (long long)band_count, (long long)nb);
+  int64_t total = 0;
+  QI_TRY(csd_bands_layout(n, band_count, terms, hop, stride, nullptr, &total));
+  QI_REQUIRE(C < (1ll << 20) && total <= (1ll << 40) / (C * C), "cross-spectral matrices of %lld windows x %lld^2 records are too large",
+             (long long)total, (long long)C);
+  const int64_t ntile = ceil_div(C, kCsdTile);
+  const int64_t items = ntile * (ntile + 1) / 2;  // (>= the tile groups; < 2^40)
+  QI_REQUIRE(items < (1ll << 31) && ceil_div(total, kCsdWaves) < (1ll << 31) / items, "request too large");
+  QI_REQUIRE(C * nb < (1ll << 62) / n / 16, "panel too large");
+  *total_out = total;
+  return QI_OK;
+}
+
+// words of the device tables: offset [band_count + 1] | terms | hop | stride | weight, band_count each
+size_t csd_bands_words(int64_t band_count) { return 5 * (size_t)band_count + 1; }
+size_t cross_spectra_bands_scratch(int dtype, int64_t C, int64_t band_count, int64_t total) {
+  return align_up(csd_bands_words(band_count) * 8) + align_up((size_t)total * C * C * 2 * elem_size(dtype));
+}
+
+// `tables`: the device tables in csd_bands_words' order (has_weight: the last of them is filled); terms: the HOST table,
+// for the coherence's one-term rule; `matrices`: the second region of the scratch
+template <typename T>
+int launch_cross_spectra_bands(const cplx<T>* Z, int64_t C, int64_t nb, int64_t n, int64_t band_first, int64_t band_count, int64_t total,
+                               const int64_t* tables, bool has_weight, const int64_t* terms, const int64_t* offsets, cplx<T>* csd,
+                               T* coherence, void* matrices, hipStream_t st) {
+  CsdBandArgs a{};
+  a.p.C = C;
+  a.p.nf = nb;
+  a.p.nseg = n;
+  a.p.ntile = ceil_div(C, kCsdTile);
+  a.p.nfb = ceil_div(total, kCsdWaves);
+  a.band_first = band_first;
+  a.band_count = band_count;
+  a.total = total;
+  a.offset = tables;
+  a.terms = a.offset + band_count + 1;
+  a.hop = a.terms + band_count;
+  a.stride = a.hop + band_count;
+  a.weight = has_weight ? reinterpret_cast<const double*>(a.stride + band_count) : nullptr;
+  cplx<T>* S = csd ? csd : static_cast<cplx<T>*>(matrices);
+  const int nj = a.p.ntile == 1 ? 1 : 2;  // (see csd_band_waves)
+  const dim3 grid((unsigned)(csd_groups(a.p.ntile, nj) * a.p.nfb));
+  if (nj == 1) k_cross_spectra_bands<T, 1><<<grid, kCsdWaves * kWave, 0, st>>>(Z, S, a);
+  else k_cross_spectra_bands<T, 2><<<grid, kCsdWaves * kWave, 0, st>>>(Z, S, a);
+  QI_LAUNCH_CHECK();
+  if (!coherence) return QI_OK;
+  // k_coherence's one-segment rule goes by the launch: one launch per run of bands on the same side of terms == 1 (one in
+  // all, unless bands of a single term are mixed with longer ones)
+  const int64_t CC = C * C;
+  for (int64_t b0 = 0; b0 < band_count;) {
+    int64_t b1 = b0 + 1;
+    while (b1 < band_count && (terms[b1] == 1) == (terms[b0] == 1)) ++b1;
+    const int64_t count = (offsets[b1] - offsets[b0]) * CC;
+    k_coherence<T><<<dim3((unsigned)ceil_div(count, 256)), 256, 0, st>>>(S + offsets[b0] * CC, coherence + offsets[b0] * CC, C, count,
+                                                                         terms[b0] == 1);
+    QI_LAUNCH_CHECK();
+    b0 = b1;
+  }
   return QI_OK;
 }
 
@@ -309,6 +467,51 @@ int qi_cross_spectra_windows(int dtype, int device, const void* Z, int64_t C, in
     using T = decltype(t);
     return launch_cross_spectra_windows<T>((const cplx<T>*)Z, C, nf, nseg, bin_first, bin_count, win, hop, w, (cplx<T>*)csd,
                                            (T*)coherence, matrices, st);
+  });
+}
+
+int64_t qi_cross_spectra_bands_layout(int64_t n, int64_t band_count, const int64_t* terms, const int64_t* hop, const int64_t* stride,
+                                      int64_t* offsets_out) {
+  int64_t total = 0;
+  QI_TRY(csd_bands_layout(n, band_count, terms, hop, stride, offsets_out, &total));
+  return total;
+}
+
+int64_t qi_cross_spectra_bands_scratch_bytes(int dtype, int64_t C, int64_t nb, int64_t n, int64_t band_first, int64_t band_count,
+                                             const int64_t* terms, const int64_t* hop, const int64_t* stride) {
+  int64_t total = 0;
+  QI_TRY(csd_bands_check(dtype, C, nb, n, band_first, band_count, terms, hop, stride, &total));
+  return (int64_t)cross_spectra_bands_scratch(dtype, C, band_count, total);
+}
+
+int qi_cross_spectra_bands(int dtype, int device, const void* Z, int64_t C, int64_t nb, int64_t n, int64_t band_first,
+                           int64_t band_count, const int64_t* terms, const int64_t* hop, const int64_t* stride, const double* weight,
+                           void* csd, void* coherence, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_REQUIRE(Z && scratch, "null argument");
+  QI_REQUIRE(csd || coherence, "nothing to produce");
+  int64_t total = 0;
+  QI_TRY(csd_bands_check(dtype, C, nb, n, band_first, band_count, terms, hop, stride, &total));
+  QI_TRY(require_scratch(scratch_bytes, (int64_t)cross_spectra_bands_scratch(dtype, C, band_count, total)));
+  QI_REQUIRE(aligned(Z, 2 * elem_size(dtype)) && aligned(csd, 2 * elem_size(dtype)) && aligned(coherence, elem_size(dtype)) &&
+                 aligned(scratch, 16),
+             "misaligned pointer");
+  // the device tables, assembled on the host: offset | terms | hop | stride | weight.  As qi_cross_spectra_windows' weights
+  // they ride in kernel arguments: stream-ordered, and the caller's arrays are free at return
+  const size_t bc = (size_t)band_count;
+  std::vector<int64_t> words(csd_bands_words(band_count));
+  QI_TRY(csd_bands_layout(n, band_count, terms, hop, stride, words.data(), &total));
+  std::memcpy(words.data() + bc + 1, terms, bc * 8);
+  std::memcpy(words.data() + 2 * bc + 1, hop, bc * 8);
+  std::memcpy(words.data() + 3 * bc + 1, stride, bc * 8);
+  if (weight) std::memcpy(words.data() + 4 * bc + 1, weight, bc * 8);
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  QI_TRY(qi::host::put_words(scratch, words.data(), (int64_t)(weight ? words.size() : words.size() - bc), st));
+  void* matrices = static_cast<char*>(scratch) + align_up(csd_bands_words(band_count) * 8);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_cross_spectra_bands<T>((const cplx<T>*)Z, C, nb, n, band_first, band_count, total, static_cast<const int64_t*>(scratch),
+                                         weight != nullptr, terms, words.data(), (cplx<T>*)csd, (T*)coherence, matrices, st);
   });
 }
 

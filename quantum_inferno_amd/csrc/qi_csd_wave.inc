@@ -1,11 +1,14 @@
-// The body of k_cross_spectra and k_cross_spectra_windows (qi_csd.hip), included inside both: what one wave does.  The text
-// is shared as text, not as a function: an inlined callee's __restrict__ scopes reorder k_cross_spectra's store epilogue,
-// and that kernel's device code is kept as it was.
+// The body of k_cross_spectra, k_cross_spectra_windows and k_cross_spectra_bands (qi_csd.hip), included inside all three:
+// what one wave does.  The text is shared as text, not as a function: an inlined callee's __restrict__ scopes reorder
+// k_cross_spectra's store epilogue, and that kernel's device code is kept as it was.
 // In scope: T, NJ; Z, S (the kernel's arguments); const CsdArgs& a (the panel); int64_t p (tile group, consumed), f (bin of
-// the panel), first, len (the segments summed: first .. first + len - 1), m (matrix of the stack S that is stored);
-// weight() -> double, the factor of the finished sums.
-// The multiply-add chains depend on `len` alone: segment first + k is the chain's k-th term wherever `first` lies, and a
-// segment at or past first + len is a zero operand whatever the panel holds there.
+// the panel), first, len (the segments summed: len of them from `first`), m (matrix of the stack S that is stored);
+// weight() -> double, the factor of the finished sums; and the macro CSD_WAVE_LOAD(row, on, out), the one place where the
+// kernels differ: csd_load of the contiguous segments first .. first + len - 1 for the first two -- after preprocessing their
+// text, and so their device code, is what it was before there was a third -- and csd_load_strided of the segments
+// first + k step for the banded kernel, with `step` in its scope.
+// The multiply-add chains depend on `len` alone: the k-th segment is the chain's k-th term wherever it lies in the row, and
+// a term at or past len is a zero operand whatever the panel holds there.
   using M = Mx<T>;
   using acc = typename M::acc;
   constexpr int V = M::V, STEP = 4 * V;  // segments of one iteration
@@ -38,11 +41,11 @@
   // one iteration's operands: V segments from `s` of the A record and of the B record of every tile of the group
   auto load = [&](auto check, int64_t s, cplx<T>* x, cplx<T>(*y)[V]) {
     constexpr bool CHECK = decltype(check)::value;
-    csd_load<T, CHECK>(zi, oni, s, len, x);
+    CSD_WAVE_LOAD(zi, oni, x);
 #pragma unroll
     for (int q = 0; q < NJ; ++q) {
       if (q >= nj) break;
-      if (q > 0 || !diag0) csd_load<T, CHECK>(zj[q], onj[q], s, len, y[q]);
+      if (q > 0 || !diag0) CSD_WAVE_LOAD(zj[q], onj[q], y[q]);
     }
   };
   auto tile_steps = [&](int q, const cplx<T>* x, const cplx<T>* y) {

@@ -718,6 +718,52 @@ def cross_spectra_windows(panel, window_segments, hop_segments=None, weight=None
     return finish(csd, was_numpy, False)
 
 
+def cross_spectra_bands(panel, terms, hop=None, stride=None, weight=None, bins=None, coherence=False):
+    """cross_spectra of a constant-Q panel [C, n_bands, n_time] (a CWT or Stockwell panel), every formed band in a window, hop
+    and sample stride of its own (qi_cross_spectra_bands, include/qi_bands.h): window w of band b sums the columns
+    w * hop[b] + k * stride[b], k = 0 .. terms[b] - 1; span[b] = (terms[b] - 1) * stride[b] + 1, n_windows[b] =
+    (n_time - span[b]) // hop[b] + 1, columns after a band's last window are ignored.  bins: (first, count) of the bands that
+    are formed, or None (all).  terms, hop, stride: [count] host integers, one per FORMED band; stride None: 1; hop None:
+    max(1, span // 2).  weight: [count] host values or None (1).  The matrices of all bands come from one launch as a ragged,
+    band-major stack: band b's windows are the rows offsets[b] .. offsets[b + 1] - 1, and row offsets[b] + w equals
+    cross_spectra(panel[:, first + b:first + b + 1, w * hop[b]:w * hop[b] + span[b]:stride[b]], weight[b:b + 1]) bit for bit.
+    -> (offsets [count + 1] np.int64, csd [total, C, C]), or (offsets, csd, coherence [total, C, C]) with coherence=True.
+    NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    z, was_numpy, rdtype = _matrix_stack(panel, "panel", "[C, bands, time]", square=False)
+    n_ch, n_b, n_t = z.shape
+    first, count = (0, n_b) if bins is None else (int(bins[0]), int(bins[1]))
+    if count < 1:
+        raise ValueError(f"bins must hold at least one band, got {bins}")
+
+    def table(a, what):
+        host, p = _lib.iarr(a)
+        if host.shape != (count,):
+            raise ValueError(f"{what} must hold one value per formed band ({count}), got shape {host.shape}")
+        return host, p
+
+    t_host, t_ptr = table(terms, "terms")
+    s_host, s_ptr = table(np.ones(count, dtype=np.int64) if stride is None else stride, "stride")
+    h_host, h_ptr = table(np.maximum(1, ((t_host - 1) * s_host + 1) // 2) if hop is None else hop, "hop")
+    w_host, w_ptr = (None, None)
+    if weight is not None:
+        w_host, w_ptr = _lib.darr(weight)
+        if w_host.shape != (count,):
+            raise ValueError(f"weight must hold one value per formed band ({count}), got shape {w_host.shape}")
+    dev, code = z.device, _lib.dtype_code(rdtype)
+    # (the library refuses what is wrong with the tables and the band range, before the outputs are shaped by them)
+    scratch, nbytes = _lib.scratch(lib.qi_cross_spectra_bands_scratch_bytes, dev, code, n_ch, n_b, n_t, first, count, t_ptr, h_ptr, s_ptr)
+    offsets = np.empty(count + 1, dtype=np.int64)
+    total = int(lib.qi_cross_spectra_bands_layout(n_t, count, t_ptr, h_ptr, s_ptr, offsets.ctypes.data_as(_lib._I64)))
+    csd = torch.empty((total, n_ch, n_ch), dtype=z.dtype, device=dev)
+    coh = torch.empty((total, n_ch, n_ch), dtype=rdtype, device=dev) if coherence else None
+    _lib.call(lib.qi_cross_spectra_bands, dev, code, dev.index, _lib.ptr(z), n_ch, n_b, n_t, first, count, t_ptr, h_ptr, s_ptr, w_ptr,
+              _lib.ptr(csd), _lib.ptr(coh), _lib.ptr(scratch), nbytes)
+    if coherence:
+        return offsets, finish(csd, was_numpy, False), finish(coh, was_numpy, False)
+    return offsets, finish(csd, was_numpy, False)
+
+
 def pair_lags(csd, *, bins=None, weighting="phat", halve_interior=True, normalize=True, upsample=1, max_lag=None, want_cc=False):
     """Time delays between every pair of records from their cross-spectral matrices (qi_pair_lags, include/qi_lags.h): the
     generalized cross-correlation r of pair (i, j), i < j, its first maximum inside +-max_lag and the three-point parabola

@@ -114,6 +114,13 @@ def cwt_complex_any_scale_pow2(
         # the reference's "morlet2" branch calls scipy.signal.cwt, removed from SciPy >= 1.15 which it requires
         raise ValueError(f"cwt_type {cwt_type!r} is not available; use 'fft'")
     sig, was_numpy, was_1d = engine.as_signal(sig_wf)
+    res = _cwt_panel(band_order_nth, sig, frequency_sample_rate_hz, dictionary_type)
+    time_cwt_s = np.arange(sig.shape[1]) / float(frequency_sample_rate_hz)
+    return res.frequency_hz, time_cwt_s, engine.finish(res.coef, was_numpy, was_1d, widen=True)
+
+
+def _cwt_panel(band_order_nth, sig, frequency_sample_rate_hz, dictionary_type="norm"):
+    """The order-N CWT of device records [C, n] on a borrowed plan -> its TfrResult (coef [C, B, n] on the device)."""
     n = sig.shape[1]
     fs = float(frequency_sample_rate_hz)
     key = ("styx_cwt", n, fs, float(band_order_nth), dictionary_type, sig.dtype, sig.device.index)
@@ -125,6 +132,33 @@ def cwt_complex_any_scale_pow2(
         return plan
 
     with engine.borrowed_plan(key, make) as plan:
-        res = plan.cwt(sig, coef=True)
-    time_cwt_s = np.arange(n) / fs
-    return res.frequency_hz, time_cwt_s, engine.finish(res.coef, was_numpy, was_1d, widen=True)
+        return plan.cwt(sig, coef=True)
+
+
+def wavelet_coherence_pow2(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    band_order_nth: float,
+    window_cycles: float,
+    hop_fraction: float = 0.5,
+    max_terms: int = 4096,
+    dictionary_type: str = "norm",
+):
+    """Smoothed wavelet coherence between the records of a batch [C x n], n a power of two: the magnitude-squared coherence
+    |S_ij|^2 / (S_ii S_jj) of the order-N CWT's cross-spectra, every band smoothed over a boxcar window of window_cycles of
+    its own periods (beamform.constant_q_windows: the window, its hop and the sample stride that keeps a window within
+    max_terms terms), all bands in one launch (engine.cross_spectra_bands).  Without smoothing the coherence of two
+    coefficients is identically 1: a band whose window holds a single term returns exactly that.  The smoothing is along
+    time only, not across scales.  Neither the panel nor the matrices leave the device.
+    :return: frequency_hz [count] of the bands whose window fits the record, offsets [count + 1] (band b's windows are the
+        rows offsets[b] .. offsets[b + 1] - 1), window_time_s [total] (the centre of every window), coherence [total x C x C]"""
+    from . import beamform
+
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    res = _cwt_panel(band_order_nth, sig, frequency_sample_rate_hz, dictionary_type)
+    f_hz = np.asarray(res.frequency_hz, dtype=np.float64)
+    bins, terms, hop, stride = beamform.constant_q_windows(f_hz, frequency_sample_rate_hz, sig.shape[1], window_cycles, hop_fraction,
+                                                           max_terms)
+    offsets, _, coh = engine.cross_spectra_bands(res.coef, terms, hop, stride, bins=bins, coherence=True)
+    time_s = beamform.band_window_times(offsets, terms, hop, stride, frequency_sample_rate_hz)
+    return f_hz[bins[0]:bins[0] + bins[1]], offsets, time_s, engine.finish(coh, was_numpy, False)

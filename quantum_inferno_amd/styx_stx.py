@@ -18,6 +18,12 @@ def stx_complex_any_scale_pow2(band_order_nth: float, sig_wf, frequency_sample_r
     :return: frequency_stx_hz [B], time_stx_s [n], tfr_stx [B x n] (or [channels x B x n])
     """
     sig, was_numpy, was_1d = engine.as_signal(sig_wf)
+    res = _stx_panel(band_order_nth, sig, frequency_sample_rate_hz)
+    return res.frequency_hz, np.arange(sig.shape[1]) / float(frequency_sample_rate_hz), engine.finish(res.coef, was_numpy, was_1d, widen=True)
+
+
+def _stx_panel(band_order_nth, sig, frequency_sample_rate_hz):
+    """The order-N Stockwell transform of device records [C, n] on a borrowed plan -> its TfrResult (coef [C, B, n])."""
     n = sig.shape[1]
     fs = float(frequency_sample_rate_hz)
     key = ("styx_stx", n, fs, float(band_order_nth), sig.dtype, sig.device.index)
@@ -29,8 +35,7 @@ def stx_complex_any_scale_pow2(band_order_nth: float, sig_wf, frequency_sample_r
         return plan
 
     with engine.borrowed_plan(key, make) as plan:
-        res = plan.stx(sig, coef=True)
-    return res.frequency_hz, np.arange(n) / fs, engine.finish(res.coef, was_numpy, was_1d, widen=True)
+        return plan.stx(sig, coef=True)
 
 
 def sig_pad_up_to_pow2(sig_wf: np.ndarray, n_fft: int, verbosity: bool = False):
