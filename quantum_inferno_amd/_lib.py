@@ -1,5 +1,5 @@
 """ctypes binding of libqi_tfr.so (include/qi_tfr.h, qi_array.h, qi_beam.h, qi_adaptive.h, qi_subspace.h, qi_steer.h, qi_windows.h,
-qi_lags.h, qi_bands.h).  There is no CPU fallback: if the
+qi_lags.h, qi_bands.h, qi_timebeam.h).  There is no CPU fallback: if the
 library is missing or no HIP device is present, every transform raises."""
 import ctypes as C
 import os
@@ -219,6 +219,15 @@ BAND_PROTOTYPES = {
     "qi_cross_spectra_bands": (_int, [_int, _int, _P, _i64, _i64, _i64, _i64, _i64, _I64, _I64, _I64, _D, _P, _P, _P, _i64, _P]),
 }
 
+# include/qi_timebeam.h (delay-and-sum in the time domain: beam traces, power and semblance per sliding window), one to one
+TIMEBEAM_PROTOTYPES = {
+    "qi_time_beam_power_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "qi_time_beam_power": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _P, _P, _i64, _i64, _i64, _i64, _int, _P, _P, _P, _P, _i64, _P]),
+    "qi_time_beam_traces": (_int, [_int, _int, _P, _i64, _i64, _P, _i64, _i64, _P, _P, _i64, _i64, _P, _P]),
+}
+TIMEBEAM_MAX_PHASES, TIMEBEAM_TAPS = 256, (1, 2, 4, 8, 16)  # QI_TIMEBEAM_MAX_PHASES; the bank's lengths
+TIMEBEAM_MAX_SHIFT, TIMEBEAM_LDS_MAX_SHIFT = 1 << 20, 1024  # QI_TIMEBEAM_MAX_SHIFT, QI_TIMEBEAM_LDS_MAX_SHIFT
+
 _lib = None
 
 
@@ -242,7 +251,7 @@ def load():
         )
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES, **SUBSPACE_PROTOTYPES,
-                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES, **LAG_PROTOTYPES, **BAND_PROTOTYPES}.items():
+                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES, **LAG_PROTOTYPES, **BAND_PROTOTYPES, **TIMEBEAM_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -9,7 +9,9 @@ include/qi_steer.h).  fk_timeline_pow2 runs the three power forms per sliding wi
 the CWT or Stockwell panel, every band in a window of so many of its own periods (constant_q_windows, band_window_times;
 engine.cross_spectra_bands' matrices, include/qi_bands.h).  Without a grid, slowness_from_lags
 fits the slowness vector to the pair delays of styx_fft.pair_lags_pow2 (the peaks of the generalized cross-correlations,
-include/qi_lags.h) and lag_closure is their consistency check.  The reference (quantum-inferno) has no
+include/qi_lags.h) and lag_closure is their consistency check.  In the time domain, with no matrix, segment or narrow-band
+assumption: fisher_timeline, the sliding delay-and-sum F detector, and beam_traces_delay, beam waveforms for delays of any
+length (engine.time_beam_power and engine.time_beam_traces, include/qi_timebeam.h).  The reference (quantum-inferno) has no
 array processing; the conventions below are the usual ones of infrasound and seismic array work.
 
 Geometry.  Positions are [C, 2] metres (x east, y north).  A slowness vector s [s/m] points the way the wave TRAVELS; a
@@ -17,7 +19,8 @@ plane wave reaches sensor i later by tau_i = s . r_i seconds.  The back azimuth 
 -s in degrees clockwise from north; the trace velocity is 1 / |s|.
 
 The helpers are host code on torch float64; only plane_wave_delays' result and the work of fk_power_pow2,
-capon_power_pow2, music_power_pow2, fk_timeline_pow2, fk_timeline_cq, beam_stft_pow2 and beam_traces_tukey are on the device.
+capon_power_pow2, music_power_pow2, fk_timeline_pow2, fk_timeline_cq, beam_stft_pow2, beam_traces_tukey, fisher_timeline and
+beam_traces_delay are on the device.
 """
 import numpy as np
 import torch
@@ -514,7 +517,8 @@ def beam_traces_tukey(
     short against the segment (a plane wave across 60 m at 800 Hz, delays of up to 53 samples: 5 % relative RMS error at
     segments of 1024 with overlap 768 -- the records' own noise floor is 4.5 % --, 16 % at 256 / 128).  With few segments
     Capon cancels part of the signal (13 % in the same case at loading 0.1, 19 segments).  Zero delays give the mean of the
-    records.  Nothing but the traces and info leaves the device.
+    records.  Nothing but the traces and info leaves the device.  For delays that are not short against a segment -- an
+    array of 1 km has hundreds of samples -- beam_traces_delay shifts the records themselves: any delay length, no segment.
     :return: timestamps [samples] (istft_tukey's: up to the last window index), traces [K x samples] real, info: None
         (bartlett) or [bins] int32 as beam_stft_pow2 returns it"""
     sig, was_numpy, _ = engine.as_signal(sig_wf)
@@ -524,3 +528,69 @@ def beam_traces_tukey(
     beams = engine.beam_steer(panel, weights)
     timestamps, traces = short_time_fft.istft_tukey(beams, sample_rate_hz, tukey_alpha, segment_length, overlap_length, "magnitude")
     return timestamps, engine.finish(traces, was_numpy, False), (None if info is None else engine.finish(info, was_numpy, False))
+
+
+def _quantized_plane_waves(sig, sample_rate_hz, positions_m, slowness, phases, taps, beta):
+    """The tables of fisher_timeline and beam_traces_delay: the plane-wave delays of every slowness vector for the records
+    `sig` [C, n] on the device, quantised to 1 / phases of a sample, and the interpolator bank in the records' precision."""
+    tau = plane_wave_delays(positions_m, slowness, sig.device)
+    if tau.shape[1] != sig.shape[0]:
+        raise ValueError(f"{tau.shape[1]} positions for {sig.shape[0]} records")
+    shift, phase, reach = engine.quantize_delays(tau, sample_rate_hz, phases, device=sig.device)
+    return shift, phase, engine.delay_bank(phases, taps, beta, sig.dtype), reach
+
+
+def fisher_timeline(
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    positions_m,
+    slowness,
+    window_points: int,
+    hop_points: int = None,
+    phases: int = 64,
+    taps: int = 8,
+    beta: float = 5.0,
+    band_hz=None,
+):
+    """The time-domain F detector of the records of one array [C x n]: per sliding window of window_points samples
+    (hop_points apart, window_points // 2 by default) and slowness vector [G, 2] the records are delayed by
+    plane_wave_delays -- whole samples plus 1 / phases of a sample through a Kaiser-windowed sinc bank of `taps` taps
+    (engine.delay_bank, engine.quantize_delays) --, summed, and the beam's power is held against the total:
+    semblance = sum_t (sum_i y_i)^2 / (C sum_t sum_i y_i^2) (engine.time_beam_power).  No cross-spectral matrix and no Welch
+    panel stand between the records and the value: a window may be as short as one sample, a delay as long as the record,
+    and nothing assumes a narrow band.  band_hz: (low, high) passes the records through the zero-phase Butterworth band-pass
+    of utilities.picker.apply_bandpass on the device first (they become float64).  fisher is the F ratio of the best
+    slowness, fisher_from_semblance(peak_value, C); back_azimuth_and_velocity(slowness[peak_index]) completes the detection
+    timeline.  Content near Nyquist is attenuated by the interpolator (see beam_traces_delay).
+    :return: time_s [nwin] (window centres, host float64), semblance [nwin x G], peak_index [nwin] int64, peak_value [nwin],
+        fisher [nwin].  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    if band_hz is not None:
+        from .utilities import picker
+
+        sig = picker.apply_bandpass(sig, (float(band_hz[0]), float(band_hz[1])), frequency_sample_rate_hz)
+    win = int(window_points)
+    hop = max(win // 2, 1) if hop_points is None else int(hop_points)
+    shift, phase, bank, reach = _quantized_plane_waves(sig, frequency_sample_rate_hz, positions_m, slowness, phases, taps, beta)
+    semblance, index, value = engine.time_beam_power(sig, shift, phase, bank, win, hop, reach, normalize=True, peaks=True)
+    time_s = (np.arange(semblance.shape[0], dtype=np.float64) * hop + 0.5 * (win - 1)) / float(frequency_sample_rate_hz)
+    fisher = fisher_from_semblance(value, sig.shape[0])
+    return (time_s, engine.finish(semblance, was_numpy, False), engine.finish(index, was_numpy, False),
+            engine.finish(value, was_numpy, False), engine.finish(fisher, was_numpy, False))
+
+
+def beam_traces_delay(sig_wf, sample_rate_hz: float, positions_m, slowness, phases: int = 64, taps: int = 8, beta: float = 5.0):
+    """Beam waveforms of the records of one array [C x n], one real trace per slowness vector [K, 2]: delay-and-sum in the
+    time domain (engine.time_beam_traces).  Record i is read at t + tau_i, tau = plane_wave_delays -- a shift of the record
+    itself by whole samples, zeros beyond its ends, plus 1 / phases of a sample through a Kaiser-windowed sinc bank of `taps`
+    taps (engine.delay_bank) -- and the mean over the sensors is the trace.  Where it beats beam_traces_tukey: any delay
+    length and no segment -- nothing is circular, so an aperture of hundreds of samples costs no more than one of three, and
+    the plane-wave case of that docstring (delays of up to 53 samples) comes out at the records' own noise floor (4.5 %) once
+    its content lies below half of Nyquist.  Where it does not: the interpolator is short, and content near Nyquist is
+    attenuated and slightly dispersed -- on full-band white records the same trace is 15.8 % from the source with 8 taps
+    and 12.0 % with 16, against 5 % for beam_traces_tukey at segments of 1024; band-limit first, or raise `taps`.  Only
+    delay-and-sum: MVDR weights stay with beam_traces_tukey.  Zero delays give the mean of the records.
+    :return: traces [K x n] real.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    sig, was_numpy, _ = engine.as_signal(sig_wf)
+    shift, phase, bank, reach = _quantized_plane_waves(sig, sample_rate_hz, positions_m, slowness, phases, taps, beta)
+    return engine.finish(engine.time_beam_traces(sig, shift, phase, bank, reach), was_numpy, False)

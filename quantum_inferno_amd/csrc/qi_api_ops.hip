@@ -4,6 +4,7 @@
 #include "qi_array.h"
 #include "qi_windows.h"
 #include "qi_lags.h"
+#include "qi_timebeam.h"
 
 using namespace qi;
 using qi::host::align_up;
@@ -489,6 +490,76 @@ int qi_pair_lags(int dtype, int device, const void* csd, int64_t nstack, int64_t
     using T = decltype(t);
     return launch_pair_lags<T>((const cplx<T>*)csd, nstack, C, nfft, bin_lo, bin_hi, weighting, halve_interior, normalize, upsample,
                                max_lag, (T*)cc, (T*)peak_lag, (T*)peak_value, st);
+  });
+}
+
+// ---- delay-and-sum in the time domain (include/qi_timebeam.h) ------------------------------------------------------------
+// what both calls and the size query refuse of the records, the bank and the delay rows (`rows`: G or K)
+static int time_beam_shape_check(int dtype, int64_t C, int64_t n, int64_t P, int64_t T, int64_t rows, int64_t max_shift) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(C >= 2 && C <= QI_BEAM_MAX_SENSORS, "%lld sensors: 2 to %d", (long long)C, QI_BEAM_MAX_SENSORS);
+  QI_REQUIRE(P >= 1 && P <= QI_TIMEBEAM_MAX_PHASES, "%lld phases in the bank: 1 to %d", (long long)P, QI_TIMEBEAM_MAX_PHASES);
+  QI_REQUIRE(T == 1 || T == 2 || T == 4 || T == 8 || T == 16, "%lld taps: 1, 2, 4, 8 or 16", (long long)T);
+  QI_REQUIRE(n >= 1 && rows >= 1, "bad shape: %lld samples, %lld delay rows", (long long)n, (long long)rows);
+  QI_REQUIRE(n <= (1ll << 40) && rows <= (1ll << 40), "request too large");
+  QI_REQUIRE(max_shift >= 0 && max_shift <= QI_TIMEBEAM_MAX_SHIFT, "bad max_shift %lld (0 .. %d)", (long long)max_shift,
+             QI_TIMEBEAM_MAX_SHIFT);
+  return QI_OK;
+}
+
+static int time_beam_power_check(int dtype, int64_t C, int64_t n, int64_t P, int64_t T, int64_t G, int64_t win, int64_t hop,
+                                 int64_t max_shift) {
+  QI_TRY(time_beam_shape_check(dtype, C, n, P, T, G, max_shift));
+  QI_REQUIRE(win >= 1 && win <= n, "bad window of %lld samples in a record of %lld", (long long)win, (long long)n);
+  QI_REQUIRE(hop >= 1, "bad hop %lld", (long long)hop);
+  const TimeBeamUnits u = time_beam_units(n, win, hop);
+  QI_REQUIRE((double)u.count * (double)time_beam_row_blocks(G) < 0x1p31 && u.nwin < (1ll << 31) &&
+                 (double)u.count * (double)G < 0x1p40,
+             "request too large");
+  return QI_OK;
+}
+
+int64_t qi_time_beam_power_scratch_bytes(int dtype, int64_t C, int64_t n, int64_t P, int64_t T, int64_t G, int64_t win,
+                                         int64_t hop, int64_t max_shift) {
+  QI_TRY(time_beam_power_check(dtype, C, n, P, T, G, win, hop, max_shift));
+  return (int64_t)align_up((size_t)time_beam_units(n, win, hop).count * (size_t)G * 2 * elem_size(dtype));
+}
+
+int qi_time_beam_power(int dtype, int device, const void* x, int64_t C, int64_t n, const void* taps, int64_t P, int64_t T,
+                       const void* shift, const void* phase, int64_t G, int64_t max_shift, int64_t win, int64_t hop,
+                       int normalize, void* power, void* peak_index, void* peak_value, void* scratch, int64_t scratch_bytes,
+                       qi_stream stream) {
+  QI_REQUIRE(x && taps && shift && phase && scratch, "null argument");
+  QI_REQUIRE(power || peak_index || peak_value, "nothing to produce");
+  QI_TRY(time_beam_power_check(dtype, C, n, P, T, G, win, hop, max_shift));
+  QI_TRY(require_scratch(scratch_bytes, qi_time_beam_power_scratch_bytes(dtype, C, n, P, T, G, win, hop, max_shift)));
+  const size_t e = elem_size(dtype);
+  QI_REQUIRE(aligned(x, e) && aligned(taps, e) && aligned(shift, 4) && aligned(phase, 4) && aligned(power, e) &&
+                 aligned(peak_index, 8) && aligned(peak_value, e) && aligned(scratch, 16),
+             "misaligned pointer");
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  return by_dtype(dtype, [&](auto t) -> int {
+    using R = decltype(t);
+    return launch_time_beam_power<R>((const R*)x, C, n, (const R*)taps, P, T, (const int32_t*)shift, (const int32_t*)phase, G,
+                                     max_shift, win, hop, normalize, (R*)power, (int64_t*)peak_index, (R*)peak_value, (R*)scratch, st);
+  });
+}
+
+int qi_time_beam_traces(int dtype, int device, const void* x, int64_t C, int64_t n, const void* taps, int64_t P, int64_t T,
+                        const void* shift, const void* phase, int64_t K, int64_t max_shift, void* out, qi_stream stream) {
+  QI_REQUIRE(x && taps && shift && phase, "null argument");
+  QI_REQUIRE(out, "out is null: nothing to produce");
+  QI_TRY(time_beam_shape_check(dtype, C, n, P, T, K, max_shift));
+  QI_REQUIRE((double)time_beam_chunks(n) * (double)time_beam_row_blocks(K) < 0x1p31, "request too large");
+  const size_t e = elem_size(dtype);
+  QI_REQUIRE(aligned(x, e) && aligned(taps, e) && aligned(shift, 4) && aligned(phase, 4) && aligned(out, e), "misaligned pointer");
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  return by_dtype(dtype, [&](auto t) -> int {
+    using R = decltype(t);
+    return launch_time_beam_traces<R>((const R*)x, C, n, (const R*)taps, P, T, (const int32_t*)shift, (const int32_t*)phase, K,
+                                      max_shift, (R*)out, st);
   });
 }
 

@@ -229,6 +229,23 @@ int launch_pair_lags(const cplx<T>* csd, int64_t nstack, int64_t C, int64_t nfft
                      int halve_interior, int normalize, int64_t upsample, int64_t max_lag, T* cc, T* peak_lag, T* peak_value,
                      hipStream_t st);
 
+// delay-and-sum in the time domain (qi_timebeam.hip; include/qi_timebeam.h); the arguments are the checked ones of
+// qi_time_beam_power and qi_time_beam_traces.  How the power call cuts the record: `count` units of `len` samples a hop
+// apart, window w the sum of the units w .. w + per_window - 1; its scratch `sums` is [count][G][2] of the records' type.
+struct TimeBeamUnits {
+  int64_t nwin, len, per_window, count;
+};
+TimeBeamUnits time_beam_units(int64_t n, int64_t win, int64_t hop);
+int64_t time_beam_row_blocks(int64_t rows);  // workgroups across the delay rows
+int64_t time_beam_chunks(int64_t n);         // workgroups of the traces call along time
+template <typename T>
+int launch_time_beam_power(const T* x, int64_t C, int64_t n, const T* taps, int64_t P, int64_t T_taps, const int32_t* shift,
+                           const int32_t* phase, int64_t G, int64_t max_shift, int64_t win, int64_t hop, int normalize, T* power,
+                           int64_t* peak_index, T* peak_value, T* sums, hipStream_t st);
+template <typename T>
+int launch_time_beam_traces(const T* x, int64_t C, int64_t n, const T* taps, int64_t P, int64_t T_taps, const int32_t* shift,
+                            const int32_t* phase, int64_t K, int64_t max_shift, T* out, hipStream_t st);
+
 template <typename T>
 int launch_power_marginals(const T* P, int64_t C, int64_t B, int64_t n, T* power_time, double* part_band,
                            double* part_stat, hipStream_t st);

@@ -807,6 +807,117 @@ def pair_lags(csd, *, bins=None, weighting="phat", halve_interior=True, normaliz
     return tuple(finish(t, was_numpy, not stacked) for t in (peak_lag, peak_value, cc))
 
 
+def delay_bank(phases=64, taps=8, beta=5.0, dtype=torch.float32):
+    """The polyphase fractional-delay bank of time_beam_power and time_beam_traces: row p of [phases, taps] interpolates a
+    record at the fraction p / phases of a sample past the tap c = (taps - 1) // 2 -- a Kaiser-windowed sinc.  With
+    k = m - c, u = k - p / P and a = u / (T / 2): h = sinc(u) I0(beta sqrt(1 - a^2)) / I0(beta) for |a| <= 1, else 0; every row
+    is divided by its sum (unit gain at 0 Hz).  Row 0 is the exact unit impulse at m = c; taps = 1 requires phases = 1 and is
+    [[1]] (whole-sample delays).  Built on the host in float64 with NumPy alone, then rounded to `dtype`.
+    -> [phases, taps] tensor of float32 or float64 on the host (the calls take it to the records' device)."""
+    p_count, t_count = int(phases), int(taps)
+    if t_count not in _lib.TIMEBEAM_TAPS or not 1 <= p_count <= _lib.TIMEBEAM_MAX_PHASES:
+        raise ValueError(f"delay_bank takes taps of {_lib.TIMEBEAM_TAPS} and 1 .. {_lib.TIMEBEAM_MAX_PHASES} phases, got {taps} and {phases}")
+    if t_count == 1 and p_count != 1:
+        raise ValueError("a bank of one tap delays by whole samples: it has one phase")
+    rdtype = _real_dtype(dtype)
+    centre = (t_count - 1) // 2
+    k = (np.arange(t_count) - centre).astype(np.float64)[None, :]
+    u = k - (np.arange(p_count).astype(np.float64) / p_count)[:, None]
+    a = u / (t_count / 2.0)
+    inside = np.abs(a) <= 1.0
+    h = np.where(inside, np.sinc(u) * np.i0(float(beta) * np.sqrt(np.where(inside, 1.0 - a * a, 0.0))) / np.i0(float(beta)), 0.0)
+    h = h / h.sum(axis=1, keepdims=True)
+    h[0] = 0.0
+    h[0, centre] = 1.0
+    return torch.from_numpy(np.ascontiguousarray(h)).to(rdtype)
+
+
+def quantize_delays(delays_s, sample_rate_hz, phases, device=None):
+    """Delays in seconds [rows, C] (NumPy or tensor; plane_wave_delays' result) as whole samples and bank phases:
+    q = floor(tau rate P + 0.5), shift = q // P, phase = q mod P (floor division: 0 <= phase < P for negative delays too).
+    The beam of time_beam_power / time_beam_traces aligns with x_i[t + tau_i]: a plane wave that reaches sensor i later by
+    tau_i = plane_wave_delays(...) adds coherently at its own slowness, the sign convention of beamform.
+    -> (shift [rows, C] int32, phase [rows, C] int32, both on the device; max_shift: the largest |shift|, a Python int)."""
+    tau = delays_s.detach().cpu().to(torch.float64).numpy() if isinstance(delays_s, torch.Tensor) else np.asarray(delays_s, dtype=np.float64)
+    p_count = int(phases)
+    if tau.ndim != 2 or tau.size == 0 or not np.isfinite(tau).all() or p_count < 1:
+        raise ValueError(f"delays_s must be a finite non-empty [rows, C] and phases positive, got shape {tuple(tau.shape)} and {phases}")
+    q = np.floor(tau * float(sample_rate_hz) * p_count + 0.5)
+    shift = np.floor_divide(q, p_count)
+    phase = q - shift * p_count
+    if np.abs(shift).max() >= 2.0 ** 31:
+        raise ValueError("a delay of more than 2^31 samples")
+    if device is None:
+        device = delays_s.device if isinstance(delays_s, torch.Tensor) and delays_s.is_cuda else default_device()
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(device)  # noqa: E731
+    return to_dev(shift), to_dev(phase), int(np.abs(shift).max())
+
+
+def _time_beam_inputs(sig, shift, phase, bank, max_shift):
+    """What time_beam_power and time_beam_traces share -> (records [C, n] on the device, was_numpy, shift, phase, bank on
+    that device and contiguous, rows, phases, taps, max_shift)."""
+    x, was_numpy, _ = as_signal(sig)
+    x = x.contiguous()
+    dev = x.device
+    tables = []
+    for name, t in (("shift", shift), ("phase", phase)):
+        t = torch.from_numpy(np.ascontiguousarray(t)) if not isinstance(t, torch.Tensor) else t
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != x.shape[0] or t.dtype.is_floating_point or t.dtype.is_complex:
+            raise ValueError(f"{name} must be whole numbers [rows, {x.shape[0]}], got {t.dtype} {tuple(t.shape)}")
+        tables.append(t.to(dev).to(torch.int32).contiguous())
+    if tables[0].shape != tables[1].shape:
+        raise ValueError(f"shift {tuple(tables[0].shape)} and phase {tuple(tables[1].shape)} differ in shape")
+    h = torch.from_numpy(np.ascontiguousarray(bank)) if not isinstance(bank, torch.Tensor) else bank
+    if h.dim() != 2 or 0 in h.shape:
+        raise ValueError(f"bank must be [phases, taps], got shape {tuple(h.shape)}")
+    h = h.to(dev).to(x.dtype).contiguous()
+    return x, was_numpy, tables[0], tables[1], h, tables[0].shape[0], h.shape[0], h.shape[1], int(max_shift)
+
+
+def time_beam_power(sig, shift, phase, bank, window_points, hop_points, max_shift, normalize=True, peaks=True):
+    """Delay-and-sum power of the records of an array per sliding window and delay row, in the time domain
+    (qi_time_beam_power, include/qi_timebeam.h): y[g, i, t] = sum_m bank[phase[g, i], m] x[i, t + shift[g, i] + m - c],
+    c = (taps - 1) // 2, x zero outside the record; b = sum_i y; over the window t in [w hop, w hop + win):
+    normalize=False -> sum b^2 / (C^2 win), the mean square of the beam; normalize=True -> sum b^2 / (C sum_i sum y^2), the
+    semblance in [0, 1] (NaN where the delayed records are all zero).  sig: [C, n] float32 / float64, 2 <= C <= 64; shift,
+    phase: [G, C] whole numbers (quantize_delays); bank: [P, T] (delay_bank); max_shift: the largest |shift| the call has
+    to take -- a row beyond it, or with a phase outside 0 .. P - 1, is NaN.  Any delay length: up to max_shift = 1024 the
+    records are staged in LDS, beyond that the same arithmetic reads through L2 (the same bits, slower).
+    -> power [nwin, G], or (power, peak_index [nwin] int64, peak_value [nwin]) with peaks=True: np.argmax of every window's
+    row and that entry.  nwin = 1 + (n - win) // hop.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    x, was_numpy, sh, ph, h, n_rows, n_phase, n_taps, reach = _time_beam_inputs(sig, shift, phase, bank, max_shift)
+    n_ch, n = x.shape
+    win, hop = int(window_points), int(hop_points)
+    dev, code = x.device, _lib.dtype_code(x.dtype)
+    # (the library refuses what is wrong with the shape, before the outputs are shaped by it)
+    scratch, nbytes = _lib.scratch(lib.qi_time_beam_power_scratch_bytes, dev, code, n_ch, n, n_phase, n_taps, n_rows, win, hop, reach)
+    n_win = 1 + (n - win) // hop
+    power = torch.empty((n_win, n_rows), dtype=x.dtype, device=dev)
+    index = torch.empty(n_win, dtype=torch.int64, device=dev) if peaks else None
+    value = torch.empty(n_win, dtype=x.dtype, device=dev) if peaks else None
+    _lib.call(lib.qi_time_beam_power, dev, code, dev.index, _lib.ptr(x), n_ch, n, _lib.ptr(h), n_phase, n_taps, _lib.ptr(sh), _lib.ptr(ph),
+              n_rows, reach, win, hop, int(bool(normalize)), _lib.ptr(power), _lib.ptr(index), _lib.ptr(value), _lib.ptr(scratch), nbytes)
+    if not peaks:
+        return finish(power, was_numpy, False)
+    return tuple(finish(t, was_numpy, False) for t in (power, index, value))
+
+
+def time_beam_traces(sig, shift, phase, bank, max_shift):
+    """Delay-and-sum beam traces of the records of an array (qi_time_beam_traces, include/qi_timebeam.h): traces[k, t] =
+    (1 / C) sum_i sum_m bank[phase[k, i], m] x[i, t + shift[k, i] + m - c] for every sample of the record, x zero outside
+    it; the arguments are time_beam_power's.  One launch; no [K, C, n] intermediate exists.  Zero delays and the impulse
+    bank give the mean of the records.  -> traces [K, n].  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    x, was_numpy, sh, ph, h, n_rows, n_phase, n_taps, reach = _time_beam_inputs(sig, shift, phase, bank, max_shift)
+    n_ch, n = x.shape
+    dev, code = x.device, _lib.dtype_code(x.dtype)
+    out = torch.empty((n_rows, n), dtype=x.dtype, device=dev)
+    _lib.call(lib.qi_time_beam_traces, dev, code, dev.index, _lib.ptr(x), n_ch, n, _lib.ptr(h), n_phase, n_taps, _lib.ptr(sh), _lib.ptr(ph),
+              n_rows, reach, _lib.ptr(out))
+    return finish(out, was_numpy, False)
+
+
 def _delay_grid_form(name, matrices, what, frequency_hz, delays_s, bands, peaks, *form_args, form_first=()):
     """What beam_power, capon_power and music_power share: the checks of the stack `what`, of frequency_hz, delays_s and bands,
     the scratch of qi_<name>_scratch_bytes, the outputs, the call of qi_<name> (form_first: what it takes between nf and
