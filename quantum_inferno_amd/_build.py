@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libqi_tfr.so")
-SOURCES = ["qi_api.hip", "qi_api_ops.hip", "qi_host_util.hip", "qi_plan_build.hip", "qi_run.hip", "qi_kernels.hip", "qi_native.hip", "qi_block.hip", "qi_zoom.hip", "qi_shannon1d.hip", "qi_stft_hipfft.hip", "qi_stft_fused.hip", "qi_zoom64.hip", "qi_pool.hip", "qi_small.hip", "qi_filter.hip", "qi_peaks.hip", "qi_resample.hip", "qi_calculus.hip", "qi_synth.hip", "qi_csd.hip", "qi_beam.hip", "qi_whiten.hip", "qi_eigh.hip", "qi_steer.hip", "qi_lags.hip", "qi_timebeam.hip"]
+SOURCES = ["qi_api.hip", "qi_api_ops.hip", "qi_host_util.hip", "qi_plan_build.hip", "qi_run.hip", "qi_kernels.hip", "qi_native.hip", "qi_block.hip", "qi_zoom.hip", "qi_shannon1d.hip", "qi_stft_hipfft.hip", "qi_stft_fused.hip", "qi_zoom64.hip", "qi_pool.hip", "qi_small.hip", "qi_filter.hip", "qi_peaks.hip", "qi_resample.hip", "qi_calculus.hip", "qi_synth.hip", "qi_csd.hip", "qi_beam.hip", "qi_whiten.hip", "qi_eigh.hip", "qi_steer.hip", "qi_lags.hip", "qi_timebeam.hip", "qi_squeeze.hip"]
 ARCH = "gfx950"
 # the FFT kernels lose ~10 % to the register shuffles of SLP-packed v_pk_* arithmetic (no throughput gain on gfx950)
 PER_FILE_FLAGS = {"qi_native.hip": ("-fno-slp-vectorize",), "qi_block.hip": ("-fno-slp-vectorize",), "qi_zoom.hip": ("-fno-slp-vectorize",),
@@ -29,7 +29,9 @@ PER_FILE_FLAGS = {"qi_native.hip": ("-fno-slp-vectorize",), "qi_block.hip": ("-f
                   # the argument of every transcendental is NumPy's bit for bit, and so is every formula without one
                   "qi_synth.hip": ("-ffp-contract=off",),
                   # the order and the rounding of every sum are the header's contract: the fused multiply-adds are written out
-                  "qi_timebeam.hip": ("-ffp-contract=off",)}
+                  "qi_timebeam.hip": ("-ffp-contract=off",),
+                  # a product is rounded before it is added, and the fused call equals the two-call composition bit for bit
+                  "qi_squeeze.hip": ("-ffp-contract=off",)}
 
 
 def torch_lib_dir():
@@ -50,6 +52,7 @@ def needs_build():
              os.path.join(ROOT, "include", "qi_adaptive.h"), os.path.join(ROOT, "include", "qi_subspace.h"), os.path.join(ROOT, "include", "qi_steer.h"),
              os.path.join(ROOT, "include", "qi_windows.h"), os.path.join(ROOT, "include", "qi_lags.h"),
              os.path.join(ROOT, "include", "qi_bands.h"), os.path.join(ROOT, "include", "qi_timebeam.h"),
+             os.path.join(ROOT, "include", "qi_squeeze.h"),
              os.path.abspath(__file__)]  # (the flags live in this file)
     return any(os.path.getmtime(d) > t for d in deps)
 

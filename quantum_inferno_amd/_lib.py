@@ -1,5 +1,5 @@
 """ctypes binding of libqi_tfr.so (include/qi_tfr.h, qi_array.h, qi_beam.h, qi_adaptive.h, qi_subspace.h, qi_steer.h, qi_windows.h,
-qi_lags.h, qi_bands.h, qi_timebeam.h).  There is no CPU fallback: if the
+qi_lags.h, qi_bands.h, qi_timebeam.h, qi_squeeze.h).  There is no CPU fallback: if the
 library is missing or no HIP device is present, every transform raises."""
 import ctypes as C
 import os
@@ -228,6 +228,15 @@ TIMEBEAM_PROTOTYPES = {
 TIMEBEAM_MAX_PHASES, TIMEBEAM_TAPS = 256, (1, 2, 4, 8, 16)  # QI_TIMEBEAM_MAX_PHASES; the bank's lengths
 TIMEBEAM_MAX_SHIFT, TIMEBEAM_LDS_MAX_SHIFT = 1 << 20, 1024  # QI_TIMEBEAM_MAX_SHIFT, QI_TIMEBEAM_LDS_MAX_SHIFT
 
+# include/qi_squeeze.h (synchrosqueezing: instantaneous frequencies of a panel, reassignment to frequency bins), one to one
+SQUEEZE_PROTOTYPES = {
+    "qi_tfr_squeeze_scratch_bytes": (_i64, [_int, _i64, _i64, _i64, _i64]),
+    "qi_tfr_ifreq": (_int, [_int, _int, _P, _i64, _i64, _i64, _D, _dbl, _dbl, _P, _P, _i64, _P]),
+    "qi_tfr_squeeze": (_int, [_int, _int, _P, _P, _i64, _i64, _i64, _D, _i64, _D, _P, _P, _i64, _P]),
+    "qi_tfr_synchrosqueeze": (_int, [_int, _int, _P, _i64, _i64, _i64, _D, _dbl, _dbl, _D, _i64, _D, _P, _P, _i64, _P]),
+}
+SQUEEZE_MAX_BINS, SQUEEZE_MAX_BANDS, SQUEEZE_TILE = 4096, 65536, 256  # QI_SQUEEZE_MAX_BINS, QI_SQUEEZE_MAX_BANDS, QI_SQUEEZE_TILE
+
 _lib = None
 
 
@@ -251,7 +260,8 @@ def load():
         )
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **ARRAY_PROTOTYPES, **BEAM_PROTOTYPES, **ADAPTIVE_PROTOTYPES, **SUBSPACE_PROTOTYPES,
-                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES, **LAG_PROTOTYPES, **BAND_PROTOTYPES, **TIMEBEAM_PROTOTYPES}.items():
+                               **STEER_PROTOTYPES, **WINDOW_PROTOTYPES, **LAG_PROTOTYPES, **BAND_PROTOTYPES, **TIMEBEAM_PROTOTYPES,
+                               **SQUEEZE_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -5,6 +5,7 @@
 #include "qi_windows.h"
 #include "qi_lags.h"
 #include "qi_timebeam.h"
+#include "qi_squeeze.h"
 
 using namespace qi;
 using qi::host::align_up;
@@ -561,6 +562,123 @@ int qi_time_beam_traces(int dtype, int device, const void* x, int64_t C, int64_t
     return launch_time_beam_traces<R>((const R*)x, C, n, (const R*)taps, P, T, (const int32_t*)shift, (const int32_t*)phase, K,
                                       max_shift, (R*)out, st);
   });
+}
+
+// ---- synchrosqueezing (include/qi_squeeze.h) -------------------------------------------------------------------------------
+// what the three calls and the size query refuse of the shape
+static int squeeze_shape_check(int dtype, int64_t C, int64_t nb, int64_t n, int64_t nbin) {
+  QI_REQUIRE(dtype == QI_F32 || dtype == QI_F64, "bad dtype %d", dtype);
+  QI_REQUIRE(C >= 1 && nb >= 1 && nbin >= 1, "bad shape: %lld records, %lld bands, %lld bins", (long long)C, (long long)nb,
+             (long long)nbin);
+  QI_REQUIRE(n >= 2, "bad panel length %lld (a column and its partner: 2 at least)", (long long)n);
+  QI_REQUIRE(nbin <= QI_SQUEEZE_MAX_BINS, "%lld bins: %d at most", (long long)nbin, QI_SQUEEZE_MAX_BINS);
+  QI_REQUIRE(C <= (1ll << 40) && nb <= QI_SQUEEZE_MAX_BANDS && n <= (1ll << 40) && (double)C * (double)nb * (double)n <= 0x1p40 &&
+                 (double)C * (double)nbin * (double)n <= 0x1p40 && (double)C * (double)nb * (double)squeeze_tiles(n) < 0x1p31,
+             "request too large");
+  return QI_OK;
+}
+
+// the tables in the scratch: edges [nbin + 1] | carrier [nb] | weight [nb] of the panel's type, each on a multiple of 16 bytes
+static SqueezeTables squeeze_layout(int dtype, int64_t nb, int64_t nbin, size_t* total) {
+  const size_t e = elem_size(dtype);
+  SqueezeTables tb{};
+  tb.edges = 0;
+  tb.carrier = align_up((size_t)(nbin + 1) * e, 16);
+  tb.weight = tb.carrier + align_up((size_t)nb * e, 16);
+  *total = align_up(tb.weight + (size_t)nb * e);
+  return tb;
+}
+
+extern "C++" {  // (templates: C++ linkage)
+// the host tables rounded to T into `words` (laid out by `tb`), refused as the header says; a null table: `fill`
+template <typename T>
+static int squeeze_round(const double* src, int64_t count, double fill, const char* what, std::vector<uint64_t>& words, size_t at) {
+  T* dst = reinterpret_cast<T*>(reinterpret_cast<char*>(words.data()) + at);
+  for (int64_t i = 0; i < count; ++i) {
+    dst[i] = (T)(src ? src[i] : fill);
+    QI_REQUIRE(std::isfinite(dst[i]), "%s[%lld] is not finite", what, (long long)i);
+  }
+  return QI_OK;
+}
+
+template <typename T>
+static int squeeze_tables(int64_t nb, int64_t nbin, const double* carrier, const double* edges, const double* weight,
+                          const SqueezeTables& tb, std::vector<uint64_t>& words) {
+  QI_TRY(squeeze_round<T>(carrier, nb, 0.0, "carrier_hz", words, tb.carrier));
+  QI_TRY(squeeze_round<T>(weight, nb, 1.0, "weight", words, tb.weight));
+  if (!edges) return QI_OK;  // (qi_tfr_ifreq: no bins)
+  QI_TRY(squeeze_round<T>(edges, nbin + 1, 0.0, "edges_hz", words, tb.edges));
+  const T* e = reinterpret_cast<const T*>(reinterpret_cast<const char*>(words.data()) + tb.edges);
+  for (int64_t i = 0; i < nbin; ++i)
+    QI_REQUIRE(e[i] < e[i + 1], "edges_hz is not strictly ascending at %lld (as rounded to the panel's precision)", (long long)i);
+  return QI_OK;
+}
+}  // extern "C++"
+
+static int squeeze_rate_check(int dtype, double rate, double floor) {
+  const double r = dtype == QI_F64 ? rate : (double)(float)rate, f = dtype == QI_F64 ? floor : (double)(float)floor;
+  QI_REQUIRE(std::isfinite(r) && r > 0.0, "bad sample_rate_hz %g (finite and above 0)", rate);
+  QI_REQUIRE(floor >= 0.0 && std::isfinite(f), "bad power_floor %g (finite, 0 or more)", floor);
+  return QI_OK;
+}
+
+// the three calls behind their null checks: want_ifreq / want_out say which kernels run
+static int squeeze_run(int dtype, int device, const void* Z, const void* ifreq_in, int64_t C, int64_t nb, int64_t n,
+                       const double* carrier, double rate, double floor, bool estimates, const double* edges, int64_t nbin,
+                       const double* weight, void* ifreq_out, void* out, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_TRY(squeeze_shape_check(dtype, C, nb, n, nbin));
+  if (estimates) QI_TRY(squeeze_rate_check(dtype, rate, floor));
+  size_t total = 0;
+  SqueezeTables tb = squeeze_layout(dtype, nb, nbin, &total);
+  std::vector<uint64_t> words(total / 8);
+  QI_TRY(by_dtype(dtype, [&](auto t) -> int { return squeeze_tables<decltype(t)>(nb, nbin, carrier, edges, weight, tb, words); }));
+  QI_TRY(require_scratch(scratch_bytes, (int64_t)total));
+  const size_t e = elem_size(dtype);
+  QI_REQUIRE(aligned(Z, 2 * e) && aligned(ifreq_in, e) && aligned(ifreq_out, e) && aligned(out, 2 * e) && aligned(scratch, 16),
+             "misaligned pointer");
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  // the host arrays ride in kernel arguments: stream-ordered, and the caller's arrays are free at return
+  QI_TRY(qi::host::put_words(scratch, words.data(), (int64_t)words.size(), st));
+  tb.base = scratch;
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (ifreq_out) return launch_tfr_ifreq<T>((const cplx<T>*)Z, C, nb, n, tb, rate, floor, (T*)ifreq_out, st);
+    return launch_tfr_squeeze<T>((const cplx<T>*)Z, (const T*)ifreq_in, C, nb, n, nbin, tb, rate, floor, (cplx<T>*)out, st);
+  });
+}
+
+int64_t qi_tfr_squeeze_scratch_bytes(int dtype, int64_t C, int64_t nb, int64_t n, int64_t nbin) {
+  QI_TRY(squeeze_shape_check(dtype, C, nb, n, nbin));
+  size_t total = 0;
+  squeeze_layout(dtype, nb, nbin, &total);
+  return (int64_t)total;
+}
+
+int qi_tfr_ifreq(int dtype, int device, const void* Z, int64_t C, int64_t nb, int64_t n, const double* carrier_hz,
+                 double sample_rate_hz, double power_floor, void* ifreq, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_REQUIRE(Z && scratch, "null argument");
+  QI_REQUIRE(ifreq, "ifreq is null: nothing to produce");
+  return squeeze_run(dtype, device, Z, nullptr, C, nb, n, carrier_hz, sample_rate_hz, power_floor, true, nullptr, 1, nullptr, ifreq,
+                     nullptr, scratch, scratch_bytes, stream);
+}
+
+int qi_tfr_squeeze(int dtype, int device, const void* Z, const void* ifreq, int64_t C, int64_t nb, int64_t n,
+                   const double* edges_hz, int64_t nbin, const double* weight, void* out, void* scratch, int64_t scratch_bytes,
+                   qi_stream stream) {
+  QI_REQUIRE(Z && ifreq && scratch && edges_hz, "null argument");
+  QI_REQUIRE(out, "out is null: nothing to produce");
+  return squeeze_run(dtype, device, Z, ifreq, C, nb, n, nullptr, 1.0, 0.0, false, edges_hz, nbin, weight, nullptr, out, scratch,
+                     scratch_bytes, stream);
+}
+
+int qi_tfr_synchrosqueeze(int dtype, int device, const void* Z, int64_t C, int64_t nb, int64_t n, const double* carrier_hz,
+                          double sample_rate_hz, double power_floor, const double* edges_hz, int64_t nbin, const double* weight,
+                          void* out, void* scratch, int64_t scratch_bytes, qi_stream stream) {
+  QI_REQUIRE(Z && scratch && edges_hz, "null argument");
+  QI_REQUIRE(out, "out is null: nothing to produce");
+  return squeeze_run(dtype, device, Z, nullptr, C, nb, n, carrier_hz, sample_rate_hz, power_floor, true, edges_hz, nbin, weight,
+                     nullptr, out, scratch, scratch_bytes, stream);
 }
 
 // ---- tfr_info -------------------------------------------------------------------------------------

@@ -246,6 +246,21 @@ template <typename T>
 int launch_time_beam_traces(const T* x, int64_t C, int64_t n, const T* taps, int64_t P, int64_t T_taps, const int32_t* shift,
                             const int32_t* phase, int64_t K, int64_t max_shift, T* out, hipStream_t st);
 
+// synchrosqueezing (qi_squeeze.hip; include/qi_squeeze.h); the arguments are the checked ones of the three calls.  The
+// tables lie in the caller's scratch, rounded to the panel's type: byte offsets from `base` of edges [nbin + 1], carrier
+// [nb] and weight [nb].  launch_tfr_squeeze with a null ifreq forms the frequencies itself (the fused call).
+struct SqueezeTables {
+  const void* base;
+  size_t edges, carrier, weight;
+};
+int64_t squeeze_tiles(int64_t n);  // workgroups along time
+template <typename T>
+int launch_tfr_ifreq(const cplx<T>* Z, int64_t C, int64_t nb, int64_t n, const SqueezeTables& tb, double rate, double floor, T* ifreq,
+                     hipStream_t st);
+template <typename T>
+int launch_tfr_squeeze(const cplx<T>* Z, const T* ifreq, int64_t C, int64_t nb, int64_t n, int64_t nbin, const SqueezeTables& tb,
+                       double rate, double floor, cplx<T>* out, hipStream_t st);
+
 template <typename T>
 int launch_power_marginals(const T* P, int64_t C, int64_t B, int64_t n, T* power_time, double* part_band,
                            double* part_stat, hipStream_t st);

@@ -764,6 +764,85 @@ def cross_spectra_bands(panel, terms, hop=None, stride=None, weight=None, bins=N
     return offsets, finish(csd, was_numpy, False)
 
 
+def _band_table(values, count, what):
+    """A host table of one float64 per band, or None -> (array kept alive, pointer for the library)."""
+    if values is None:
+        return None, None
+    host, p = _lib.darr(values)
+    if host.shape != (count,):
+        raise ValueError(f"{what} must hold one value per band ({count}), got shape {host.shape}")
+    return host, p
+
+
+def _bin_edges(edges_hz):
+    host, p = _lib.darr(edges_hz)
+    if host.ndim != 1 or len(host) < 2:
+        raise ValueError(f"edges_hz must hold the edges of one bin at least, got shape {host.shape}")
+    return host, p, len(host) - 1
+
+
+def instantaneous_frequency(panel, sample_rate_hz, carrier_hz=None, power_floor=0.0):
+    """The instantaneous frequency in Hz of every coefficient of a panel [C, n_bands, n_time] (a CWT or Stockwell panel,
+    complex64 or complex128), from the forward phase difference along time (qi_tfr_ifreq, include/qi_squeeze.h):
+    carrier_hz[b] + sample_rate_hz * angle(panel[.., t + 1] * conj(panel[.., t])) / (2 pi); the last column takes the
+    difference behind it.  carrier_hz: [n_bands] host values or None (0) -- the frequency band b has been demodulated by: 0
+    for a CWT panel, the snapped bin frequency stx_shift_indices * sample_rate_hz / n for a Stockwell panel.  An element is
+    NaN where |coefficient|^2 of it or of its partner is below power_floor or not finite.  -> [C, n_bands, n_time] real.
+    NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    z, was_numpy, rdtype = _matrix_stack(panel, "panel", "[C, bands, time]", square=False)
+    n_ch, n_b, n_t = z.shape
+    c_host, c_ptr = _band_table(carrier_hz, n_b, "carrier_hz")
+    dev, code = z.device, _lib.dtype_code(rdtype)
+    scratch, nbytes = _lib.scratch(lib.qi_tfr_squeeze_scratch_bytes, dev, code, n_ch, n_b, n_t, 1)
+    out = torch.empty((n_ch, n_b, n_t), dtype=rdtype, device=dev)
+    _lib.call(lib.qi_tfr_ifreq, dev, code, dev.index, _lib.ptr(z), n_ch, n_b, n_t, c_ptr, float(sample_rate_hz), float(power_floor),
+              _lib.ptr(out), _lib.ptr(scratch), nbytes)
+    return finish(out, was_numpy, False)
+
+
+def squeeze(panel, ifreq, edges_hz, weight=None):
+    """Reassignment of a panel [C, n_bands, n_time] to frequency bins by the frequencies it is handed (qi_tfr_squeeze):
+    out[c, k, t] = sum of weight[b] * panel[c, b, t] over the bands with edges_hz[k] <= ifreq[c, b, t] < edges_hz[k + 1], added
+    in ascending b in the panel's precision.  ifreq: [C, n_bands, n_time] real of the panel's precision (NaN: the element is
+    dropped); edges_hz: [n_bins + 1] strictly ascending host values; weight: [n_bands] host values or None (1).  The result
+    is exact given the frequencies, the same bits in every run: no atomics.  -> [C, n_bins, n_time] complex.  NumPy in ->
+    NumPy out, CUDA tensor in -> CUDA tensor out (the panel decides)."""
+    lib = _lib.require_gpu()
+    z, was_numpy, rdtype = _matrix_stack(panel, "panel", "[C, bands, time]", square=False)
+    n_ch, n_b, n_t = z.shape
+    f = torch.from_numpy(np.ascontiguousarray(ifreq)) if not isinstance(ifreq, torch.Tensor) else ifreq
+    if f.dtype != rdtype or tuple(f.shape) != tuple(z.shape):
+        raise ValueError(f"ifreq must be {rdtype} {tuple(z.shape)}, got {f.dtype} {tuple(f.shape)}")
+    f = f.to(z.device).contiguous()
+    e_host, e_ptr, n_bins = _bin_edges(edges_hz)
+    w_host, w_ptr = _band_table(weight, n_b, "weight")
+    dev, code = z.device, _lib.dtype_code(rdtype)
+    scratch, nbytes = _lib.scratch(lib.qi_tfr_squeeze_scratch_bytes, dev, code, n_ch, n_b, n_t, n_bins)
+    out = torch.empty((n_ch, n_bins, n_t), dtype=z.dtype, device=dev)
+    _lib.call(lib.qi_tfr_squeeze, dev, code, dev.index, _lib.ptr(z), _lib.ptr(f), n_ch, n_b, n_t, e_ptr, n_bins, w_ptr, _lib.ptr(out),
+              _lib.ptr(scratch), nbytes)
+    return finish(out, was_numpy, False)
+
+
+def synchrosqueeze(panel, sample_rate_hz, edges_hz, carrier_hz=None, weight=None, power_floor=0.0):
+    """The synchrosqueezed panel in one pass (qi_tfr_synchrosqueeze): squeeze(panel, instantaneous_frequency(panel,
+    sample_rate_hz, carrier_hz, power_floor), edges_hz, weight) bit for bit, without the frequencies ever reaching device
+    memory.  -> [C, n_bins, n_time] complex.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    lib = _lib.require_gpu()
+    z, was_numpy, rdtype = _matrix_stack(panel, "panel", "[C, bands, time]", square=False)
+    n_ch, n_b, n_t = z.shape
+    c_host, c_ptr = _band_table(carrier_hz, n_b, "carrier_hz")
+    w_host, w_ptr = _band_table(weight, n_b, "weight")
+    e_host, e_ptr, n_bins = _bin_edges(edges_hz)
+    dev, code = z.device, _lib.dtype_code(rdtype)
+    scratch, nbytes = _lib.scratch(lib.qi_tfr_squeeze_scratch_bytes, dev, code, n_ch, n_b, n_t, n_bins)
+    out = torch.empty((n_ch, n_bins, n_t), dtype=z.dtype, device=dev)
+    _lib.call(lib.qi_tfr_synchrosqueeze, dev, code, dev.index, _lib.ptr(z), n_ch, n_b, n_t, c_ptr, float(sample_rate_hz),
+              float(power_floor), e_ptr, n_bins, w_ptr, _lib.ptr(out), _lib.ptr(scratch), nbytes)
+    return finish(out, was_numpy, False)
+
+
 def pair_lags(csd, *, bins=None, weighting="phat", halve_interior=True, normalize=True, upsample=1, max_lag=None, want_cc=False):
     """Time delays between every pair of records from their cross-spectral matrices (qi_pair_lags, include/qi_lags.h): the
     generalized cross-correlation r of pair (i, j), i < j, its first maximum inside +-max_lag and the three-point parabola

@@ -216,3 +216,26 @@ def stx_shift_indices(frequency_stx_hz: np.ndarray, fft_points: int, frequency_s
     inside the Stockwell loop (ref styx_stx.py:216,233)."""
     grid = np.fft.fftfreq(fft_points, 1 / frequency_sample_rate_hz)
     return np.array([np.abs(grid - f).argmin() for f in np.atleast_1d(frequency_stx_hz)], dtype=np.int64)
+
+
+def squeeze_bin_edges(frequency_hz: np.ndarray, bins_per_band: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """Frequency bins for a synchrosqueezed panel from a band table (engine.synchrosqueeze): bins_per_band bins to a band,
+    even in log2 f.  log2 f is taken linear in the band index between the bands, with the first and the last slope extended
+    past the ends; the edges sit at the indices m / bins_per_band - 1/2, m = 0 .. B * bins_per_band, so that with one bin per
+    band every band centre lies in the middle (in index) of its own bin.  Host, float64.  The table must be ascending, finite
+    and positive, with two bands at least.
+    :return: edges_hz [B * bins_per_band + 1], centre_hz [B * bins_per_band] (the bins' middles in index)"""
+    f = np.asarray(frequency_hz, dtype=np.float64)
+    per = int(bins_per_band)
+    if f.ndim != 1 or len(f) < 2 or not np.all(np.isfinite(f)) or not np.all(f > 0.0) or not np.all(np.diff(f) > 0.0):
+        raise ValueError("frequency_hz must be a finite, positive, strictly ascending table of two bands at least")
+    if per < 1 or per != bins_per_band:
+        raise ValueError(f"bins_per_band must be a whole number of 1 or more, got {bins_per_band}")
+    log2_f = np.log2(f)
+
+    def at(index):
+        below = np.clip(np.floor(index), 0, len(f) - 2).astype(np.int64)
+        return np.exp2(log2_f[below] + (index - below) * (log2_f[below + 1] - log2_f[below]))
+
+    m = np.arange(len(f) * per + 1, dtype=np.float64)
+    return at(m / per - 0.5), at((m[:-1] + 0.5) / per - 0.5)

@@ -135,6 +135,30 @@ def _cwt_panel(band_order_nth, sig, frequency_sample_rate_hz, dictionary_type="n
         return plan.cwt(sig, coef=True)
 
 
+def cwt_synchrosqueezed_pow2(
+    band_order_nth: float,
+    sig_wf,
+    frequency_sample_rate_hz: float,
+    bins_per_band: int = 1,
+    power_floor: float = 0.0,
+    dictionary_type: str = "norm",
+):
+    """The synchrosqueezed order-N CWT of one record [n] or of every row of a batch [C x n], n a power of two: every
+    coefficient of cwt_complex_any_scale_pow2's panel is moved to the frequency bin where its instantaneous frequency -- the
+    forward phase difference along time -- lies (engine.synchrosqueeze; the bins: scales.squeeze_bin_edges, bins_per_band to
+    a band).  A coefficient whose power, or whose neighbour's, is below power_floor stays out.  The panel never leaves the
+    device between the transform and the squeeze.  NumPy in -> NumPy out; CUDA tensor in -> CUDA tensors out.
+    Out of scope: the derivative-wavelet estimator, reconstruction weights and the inverse, ridge tracking, reassignment
+    along time, streamed records.
+    :return: centre_hz [B * bins_per_band], time_s [n], squeezed panel [B * bins_per_band x n] (or [C x ... x n])"""
+    sig, was_numpy, was_1d = engine.as_signal(sig_wf)
+    fs = float(frequency_sample_rate_hz)
+    res = _cwt_panel(band_order_nth, sig, fs, dictionary_type)
+    edges_hz, centre_hz = scales.squeeze_bin_edges(res.frequency_hz, bins_per_band)
+    out = engine.synchrosqueeze(res.coef, fs, edges_hz, power_floor=power_floor)
+    return centre_hz, np.arange(sig.shape[1]) / fs, engine.finish(out, was_numpy, was_1d, widen=True)
+
+
 def wavelet_coherence_pow2(
     sig_wf,
     frequency_sample_rate_hz: float,

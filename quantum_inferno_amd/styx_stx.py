@@ -38,6 +38,23 @@ def _stx_panel(band_order_nth, sig, frequency_sample_rate_hz):
         return plan.stx(sig, coef=True)
 
 
+def stx_synchrosqueezed_pow2(band_order_nth: float, sig_wf, frequency_sample_rate_hz: float, bins_per_band: int = 1,
+                             power_floor: float = 0.0):
+    """The synchrosqueezed order-N Stockwell transform of one record [n] or of every row of a batch [C x n]: as
+    styx_cwt.cwt_synchrosqueezed_pow2 on stx_complex_any_scale_pow2's panel.  A Stockwell band is demodulated by the FFT bin
+    its centre was snapped to, so its phase turns at f minus that bin's frequency: the carrier handed to
+    engine.synchrosqueeze is the snapped one, scales.stx_shift_indices * fs / n, not the band's nominal centre.
+    NumPy in -> NumPy out; CUDA tensor in -> CUDA tensors out.
+    :return: centre_hz [B * bins_per_band], time_s [n], squeezed panel [B * bins_per_band x n] (or [C x ... x n])"""
+    sig, was_numpy, was_1d = engine.as_signal(sig_wf)
+    n, fs = sig.shape[1], float(frequency_sample_rate_hz)
+    res = _stx_panel(band_order_nth, sig, fs)
+    edges_hz, centre_hz = scales.squeeze_bin_edges(res.frequency_hz, bins_per_band)
+    carrier_hz = scales.stx_shift_indices(res.frequency_hz, n, fs) * fs / n
+    out = engine.synchrosqueeze(res.coef, fs, edges_hz, carrier_hz=carrier_hz, power_floor=power_floor)
+    return centre_hz, np.arange(n) / fs, engine.finish(out, was_numpy, was_1d, widen=True)
+
+
 def sig_pad_up_to_pow2(sig_wf: np.ndarray, n_fft: int, verbosity: bool = False):
     """Zero-pad to n_fft points (ref styx_stx.py:15-48).  Upstream this helper raises TypeError as soon as padding
     is actually needed (tuple + int at :44) and for n_fft=None (comparison at :30); here both cases are handled as
